@@ -12,12 +12,17 @@ the build that meets the logit clause of north_star -- bf16 runs beside it as `a
 N > 1 -- the RCCL gather of the token ids to rank 0.  Images shard data-parallel across ranks with no
 collective on the data path ("scaling": "weak").
 
-Rank 0 prints ONE JSON line.  `value` is whole-job captions/s.  `roofline` describes the dominant
+Rank 0 prints ONE JSON line.  `value` is whole-job captions/s, `ms_per_step` the wall time of one timed step.  A plain
+run does only what that figure needs: set-up, warm-up, the timed steps, `--dump-outputs DIR` if given (the ids, log-probs
+and info of the last timed step as .npy files), the line.  Everything below runs with `--full` only.
+
+With `--full`: `roofline` describes the dominant
 kernel (the 16-bit MFMA GEMM inside the image encoder, MFMA-bound; fp16 and bf16 MFMAs share one peak on gfx950) from a separate HIP-event-instrumented
 pass of the same workload; `roofline_decode` the HBM-bound decode step (hipGraph replays, events around the
 decode graph); `parity` compares the generated ids with the reference's ids for this very workload
 (tests/golden/full_*.npz, PARITY_GOLDENS); `cpu_baseline` times the CPU oracle (a port of the reference
-algorithm, full recompute like the reference) on a bounded sample.
+algorithm, full recompute like the reference) on a bounded sample; for N > 1 `gather` reports the cost of the one
+collective.
 
 Without a launcher, `python bench.py --gpus N` starts the N ranks itself (torch.distributed.run, one process per GPU)
 and refuses to print a line whose n_gpus differs from --gpus.
@@ -59,6 +64,17 @@ def gather_results(tokens: torch.Tensor, logprobs: torch.Tensor):
         return None, None
     allp = torch.cat(out, 0)
     return allp[:, :-1].contiguous(), allp[:, -1].to(torch.int32).view(torch.float32)
+
+
+def dump_outputs(out_dir: str, tokens: torch.Tensor, logprobs: torch.Tensor, info: torch.Tensor) -> None:
+    """--dump-outputs: what the caller of the timed path received from its last step (N > 1: the rows of every rank, as
+    gathered to rank 0), so that two builds can be compared output for output.  Ids and info are exact in float64; the
+    whole set is a few KB per 64 images."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "tokens.npy"), tokens.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "logprobs.npy"), logprobs.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "info.npy"), info.cpu().numpy().astype(np.float64))
 
 
 def _cpu_run(sample_batch: int, max_steps: int, threads: int):
@@ -334,7 +350,7 @@ def bench_trained_statistics(args, cfg, device):
 
 
 def child_line(argv_child, timeout_s=150):
-    """One `python bench.py ... --brief` child on this (now idle) GPU -> its parsed JSON line, or {"error": ...}.  Short
+    """One `python bench.py ... --full --brief` child on this (now idle) GPU -> its parsed JSON line, or {"error": ...}.  Short
     timeout: the headline line must not die with a side measurement."""
     cmd = [sys.executable, os.path.abspath(__file__)] + argv_child
     try:
@@ -348,7 +364,7 @@ def child_line(argv_child, timeout_s=150):
 def alt_precision_line(argv_child):
     """The OTHER 16-bit operand build (headline fp16 -> libgitmi.so with bf16 operands, BASELINE.json's named precision; the
     same kernels at the same MFMA rate, 3 fewer mantissa bits per operand) on the SAME workload and schedule, run as a child
-    `python bench.py --precision bf16 --brief` after this process has gone idle: captions/s of a short timed loop and the same
+    `python bench.py --precision bf16 --full --brief` after this process has gone idle: captions/s of a short timed loop and the same
     `parity` object, so the default line carries both builds."""
     c = child_line(argv_child)
     if "error" in c:
@@ -359,7 +375,7 @@ def alt_precision_line(argv_child):
 
 
 # the other BASELINE.json configurations that fit one GPU (configs[2], [3] per GPU, [4]); the default line runs each as a
-# short --brief child after its own timed region so that the driver's record carries all four workloads
+# short --full --brief child after its own timed region so that the driver's record carries all four workloads
 OTHER_CONFIGS = {
     "cfg3_base_b64_beam4": ["--model", "GIT_BASE", "--batch", "64", "--search", "beam"],
     "cfg4_large_b32_greedy": ["--model", "GIT_LARGE", "--batch", "32"],
@@ -370,7 +386,7 @@ OTHER_CONFIGS = {
 def other_configs_lines(args):
     out = {}
     for key, wl in OTHER_CONFIGS.items():
-        c = child_line(wl + ["--precision", args.precision, "--brief", "--no-cpu-baseline", "--no-teacher-forced",
+        c = child_line(wl + ["--precision", args.precision, "--brief", "--full", "--no-cpu-baseline", "--no-teacher-forced",
                              "--steps", str(args.steps), "--warmup", str(args.warmup)])
         if "error" in c:
             out[key] = c
@@ -516,8 +532,14 @@ def main(argv=None, engine_factory=None):
                     help="N > 1: N requests of --batch images are served by ONE engine pass over N x batch rows "
                          "(Engine.generate_coalesced; the concatenation is inside the timed region).  A step is still one "
                          "request of --batch images; the default 1 is the BASELINE configuration (one pass per request)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything besides the headline figure: roofline passes, parity legs, the "
+                         "alt_precision and other_configs children, the CPU baseline, the gather figures for N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the ids, log-probs and info of the last timed step to DIR/{tokens,logprobs,info}.npy")
     ap.add_argument("--brief", action="store_true",
-                    help="timed loop + parity only: no roofline passes, no CPU baseline (what the alt_precision child runs)")
+                    help="with --full: timed loop + parity only, no roofline passes, no CPU baseline (what the alt_precision "
+                         "and other_configs children run)")
     ap.add_argument("--no-teacher-forced", action="store_true",
                     help="skip parity.teacher_forced (its f32-mode engine adds ~2 300 fp32 launches to a kernel trace of the run)")
     ap.add_argument("--no-alt-precision", action="store_true",
@@ -533,6 +555,8 @@ def main(argv=None, engine_factory=None):
     ap.add_argument("--cpu-sweep", action="store_true",
                     help="only time the CPU port at several thread counts (median of 3, bs=8) and print JSON")
     args = ap.parse_args(argv)
+    if args.brief and not args.full:
+        ap.error("--brief narrows what --full adds: give both")
     if args.e2e_tsv:
         from tools.e2e_tsv import main as e2e_main
         e2e_main(["--rows", str(args.e2e_tsv), "--precision", args.precision, "--batch", str(args.batch),
@@ -628,6 +652,7 @@ def main(argv=None, engine_factory=None):
     lat_events = []
     gather_events = []          # N > 1: events around the batch's ONE collective on its stream
     last_lp = [None]
+    last_out = [None]           # (ids, log-probs, info) as the caller of the last step receives them (--dump-outputs)
 
     def step(record_latency=False):
         i = counter[0] % len(ctxs)
@@ -638,11 +663,12 @@ def main(argv=None, engine_factory=None):
                 e0.record()
             tokens, logprobs, info = ctxs[i].generate(frames, search, sync=False)
             last_lp[0] = logprobs
+            last_out[0] = (tokens, logprobs, info)
             if world > 1:
                 if record_latency:
                     g0, g1 = dev.Event(enable_timing=True), dev.Event(enable_timing=True)
                     g0.record()
-                gather_results(tokens, logprobs)
+                last_out[0] = gather_results(tokens, logprobs) + (info,)
                 if record_latency:
                     g1.record()
                     gather_events.append((g0, g1))
@@ -665,9 +691,10 @@ def main(argv=None, engine_factory=None):
                 e0, e1 = dev.Event(enable_timing=True), dev.Event(enable_timing=True)
                 e0.record()
             outs, info = ctxs[i].generate_coalesced([frames] * n, search, sync=False)
+            last_out[0] = outs[-1] + (info,)
             if world > 1:
                 for tk, lp in outs:
-                    gather_results(tk, lp)
+                    last_out[0] = gather_results(tk, lp) + (info,)
             if record_latency:
                 e1.record()
                 lat_events.extend([(e0, e1)] * n)
@@ -700,12 +727,14 @@ def main(argv=None, engine_factory=None):
         t = torch.tensor([elapsed], device="cpu" if standin else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out[0])
 
     # N > 1: what the one collective of the path costs ("report the gather latency separately") -- in the timed
     # schedule (device time between the events around it on the batch's stream: it queues behind the batch's decode chain
     # and waits for the slowest rank) and alone (one gather + stream synchronisation at a time, after the timed region)
     gather_stats = None
-    if world > 1 and tokens is not None:
+    if world > 1 and tokens is not None and args.full:
         g_in = sorted(a.elapsed_time(b) for a, b in gather_events)
         alone = []
         lp_probe = last_lp[0] if last_lp[0] is not None and last_lp[0].shape[0] == tokens.shape[0] else \
@@ -755,7 +784,7 @@ def main(argv=None, engine_factory=None):
 
     # ---- roofline passes: one context alone on rank 0's GPU after the timed region (N > 1: the other ranks wait at the final
     #      barrier, so every line -- 1, 2, 4, 8 GPUs -- carries `roofline` / `roofline_decode`) -----------------------------
-    if rank == 0 and not standin and args.brief:
+    if rank == 0 and not standin and args.full and args.brief:
         # one context alone: the ids the parity legs compare, and the decode step of the production launch path
         eng.profile_enable(2)
         for it in range(4):
@@ -766,7 +795,7 @@ def main(argv=None, engine_factory=None):
         eng.profile_enable(0)
         result["roofline_decode"] = {"avg_step_ms": round(bprof["decode_step_ms"], 4), "steps": bprof["decode_steps"],
                                      "bytes_per_step": bprof["decode_step_bytes"]}
-    if rank == 0 and not standin and not args.brief:
+    if rank == 0 and not standin and args.full and not args.brief:
         pmc = pmc_profile({"gemm": "gemm_p8", "attn_decode": "attn_decode", "dgemm": "dgemm_kernel", "vocab": "vocab_topm"})
         # (1) eager launches, HIP events around every GEMM launch on the launch stream: per-kernel durations
         eng.profile_enable(1)
@@ -871,7 +900,7 @@ def main(argv=None, engine_factory=None):
         result["phases_ms"] = {k: round(prof[k], 3) for k in ("vit_ms", "prefill_ms", "decode_ms", "total_ms", "gemm_ms")}
         result["phases_ms"]["graph_encode_prefill_ms"] = round(gprof["vit_ms"], 3)
         result["phases_ms"]["graph_decode_ms"] = round(gprof["decode_ms"], 3)
-    if rank == 0 and not standin:
+    if rank == 0 and not standin and args.full:
         # the ids of the timed schedule's last batch are the ids of the solo pass (same images, same weights)
         result["timed_ids_equal_solo"] = bool(torch.equal(tokens.cpu(), tokens_solo.cpu()))
         result["nonfinite_sequences"] = int(info.tolist()[3]) + int(info_solo.tolist()[3])
@@ -887,13 +916,13 @@ def main(argv=None, engine_factory=None):
             if result["nonfinite_sequences"]:
                 result["parity"]["ok"] = False
                 result["parity"].setdefault("violation", "non-finite log-probabilities in the timed run")
-    if rank == 0 and world == 1 and not standin and not args.brief:
+    if rank == 0 and world == 1 and not standin and args.full and not args.brief:
         if (args.precision in ("f16", "bf16") and not args.no_alt_precision and not args.experiment and coalesce == 1
                 and golden_name is not None):
             # the other 16-bit operand build on the same workload and schedule, in a child process, with this process idle
             dev.synchronize()
             other = "bf16" if args.precision == "f16" else "f16"
-            child = ["--precision", other, "--brief", "--no-cpu-baseline", "--steps", str(args.steps), "--warmup", str(args.warmup),
+            child = ["--precision", other, "--brief", "--full", "--no-cpu-baseline", "--steps", str(args.steps), "--warmup", str(args.warmup),
                      "--batch", str(args.batch), "--model", args.model, "--search", args.search, "--max-steps", str(args.max_steps),
                      "--frames", str(args.frames), "--contexts", str(args.contexts), "--encoder-chains", str(args.encoder_chains)]
             child += ["--solo-policy"] if args.solo_policy else []

@@ -46,6 +46,9 @@ def _task_worker(rank, world, port, tmpdir, with_questions, rendezvous):
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch.distributed as dist
     from generativeimage2text_amd import inference
+    # the task's CPU path (gloo) on every host: with a GPU visible it would pick RCCL, which needs one device per rank --
+    # these ranks select none, so on a GPU box both would sit on device 0
+    torch.cuda.is_available = lambda: False
     assert not dist.is_initialized()
     inference.run_tsv_inference(
         os.path.join(tmpdir, "img.tsv"), os.path.join(tmpdir, "q.tsv") if with_questions else None,
@@ -149,8 +152,9 @@ def _bench_main_worker(rank, world, port, tmpdir):
         gathered.append(out)
         return out
     bench.gather_results = spy
+    dump = os.path.join(tmpdir, "dump")
     res = bench.main(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--batch", "3", "--contexts", "2",
-                      "--no-cpu-baseline"],
+                      "--no-cpu-baseline", "--full", "--dump-outputs", dump],
                      engine_factory=lambda args, r: (_StandInEngine(r, args.batch, args.max_steps), [torch.zeros(1)]))
     if rank == 0:
         assert res["n_gpus"] == world and res["config"]["global_batch"] == world * 3 and res["config"]["parallelism"] == f"dp{world}"
@@ -162,6 +166,11 @@ def _bench_main_worker(rank, world, port, tmpdir):
         # the path's one collective is reported on its own: in the schedule and alone
         g = res["gather"]
         assert g["bytes_per_rank"] == 3 * 21 * 8 and g["alone_ms"]["median"] > 0 and g["in_schedule_ms"]["median"] >= 0
+        # --dump-outputs writes what rank 0 received from the last timed step: the rows of every rank
+        import numpy as np
+        dt = np.load(os.path.join(dump, "tokens.npy"))
+        assert dt.shape == (world * 3, 20) and (dt == t.numpy()).all()
+        assert (np.load(os.path.join(dump, "logprobs.npy")) == l.numpy()).all()
         open(os.path.join(tmpdir, "ok"), "w").write(json.dumps(res))
     else:
         assert res is None and gathered[-1] == (None, None)

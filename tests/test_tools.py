@@ -191,8 +191,8 @@ def _run_bench_with_fakes(monkeypatch, capsys, argv):
 
 
 def test_bench_control_flow_all_schedules(monkeypatch, capsys):
-    # the contract's fields, default (mixed) schedule
-    d, log = _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "3"])
+    # the contract's fields, default (mixed) schedule, everything the line reports with --full
+    d, log = _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "3", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "roofline_decode", "parity"):
         assert k in d, k
@@ -209,7 +209,7 @@ def test_bench_control_flow_all_schedules(monkeypatch, capsys):
     assert tf["decisions"] == 64 * 19 and 0 < tf["decidable"] <= tf["decisions"] and "max_logit_err" in tf
     assert tf["spec_logit_frac"] == pytest.approx(1e-3) and tf["logit_err_bound"] == pytest.approx(1e-3 * tf["logit_span"], rel=1e-3)
     child = d["alt_precision"]["child_argv"]
-    assert child[:3] == ["--precision", "bf16", "--brief"] and child[child.index("--steps") + 1] == "8"
+    assert child[:3] == ["--precision", "bf16", "--brief"] and "--full" in child and child[child.index("--steps") + 1] == "8"
     # the second parity leg: trained-checkpoint statistics, same geometry, every row required of the headline build
     tr = d["parity"]["trained_statistics"]
     assert tr["reference"].endswith("full_trained_b64_greedy.npz") and tr["required"] == 64 and tr["teacher_forced"]["decisions"] == 64 * 19
@@ -217,10 +217,10 @@ def test_bench_control_flow_all_schedules(monkeypatch, capsys):
     # the other BASELINE configurations ride in the same line, one short child each, in this run's precision
     assert set(d["other_configs"]) == {"cfg3_base_b64_beam4", "cfg4_large_b32_greedy", "cfg5_vatex_b16_6frames"}
     import bench
-    assert all(c[c.index("--precision") + 1] == "f16" and "--brief" in c for c in bench._test_children)
+    assert all(c[c.index("--precision") + 1] == "f16" and "--brief" in c and "--full" in c for c in bench._test_children)
     assert d["other_configs"]["cfg3_base_b64_beam4"]["parity"]["identical"] == 60
     # --brief (what that child runs): timed loop + parity, no roofline passes
-    d, log = _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "3", "--brief", "--precision", "f16"])
+    d, log = _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "3", "--full", "--brief", "--precision", "f16"])
     assert "roofline" not in d and "alt_precision" not in d and "other_configs" not in d and "parity" in d and d["dtype"] == "f16"
     assert d["roofline_decode"]["avg_step_ms"] == 0.25
     # coalesced: two requests per engine pass
@@ -234,6 +234,29 @@ def test_bench_control_flow_all_schedules(monkeypatch, capsys):
     for flags in (["--decode-group", "2"], ["--phased", "4"]):
         with pytest.raises(SystemExit):
             _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "4"] + flags)
+
+
+def test_bench_plain_run_times_and_dumps_only(monkeypatch, capsys, tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps, --dump-outputs and the line: no pass after the timed
+    region, no child, no side measurement.  The dump is what the caller of the last timed step received, in float."""
+    import numpy as np
+    import bench
+    out = tmp_path / "dump"
+    d, log = _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--warmup", "3", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 8 and d["ms_per_step"] > 0 and d["dtype"] == "f16" and d["higher_is_better"] is True
+    for k in ("roofline", "roofline_decode", "parity", "alt_precision", "other_configs", "cpu_baseline", "timed_ids_equal_solo"):
+        assert k not in d, k
+    assert len([e for e in log if e[0] == "generate"]) == 4 + 3 + 8      # priming pass over the contexts + warm-up + timed
+    assert bench._test_children == []
+    tokens, logprobs, info = (np.load(out / f"{n}.npy") for n in ("tokens", "logprobs", "info"))
+    assert tokens.dtype == np.float64 and tokens.shape == (64, 20) and (tokens == 7).all()
+    assert logprobs.dtype == np.float32 and logprobs.shape == (64,)
+    assert info.dtype == np.float64 and info.tolist() == [20, 0, 19, 0]
+    # --brief only narrows --full
+    with pytest.raises(SystemExit):
+        _run_bench_with_fakes(monkeypatch, capsys, ["--steps", "8", "--brief"])
 
 
 def test_bench_reads_the_pmc_summary_taken_for_this_csrc(tmp_path, monkeypatch):

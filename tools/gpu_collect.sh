@@ -3,16 +3,18 @@
 #   bash tools/gpu_collect.sh TAG [section ...]        sections, default "pmc bench stats suite configs smoke":
 #     pmc      rocprofv3 --pmc passes of tools/pmc_workload.py for the CURRENT csrc -> profiles/TAG_pmc_summary.tsv (bench.py reads
 #              the newest summary whose csrc hash matches; copied to profiles/ FIRST so that `bench` below reports fresh traffic)
-#     bench    the default line (python bench.py, cpu_baseline included) -> TAG_bench.json, and a 200-step line
-#     stats    the default line under rocprofv3 --kernel-trace --stats -> TAG_default_kernel_stats.txt (+ solo policy, beam-4, GIT_LARGE, VATEX;
+#     bench    the --full line (python bench.py --full, cpu_baseline included) -> TAG_bench.json, and a 200-step line
+#     stats    the --full line under rocprofv3 --kernel-trace --stats -> TAG_default_kernel_stats.txt (+ solo policy, beam-4, GIT_LARGE, VATEX;
 #              one row per (kernel, workgroup count), csrc hash in the header)
 #     suite    python -m pytest tests -m gpu -> TAG_pytest_gpu.txt, TAG_parity_measured.jsonl
 #     configs  bench lines of the other BASELINE configurations (beam 4, GIT_LARGE bs 32, VATEX 6 frames bs 16), bf16 and f16 builds
 #     smoke    __graft_entry__.smoke()
 #     attrib   tools/error_attribution.py on the benchmark's, the oracle's and the trained-statistics weights -> TAG_error_attribution_*.txt
-# Everything lands in gpurun_out/ (merged back by gpurun); copy what is cited into profiles/.
+# The bench, stats and configs sections write to $BENCH_OUT (default out/), the other sections where their tools write;
+# copy what is cited into profiles/.
 set -u; mkdir -p gpurun_out; export PYTHONUNBUFFERED=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 R=$PWD; TAG=${1:-collect}; shift || true; SECTIONS=${*:-pmc bench stats suite configs smoke}
+mkdir -p "${BENCH_OUT:-out}"; OUT=$(cd "${BENCH_OUT:-out}" && pwd)
 T0=$(date +%s); t() { echo "[t+$(( $(date +%s) - T0 ))s] $*"; }
 line() { python tools/bench_lines.py "$1" | cut -c1-230; }
 for sec in $SECTIONS; do case $sec in
@@ -21,19 +23,19 @@ pmc)
   cp gpurun_out/pmc_summary.tsv gpurun_out/${TAG}_pmc_summary.tsv && cp gpurun_out/pmc_summary.tsv profiles/${TAG}_pmc_summary.tsv
   rm -rf gpurun_out/pmc; grep csrc_sha gpurun_out/${TAG}_pmc_summary.tsv | cut -c1-120 ;;
 bench)
-  t "default line"; timeout 600 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "rc=$?"; line gpurun_out/${TAG}_bench.json
-  t "200 steps"; timeout 200 python bench.py --no-cpu-baseline --steps 200 --warmup 8 > gpurun_out/${TAG}_bench_200steps.json 2> /dev/null; line gpurun_out/${TAG}_bench_200steps.json
-  t "one context, solo policy"; timeout 200 python bench.py --no-cpu-baseline --contexts 1 --steps 10 --warmup 2 > gpurun_out/${TAG}_solo_bench.json 2> /dev/null; line gpurun_out/${TAG}_solo_bench.json ;;
+  t "full line"; timeout 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "rc=$?"; line $OUT/${TAG}_bench.json
+  t "200 steps"; timeout 200 python bench.py --full --no-cpu-baseline --steps 200 --warmup 8 > $OUT/${TAG}_bench_200steps.json 2> /dev/null; line $OUT/${TAG}_bench_200steps.json
+  t "one context, solo policy"; timeout 200 python bench.py --full --no-cpu-baseline --contexts 1 --steps 10 --warmup 2 > $OUT/${TAG}_solo_bench.json 2> /dev/null; line $OUT/${TAG}_solo_bench.json ;;
 stats)
-  t "rocprofv3 --kernel-trace --stats: default line"
+  t "rocprofv3 --kernel-trace --stats: full line"
   ( cd /tmp; export TMPDIR=/tmp
     for v in "default:" "solo:--contexts 1 --steps 10 --warmup 2" "beam4:--search beam --contexts 1 --steps 10 --warmup 2" \
              "large_b32:--model GIT_LARGE --batch 32 --contexts 1 --steps 8 --warmup 2" \
              "vatex_b16:--model GIT_BASE_VATEX --frames 6 --batch 16 --contexts 1 --steps 8 --warmup 2"; do
       n=${v%%:*}; a=${v#*:}
-      timeout 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$n -o bench -- python $R/bench.py --no-cpu-baseline --no-alt-precision --no-teacher-forced $a > $R/gpurun_out/${TAG}_${n}_rocprof_bench.json 2> $R/gpurun_out/${TAG}_${n}_rocprof.err
-      python $R/tools/rocprof_summary.py $R/gpurun_out/prof_$n/bench_results.db $R/gpurun_out/${TAG}_${n}_kernel_stats.txt > /dev/null
-      rm -rf $R/gpurun_out/prof_$n; head -n 12 $R/gpurun_out/${TAG}_${n}_kernel_stats.txt | cut -c1-200
+      timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$n -o bench -- python $R/bench.py --full --no-cpu-baseline --no-alt-precision --no-teacher-forced $a > $OUT/${TAG}_${n}_rocprof_bench.json 2> $OUT/${TAG}_${n}_rocprof.err
+      python $R/tools/rocprof_summary.py $OUT/prof_$n/bench_results.db $OUT/${TAG}_${n}_kernel_stats.txt > /dev/null
+      rm -rf $OUT/prof_$n; head -n 12 $OUT/${TAG}_${n}_kernel_stats.txt | cut -c1-200
     done ) ;;
 suite)
   rm -f gpurun_out/parity_measured.jsonl
@@ -43,10 +45,10 @@ configs)
   for c in "beam4:--search beam" "large_b32:--model GIT_LARGE --batch 32" "vatex_b16:--model GIT_BASE_VATEX --frames 6 --batch 16"; do
     n=${c%%:*}; a=${c#*:}
     for prec in bf16 f16; do
-      t "$n $prec"; timeout 300 python bench.py --no-cpu-baseline --precision $prec $a > gpurun_out/${TAG}_${n}_${prec}_bench.json 2> /dev/null; line gpurun_out/${TAG}_${n}_${prec}_bench.json
+      t "$n $prec"; timeout 300 python bench.py --full --no-cpu-baseline --precision $prec $a > $OUT/${TAG}_${n}_${prec}_bench.json 2> /dev/null; line $OUT/${TAG}_${n}_${prec}_bench.json
     done
   done
-  t "base f16"; timeout 300 python bench.py --no-cpu-baseline --precision f16 > gpurun_out/${TAG}_base_f16_bench.json 2> /dev/null; line gpurun_out/${TAG}_base_f16_bench.json ;;
+  t "base f16"; timeout 300 python bench.py --full --no-cpu-baseline --precision f16 > $OUT/${TAG}_base_f16_bench.json 2> /dev/null; line $OUT/${TAG}_base_f16_bench.json ;;
 smoke)
   t smoke; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.txt 2>&1; echo "rc=$?"; tail -n 2 gpurun_out/${TAG}_smoke.txt | cut -c1-200 ;;
 attrib)

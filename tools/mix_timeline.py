@@ -2,7 +2,7 @@
 """Where does the wall time of the mixed schedule go?  Timeline analysis of a rocprofv3 --kernel-trace database
 (rocpd sqlite, view `kernels`: name, start, end, queue_id, stream_id; ns) of `bench.py` with several contexts in flight.
 
-    rocprofv3 --kernel-trace -d out -o bench -- python bench.py --no-cpu-baseline --steps 40
+    rocprofv3 --kernel-trace -d out -o bench -- python bench.py --full --no-cpu-baseline --steps 40
     python tools/mix_timeline.py out/bench_results.db [--lo 0.35 --hi 0.75] [--solo solo_results.db]
 
 The kernels of a pass fall into two classes: ENCODER (image encoder + decoder prefill: the MFMA GEMMs, LayerNorms, full
