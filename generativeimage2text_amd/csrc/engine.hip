@@ -220,6 +220,16 @@ struct gitmi_engine {
     int* out_sent = nullptr;           // [max_batch][2] per-sentence (length, early) of the last generate
     hipStream_t own_stream = nullptr;  // used when the caller passes the (uncapturable) null stream
     hipEvent_t fence_in = nullptr, fence_out = nullptr;
+
+    // caption scoring (GITMI_SEARCH_SCORE, kernels_score.hip): workspaces of the text pass over (sentence, position) rows,
+    // allocated by the first score call and grown to the rows of a larger call (score_alloc)
+    size_t sc_rows = 0;                 // rows the current workspaces hold (0: none)
+    std::vector<void*> sc_allocs;
+    float *sc_hf = nullptr, *sc_y = nullptr, *sc_zt = nullptr;
+    void *sc_ht = nullptr, *sc_qkv = nullptr, *sc_ctx = nullptr, *sc_u = nullptr;
+    float4* sc_part = nullptr;
+    int *sc_tgt = nullptr, *sc_lens = nullptr, *sc_img = nullptr, *sc_bad = nullptr, *sc_info = nullptr;
+    float2* sc_out = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -447,6 +457,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     if (e->enc_done) hipEventDestroy(e->enc_done);
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
+    for (void* p : e->sc_allocs) hipFree(p);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -1518,6 +1529,7 @@ extern "C" int gitmi_search_begin(gitmi_engine* e, const gitmi_search* sp, int B
     if (!start_host) return fail("search_begin: null start");
     if (B < 1 || B > e->cfg.max_batch || P < 1 || P > e->cfg.max_text_len) return fail("search_begin: bad B/P");
     if (vocab < 2) return fail("search_begin: bad vocab");
+    if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("search_begin: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)");
     hipStream_t s = (hipStream_t)stream;
     // start_host is [B, P]: one row per sentence, written into the engine's [B, max_text_len] start table
     HIPCK(hipMemcpy2DAsync(e->start_dev, (size_t)e->cfg.max_text_len * sizeof(long long), start_host,
@@ -1742,6 +1754,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
                               void* stream) {
     RCK(check_ready(e));
     const gitmi_config& c = e->cfg;
+    if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
     if (!frames || !sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
     if (F < 1 || F > c.max_frames) return fail("generate: F=%d outside [1,%d]", F, c.max_frames);
     if (B < 1 || B > c.max_batch) return fail("generate: B=%d outside [1,%d]", B, c.max_batch);
@@ -1754,6 +1767,94 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     return generate_run(e, frames, F, B, B, P, P, false, sp, tokens_out, logprob_out, info_out, nullptr, s);
 }
 
+// ---- caption scoring (GITMI_SEARCH_SCORE) -------------------------------------------------------------------------
+static void score_free(gitmi_engine* e) {
+    for (void* p : e->sc_allocs) hipFree(p);
+    e->sc_allocs.clear();
+    e->sc_rows = 0;
+}
+// Workspaces of a score call with `rows` text rows (Q x Lp): allocated by the first score call and grown when a later call
+// needs more rows, so an engine that never scores keeps its footprint and one that scores short sentences pays for those.
+// Per-sentence buffers are sized for the capacity (max_batch x max_beams sentences x max_text_len; a few hundred KiB).
+static int score_alloc(gitmi_engine* e, size_t rows_needed) {
+    const size_t rows = (size_t)round_up((int)rows_needed, 128);    // the head's 128-row tiles (its loads clamp to M - 1)
+    if (e->sc_rows >= rows) return 0;
+    score_free(e);
+    const gitmi_config& c = e->cfg;
+    const int d = c.dec_hidden;
+    const size_t Qmax = (size_t)c.max_batch * c.max_beams;
+    const size_t esz = e->esz;
+    auto alloc = [&](auto** p, size_t bytes) -> bool {
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) return false;
+        e->sc_allocs.push_back(q);
+        *reinterpret_cast<void**>(p) = q;
+        return true;
+    };
+    const bool ok = alloc(&e->sc_hf, rows * d * 4) && alloc(&e->sc_y, rows * d * 4) && alloc(&e->sc_ht, rows * d * esz) &&
+                    alloc(&e->sc_qkv, rows * 3 * d * esz) && alloc(&e->sc_ctx, rows * d * esz) &&
+                    alloc(&e->sc_u, rows * c.dec_ffn * esz) &&
+                    alloc(&e->sc_part, rows * (size_t)(e->f32 ? 1 : score_head_tiles(c.vocab)) * sizeof(float4)) &&
+                    alloc(&e->sc_zt, rows * 4) && alloc(&e->sc_tgt, rows * 4) && alloc(&e->sc_lens, Qmax * 4) &&
+                    alloc(&e->sc_img, Qmax * 4) && alloc(&e->sc_bad, Qmax * 4) && alloc(&e->sc_info, 16) &&
+                    alloc(&e->sc_out, Qmax * (size_t)c.max_text_len * sizeof(float2));
+    if (!ok) {
+        score_free(e);
+        (void)hipGetLastError();
+        return fail("score: out of device memory for the workspaces of %zu text rows", rows);
+    }
+    e->sc_rows = rows;
+    return 0;
+}
+
+// One pass of the textual head over whole sentences (CaptioningModel.forward_one_ce, decoder.py:916-972) after the
+// usual encode + prefill: embedding of every position, the decoder layers over all text rows at once (generic GEMM +
+// LayerNorm launches, the attention of kernels_score.hip against the prefill's image K/V), then the vocabulary head
+// reduced to (lp, mean_lp) per position.  tokens [Q][ld] device int64; lens / image_of already on the device.
+static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B, const long long* tokens, int ld, int Q, int maxlen,
+                      float* out, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    const int d = c.dec_hidden, ffn = c.dec_ffn, V = c.vocab;
+    RCK(generate_encode(e, frames, F, B, s));
+    const int Lp = round_up(maxlen, 16), M = Q * Lp;
+    SpanGuard phase(e, s, TAG_DECODE, 0);
+    HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->words_f, e->positions_f, e->emb_lng, e->emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
+                                e->f32, d, V, c.max_pos, s));
+    for (int l = 0; l < c.dec_layers; ++l) {
+        const DecLayerW& L = e->dec[l];
+        RCK(gemm(e, s, e->sc_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
+        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->f32, s));
+        RCK(gemm(e, s, e->sc_ctx, d, L.wo, L.bo, e->sc_hf, d, e->sc_y, d, true, M, d, d, 0, TAG_GEMM_OTHER));
+        HIPCK(launch_layernorm(e->sc_y, d, L.lnag, L.lnab, 1e-12f, nullptr, e->sc_ht, d, e->f32, e->sc_hf, d, M, d, 0, 0, 0, s));
+        RCK(gemm(e, s, e->sc_ht, d, L.w1, L.b1, nullptr, 0, e->sc_u, ffn, e->f32, M, ffn, d, 2, TAG_GEMM_OTHER));
+        RCK(gemm(e, s, e->sc_u, ffn, L.w2, L.b2, e->sc_hf, d, e->sc_y, d, true, M, d, ffn, 0, TAG_GEMM_OTHER));
+        HIPCK(launch_layernorm(e->sc_y, d, L.lnog, L.lnob, 1e-12f, nullptr, e->sc_ht, d, e->f32, e->sc_hf, d, M, d, 0, 0, 0, s));
+    }
+    HIPCK(launch_score_targets(tokens, ld, Lp, e->sc_lens, V, M, e->sc_tgt, s));
+    int ntiles = 1;
+    if (e->f32) {
+        // parity mode: logits in chunks of the decode workspace's rows, then one statistics row each
+        const int chunk = round_up(c.max_batch * c.max_beams, 64);
+        for (int r0 = 0; r0 < M; r0 += chunk) {
+            const int rows = std::min(chunk, M - r0);
+            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->out_w, e->out_b, nullptr, 0, e->logits, e->ldl, true, rows,
+                     V, d, 0, TAG_GEMM_OTHER));
+            HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
+        }
+    } else {
+        SpanGuard sp(e, s, TAG_GEMM_OTHER, 2.0 * (double)M * (double)V * (double)d);
+        ntiles = score_head_tiles(V);
+        HIPCK(launch_score_head(e->sc_ht, d, e->out_w, e->out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
+    }
+    HIPCK(hipMemsetAsync(e->sc_out, 0, (size_t)Q * ld * sizeof(float2), s));
+    HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
+    HIPCK(launch_score_combine(e->sc_part, ntiles, e->sc_zt, e->sc_tgt, M, Lp, ld, V, e->sc_out, e->sc_bad, s));
+    HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s));
+    HIPCK(hipMemcpyAsync(out, e->sc_out, (size_t)Q * ld * sizeof(float2), hipMemcpyDefault, s));
+    HIPCK(hipMemcpyAsync(info_out, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
+    return 0;
+}
+
 // Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V).
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
@@ -1761,6 +1862,32 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
                                        int32_t* sent_out, int32_t* info_out, void* stream) {
     RCK(check_ready(e));
     const gitmi_config& c = e->cfg;
+    if (sp && sp->kind == GITMI_SEARCH_SCORE) {
+        if (!frames || !logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("score: null argument");
+        if (F < 1 || F > c.max_frames) return fail("score: F=%d outside [1,%d]", F, c.max_frames);
+        if (B < 1 || B > c.max_batch) return fail("score: B=%d outside [1,%d]", B, c.max_batch);
+        if (Q < 1 || Q > c.max_batch * c.max_beams)
+            return fail("score: Q=%d sentences outside [1,%d] (max_batch x max_beams)", Q, c.max_batch * c.max_beams);
+        if (!image_of_host && Q != B) return fail("score: without image_of, Q must equal B");
+        if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("score: ld=%d outside [1,%d] (max_text_len)", ld_prefix, c.max_text_len);
+        int maxlen = 0;
+        e->plen_host.assign(prefix_len_host, prefix_len_host + Q);
+        e->img_of_host.resize(Q);
+        for (int q = 0; q < Q; ++q) {
+            const int p = prefix_len_host[q];
+            if (p < 1 || p > ld_prefix) return fail("score: length %d of sentence %d outside [1,%d]", p, q, ld_prefix);
+            maxlen = std::max(maxlen, p);
+            const int im = image_of_host ? image_of_host[q] : q;
+            if (im < 0 || im >= B) return fail("score: sentence %d names image %d of %d", q, im, B);
+            e->img_of_host[q] = im;
+        }
+        hipStream_t s = (hipStream_t)stream;
+        HIPCK(hipStreamSynchronize(s));
+        RCK(score_alloc(e, (size_t)Q * round_up(maxlen, 16)));
+        HIPCK(hipMemcpy(e->sc_lens, e->plen_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(e->sc_img, e->img_of_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
+        return score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, maxlen, logprob_out, info_out, s);
+    }
     if (!frames || !sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
         return fail("generate_prefixed: null argument");
     if (F < 1 || F > c.max_frames) return fail("generate_prefixed: F=%d outside [1,%d]", F, c.max_frames);
@@ -1950,4 +2077,53 @@ GITMI_EXP_EXPORT int gitmi_debug_head_from(gitmi_engine* dst, gitmi_engine* src,
     HIPCK(launch_chain_input(src->d_y, dst->xo_b, dst->stats_o, R, c.dec_hidden, s));   // d_y: pre-LayerNorm sum of the last layer
     StepCands cands{};
     return decode_head_impl(dst, nullptr, c.max_text_len, 1, R, 1, 0, 1, logits_out, c.vocab, s, &cands);
+}
+
+// ---- op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py) -----------------------
+// attention: qkv [Q * Lp][3 H 64] text rows, img_kv [B * N_img][3 H 64] prefill rows, image_of int32 [Q] -> out [Q * Lp][H 64]
+// (dtype GITMI_DTYPE_F32: the fp32 kernel of the parity mode; the build's 16-bit operand dtype: the MFMA kernel)
+GITMI_EXP_EXPORT int gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H,
+                                            int N_img, int Lp, int dtype, void* stream) {
+    if (!qkv || !img_kv || !image_of || !out) return fail("debug_score_attn: null argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_attn: dtype %d not served by this build", dtype);
+    HIPCK(launch_score_attn(qkv, img_kv, image_of, out, Q, H, H * 64, N_img, Lp, 0.125f, dtype == GITMI_DTYPE_F32,
+                            (hipStream_t)stream));
+    return 0;
+}
+// head + combine: logits z = A [M][K] W [V][K]^T + bias (never stored in the 16-bit form) -> out fp32 [M][2] =
+// (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) for rows with tgt[m] >= 0, 0 elsewhere.  Synchronises the stream.
+GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K,
+                                            int dtype, float* out, void* stream) {
+    if (!A || !W || !bias || !tgt || !out || M < 1 || V < 2 || K < 32 || K % 32) return fail("debug_score_head: bad argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_head: dtype %d not served by this build", dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const bool f32 = dtype == GITMI_DTYPE_F32;
+    const int ntiles = f32 ? 1 : score_head_tiles(V);
+    const int ldl = round_up(V, 8);
+    float4* part = nullptr; float* zt = nullptr; float2* o2 = nullptr; int* bad = nullptr; float* logits = nullptr;
+    int rc = 0;
+    auto body = [&]() -> int {
+        HIPCK(hipMalloc(&part, (size_t)M * ntiles * sizeof(float4)));
+        HIPCK(hipMalloc(&zt, (size_t)M * sizeof(float)));
+        HIPCK(hipMalloc(&o2, (size_t)(M + 1) * sizeof(float2)));
+        HIPCK(hipMalloc(&bad, (size_t)M * sizeof(int)));
+        if (f32) {
+            HIPCK(hipMalloc(&logits, (size_t)M * ldl * sizeof(float)));
+            GemmArgs g{};
+            g.A = A; g.W = W; g.bias = bias; g.C = logits; g.M = M; g.N = V; g.K = K; g.lda = K; g.ldc = ldl;
+            HIPCK(launch_gemm(g, true, true, s));
+            HIPCK(launch_score_rowstats(logits, ldl, V, tgt, 0, M, part, zt, s));
+        } else {
+            HIPCK(launch_score_head(A, K, W, bias, tgt, M, V, K, part, zt, s));
+        }
+        HIPCK(hipMemsetAsync(o2, 0, (size_t)(M + 1) * sizeof(float2), s));
+        // one position per "sentence" (Lp = ld = 1): row m lands in o2[m + 1]
+        HIPCK(launch_score_combine(part, ntiles, zt, tgt, M, 1, 1, V, o2, bad, s));
+        HIPCK(hipMemcpyAsync(out, o2 + 1, (size_t)M * sizeof(float2), hipMemcpyDefault, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    rc = body();
+    hipFree(part); hipFree(zt); hipFree(o2); hipFree(bad); hipFree(logits);
+    return rc;
 }

@@ -1,0 +1,550 @@
+// Caption scoring (GITMI_SEARCH_SCORE): the textual head run once over whole token sequences, as
+// CaptioningModel.forward_one_ce does (decoder.py:916-972), with the vocabulary head reduced to the two numbers per
+// position the reference's losses need -- lp = log_softmax(z)[target] and mean_lp = mean_c log_softmax(z)[c].
+//
+// Rows of the text pass: sentence q, position j -> row q * Lp + j (Lp = the call's longest sentence rounded up to 16).
+//   score_embed_ln_kernel  WordAndPositionalEmbedding + LayerNorm (decoder.py:41-90) of every position of every row
+//   score_attn_mfma_kernel text-row attention of one decoder layer (16-bit modes; score_attn_kernel: the fp32 form of the
+//                          f32 parity mode): the image K/V of the sentence's image (prefill layout, [B * N_img, 3d] packed
+//                          q|k|v rows), then the sentence's own text keys, causal
+//   score_head_kernel      logits tile on the matrix cores; the epilogue keeps (max, sum exp, sum (z - max)) per
+//                          (row, 128-column tile) and z at the row's target column -- the logits never reach HBM
+//   score_rowstats_kernel  the same statistics from materialised fp32 logits (f32 parity mode)
+//   score_combine_kernel   tiles -> (lp, mean_lp) per position, non-finite flags per sentence
+#include "gitmi_common.h"
+#include "launchers.h"
+
+#include <math.h>
+
+namespace gitmi {
+
+// ---- embedding + LayerNorm of every text position --------------------------------------------------------------
+// tokens int64 [Q][ld]; positions j >= ld are padding id 0 (text attention is causal: they change nothing before them)
+template <typename TOut>
+__global__ __launch_bounds__(256) void score_embed_ln_kernel(const long long* __restrict__ tokens, int ld, int Lp,
+                                                             const float* __restrict__ words,
+                                                             const float* __restrict__ positions,
+                                                             const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps,
+                                                             float* __restrict__ h_f, TOut* __restrict__ h_t, int D,
+                                                             int vocab, int max_pos) {
+    __shared__ float s_part[8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.x;
+    const int q = row / Lp, j = row - q * Lp;
+    long long t = j < ld ? tokens[(size_t)q * ld + j] : 0;
+    const int tok = t < 0 ? 0 : (t >= vocab ? vocab - 1 : (int)t);
+    const int pos = j < max_pos ? j : max_pos - 1;
+    const int c = tid * 4;
+    const bool on = c < D;
+    f32x4_t a = {0.f, 0.f, 0.f, 0.f}, g4 = a, b4 = a;
+    if (on) {
+        const f32x4_t w4 = *reinterpret_cast<const f32x4_t*>(words + (size_t)tok * D + c);
+        const f32x4_t p4 = *reinterpret_cast<const f32x4_t*>(positions + (size_t)pos * D + c);
+        g4 = *reinterpret_cast<const f32x4_t*>(gamma + c);
+        b4 = *reinterpret_cast<const f32x4_t*>(beta + c);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a[r] = w4[r] + p4[r];
+    }
+    const float sum = wave_sum(a[0] + a[1] + a[2] + a[3]);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    const float mean = (s_part[0] + s_part[1] + s_part[2] + s_part[3]) / (float)D;
+    float sq = 0.f;
+    if (on) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const float dv = a[r] - mean; sq += dv * dv; }
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) s_part[4 + wave] = sq;
+    __syncthreads();
+    const float rstd = rsqrtf((s_part[4] + s_part[5] + s_part[6] + s_part[7]) / (float)D + eps);
+    if (on) {
+        float o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (a[r] - mean) * rstd * g4[r] + b4[r];
+        *reinterpret_cast<f32x4_t*>(h_f + (size_t)row * D + c) = f32x4_t{o[0], o[1], o[2], o[3]};
+        if constexpr (sizeof(TOut) == 4) {
+            *reinterpret_cast<f32x4_t*>(h_t + (size_t)row * D + c) = f32x4_t{o[0], o[1], o[2], o[3]};
+        } else {
+            uint2 u;
+            u.x = pack2bf(o[0], o[1]);
+            u.y = pack2bf(o[2], o[3]);
+            *reinterpret_cast<uint2*>(h_t + (size_t)row * D + c) = u;
+        }
+    }
+}
+
+hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp, const float* words, const float* positions,
+                                 const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
+                                 int D, int vocab, int max_pos, hipStream_t s) {
+    if (D > 1024 || (D & 3) || Q < 1 || Lp < 1 || max_pos < 1) return hipErrorInvalidValue;
+    const dim3 grid(Q * Lp), block(256);
+    if (t_is_f32)
+        hipLaunchKernelGGL(score_embed_ln_kernel<float>, grid, block, 0, s, tokens, ld, Lp, words, positions, gamma, beta,
+                           eps, h_f, (float*)h_t, D, vocab, max_pos);
+    else
+        hipLaunchKernelGGL(score_embed_ln_kernel<bf16_t>, grid, block, 0, s, tokens, ld, Lp, words, positions, gamma, beta,
+                           eps, h_f, (bf16_t*)h_t, D, vocab, max_pos);
+    return hipGetLastError();
+}
+
+// sums / maxima over the 16 lanes that share lane / 16 (one row of an MFMA 16x16 output fragment)
+__device__ __forceinline__ float xor16_max(float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float xor16_sum(float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ---- text attention ------------------------------------------------------------------------------------------------
+// One wave per (sentence, head, 64-query tile); lane = query position.  Keys and values pass through LDS in chunks of
+// SA_KC rows (fp32), every lane reads the same LDS row (broadcast): scores and P V are 64 fused multiply-adds per key
+// and lane with the query and the output accumulator in registers.  Online softmax in fp32 over sub-chunks of 16 keys.
+constexpr int SA_KC = 64;
+__device__ __forceinline__ float ld_elem(const float* p) { return *p; }
+__device__ __forceinline__ float ld_elem(const bf16_t* p) { return bf2f(*p); }
+__device__ __forceinline__ void ld8(const float* p, float* o) {
+    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p), b = *reinterpret_cast<const f32x4_t*>(p + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { o[i] = a[i]; o[4 + i] = b[i]; }
+}
+__device__ __forceinline__ void ld8(const bf16_t* p, float* o) {
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    unpack2op(u.x, o[0], o[1]);
+    unpack2op(u.y, o[2], o[3]);
+    unpack2op(u.z, o[4], o[5]);
+    unpack2op(u.w, o[6], o[7]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ img_kv,
+                                                        const int* __restrict__ image_of, T* __restrict__ out, int d,
+                                                        int N_img, int Lp, float scale) {
+    __shared__ float sK[SA_KC][64];
+    __shared__ float sV[SA_KC][64];
+    const int lane = threadIdx.x;
+    const int q = blockIdx.x, h = blockIdx.y, j0 = blockIdx.z * 64;
+    const int j = j0 + lane;
+    const int ld3 = 3 * d;
+    const size_t row_base = (size_t)q * Lp;
+    const int jq = j < Lp ? j : Lp - 1;              // lanes past the sentence's rows compute a copy of the last row
+    float qv[64], acc[64];
+    {
+        const T* qp = qkv + (row_base + jq) * ld3 + h * 64;
+#pragma unroll
+        for (int c = 0; c < 64; c += 8) {
+            float t8[8];
+            ld8(qp + c, t8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) qv[c + i] = t8[i] * scale;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 64; ++c) acc[c] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    const int img = image_of[q];
+    const int j_last = min(Lp, j0 + 64) - 1;         // the last text key any lane of the tile may see
+    const int n_keys = N_img + j_last + 1;
+    // staging: 8 lanes per key row (8 elements each), 8 rows per pass
+    const int sr = lane >> 3, sc = (lane & 7) * 8;
+    for (int k0 = 0; k0 < n_keys; k0 += SA_KC) {
+        const int kc = min(SA_KC, n_keys - k0);
+        __syncthreads();
+        for (int r = sr; r < kc; r += 8) {
+            const int key = k0 + r;
+            const T* src = key < N_img ? img_kv + ((size_t)img * N_img + key) * ld3
+                                       : qkv + (row_base + (key - N_img)) * ld3;
+            float t8[8];
+            ld8(src + d + h * 64 + sc, t8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sK[r][sc + i] = t8[i];
+            ld8(src + 2 * d + h * 64 + sc, t8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sV[r][sc + i] = t8[i];
+        }
+        __syncthreads();
+        for (int u0 = 0; u0 < kc; u0 += 16) {
+            float sv[16];
+            float mx = m;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int r = u0 + u;
+                const int key = k0 + r;
+                float sdot = -INFINITY;
+                if (r < kc && (key < N_img || key - N_img <= jq)) {
+                    sdot = 0.f;
+#pragma unroll
+                    for (int c = 0; c < 64; c += 4) {
+                        const f32x4_t k4 = *reinterpret_cast<const f32x4_t*>(&sK[r][c]);
+                        sdot = fmaf(qv[c], k4[0], sdot);
+                        sdot = fmaf(qv[c + 1], k4[1], sdot);
+                        sdot = fmaf(qv[c + 2], k4[2], sdot);
+                        sdot = fmaf(qv[c + 3], k4[3], sdot);
+                    }
+                }
+                sv[u] = sdot;
+                mx = fmaxf(mx, sdot);
+            }
+            if (mx == -INFINITY) continue;           // nothing visible in this sub-chunk yet (cannot happen after key 0)
+            const float corr = __expf(m - mx);
+            l *= corr;
+#pragma unroll
+            for (int c = 0; c < 64; ++c) acc[c] *= corr;
+            m = mx;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const float p = __expf(sv[u] - mx);
+                if (sv[u] == -INFINITY) continue;
+                l += p;
+                const int r = u0 + u;
+#pragma unroll
+                for (int c = 0; c < 64; c += 4) {
+                    const f32x4_t v4 = *reinterpret_cast<const f32x4_t*>(&sV[r][c]);
+                    acc[c] = fmaf(p, v4[0], acc[c]);
+                    acc[c + 1] = fmaf(p, v4[1], acc[c + 1]);
+                    acc[c + 2] = fmaf(p, v4[2], acc[c + 2]);
+                    acc[c + 3] = fmaf(p, v4[3], acc[c + 3]);
+                }
+            }
+        }
+    }
+    if (j >= Lp) return;
+    const float inv = 1.0f / l;
+    T* op = out + (row_base + j) * d + h * 64;
+    if constexpr (sizeof(T) == 4) {
+#pragma unroll
+        for (int c = 0; c < 64; c += 4)
+            *reinterpret_cast<f32x4_t*>(op + c) = f32x4_t{acc[c] * inv, acc[c + 1] * inv, acc[c + 2] * inv, acc[c + 3] * inv};
+    } else {
+#pragma unroll
+        for (int c = 0; c < 64; c += 8) {
+            uint4 u;
+            u.x = pack2bf(acc[c] * inv, acc[c + 1] * inv);
+            u.y = pack2bf(acc[c + 2] * inv, acc[c + 3] * inv);
+            u.z = pack2bf(acc[c + 4] * inv, acc[c + 5] * inv);
+            u.w = pack2bf(acc[c + 6] * inv, acc[c + 7] * inv);
+            *reinterpret_cast<uint4*>(op + c) = u;
+        }
+    }
+}
+
+// 16-bit modes: the same attention on the matrix cores.  Workgroup = 4 waves for (sentence, head, 64-query tile), wave w
+// owns the 16 queries j0 + 16 w ..; keys in blocks of 32 staged through LDS by the whole workgroup: K row-major (the B
+// operand of S = Q K^T), V transposed (the B operand of O = P V).  S and O on mfma_f32_16x16x32 (fp32 accumulation),
+// online softmax in fp32 on the S fragments (lane holds queries 4 (lane / 16) + i, key lane % 16), P rounded to the
+// operand type and passed through a per-wave LDS tile into the A-operand layout.
+constexpr int SM_KB = 32;                 // keys per block
+constexpr int SM_KP = 64 + 8;             // padded LDS row of sK (elements)
+constexpr int SM_VP = SM_KB + 8;          // padded LDS row of sVt / sP
+__global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ img_kv,
+                                                              const int* __restrict__ image_of, bf16_t* __restrict__ out,
+                                                              int d, int N_img, int Lp, float scale) {
+    __shared__ __attribute__((aligned(16))) bf16_t sK[SM_KB][SM_KP];
+    __shared__ __attribute__((aligned(16))) bf16_t sVt[64][SM_VP];
+    __shared__ __attribute__((aligned(16))) bf16_t sP[4][16][SM_VP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x, h = blockIdx.y, j0 = blockIdx.z * 64;
+    const int jw = j0 + wave * 16;                   // first query of this wave
+    const int g = lane >> 4, c = lane & 15;
+    const int ld3 = 3 * d;
+    const size_t row_base = (size_t)q * Lp;
+    const int img = image_of[q];
+    const int j_last = min(Lp, j0 + 64) - 1;
+    const int n_keys = N_img + j_last + 1;
+    // Q fragments (A operand): row = query jw + c (clamped), dims kk * 32 + 8 g ..
+    bf16x8_t qf[2];
+    {
+        const bf16_t* qp = qkv + (row_base + min(jw + c, Lp - 1)) * ld3 + h * 64 + 8 * g;
+        qf[0] = *reinterpret_cast<const bf16x8_t*>(qp);
+        qf[1] = *reinterpret_cast<const bf16x8_t*>(qp + 32);
+    }
+    f32x4_t acc[4];
+#pragma unroll
+    for (int db = 0; db < 4; ++db) acc[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m[4], l[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
+    const int sk = tid >> 3, sc = (tid & 7) * 8;     // staging: key sk of the block, dims sc .. sc + 8
+    for (int k0 = 0; k0 < n_keys; k0 += SM_KB) {
+        __syncthreads();
+        {
+            const int key = k0 + sk;
+            uint4 kv = make_uint4(0, 0, 0, 0), vv = kv;
+            if (key < n_keys) {
+                const bf16_t* src = key < N_img ? img_kv + ((size_t)img * N_img + key) * ld3 : qkv + (row_base + (key - N_img)) * ld3;
+                kv = *reinterpret_cast<const uint4*>(src + d + h * 64 + sc);
+                vv = *reinterpret_cast<const uint4*>(src + 2 * d + h * 64 + sc);
+            }
+            *reinterpret_cast<uint4*>(&sK[sk][sc]) = kv;
+            const bf16_t* v8 = reinterpret_cast<const bf16_t*>(&vv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sVt[sc + e][sk] = v8[e];
+        }
+        __syncthreads();
+        f32x4_t sfr[2];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            sfr[blk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(&sK[blk * 16 + c][kk * 32 + 8 * g]);
+                sfr[blk] = mfma16(qf[kk], b, sfr[blk]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = jw + 4 * g + i;                // query row of this lane's element i
+            float x[2];
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk) {
+                const int key = k0 + blk * 16 + c;
+                const bool ok = key < n_keys && (key < N_img || key - N_img <= j);
+                x[blk] = ok ? sfr[blk][i] * scale : -INFINITY;
+            }
+            const float mx = xor16_max(fmaxf(x[0], x[1]));
+            const float mn = fmaxf(m[i], mx);
+            const float corr = mn == -INFINITY ? 1.f : __expf(m[i] - mn);
+            const float p0 = mn == -INFINITY ? 0.f : __expf(x[0] - mn);
+            const float p1 = mn == -INFINITY ? 0.f : __expf(x[1] - mn);
+            l[i] = l[i] * corr + xor16_sum(p0 + p1);
+            m[i] = mn;
+#pragma unroll
+            for (int db = 0; db < 4; ++db) acc[db][i] *= corr;
+            sP[wave][4 * g + i][c] = f2bf(p0);
+            sP[wave][4 * g + i][16 + c] = f2bf(p1);
+        }
+        __syncthreads();
+        const bf16x8_t pa = *reinterpret_cast<const bf16x8_t*>(&sP[wave][c][8 * g]);
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+            const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(&sVt[db * 16 + c][8 * g]);
+            acc[db] = mfma16(pa, b, acc[db]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = jw + 4 * g + i;
+        if (j >= Lp) continue;
+        const float inv = 1.0f / l[i];
+        bf16_t* op = out + (row_base + j) * d + h * 64 + c;
+#pragma unroll
+        for (int db = 0; db < 4; ++db) op[db * 16] = f2bf(acc[db][i] * inv);
+    }
+}
+
+hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s) {
+    if (d != H * 64 || Q < 1 || Lp < 1 || N_img < 1) return hipErrorInvalidValue;
+    const dim3 grid(Q, H, (Lp + 63) / 64);
+    if (is_f32)
+        hipLaunchKernelGGL(score_attn_kernel<float>, grid, dim3(64), 0, s, (const float*)qkv, (const float*)img_kv, image_of,
+                           (float*)out, d, N_img, Lp, scale);
+    else
+        hipLaunchKernelGGL(score_attn_mfma_kernel, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv,
+                           image_of, (bf16_t*)out, d, N_img, Lp, scale);
+    return hipGetLastError();
+}
+
+// ---- vocabulary head with fused log-softmax statistics (16-bit operands) ------------------------------------------
+// Workgroup: 4 waves, 128 rows x 128 columns; wave w owns rows [32 w, 32 w + 32) of the tile.  Operands are loaded
+// straight from the row-major activations A [M][lda] and weights W [V][K] in MFMA operand order (one 16-byte load per
+// lane and fragment).  Rows >= M and columns >= V are clamped for loading and masked in the epilogue.
+// part[row][tile] = (max z, sum exp(z - max), sum (z - max)) over the tile's valid columns; zt[row] = z at the row's target.
+// (Sums relative to the tile maximum keep mean_lp exact when every logit of a row carries a large common offset.)
+constexpr int SH_ROWS = 128, SH_COLS = 128;
+
+__global__ __launch_bounds__(256) void score_head_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
+                                                         const float* __restrict__ bias, const int* __restrict__ tgt, int M,
+                                                         int V, int K, float4* __restrict__ part, float* __restrict__ zt,
+                                                         int ntiles) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tile = blockIdx.x;
+    const int col0 = tile * SH_COLS;
+    const int row0 = blockIdx.y * SH_ROWS + wave * 32;
+    const int rl = lane & 15, kq = (lane >> 4) * 8;
+    const bf16_t* ap[2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) ap[rb] = A + (size_t)min(row0 + rb * 16 + rl, M - 1) * lda + kq;
+    const bf16_t* wp[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) wp[cb] = W + (size_t)min(col0 + cb * 16 + rl, V - 1) * K + kq;
+    f32x4_t acc[2][8];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) acc[rb][cb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += 32) {
+        bf16x8_t a[2], b[8];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) a[rb] = *reinterpret_cast<const bf16x8_t*>(ap[rb] + k0);
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) b[cb] = *reinterpret_cast<const bf16x8_t*>(wp[cb] + k0);
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb) acc[rb][cb] = mfma16(a[rb], b[cb], acc[rb][cb]);
+    }
+    // epilogue: acc[rb][cb][i] = z of row row0 + rb * 16 + 4 * (lane / 16) + i, column col0 + cb * 16 + lane % 16
+    float bcol[8];
+    bool cval[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+        const int col = col0 + cb * 16 + rl;
+        cval[cb] = col < V;
+        bcol[cb] = cval[cb] ? bias[col] : 0.f;
+    }
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = row0 + rb * 16 + (lane >> 4) * 4 + i;
+            const int t = row < M ? tgt[row] : -1;
+            float z[8];
+            float mx = -INFINITY, sz = 0.f;
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb) {
+                z[cb] = acc[rb][cb][i] + bcol[cb];
+                if (cval[cb]) mx = fmaxf(mx, z[cb]);
+                if (col0 + cb * 16 + rl == t) zt[row] = z[cb];
+            }
+            mx = xor16_max(mx);
+            float se = 0.f;
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb)
+                if (cval[cb]) { se += __expf(z[cb] - mx); sz += z[cb] - mx; }
+            se = xor16_sum(se);
+            sz = xor16_sum(sz);
+            if (rl == 0 && row < M) part[(size_t)row * ntiles + tile] = make_float4(mx, se, sz, 0.f);
+        }
+}
+
+int score_head_tiles(int V) { return (V + SH_COLS - 1) / SH_COLS; }
+
+hipError_t launch_score_head(const void* A, int lda, const void* W, const float* bias, const int* tgt, int M, int V, int K,
+                             float4* part, float* zt, hipStream_t s) {
+    if (M < 1 || V < 1 || K % 32 || lda % 8) return hipErrorInvalidValue;
+    const dim3 grid(score_head_tiles(V), (M + SH_ROWS - 1) / SH_ROWS), block(256);
+    hipLaunchKernelGGL(score_head_kernel, grid, block, 0, s, (const bf16_t*)A, lda, (const bf16_t*)W, bias, tgt, M, V, K,
+                       part, zt, score_head_tiles(V));
+    return hipGetLastError();
+}
+
+// ---- f32 mode: the same statistics from materialised logits rows (one part per row) -------------------------------
+__global__ __launch_bounds__(256) void score_rowstats_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                             const int* __restrict__ tgt, int row_off,
+                                                             float4* __restrict__ part, float* __restrict__ zt) {
+    __shared__ float s_red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.x, row = row_off + r;
+    const float* x = logits + (size_t)r * ldl;
+    float mx = -INFINITY;
+    for (int c = tid; c < V; c += 256) mx = fmaxf(mx, x[c]);
+    mx = wave_max(mx);
+    if (lane == 0) s_red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    __syncthreads();
+    float se = 0.f, sz = 0.f;
+    for (int c = tid; c < V; c += 256) { se += __expf(x[c] - mx); sz += x[c] - mx; }
+    se = wave_sum(se);
+    sz = wave_sum(sz);
+    __shared__ float s_red2[8];
+    if (lane == 0) { s_red2[wave] = se; s_red2[4 + wave] = sz; }
+    __syncthreads();
+    if (tid == 0) {
+        part[row] = make_float4(mx, s_red2[0] + s_red2[1] + s_red2[2] + s_red2[3], s_red2[4] + s_red2[5] + s_red2[6] + s_red2[7], 0.f);
+        const int t = tgt[row];
+        if (t >= 0 && t < V) zt[row] = x[t];
+    }
+}
+
+hipError_t launch_score_rowstats(const float* logits, int ldl, int V, const int* tgt, int row_off, int rows, float4* part,
+                                 float* zt, hipStream_t s) {
+    if (rows < 1) return hipSuccess;
+    hipLaunchKernelGGL(score_rowstats_kernel, dim3(rows), dim3(256), 0, s, logits, ldl, V, tgt, row_off, part, zt);
+    return hipGetLastError();
+}
+
+// ---- targets of every head row: row (q, j) predicts tokens[q][j + 1] when j + 1 < len_q, else -1 (no target) -------
+__global__ void score_targets_kernel(const long long* __restrict__ tokens, int ld, int Lp, const int* __restrict__ lens,
+                                     int V, int M, int* __restrict__ tgt) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= M) return;
+    const int q = row / Lp, j = row - q * Lp;
+    int t = -1;
+    if (j + 1 < lens[q]) {
+        const long long v = tokens[(size_t)q * ld + j + 1];
+        t = v < 0 ? 0 : (v >= V ? V - 1 : (int)v);
+    }
+    tgt[row] = t;
+}
+
+hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const int* lens, int V, int M, int* tgt,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(score_targets_kernel, dim3((M + 255) / 256), dim3(256), 0, s, tokens, ld, Lp, lens, V, M, tgt);
+    return hipGetLastError();
+}
+
+// ---- combine: per head row with a target, LSE over the tiles -> out[q][j + 1] = (lp, mean_lp); bad[q] = 1 when either
+// value is not finite.  One wave per row.  Tile t covers min(tile_w, V - t tile_w) columns; with M = max over the tiles,
+// S = sum_t se_t exp(m_t - M), D = sum_t (sz_t + n_t (m_t - M)) = sum_c (z_c - M):  LSE = M + log S, mean_lp = D / V - log S.
+__global__ __launch_bounds__(64) void score_combine_kernel(const float4* __restrict__ part, int ntiles, int tile_w,
+                                                           const float* __restrict__ zt, const int* __restrict__ tgt,
+                                                           int Lp, int ld, int V, float2* __restrict__ out,
+                                                           int* __restrict__ bad) {
+    const int lane = threadIdx.x;
+    const int row = blockIdx.x;
+    if (tgt[row] < 0) return;
+    const float4* p = part + (size_t)row * ntiles;
+    float mx = -INFINITY;
+    for (int t = lane; t < ntiles; t += 64) mx = fmaxf(mx, p[t].x);
+    mx = wave_max(mx);
+    float se = 0.f, sd = 0.f;
+    for (int t = lane; t < ntiles; t += 64) {
+        const float4 v = p[t];
+        const float n = (float)min(tile_w, V - t * tile_w);
+        se += v.y * __expf(v.x - mx);
+        sd += v.z + n * (v.x - mx);
+    }
+    se = wave_sum(se);
+    sd = wave_sum(sd);
+    if (lane == 0) {
+        const float ls = logf(se);
+        const float lp = (zt[row] - mx) - ls;
+        const float mean = sd / (float)V - ls;
+        const int q = row / Lp, j = row - q * Lp;
+        out[(size_t)q * ld + j + 1] = make_float2(lp, mean);
+        if (!isfinite(lp) || !isfinite(mean)) bad[q] = 1;
+    }
+}
+
+hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt, const int* tgt, int M, int Lp, int ld, int V,
+                                float2* out, int* bad, hipStream_t s) {
+    const int tile_w = ntiles == 1 ? V : SH_COLS;     // one statistics row per logits row (f32 mode) or the head's tiles
+    hipLaunchKernelGGL(score_combine_kernel, dim3(M), dim3(64), 0, s, part, ntiles, tile_w, zt, tgt, Lp, ld, V, out, bad);
+    return hipGetLastError();
+}
+
+// info = {ld, 0, 0, sentences with a non-finite value}
+__global__ void score_info_kernel(const int* __restrict__ bad, int Q, int ld, int* __restrict__ info) {
+    __shared__ int s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    int n = 0;
+    for (int q = threadIdx.x; q < Q; q += blockDim.x) n += bad[q] ? 1 : 0;
+    atomicAdd(&s_n, n);
+    __syncthreads();
+    if (threadIdx.x == 0) { info[0] = ld; info[1] = 0; info[2] = 0; info[3] = s_n; }
+}
+
+hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s) {
+    hipLaunchKernelGGL(score_info_kernel, dim3(1), dim3(256), 0, s, bad, Q, ld, info);
+    return hipGetLastError();
+}
+
+}  // namespace gitmi

@@ -199,6 +199,25 @@ hipError_t launch_fill_start(long long* start, int ld, const long long* prefix, 
                              hipStream_t s);
 hipError_t launch_load_ids(const long long* tokens, int R, int t, int* ids, int* kv_src, int ld, hipStream_t s);
 
+// caption scoring (kernels_score.hip): rows of the text pass are (sentence q, position j) -> q * Lp + j
+hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp, const float* words, const float* positions,
+                                 const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
+                                 int D, int vocab, int max_pos, hipStream_t s);
+// qkv [Q * Lp][3d] text rows, img_kv [B * N_img][3d] prefill rows of the same layer, image_of [Q] -> out [Q * Lp][d]
+hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s);
+int score_head_tiles(int V);      // 128-column tiles of the fused head
+// part [M][score_head_tiles(V)] = (max, sum exp, sum z), zt [M] = z at tgt[row] (tgt < 0: none); 16-bit A [M][lda], W [V][K]
+hipError_t launch_score_head(const void* A, int lda, const void* W, const float* bias, const int* tgt, int M, int V, int K,
+                             float4* part, float* zt, hipStream_t s);
+hipError_t launch_score_rowstats(const float* logits, int ldl, int V, const int* tgt, int row_off, int rows, float4* part,
+                                 float* zt, hipStream_t s);
+hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const int* lens, int V, int M, int* tgt,
+                                hipStream_t s);
+hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt, const int* tgt, int M, int Lp, int ld, int V,
+                                float2* out, int* bad, hipStream_t s);
+hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s);
+
 // GPU image transform (Pillow-exact bicubic resize + centre crop + CLIP normalisation)
 hipError_t launch_preprocess(const unsigned char* rgb, int H, int W, int crop, unsigned char* tmp, float* out, hipStream_t s);
 hipError_t launch_preprocess_batch(const unsigned char* rgb, const long long* desc, int n, int crop, unsigned char* tmp, float* out,

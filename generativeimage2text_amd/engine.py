@@ -20,6 +20,7 @@ LIB_PATH_EXP = os.path.join(_HERE, "libgitmi_exp.so")         # measurement buil
 PREC_BF16, PREC_F32 = 0, 1
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 SEARCH_AUTOREGRESSIVE, SEARCH_GENERATOR, SEARCH_TRIE = 0, 1, 2
+SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given sentences (Engine.score)
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
 
 EXPORTED_SYMBOLS = [
@@ -36,6 +37,7 @@ EXPORTED_SYMBOLS = [
 # libgitmi_exp.so only (include/gitmi_experiment.h): schedules that measured slower than the default, debug hooks
 EXPERIMENT_SYMBOLS = [
     "gitmi_debug_import_stage", "gitmi_debug_head_from", "gitmi_debug_set_gemm_impl", "gitmi_debug_set_dgemm",
+    "gitmi_debug_score_attn", "gitmi_debug_score_head",
 ]
 
 
@@ -141,6 +143,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_head_from.argtypes = [vp, vp, i32, vp, vp]
         lib.gitmi_debug_set_gemm_impl.argtypes = [i32]
         lib.gitmi_debug_set_dgemm.argtypes = [i32]
+        lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands == "exp" else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -408,6 +412,50 @@ class Engine:
             torch.cuda.current_stream().synchronize()
             self.check_finite(info)
         return tokens, logprobs, sent, info
+
+    def score(self, frames: Sequence[torch.Tensor], tokens, lengths: Optional[Sequence[int]] = None,
+              image_of: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Per-token log-probabilities of given sentences (include/gitmi.h GITMI_SEARCH_SCORE; the textual head of
+        CaptioningModel.forward_one_ce, decoder.py:916-972, run once over whole sequences).
+        tokens: int [Q, L] (each row starts with [CLS]; entries past a row's length are ignored), lengths: [Q] (default L),
+        image_of: [Q] image of the encoded batch every sentence belongs to (default: sentence q <-> image q, Q == B).
+        -> fp32 [Q, L, 2] on the device: (lp, mean_lp) at position j = (log_softmax(z)[tokens[q, j]],
+        mean_c log_softmax(z)[c]) with z the logits at position j - 1; position 0 and positions >= length are 0."""
+        arr, keep, B = self._frames_arg(frames)
+        dev = keep[0].device
+        tok = torch.as_tensor(tokens).detach().to("cpu", torch.int64)
+        if tok.dim() != 2 or tok.shape[1] < 1:
+            raise ValueError(f"tokens must be [Q, L], got {tuple(tok.shape)}")
+        Q, L = int(tok.shape[0]), int(tok.shape[1])
+        lens = [L] * Q if lengths is None else [int(v) for v in lengths]
+        if len(lens) != Q or any(v < 1 or v > L for v in lens):
+            raise ValueError(f"lengths must be {Q} values in [1, {L}]")
+        if Q > self.c.max_batch * self.c.max_beams:
+            raise GitmiError(f"{Q} sentences exceed the capacity max_batch x max_beams = {self.c.max_batch * self.c.max_beams}")
+        if L > self.c.max_text_len:
+            raise GitmiError(f"sentences of {L} tokens exceed max_text_len={self.c.max_text_len}")
+        valid = torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None]
+        ids = tok[valid]
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.c.vocab):
+            raise ValueError(f"token ids outside [0, {self.c.vocab})")
+        tok = torch.where(valid, tok, torch.zeros_like(tok)).to(dev)
+        if image_of is None and Q != B:
+            raise ValueError(f"{Q} sentences over {B} images: image_of is required")
+        if image_of is not None and len(image_of) != Q:
+            raise ValueError(f"image_of has {len(image_of)} entries for {Q} sentences")
+        out = torch.empty(Q, L, 2, device=dev, dtype=torch.float32)
+        info = torch.empty(4, device=dev, dtype=torch.int32)
+        search = GitmiSearch()
+        search.kind = SEARCH_SCORE
+        lens_c = (C.c_int32 * Q)(*lens)
+        img_c = None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
+        self._ck(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, tok.data_ptr(), L, lens_c, img_c, Q,
+                                                  C.byref(search), None, out.data_ptr(), None, info.data_ptr(), _stream()))
+        self._cur_B = B
+        self._cur_F = min(len(keep), self.c.num_frames) if self.c.num_frames > 0 else len(keep)
+        torch.cuda.current_stream().synchronize()
+        self.check_finite(info)
+        return out
 
     # -- search seam ---------------------------------------------------------------------------
     def search_begin(self, search: GitmiSearch, start: torch.Tensor, vocab: int) -> None:
@@ -678,6 +726,32 @@ def op_attn_decode(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, 
     _ck(lib.gitmi_op_attn_decode(qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(),
                                  kv_src.data_ptr(), out.data_ptr(), B, H, N_img, T_max, pos, beams, _torch_dtype_code(qkv),
                                  dbg, _stream()), lib)
+    return out
+
+
+def op_score_attn(qkv: torch.Tensor, img_kv: torch.Tensor, image_of: torch.Tensor, Q: int, H: int, N_img: int,
+                  Lp: int) -> torch.Tensor:
+    """Text attention of the score path (measurement build): qkv [Q * Lp, 3 H 64], img_kv [B * N_img, 3 H 64] (fp32 or the
+    build's 16-bit dtype), image_of int [Q] -> [Q * Lp, H 64] in the input dtype."""
+    lib = load_library()
+    img = image_of.to(device=qkv.device, dtype=torch.int32).contiguous()
+    out = torch.empty(Q * Lp, H * 64, device=qkv.device, dtype=qkv.dtype)
+    _ck(_experiment_only(lib, "gitmi_debug_score_attn")(qkv.data_ptr(), img_kv.data_ptr(), img.data_ptr(), out.data_ptr(), Q, H,
+                                                        N_img, Lp, _torch_dtype_code(qkv), _stream()), lib)
+    return out
+
+
+def op_score_head(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+    """Vocabulary head of the score path with its log-softmax statistics (measurement build): A [M, K], W [V, K] (fp32 or the
+    build's 16-bit dtype), bias fp32 [V], tgt int [M] (< 0: no target) -> fp32 [M, 2] = (lp, mean_lp)."""
+    lib = load_library()
+    M, K = A.shape
+    V = W.shape[0]
+    t = tgt.to(device=A.device, dtype=torch.int32).contiguous()
+    out = torch.zeros(M, 2, device=A.device, dtype=torch.float32)
+    _ck(_experiment_only(lib, "gitmi_debug_score_head")(A.data_ptr(), W.data_ptr(), bias.float().contiguous().data_ptr(),
+                                                        t.data_ptr(), M, V, K, _torch_dtype_code(A), out.data_ptr(),
+                                                        _stream()), lib)
     return out
 
 

@@ -12,6 +12,7 @@ behind `decoder.search(start_predictions, step)` for callers that bring their ow
 from __future__ import annotations
 
 import logging
+import math
 from typing import Dict, Mapping, Optional, Sequence, Union
 
 import torch
@@ -295,6 +296,37 @@ def expected_state_dict_keys(cfg: GitModelConfig, tied_output: bool = False) -> 
     return keys
 
 
+def caption_loss(lp, mean_lp, tokens, need_predict, loss_type: Optional[str] = "smooth", eps: float = 0.1,
+                 vocab: int = 30522, padding_idx: int = 0) -> float:
+    """The reference's caption loss (CaptioningModel.forward_one_ce, decoder.py:938-966) from per-position scores, in fp64.
+
+    lp, mean_lp: [Q, L] as Engine.score returns them (position j = the prediction of tokens[:, j]); tokens, need_predict
+    [Q, L].  The positions counted are j >= 1 with need_predict[:, j] == 1 and tokens[:, j] != padding_idx (the reference
+    sets the target of need_predict == 0 to padding_idx and both losses ignore it).
+      loss_type None    : nn.CrossEntropyLoss (decoder.py:814-815): mean of -lp (nan when nothing is counted, as torch)
+      loss_type 'smooth': SmoothLabelCrossEntropyLoss(eps) (decoder.py:620-671): mean over the positions of
+                          KL(one-hot smoothed to eps / (V - 1) || softmax) =
+                          (1-eps) log(1-eps) + eps log(eps/(V-1)) - [(1-eps) lp + eps/(V-1) (V mean_lp - lp)]
+                          (asserts that something is counted, like the reference)."""
+    lp = torch.as_tensor(lp).detach().double().cpu()
+    mean_lp = torch.as_tensor(mean_lp).detach().double().cpu()
+    tokens = torch.as_tensor(tokens).cpu()
+    need_predict = torch.as_tensor(need_predict).cpu()
+    sel = (need_predict[:, 1:] == 1) & (tokens[:, 1:] != padding_idx)
+    a = lp[:, 1:][sel]
+    if loss_type is None:
+        return float((-a).mean()) if a.numel() else float("nan")
+    if loss_type != "smooth":
+        raise NotImplementedError(loss_type)
+    assert a.numel() > 0, "no position to predict (SmoothLabelCrossEntropyLoss asserts target.numel() > 0)"
+    m = mean_lp[:, 1:][sel]
+    V = float(vocab)
+    off = eps / (V - 1.0)
+    const = (1.0 - eps) * math.log(1.0 - eps) + eps * math.log(off)
+    per = const - ((1.0 - eps) * a + off * (V * m - a))
+    return float(per.mean())
+
+
 class CaptioningModel:
     """Callable like the reference model: ``model(batch) -> {'predictions', 'logprobs'}``.
 
@@ -319,12 +351,24 @@ class CaptioningModel:
                              max_beams=max(1, int(decoder.beam_size)), max_frames=max_frames,
                              max_text_len=max_text_len, device=device)
         self._loaded = False
+        # loss of the training-mode forward (model.py:55 builds the reference with loss_type='smooth'; None = cross entropy)
+        self.loss_type: Optional[str] = "smooth"
+        self.label_smoothing = 0.1
+        # training: model(batch) returns the caption loss {'vl_l_loss'} (decoder.py:938-966) instead of searching
+        self.training = False
 
     # nn.Module look-alikes so that reference call sites (`model.cuda(); model.eval()`) keep working
     def cuda(self, *a, **k):
         return self
 
     def eval(self):
+        return self.train(False)
+
+    def train(self, mode: bool = True):
+        """training = True: model(batch) evaluates the caption loss of batch['caption_tokens'] (decoder.py:938-966).  There is
+        no dropout and no backward pass: the value is the reference's with dropout inactive (CaptioningModel.training set,
+        its submodules in eval mode); the reference in .train() applies dropout 0.1 (decoder.py:198-199) and is stochastic."""
+        self.training = bool(mode)
         return self
 
     def load_state_dict(self, state_dict: Mapping[str, torch.Tensor], strict: bool = False):
@@ -464,6 +508,8 @@ class CaptioningModel:
 
     def forward(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
                 search_param: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+        if self.training:
+            return self._loss_forward(batch)
         saved, self._ctxs = getattr(self, "_ctxs", None), None              # model(batch): context 0, the caller's stream
         try:
             return self.submit(batch, search_param).result()
@@ -471,6 +517,53 @@ class CaptioningModel:
             self._ctxs = saved
 
     __call__ = forward
+
+    def _loss_forward(self, batch) -> Dict[str, torch.Tensor]:
+        """forward_one_ce with self.training (decoder.py:938-966): {'vl_l_loss': loss} over batch['caption_tokens'] /
+        batch['need_predict'] of the images in batch['image'] (a tensor or a list of frames)."""
+        if "image" not in batch:
+            raise NotImplementedError("the text-only branch ('l_*_loss') is not implemented")
+        if "context" in batch or batch.get("bi_valid_mask_caption") is not None:
+            raise NotImplementedError("'context' / 'bi_valid_mask_caption' inputs are not implemented")
+        tokens = torch.as_tensor(batch["caption_tokens"]).cpu()
+        need_predict = torch.as_tensor(batch["need_predict"]).cpu()
+        out = self.score(batch["image"], tokens, need_predict=need_predict)
+        loss = caption_loss(out["logprobs"], out["mean_logprobs"], tokens, need_predict, self.loss_type,
+                            self.label_smoothing, self.cfg.vocab)
+        return {"vl_l_loss": torch.tensor(loss, dtype=torch.float32)}
+
+    def score(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], captions, image_of: Optional[Sequence[int]] = None,
+              need_predict=None) -> Dict[str, torch.Tensor]:
+        """Log-likelihood of given captions (validation loss / perplexity, reranking, retrieval, closed-set VQA).
+        captions: int [Q, L] padded with 0 (or a list of id lists), each starting with [CLS]; caption q belongs to image
+        image_of[q] of `images` (default: caption q <-> image q).  need_predict [Q, L] (default: the non-padding positions
+        after [CLS]) selects the positions that count, e.g. 0 on a VQA question prefix.
+        -> {'logprobs' [Q, L] (lp of tokens[:, j], 0 at position 0), 'mean_logprobs' [Q, L] (mean log-prob over the
+            vocabulary at that position), 'sum' [Q], 'mean' [Q] (over the counted positions)}, all fp32 on the CPU."""
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if not isinstance(captions, torch.Tensor):
+            L = max(len(c) for c in captions)
+            tab = torch.zeros(len(captions), L, dtype=torch.int64)
+            for q, c in enumerate(captions):
+                tab[q, :len(c)] = torch.as_tensor(list(c), dtype=torch.int64)
+            captions = tab
+        tokens = captions.detach().cpu().long()
+        is_list = isinstance(images, (list, tuple))
+        frames = list(images) if is_list else [images]
+        self.engine.set_temporal_embedding(is_list)                          # decoder.py:845-857: list branch only
+        out = self.engine.score(frames, tokens, image_of=image_of).cpu()
+        lp, mean_lp = out[..., 0], out[..., 1]
+        if need_predict is None:
+            need_predict = (tokens != 0).long()
+            need_predict[:, 0] = 0
+        need_predict = torch.as_tensor(need_predict).cpu()
+        sel = torch.zeros_like(tokens, dtype=torch.bool)
+        sel[:, 1:] = (need_predict[:, 1:] == 1) & (tokens[:, 1:] != 0)
+        total = torch.where(sel, lp, torch.zeros_like(lp)).sum(1)
+        n = sel.sum(1)
+        return {"logprobs": lp, "mean_logprobs": mean_lp, "sum": total,
+                "mean": total / n.clamp(min=1).to(total.dtype)}
 
     def submit_answers(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
                        image_of: Optional[Sequence[int]] = None) -> "Pending":

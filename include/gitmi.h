@@ -44,6 +44,8 @@ extern "C" {
 #define GITMI_SEARCH_AUTOREGRESSIVE 0  /* AutoRegressiveBeamSearch   decoder.py:208-440  */
 #define GITMI_SEARCH_GENERATOR      1  /* GeneratorWithBeamSearch    decoder.py:1056-1290 */
 #define GITMI_SEARCH_TRIE           2  /* TrieAutoRegressiveBeamSearch (beam 1, token trie: gitmi_set_trie)  trie_decoder.py:27-218 */
+#define GITMI_SEARCH_SCORE          3  /* not a search: score given sentences (CaptioningModel.forward_one_ce, decoder.py:916-972);
+                                        * gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -238,6 +240,19 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  *   image_of_host   : int32 [Q] HOST, image index of every sentence, or NULL (Q == B, sentence q <-> image q)
  *   tokens_out      : int64 [Q, max_steps], logprob_out fp32 [Q] as in gitmi_generate
  *   sent_out        : int32 [Q, 2] = (length of the sequence returned for this sentence, its early-return flag) or NULL */
+/* ---- caption scoring: search->kind == GITMI_SEARCH_SCORE turns gitmi_generate_prefixed into the mirror of the reference's
+ * `forward` choosing forward_one_ce over infer (decoder.py:916-972): the textual head runs once over whole sentences and
+ * the vocabulary head returns, for every position j >= 1 of sentence q, with z the fp32 logits at position j - 1 over
+ * [image | tokens[q, 0..j)] (joint mask of decoder.py:111-149, 602-610):
+ *     lp[q, j] = log_softmax(z)[tokens[q, j]],   mean_lp[q, j] = mean_c log_softmax(z)[c] = sum(z) / V - LSE(z)
+ * (position 0 and positions >= len_q: 0).  The reference's CE and label-smoothed losses reduce exactly from these two.
+ *   prefixes        : int64 [Q, ld] DEVICE, the sentences to score (each starts with [CLS]); ld <= max_text_len
+ *   prefix_len_host : their lengths (>= 1); image_of_host as above; Q <= max_batch x max_beams (candidates per image)
+ *   logprob_out     : fp32 [Q, ld, 2] = (lp, mean_lp), device or page-locked host buffer
+ *   tokens_out, sent_out: ignored (may be NULL); info_out = { ld, 0, 0, sentences with a non-finite value }
+ *   the other gitmi_search fields are ignored.  gitmi_generate and gitmi_search_begin refuse this kind.
+ * Like a generate call it replaces the engine's encoded images and prefill; its workspaces are allocated by the first
+ * score call (engines that never score keep their footprint). */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

@@ -34,6 +34,18 @@ int  gitmi_debug_set_gemm_impl(int impl);
 /* timing bits of the decode-chain GEMMs (kernels_dgemm.hip; tools/dgemm_bench.py) for gitmi_op_dgemm / gitmi_op_dgemm_res */
 int  gitmi_debug_set_dgemm(int dbg);
 
+/* op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py).  dtype: GITMI_DTYPE_F32 (the
+ * kernels of the f32 parity mode) or the build's 16-bit operand dtype (gitmi_operand_dtype).
+ *   score_attn: text-row attention of one layer -- qkv [Q * Lp][3 H 64] packed q|k|v text rows (sentence q, position j at
+ *               row q * Lp + j), img_kv [B * N_img][3 H 64] prefill rows, image_of int32 [Q] -> out [Q * Lp][H 64]; every
+ *               text row attends to all N_img image keys of its image and causally to its sentence's text keys, scale 1/8.
+ *   score_head: out fp32 [M][2] = (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) of z = A [M][K] W [V][K]^T + bias for
+ *               rows with tgt[m] >= 0 (0 elsewhere).  Synchronises the stream. */
+int  gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int N_img, int Lp,
+                            int dtype, void* stream);
+int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K, int dtype,
+                            float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
