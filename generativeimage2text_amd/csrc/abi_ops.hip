@@ -188,6 +188,42 @@ extern "C" int gitmi_op_kv_repack(const void* qkv_rows, void* kf, void* vt, int 
     return 0;
 }
 
+// ---- ragged batches (measurement build; tests/test_gpu_ragged_ops.py): the attention kernels with per-image key counts.
+// ntok: int32 [B] DEVICE, image b's rows (<= N; N stays the row stride of an image's block).  Same layouts as gitmi_op_attention /
+// gitmi_op_attn_decode; impl of the full attention: 0 VALU (f32), 1 by geometry (short single-pass / flash), 2 flash forced.
+GITMI_EXP_EXPORT int gitmi_debug_attention_ragged(const void* qkv, void* out, const int* ntok, int B, int N, int H, int dtype, int impl,
+                                                  void* stream) {
+    if (!ntok) return fail("debug_attention_ragged: ntok is required");
+    const size_t esz = dtype == GITMI_DTYPE_F32 ? 4 : 2;
+    const int D = H * 64;
+    AttnFullArgs a{};
+    a.q = qkv;
+    a.k = (const char*)qkv + (size_t)D * esz;
+    a.v = (const char*)qkv + (size_t)2 * D * esz;
+    a.out = out;
+    a.ldq = a.ldk = a.ldv = 3 * D;
+    a.ldo = D;
+    a.N = N; a.H = H; a.scale = 0.125f; a.ntok = ntok;
+    HIPCK(launch_attn_full(a, B, dtype == GITMI_DTYPE_F32, impl, (hipStream_t)stream));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                                    const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max,
+                                                    int pos, int beams, int dtype, void* stream) {
+    if (!ntok) return fail("debug_attn_decode_ragged: ntok is required");
+    AttnDecodeArgs a{};
+    a.qkv = qkv; a.img_k = img_k; a.img_v = img_v; a.txt_k = txt_k; a.txt_v = txt_v; a.out = out;
+    a.kv_src = kv_src; a.ld_src = T_max; a.d = H * 64; a.N_img = N_img; a.T_max = T_max; a.pos = pos; a.beams = beams;
+    a.scale = 0.125f; a.ntok = ntok;
+    if (dtype == GITMI_DTYPE_F32) {
+        HIPCK(launch_attn_decode(a, B, H, true, (hipStream_t)stream));
+        return 0;
+    }
+    a.N_pad = round_up(N_img, 32);
+    HIPCK(launch_attn_decode_mfma(a, B, H, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- GPU image transform -------------------------------------------------------
 extern "C" int gitmi_preprocess_image(const uint8_t* rgb_hwc, int H, int W, int crop, uint8_t* tmp, size_t tmp_bytes,
                                       float* out_chw, void* stream) {

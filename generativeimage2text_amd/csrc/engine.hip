@@ -96,6 +96,11 @@ struct gitmi_engine {
     size_t max_pixels = 0;
     float* pos_var = nullptr;          // [Nmax, D] positional table resized to the current grid
     const float* pos_cur = nullptr;    // pos (native grid) or pos_var
+    // ragged batches (gitmi_set_image_shape(e, 0, 0)): every image of a call has its own size, read from the input's
+    // descriptor on the device; image b owns rows [b * Nmax, b * Nmax + ntok[b]) of the encoder / prefill blocks (N = Nmax)
+    bool ragged = false;
+    int4* rg_meta = nullptr;           // [max_batch] {h, w, ntok, rejected} of the staged call
+    int* rg_ntok = nullptr;            // [max_batch] token rows of every image (class token included)
 
     // packed weights
     void* conv_w = nullptr;
@@ -671,6 +676,8 @@ static int alloc_workspaces(gitmi_engine* e) {
     e->frame_stage.resize(c.max_frames);
     for (int f = 0; f < c.max_frames; ++f)
         RCK(dev_alloc_t(e, &e->frame_stage[f], (size_t)c.max_batch * 3 * e->max_pixels));
+    RCK(dev_alloc_t(e, &e->rg_meta, (size_t)c.max_batch));
+    RCK(dev_alloc_t(e, &e->rg_ntok, (size_t)c.max_batch));
     return 0;
 }
 
@@ -970,13 +977,23 @@ extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream
     if (!e) return fail("null engine");
     if (!e->finalized) return fail("weights not finalized");
     const gitmi_config& c = e->cfg;
+    if (H == 0 && W == 0) {         // ragged batches: the shapes travel with the input (include/gitmi.h)
+        if (!e->ragged) {
+            e->ragged = true;
+            e->H = e->W = e->gh = e->gw = 0;
+            e->N = e->Nmax;
+            e->have_feats = e->have_prefill = false;
+        }
+        return 0;
+    }
     if (H < c.patch || W < c.patch) return fail("image %dx%d is smaller than one %d-pixel patch", H, W, c.patch);
     const int gh = H / c.patch, gw = W / c.patch;
     if ((size_t)H * W > e->max_pixels)
         return fail("image %dx%d exceeds the max_image_pixels capacity (%zu)", H, W, e->max_pixels);
     if (gh * gw + 1 > e->Nmax)
         return fail("a %dx%d token grid exceeds the max_image_tokens capacity (%d)", gh, gw, e->Nmax);
-    if (H == e->H && W == e->W) return 0;
+    if (H == e->H && W == e->W && !e->ragged) return 0;
+    e->ragged = false;
     HIPCK(hipSetDevice(e->device));
     if (gh == e->g_nat && gw == e->g_nat) {
         e->pos_cur = e->pos;
@@ -1001,7 +1018,11 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
     // frame, decoder.py:847; per-image results are identical, the GEMMs just see M = F*B*197 rows)
     const int BI = F_eff * B;                // images in the pass
     const int M = BI * N;
-    const int g2 = e->gh * e->gw;
+    const int g2 = N - 1;                    // patch rows per image (ragged: the capacity grid, zeros past each image's own)
+    const size_t slot = (size_t)3 * e->max_pixels;
+    if (e->ragged)      // F == 1; the images were staged by ragged_stage (the `frames` pointer is not read)
+        HIPCK(launch_im2col_ragged(e->frame_stage[0], slot, e->rg_meta, e->patches, e->f32, B, N, c.patch, e->Kp, e->Kp_pad, s));
+    else
     for (int fr = 0; fr < F_eff; ++fr)
         HIPCK(launch_im2col(frames[fr], (char*)e->patches + (size_t)fr * B * g2 * e->Kp_pad * e->esz, e->f32, B,
                             e->H, e->W, c.patch, e->Kp, e->Kp_pad, s));
@@ -1014,6 +1035,10 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
                       on_p8(e->v_ctx, D, e->vit[0].wo, e->v_x, D, M, D, D, true) && on_p8(e->v_u, 4 * D, e->vit[0].w2, e->v_x, D, M, D, 4 * D, true);
     LnRef vln;
     vln.part = e->v_part; vln.nparts = D / 256; vln.D = D; vln.eps = 1e-5f;
+    if (e->ragged)
+        HIPCK(launch_vit_assemble_ragged(e->patch_out, e->cls, e->pos, e->g_nat, e->rg_meta, e->lnpre_g, e->lnpre_b, 1e-5f, e->v_x,
+                                         e->stream_f16, BI, N, c.patch, D, fold ? e->v_part : nullptr, s));
+    else
     HIPCK(launch_vit_assemble_ln(e->patch_out, e->cls, e->pos_cur, e->lnpre_g, e->lnpre_b, 1e-5f, e->v_x, e->stream_f16, BI, N, D,
                                  fold ? e->v_part : nullptr, D / 256, s));
     for (int l = 0; l < c.vit_layers; ++l) {
@@ -1032,6 +1057,7 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
         a.ldq = a.ldk = a.ldv = 3 * D;
         a.ldo = D;
         a.N = N; a.H = c.vit_heads; a.scale = 0.125f;
+        a.ntok = e->ragged ? e->rg_ntok : nullptr;
         HIPCK(launch_attn_full(a, BI, e->f32, e->attn_impl, s));
         if (fold) {     // pre-norm blocks: the residual is the raw stream; every producer leaves the partials of its rows
             RCK(gemm_stream_part(e, s, e->v_ctx, D, L.wo, L.bo, e->v_x, D, nullptr, e->v_x, D, e->v_part, M, D, D, TAG_GEMM_VIT));
@@ -1059,6 +1085,10 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
             HIPCK(launch_layernorm(e->v_x + (size_t)fr * B * N * D, D, e->lnpost_g, e->lnpost_b, 1e-5f, te, e->feats, D, e->f32,
                                    feats_out, D, B * N, D, N, Nimg, fr * N, s));
         }
+    }
+    if (e->ragged) {    // padding rows of the features are zeros (prefill rows past an image stay finite and are never keys)
+        HIPCK(launch_zero_pad_rows(e->feats, e->f32, D, e->rg_ntok, B, N, s));
+        if (feats_out) HIPCK(launch_zero_pad_rows(feats_out, true, D, e->rg_ntok, B, N, s));
     }
 
     e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = Nimg;
@@ -1115,6 +1145,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
             a.ldq = a.ldk = a.ldv = 3 * d;
             a.ldo = d;
             a.N = Nimg; a.H = c.dec_heads; a.scale = 0.125f;
+            a.ntok = e->ragged ? e->rg_ntok : nullptr;
             HIPCK(launch_attn_full(a, B, e->f32, e->attn_impl, s));
             RCK(gemm_stream_part(e, s, e->p_ctx, d, L.wo, L.bo, e->p_y, d, &ln, e->p_y, d, e->p_part[cur ^ 1], M, d, d, TAG_GEMM_OTHER));
             cur ^= 1;
@@ -1150,6 +1181,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
         a.ldq = a.ldk = a.ldv = 3 * d;
         a.ldo = d;
         a.N = Nimg; a.H = c.dec_heads; a.scale = 0.125f;
+        a.ntok = e->ragged ? e->rg_ntok : nullptr;
         HIPCK(launch_attn_full(a, B, e->f32, e->attn_impl, s));
         RCK(gemm_stream(e, s, e->p_ctx, d, L.wo, L.bo, e->p_hf, d, e->p_y, d, M, d, d, TAG_GEMM_OTHER));
         RCK(ln_stream(e, s, e->p_y, d, L.lnag, L.lnab, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
@@ -1240,6 +1272,7 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         // of the streaming kernel only stretch the launch (profiles/r04_f_*)
         const bool stream_ok = !e->shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->attn_nh != 2;
         a.stream_wgs = e->attn_stream >= 0 ? e->attn_stream : stream_ok ? 192 : 0;
+        if (e->ragged) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }      // per-image key counts: the register kernels
         if (e->f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, true, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
@@ -1339,11 +1372,23 @@ static int check_ready(gitmi_engine* e) {
     return 0;
 }
 
+// ragged batches: frames[0] is the caller's descriptor + planes buffer (include/gitmi.h).  One launch validates every entry
+// on the device and copies the valid images into fixed slots of frame_stage[0], outside any captured graph: the encoder
+// then reads the slots and the per-image meta, so one graph (keyed on the capacity) serves every mix of shapes.
+static int ragged_prepare(gitmi_engine* e, const float* const* frames, int F, int B, hipStream_t s) {
+    if (!e->ragged) return 0;
+    if (F != 1 || !frames[0]) return fail("ragged input (gitmi_set_image_shape(e, 0, 0)): F must be 1, frames[0] the descriptor buffer");
+    HIPCK(launch_ragged_stage(frames[0], e->frame_stage[0], (size_t)3 * e->max_pixels, e->rg_meta, e->rg_ntok, B, e->cfg.patch,
+                              e->max_pixels, e->Nmax, s));
+    return 0;
+}
+
 extern "C" int gitmi_encode_frames(gitmi_engine* e, const float* const* frames, int F, int B, float* feats_out,
                                    void* stream) {
     RCK(check_ready(e));
     if (!frames || F < 1 || F > e->cfg.max_frames) return fail("encode_frames: F=%d outside [1,%d]", F, e->cfg.max_frames);
     if (B < 1 || B > e->cfg.max_batch) return fail("encode_frames: B=%d outside [1,%d]", B, e->cfg.max_batch);
+    RCK(ragged_prepare(e, frames, F, B, (hipStream_t)stream));
     return encode_frames_impl(e, frames, F, B, feats_out, (hipStream_t)stream);
 }
 
@@ -1631,6 +1676,9 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool ragg
         }
     }
     HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, tokens_out, logprob_out, info_out, sent_out, s));
+    if (e->ragged)      // sentences over a rejected image: NaN log-probs, counted with the non-finite ones (info[3])
+        HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q,
+                                   sp->num_keep_best > 1 ? sp->num_keep_best : 1, logprob_out, info_out, nullptr, s));
     // algorithmic bytes of one decode step: all decoder weights once +
     // per sentence the K/V of every layer (image part shared by beams, text part per beam)
     const double kv = (double)Q * c.dec_layers * 2.0 * ((double)e->cur_Nimg + k * 0.5 * (minP + T)) * c.dec_hidden * e->esz;
@@ -1667,6 +1715,7 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
     }
     const size_t frame_bytes = (size_t)B * 3 * e->H * e->W * sizeof(float);
     const int F_eff = c.num_frames > 0 ? std::min(F, c.num_frames) : F;
+    if (!e->ragged)     // ragged: ragged_prepare staged the images already
     for (int f = 0; f < F_eff; ++f)
         HIPCK(hipMemcpyAsync(e->frame_stage[f], frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
     gitmi_engine::GraphKey key{};
@@ -1762,6 +1811,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (P < 1 || P > c.max_text_len) return fail("generate: prefix length %d outside [1,%d]", P, c.max_text_len);
     if (sp->max_steps < P || sp->max_steps > c.max_text_len) return fail("generate: max_steps %d outside [P,%d]", sp->max_steps, c.max_text_len);
     hipStream_t s = (hipStream_t)stream;
+    RCK(ragged_prepare(e, frames, F, B, s));
     // start tokens [B, P] on device (shared prefix, or [CLS]) -- filled by a kernel, no host copy
     RCK(fill_uniform_sentences(e, B, (const long long*)prefix, P, s));
     return generate_run(e, frames, F, B, B, P, P, false, sp, tokens_out, logprob_out, info_out, nullptr, s);
@@ -1823,7 +1873,8 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayerW& L = e->dec[l];
         RCK(gemm(e, s, e->sc_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
-        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->f32, s));
+        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->f32, s,
+                                e->ragged ? e->rg_ntok : nullptr));
         RCK(gemm(e, s, e->sc_ctx, d, L.wo, L.bo, e->sc_hf, d, e->sc_y, d, true, M, d, d, 0, TAG_GEMM_OTHER));
         HIPCK(launch_layernorm(e->sc_y, d, L.lnag, L.lnab, 1e-12f, nullptr, e->sc_ht, d, e->f32, e->sc_hf, d, M, d, 0, 0, 0, s));
         RCK(gemm(e, s, e->sc_ht, d, L.w1, L.b1, nullptr, 0, e->sc_u, ffn, e->f32, M, ffn, d, 2, TAG_GEMM_OTHER));
@@ -1849,6 +1900,7 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
     HIPCK(hipMemsetAsync(e->sc_out, 0, (size_t)Q * ld * sizeof(float2), s));
     HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
     HIPCK(launch_score_combine(e->sc_part, ntiles, e->sc_zt, e->sc_tgt, M, Lp, ld, V, e->sc_out, e->sc_bad, s));
+    if (e->ragged) HIPCK(launch_ragged_report(e->rg_meta, e->sc_img, Q, 0, nullptr, nullptr, e->sc_bad, s));
     HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s));
     HIPCK(hipMemcpyAsync(out, e->sc_out, (size_t)Q * ld * sizeof(float2), hipMemcpyDefault, s));
     HIPCK(hipMemcpyAsync(info_out, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
@@ -1886,6 +1938,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         RCK(score_alloc(e, (size_t)Q * round_up(maxlen, 16)));
         HIPCK(hipMemcpy(e->sc_lens, e->plen_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
         HIPCK(hipMemcpy(e->sc_img, e->img_of_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
+        RCK(ragged_prepare(e, frames, F, B, s));
         return score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, maxlen, logprob_out, info_out, s);
     }
     if (!frames || !sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
@@ -1916,6 +1969,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     HIPCK(hipMemcpy2D(e->start_dev, (size_t)c.max_text_len * sizeof(long long), prefixes, (size_t)ld_prefix * sizeof(long long),
                       (size_t)maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
     e->img_identity = ident;
+    RCK(ragged_prepare(e, frames, F, B, s));
     return generate_run(e, frames, F, B, Q, minP, maxP, true, sp, tokens_out, logprob_out, info_out, sent_out, s);
 }
 

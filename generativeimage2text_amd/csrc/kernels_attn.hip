@@ -39,24 +39,32 @@ __global__ __launch_bounds__(256) void attn_full_valu_kernel(AttnFullArgs a) {
     const T* V = reinterpret_cast<const T*>(a.v);
     T* O = reinterpret_cast<T*>(a.out);
     const size_t base_row = (size_t)b * a.N;
+    const int n = a.ntok ? a.ntok[b] : a.N;          // real rows of this image (ragged batches), else all N
+    if (q0 >= n) {                                   // ragged: a tile of padding queries -- zeros
+        for (int i = tid; i < 16 * HD; i += 256) {
+            const int qr = q0 + i / HD;
+            if (qr < a.N) st<T>(O + (base_row + qr) * a.ldo + h * HD + i % HD, 0.f);
+        }
+        return;
+    }
 
     for (int i = tid; i < 16 * HD; i += 256) {
         const int qi = i / HD, d = i % HD;
         const int qr = q0 + qi;
-        qs[qi][d] = qr < a.N ? ld<T>(Q + (base_row + qr) * a.ldq + h * HD + d) * a.scale : 0.f;
+        qs[qi][d] = qr < n ? ld<T>(Q + (base_row + qr) * a.ldq + h * HD + d) * a.scale : 0.f;
     }
 
     float m_run[4], l_run[4], o_acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { m_run[j] = -INFINITY; l_run[j] = 0.f; o_acc[j] = 0.f; }
 
-    for (int kt = 0; kt < a.N; kt += 64) {
+    for (int kt = 0; kt < n; kt += 64) {
         __syncthreads();   // previous tile fully consumed (also orders the qs fill on the first pass)
         for (int i = tid; i < 64 * HD; i += 256) {
             const int key = i / HD, d = i % HD;
             const int kr = kt + key;
             float kv = 0.f, vv = 0.f;
-            if (kr < a.N) {
+            if (kr < n) {
                 kv = ld<T>(K + (base_row + kr) * a.ldk + h * HD + d);
                 vv = ld<T>(V + (base_row + kr) * a.ldv + h * HD + d);
             }
@@ -71,7 +79,7 @@ __global__ __launch_bounds__(256) void attn_full_valu_kernel(AttnFullArgs a) {
             float s = 0.f;
 #pragma unroll 16
             for (int d = 0; d < HD; ++d) s += qs[qi][d] * Ks[lane][d];
-            if (kt + lane >= a.N) s = -INFINITY;
+            if (kt + lane >= n) s = -INFINITY;
             const float m_new = fmaxf(m_run[j], wave_max(s));
             const float p = __expf(s - m_new);             // exp(-inf) = 0 for masked keys
             const float alpha = __expf(m_run[j] - m_new);  // first tile: exp(-inf) = 0
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(256) void attn_full_valu_kernel(AttnFullArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int qr = q0 + wave * 4 + j;
-        if (qr < a.N) st<T>(O + (base_row + qr) * a.ldo + h * HD + lane, o_acc[j] / l_run[j]);
+        if (qr < a.N) st<T>(O + (base_row + qr) * a.ldo + h * HD + lane, qr < n ? o_acc[j] / l_run[j] : 0.f);
     }
 }
 
@@ -127,6 +135,7 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
     const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v);
     bf16_t* O = reinterpret_cast<bf16_t*>(a.out);
     const size_t base_row = (size_t)b * a.N;
+    const int n = a.ntok ? a.ntok[b] : a.N;          // real rows of this image (ragged batches), else all N
 
     // Q^T operands (B of the first product): lane = query l15, dims lg*8 + 32*s .. +8
     bf16x8_t qf[QT][2];
@@ -135,7 +144,7 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         int qr = qbase + (t * 4 + wave) * 16 + l15;
-        qr = qr < a.N ? qr : a.N - 1;
+        qr = qr < n ? qr : n - 1;
         const bf16_t* qp = Q + (base_row + qr) * a.ldq + h * HD + lg * 8;
         qf[t][0] = *reinterpret_cast<const bf16x8_t*>(qp);
         qf[t][1] = *reinterpret_cast<const bf16x8_t*>(qp + 32);
@@ -149,13 +158,15 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
     const int ld_row = tid >> 3;          // 0..31 (+32)
     const int ld_c = (tid & 7) * 8;       // dim offset of the chunk
 
-    for (int kt = 0; kt < a.N; kt += 64) {
+    // ragged: key tiles past the image's rows are skipped (none of them exists); a workgroup of padding queries does no tile
+    const int kend = qbase < n ? n : 0;
+    for (int kt = 0; kt < kend; kt += 64) {
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int key = ld_row + it * 32;
             int kr = kt + key;
-            kr = kr < a.N ? kr : a.N - 1;          // clamped rows are masked below
+            kr = kr < n ? kr : n - 1;              // clamped rows are masked below
             const u32x4_t kc = *reinterpret_cast<const u32x4_t*>(K + (base_row + kr) * a.ldk + h * HD + ld_c);
             const u32x4_t vc = *reinterpret_cast<const u32x4_t*>(V + (base_row + kr) * a.ldv + h * HD + ld_c);
             *reinterpret_cast<u32x4_t*>(Ks + key * FA_LDK + ld_c) = kc;
@@ -169,7 +180,7 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
 
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
-            if (qbase + (t * 4 + wave) * 16 >= a.N) continue;        // wave-uniform: this query tile is empty
+            if (qbase + (t * 4 + wave) * 16 >= n) continue;          // wave-uniform: this query tile is empty (or padding)
             // ---- S^T tile: 4 key sub-tiles of 16 ---------------------------------------
             f32x4_t s_acc[4];
 #pragma unroll
@@ -188,7 +199,7 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int key = kt + st_ * 16 + lg * 4 + r;
-                    const float sv = key < a.N ? s_acc[st_][r] * a.scale : -INFINITY;
+                    const float sv = key < n ? s_acc[st_][r] * a.scale : -INFINITY;
                     s_acc[st_][r] = sv;
                     tmax = fmaxf(tmax, sv);
                 }
@@ -244,7 +255,7 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
     for (int t = 0; t < QT; ++t) {
         const int qr = qbase + (t * 4 + wave) * 16 + l15;
         if (qr < a.N) {
-            const float inv = 1.0f / l_run[t];
+            const float inv = qr < n ? 1.0f / l_run[t] : 0.f;     // ragged padding rows: zeros (o_acc is 0 there)
             bf16_t* op = O + (base_row + qr) * a.ldo + h * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
@@ -268,7 +279,8 @@ __global__ __launch_bounds__(256) void attn_full_mfma_kernel(AttnFullArgs a) {
 // (half the VALU work per score), and only ceil(N/16) key sub-tiles instead of ceil(N/64)*4.
 // Same operand conventions as attn_full_mfma_kernel (swapped products, permuted key order inside a 32-key block).
 // ---------------------------------------------------------------------------------------
-template <int NSUB>
+// RAGGED: a.ntok gives every image's rows (a separate instantiation: the uniform one is the kernel as it was)
+template <int NSUB, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullArgs a) {
     constexpr int NK = NSUB * 16;               // padded keys of the first product
     constexpr int NB = (NSUB + 1) / 2;          // 32-key blocks of the second product
@@ -285,15 +297,22 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
     const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v);
     bf16_t* O = reinterpret_cast<bf16_t*>(a.out);
     const size_t base_row = (size_t)b * a.N;
+    const int n = RAGGED ? a.ntok[b] : a.N;          // real rows of this image (ragged batches), else all N
+    if constexpr (RAGGED) {                          // padding query rows are zeros
+        for (int i = tid; i < (a.N - n) * 8; i += 256) {
+            const int qr = n + (i >> 3);
+            *reinterpret_cast<u32x4_t*>(O + (base_row + qr) * a.ldo + h * HD + (i & 7) * 8) = u32x4_t{0u, 0u, 0u, 0u};
+        }
+    }
 
-    // ---- stage K: 16-byte chunks, rows >= N are copies of the last row (masked below) ------------
+    // ---- stage K: 16-byte chunks, rows >= n are copies of the last row (masked below) ------------
 #pragma unroll
     for (int it = 0; it < (NK * 8 + 255) / 256; ++it) {
         int idx = tid + it * 256;
         const bool ok = idx < NK * 8;
         idx = ok ? idx : NK * 8 - 1;
         const int key = idx >> 3, c = idx & 7;
-        const int kr = key < a.N ? key : a.N - 1;
+        const int kr = key < n ? key : n - 1;
         const u32x4_t kc = *reinterpret_cast<const u32x4_t*>(K + (base_row + kr) * a.ldk + h * HD + c * 8);
         if (ok) *reinterpret_cast<u32x4_t*>(Ks + key * FA_LDK + c * 8) = kc;
     }
@@ -308,9 +327,9 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int key = kg * 4 + e;
-            const int kr = key < a.N ? key : a.N - 1;
+            const int kr = key < n ? key : n - 1;
             vc[e] = *reinterpret_cast<const u32x4_t*>(V + (base_row + kr) * a.ldv + h * HD + c * 8);
-            if (key >= a.N) vc[e] = u32x4_t{0u, 0u, 0u, 0u};
+            if (key >= n) vc[e] = u32x4_t{0u, 0u, 0u, 0u};
         }
         if (ok) {
 #pragma unroll
@@ -327,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
     }
     __syncthreads();
 
-    const int nqt = (a.N + 15) >> 4;
+    const int nqt = (n + 15) >> 4;
     const float c2 = a.scale * 1.4426950408889634f;           // exp(scale * (s - m)) = exp2(c2 * s - c2 * m)
 
     auto process = [&](auto nt_c, int t0) {
@@ -336,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
             int qr = (t0 + 4 * u) * 16 + l15;
-            qr = qr < a.N ? qr : a.N - 1;
+            qr = qr < n ? qr : n - 1;
             const bf16_t* qp = Q + (base_row + qr) * a.ldq + h * HD + lg * 8;
             qf[u][0] = *reinterpret_cast<const bf16x8_t*>(qp);
             qf[u][1] = *reinterpret_cast<const bf16x8_t*>(qp + 32);
@@ -360,9 +379,17 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
         float inv_l[NT];
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
+            if constexpr (RAGGED) {                            // any sub-tile may hold keys >= n
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if ((NSUB - 1) * 16 + lg * 4 + r >= a.N) sacc[u][NSUB - 1][r] = -INFINITY;
+                for (int st_ = 0; st_ < NSUB; ++st_)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (st_ * 16 + lg * 4 + r >= n) sacc[u][st_][r] = -INFINITY;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if ((NSUB - 1) * 16 + lg * 4 + r >= a.N) sacc[u][NSUB - 1][r] = -INFINITY;
+            }
             float m = -INFINITY;
 #pragma unroll
             for (int st_ = 0; st_ < NSUB; ++st_)
@@ -428,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void attn_full_mfma_short_kernel(AttnFullAr
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
             const int qr = (t0 + 4 * u) * 16 + l15;
-            if (qr < a.N) {
+            if (qr < n) {
                 bf16_t* op = O + (base_row + qr) * a.ldo + h * HD;
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
@@ -533,6 +560,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
     const int wave = tid >> 6;
 
     const int bi = a.img_of ? a.img_of[b] : b;                             // sentence -> image (several questions per image)
+    const int n_img = a.ntok ? a.ntok[bi] : a.N_img;                       // its keys (ragged batches); N_img = row stride
     const T* kbase = IMGK + ((size_t)bi * H + h) * a.N_img * HD + sub * 8;  // head-major: contiguous per (image, h)
     const T* vbase = IMGV + ((size_t)bi * H + h) * a.N_img * HD + sub * 8;
     const int nt = a.pos + 1;
@@ -558,7 +586,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
         const int n = grp + 32 * u;
-        if (n < a.N_img && !(a.dbg & 1)) { kr[u].load_nt(kbase + (size_t)n * HD); vr[u].load_nt(vbase + (size_t)n * HD); }   // streamed once per step
+        if (n < n_img && !(a.dbg & 1)) { kr[u].load_nt(kbase + (size_t)n * HD); vr[u].load_nt(vbase + (size_t)n * HD); }   // streamed once per step
         else { kr[u].zero(); vr[u].zero(); }
     }
     Raw8<T> tk[TI], tv[TI];
@@ -607,12 +635,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
     };
 
     // ---- image keys: chunks of 256 keys; two passes inside a chunk (max, then exp/accumulate) -------------
-    for (int base = 0; base < a.N_img; base += 32 * PF) {
+    for (int base = 0; base < n_img; base += 32 * PF) {
         if (base > 0) {
 #pragma unroll
             for (int u = 0; u < PF; ++u) {
                 const int n = base + grp + 32 * u;
-                if (n < a.N_img) { kr[u].load_nt(kbase + (size_t)n * HD); vr[u].load_nt(vbase + (size_t)n * HD); }
+                if (n < n_img) { kr[u].load_nt(kbase + (size_t)n * HD); vr[u].load_nt(vbase + (size_t)n * HD); }
                 else { kr[u].zero(); vr[u].zero(); }
             }
         }
@@ -622,7 +650,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
         for (int j = 0; j < KB; ++j) cm[j] = -INFINITY;
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-            const bool valid = base + grp + 32 * u < a.N_img;
+            const bool valid = base + grp + 32 * u < n_img;
             float kv[8];
             kr[u].get(kv);
 #pragma unroll
@@ -745,7 +773,9 @@ hipError_t launch_attn_full(const AttnFullArgs& a, int B, bool is_f32, int impl,
     if (impl == 1) {
         if (is_f32) return hipErrorInvalidValue;
         const int nsub = (a.N + 15) / 16;
-        if (nsub == 13) hipLaunchKernelGGL(attn_full_mfma_short_kernel<13>, dim3(a.H, B), dim3(256), 0, s, a);
+        if (nsub == 13 && a.ntok) hipLaunchKernelGGL((attn_full_mfma_short_kernel<13, true>), dim3(a.H, B), dim3(256), 0, s, a);
+        else if (nsub == 13) hipLaunchKernelGGL(attn_full_mfma_short_kernel<13>, dim3(a.H, B), dim3(256), 0, s, a);
+        else if (nsub == 17 && a.ntok) hipLaunchKernelGGL((attn_full_mfma_short_kernel<17, true>), dim3(a.H, B), dim3(256), 0, s, a);
         else if (nsub == 17) hipLaunchKernelGGL(attn_full_mfma_short_kernel<17>, dim3(a.H, B), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(attn_full_mfma_kernel, dim3((a.N + 255) / 256, a.H, B), dim3(256), 0, s, a);
     } else if (impl == 2) {                        // the 64-key flash kernel, forced (A/B and tests)

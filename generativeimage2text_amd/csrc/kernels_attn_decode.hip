@@ -83,7 +83,8 @@ constexpr int ACS = 4;          // key steps per chunk and wave
 // LOOP (packed one-wave form only): a wave serves a.pairs_per_wave pairs one after the other, the next pair's first K/V
 // chunk requested while the current pair's merge and output are worked off.  A separate instantiation: the loop-carried
 // K/V registers cost the 512-thread form a few spilled registers, which the single-pair form must not pay.
-template <int KB, int TI = 3, int PW = 1, int NH = 2, bool LOOP = false>
+// RAGGED: a.ntok gives every image's keys (a separate instantiation: the uniform ones are the kernels as they were)
+template <int KB, int TI = 3, int PW = 1, int NH = 2, bool LOOP = false, bool RAGGED = false>
 __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDecodeArgs a) {
     // every fused multiply-add of the softmax bookkeeping is written out (fmaf): with contraction left to the compiler the
     // a*b + c*d updates fuse differently per instantiation, and results must not depend on the packing or the kernel form
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
         if constexpr (NH == 2) return (int)(blockIdx.y * H + blockIdx.x);      // grid = (H, sentences)
         else return ((int)blockIdx.x * reps + r) * PW + hp;
     };
-    struct PairKV { const bf16_t* Kf; const bf16_t* Vt; int nimg_steps; };
+    struct PairKV { const bf16_t* Kf; const bf16_t* Vt; int nimg_steps, n_img; };
     auto kv_of = [&](int pair) {
         const bool on = PW == 1 || pair < a.n_pairs;
         const int h = on ? pair % H : 0, b = on ? pair / H : 0;
@@ -117,7 +118,9 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
         PairKV r;
         r.Kf = reinterpret_cast<const bf16_t*>(a.img_k) + ((size_t)bi * H + h) * Np * HD;
         r.Vt = reinterpret_cast<const bf16_t*>(a.img_v) + ((size_t)bi * H + h) * Np * HD;
-        r.nimg_steps = (!on || (a.dbg & 1)) ? 0 : nsteps;
+        // ragged batches: the image's own keys; its 32-key steps past them are skipped (N_pad stays the row stride)
+        r.n_img = RAGGED ? a.ntok[bi] : a.N_img;
+        r.nimg_steps = (!on || (a.dbg & 1)) ? 0 : RAGGED ? (r.n_img + 31) >> 5 : nsteps;
         return r;
     };
 
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
     const bool head_on = PW == 1 || pair < a.n_pairs;
     const int h = head_on ? pair % H : 0, b = head_on ? pair / H : 0;
     const int row0 = b * k;
-    const int nimg_steps = cur.nimg_steps;
+    const int nimg_steps = cur.nimg_steps, n_img = cur.n_img;
     if constexpr (LOOP) {
         if (rep > 0 && (a.dbg & 32)) load_chunk(cur, half);
     }
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if (s * 32 + t * 16 + lg * 4 + r >= a.N_img || s >= nimg_steps) sc[c][t][r] = -INFINITY;   // padded keys / steps
+                    if (s * 32 + t * 16 + lg * 4 + r >= (RAGGED ? n_img : a.N_img) || s >= nimg_steps) sc[c][t][r] = -INFINITY;   // padded keys / steps
                     cm = fmaxf(cm, sc[c][t][r]);
                 }
         }
@@ -788,6 +791,7 @@ hipError_t launch_kv_repack_frag(const void* qkv, void* kf, void* vt, int B, int
 hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.beams > 8 || a.N_pad % 32 || a.N_pad < a.N_img || a.N_img < 1) return hipErrorInvalidValue;
+    if (a.ntok && a.stream_wgs > 0) return hipErrorInvalidValue;      // ragged batches: the register kernels only
     AttnDecodeArgs p = a;
     p.n_pairs = B * H;
     // Which kernel: the GEOMETRY decides, so a model has ONE attention arithmetic (the two kernels differ in the last bits:
@@ -806,6 +810,14 @@ hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStr
         else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_stream_kernel<2, 3, 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
         else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_stream_kernel<4, 3, 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
         else hipLaunchKernelGGL((attn_decode_stream_kernel<8, 3, 8>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
+        return hipGetLastError();
+    }
+    if (a.ntok) {       // ragged batches: the two-wave kernel whatever the geometry (the VQA capacity grids choose it anyway)
+        const dim3 grid(H, B);
+        if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_mfma_kernel<1, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
+        else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_mfma_kernel<2, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
+        else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_mfma_kernel<4, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
+        else hipLaunchKernelGGL((attn_decode_mfma_kernel<8, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
         return hipGetLastError();
     }
     const bool one_wave = a.waves_per_pair == 1 || (a.waves_per_pair != 2 && a.N_pad <= 8 * 32);

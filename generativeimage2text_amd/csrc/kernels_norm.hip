@@ -312,6 +312,192 @@ __global__ __launch_bounds__(256) void vit_assemble_ln_kernel(const float* __res
     }
 }
 
+// ---- ragged image batches (gitmi_set_image_shape(e, 0, 0)) ----------------------------------------------------------
+// Every image of the call has its own (h, w): image b owns rows [b * Nmax, b * Nmax + ntok_b) of the [B, Nmax] encoder
+// blocks, ntok_b = (h / p) * (w / p) + 1; the rows past ntok_b are padding (zeros into the encoder, never keys).
+// Staging (outside any captured graph: the caller's buffer changes per call): validate the descriptor, copy the planes of
+// the valid images to fixed slots of the engine's stage buffer, meta[b] = {h, w, ntok, bad}.  Grid (blocks, B).
+template <bool VEC>
+__global__ __launch_bounds__(256) void ragged_stage_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t slot,
+                                                           int4* __restrict__ meta, int* __restrict__ ntok, int B, int p,
+                                                           long long max_pixels, int Nmax) {
+    const int b = blockIdx.y;
+    const int4 dsc = reinterpret_cast<const int4*>(src)[b];
+    const long long h = dsc.x, w = dsc.y, off = dsc.z;
+    const long long desc_floats = ((long long)B * 16 + 255) / 256 * 64;     // the descriptor block, padded to 256 bytes
+    const bool ok = h >= p && w >= p && h * w <= max_pixels && (h / p) * (w / p) + 1 <= Nmax && off >= desc_floats && (off & 3) == 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int n = ok ? (int)((h / p) * (w / p)) + 1 : 1;                   // a rejected image keeps its class token only
+        meta[b] = ok ? int4{(int)h, (int)w, n, 0} : int4{0, 0, 1, 1};
+        ntok[b] = n;
+    }
+    if (!ok) return;
+    const size_t total = (size_t)(3 * h * w);
+    const float* s0 = src + off;
+    float* d0 = dst + (size_t)b * slot;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (VEC) {                              // src + off and the slot are 16-byte aligned
+        const size_t n4 = total >> 2;
+        for (size_t j = i; j < n4; j += stride)
+            reinterpret_cast<float4*>(d0)[j] = reinterpret_cast<const float4*>(s0)[j];
+        i += n4 << 2;
+    }
+    for (; i < total; i += stride) d0[i] = s0[i];
+}
+
+// patches[b][t][Kpad] (t < Nmax - 1) = image b's patch t, zeros past its grid (and past K); the element order of im2col_kernel
+template <typename TOut>
+__global__ void im2col_ragged_kernel(const float* __restrict__ stage, size_t slot, const int4* __restrict__ meta,
+                                     TOut* __restrict__ out, int B, int Nmax, int p, int K, int Kpad) {
+    const size_t total = (size_t)B * (Nmax - 1) * Kpad;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(i % Kpad);
+        const size_t prow = i / Kpad;
+        const int t = (int)(prow % (Nmax - 1)), b = (int)(prow / (Nmax - 1));
+        const int4 m = meta[b];
+        const int gh = m.x / p, gw = m.y / p;
+        float val = 0.f;
+        if (k < K && t < gh * gw) {
+            const int kx = k % p, ky = (k / p) % p, c = k / (p * p);
+            const int gx = t % gw, gy = t / gw;
+            val = stage[(size_t)b * slot + ((size_t)c * m.x + gy * p + ky) * m.y + gx * p + kx];
+        }
+        st<TOut>(out + i, val);
+    }
+}
+
+// vit_assemble_ln_kernel for a ragged batch: the positional row of token t of image b is resized to the image's grid on the
+// fly with pos_bicubic_kernel's arithmetic (same expressions, same order: bit-identical to the table a uniform call at that
+// shape builds), the stored table itself on the native grid; padding rows are zeros (and zero LayerNorm partials)
+template <typename TS>
+__global__ __launch_bounds__(256) void vit_assemble_ragged_kernel(const float* __restrict__ patch_out,
+                                                                  const float* __restrict__ cls,
+                                                                  const float* __restrict__ pos, int g,
+                                                                  const int4* __restrict__ meta,
+                                                                  const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps,
+                                                                  TS* __restrict__ X, int B, int Nmax, int p, int D,
+                                                                  float2* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * Nmax) return;
+    const int b = row / Nmax, n = row % Nmax;
+    const int4 m = meta[b];
+    if (n >= m.z) {
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < D) st<TS>(X + (size_t)row * D + c, 0.f);
+        }
+        if (part && lane < 4) part[(size_t)row * 4 + lane] = float2{0.f, 0.f};
+        return;
+    }
+    const int gh = m.x / p, gw = m.y / p;
+    const float* src = n == 0 ? cls : patch_out + ((size_t)b * (Nmax - 1) + (n - 1)) * D;
+    const bool native = n == 0 || (gh == g && gw == g);
+    // bicubic taps of this token (pos_bicubic_kernel)
+    const float sy = (float)g / (float)gh, sx = (float)g / (float)gw;
+    const int oy = native ? 0 : (n - 1) / gw, ox = native ? 0 : (n - 1) % gw;
+    const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)ox + 0.5f) * sx - 0.5f;
+    const float y0f = floorf(fy), x0f = floorf(fx);
+    float wy[4], wx[4];
+    cubic_taps(fy - y0f, wy);
+    cubic_taps(fx - x0f, wx);
+    const int y0 = (int)y0f, x0 = (int)x0f;
+    float v[LN_MAXV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+        const int c = lane + 64 * i;
+        float pv = 0.f;
+        if (c < D) {
+            if (native) {
+                pv = pos[(size_t)n * D + c];
+            } else {
+                float acc = 0.f;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    int yy = y0 - 1 + a;
+                    yy = yy < 0 ? 0 : (yy > g - 1 ? g - 1 : yy);
+                    float rw = 0.f;
+#pragma unroll
+                    for (int bb = 0; bb < 4; ++bb) {
+                        int xx = x0 - 1 + bb;
+                        xx = xx < 0 ? 0 : (xx > g - 1 ? g - 1 : xx);
+                        rw += wx[bb] * pos[((size_t)1 + (size_t)yy * g + xx) * D + c];
+                    }
+                    acc += wy[a] * rw;
+                }
+                pv = acc;
+            }
+        }
+        v[i] = c < D ? src[c] + pv : 0.f;
+        s += v[i];
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+        const int c = lane + 64 * i;
+        const float d = c < D ? v[i] - mean : 0.f;
+        q += d * d;
+    }
+    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < D) st<TS>(X + (size_t)row * D + c, (v[i] - mean) * rstd * gamma[c] + beta[c]);
+    }
+    if (part) {
+        float sx2 = 0.f, sq = 0.f;
+#pragma unroll
+        for (int i = 0; i < LN_MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < D) {
+                const float o = (float)(TS)((v[i] - mean) * rstd * gamma[c] + beta[c]);
+                sx2 += o;
+                sq = fmaf(o, o, sq);
+            }
+        }
+        sx2 = wave_sum(sx2);
+        sq = wave_sum(sq);
+        if (lane < 4) part[(size_t)row * 4 + lane] = lane == 0 ? float2{sx2, sq} : float2{0.f, 0.f};
+    }
+}
+
+// rows t >= ntok[b] of a [B, Nmax] block of `bytes`-byte rows (a multiple of 16) set to zero: one wave per row
+__global__ __launch_bounds__(256) void zero_pad_rows_kernel(char* __restrict__ x, size_t bytes, const int* __restrict__ ntok,
+                                                            int B, int Nmax) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * Nmax || row % Nmax < ntok[row / Nmax]) return;
+    uint4* r = reinterpret_cast<uint4*>(x + (size_t)row * bytes);
+    for (size_t i = lane; i < bytes / 16; i += 64) r[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// sentences over rejected images: log-probs NaN, counted into info[3] (and flagged in bad[q] when given)
+__global__ __launch_bounds__(256) void ragged_report_kernel(const int4* __restrict__ meta, const int* __restrict__ image_of, int Q,
+                                                            int nout_per, float* __restrict__ logprob, int* __restrict__ info,
+                                                            int* __restrict__ bad) {
+    __shared__ int s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    int n = 0;
+    for (int q = threadIdx.x; q < Q; q += blockDim.x) {
+        const int im = image_of ? image_of[q] : q;
+        if (meta[im].w) {
+            ++n;
+            if (logprob)
+                for (int j = 0; j < nout_per; ++j) logprob[(size_t)q * nout_per + j] = __builtin_nanf("");
+            if (bad) bad[q] = 1;
+        }
+    }
+    atomicAdd(&s_n, n);
+    __syncthreads();
+    if (threadIdx.x == 0 && info && s_n) info[3] += s_n;
+}
+
 // x = words[ids[r, pos]] + positions[pos];  LayerNorm(eps);  -> fp32 hidden + compute-dtype hidden.
 // One 256-thread workgroup per row, one float4 per thread (D <= 1024, D % 4 == 0): a single round of loads.
 template <typename TOut>
@@ -476,6 +662,56 @@ hipError_t launch_im2col(const float* img, void* out, bool out_f32, int B, int H
 hipError_t launch_pos_bicubic(const float* pos, float* out, int g, int gh, int gw, int D, hipStream_t s) {
     const size_t total = ((size_t)gh * gw + 1) * D;
     hipLaunchKernelGGL(pos_bicubic_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, pos, out, g, gh, gw, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_stage(const float* src, float* dst, size_t slot, int4* meta, int* ntok, int B, int p, size_t max_pixels,
+                               int Nmax, hipStream_t s) {
+    if (B <= 0 || p <= 0 || Nmax < 2) return hipErrorInvalidValue;
+    // ~1 M floats per image at most: 64 blocks per image keep the copy at a few waves per CU for a batch of 64
+    const dim3 grid(64, B);
+    if (slot % 4 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0)
+        hipLaunchKernelGGL(ragged_stage_kernel<true>, grid, dim3(256), 0, s, src, dst, slot, meta, ntok, B, p, (long long)max_pixels, Nmax);
+    else
+        hipLaunchKernelGGL(ragged_stage_kernel<false>, grid, dim3(256), 0, s, src, dst, slot, meta, ntok, B, p, (long long)max_pixels, Nmax);
+    return hipGetLastError();
+}
+
+hipError_t launch_im2col_ragged(const float* stage, size_t slot, const int4* meta, void* out, bool out_f32, int B, int Nmax,
+                                int p, int K, int Kpad, hipStream_t s) {
+    const size_t total = (size_t)B * (Nmax - 1) * Kpad;
+    if (out_f32)
+        hipLaunchKernelGGL(im2col_ragged_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, s, stage, slot, meta, (float*)out,
+                           B, Nmax, p, K, Kpad);
+    else
+        hipLaunchKernelGGL(im2col_ragged_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, s, stage, slot, meta,
+                           (bf16_t*)out, B, Nmax, p, K, Kpad);
+    return hipGetLastError();
+}
+
+hipError_t launch_vit_assemble_ragged(const float* patch_out, const float* cls, const float* pos, int g, const int4* meta,
+                                      const float* gamma, const float* beta, float eps, void* X, bool x_f16, int B, int Nmax,
+                                      int p, int D, float2* part, hipStream_t s) {
+    if (D > 64 * LN_MAXV || (part && !x_f16)) return hipErrorInvalidValue;
+    if (x_f16)
+        hipLaunchKernelGGL(vit_assemble_ragged_kernel<f16_t>, dim3((B * Nmax + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, g,
+                           meta, gamma, beta, eps, (f16_t*)X, B, Nmax, p, D, part);
+    else
+        hipLaunchKernelGGL(vit_assemble_ragged_kernel<float>, dim3((B * Nmax + 3) / 4), dim3(256), 0, s, patch_out, cls, pos, g,
+                           meta, gamma, beta, eps, (float*)X, B, Nmax, p, D, (float2*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_pad_rows(void* x, bool is_f32, int ld, const int* ntok, int B, int Nmax, hipStream_t s) {
+    const size_t bytes = (size_t)ld * (is_f32 ? 4 : 2);
+    if (bytes % 16 || ((uintptr_t)x & 15)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zero_pad_rows_kernel, dim3((B * Nmax + 3) / 4), dim3(256), 0, s, (char*)x, bytes, ntok, B, Nmax);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_report(const int4* meta, const int* image_of, int Q, int nout_per, float* logprob, int* info, int* bad,
+                                hipStream_t s) {
+    hipLaunchKernelGGL(ragged_report_kernel, dim3(1), dim3(256), 0, s, meta, image_of, Q, nout_per, logprob, info, bad);
     return hipGetLastError();
 }
 

@@ -124,7 +124,7 @@ __device__ __forceinline__ void ld8(const bf16_t* p, float* o) {
 template <typename T>
 __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ img_kv,
                                                         const int* __restrict__ image_of, T* __restrict__ out, int d,
-                                                        int N_img, int Lp, float scale) {
+                                                        int N_img, int Lp, float scale, const int* __restrict__ ntok) {
     __shared__ float sK[SA_KC][64];
     __shared__ float sV[SA_KC][64];
     const int lane = threadIdx.x;
@@ -148,8 +148,9 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
     for (int c = 0; c < 64; ++c) acc[c] = 0.f;
     float m = -INFINITY, l = 0.f;
     const int img = image_of[q];
+    const int n_i = ntok ? ntok[img] : N_img;        // the image's keys (ragged batches); N_img = row stride of its block
     const int j_last = min(Lp, j0 + 64) - 1;         // the last text key any lane of the tile may see
-    const int n_keys = N_img + j_last + 1;
+    const int n_keys = n_i + j_last + 1;
     // staging: 8 lanes per key row (8 elements each), 8 rows per pass
     const int sr = lane >> 3, sc = (lane & 7) * 8;
     for (int k0 = 0; k0 < n_keys; k0 += SA_KC) {
@@ -157,8 +158,8 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
         __syncthreads();
         for (int r = sr; r < kc; r += 8) {
             const int key = k0 + r;
-            const T* src = key < N_img ? img_kv + ((size_t)img * N_img + key) * ld3
-                                       : qkv + (row_base + (key - N_img)) * ld3;
+            const T* src = key < n_i ? img_kv + ((size_t)img * N_img + key) * ld3
+                                     : qkv + (row_base + (key - n_i)) * ld3;
             float t8[8];
             ld8(src + d + h * 64 + sc, t8);
 #pragma unroll
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
                 const int r = u0 + u;
                 const int key = k0 + r;
                 float sdot = -INFINITY;
-                if (r < kc && (key < N_img || key - N_img <= jq)) {
+                if (r < kc && (key < n_i || key - n_i <= jq)) {
                     sdot = 0.f;
 #pragma unroll
                     for (int c = 0; c < 64; c += 4) {
@@ -243,7 +244,8 @@ constexpr int SM_KP = 64 + 8;             // padded LDS row of sK (elements)
 constexpr int SM_VP = SM_KB + 8;          // padded LDS row of sVt / sP
 __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ img_kv,
                                                               const int* __restrict__ image_of, bf16_t* __restrict__ out,
-                                                              int d, int N_img, int Lp, float scale) {
+                                                              int d, int N_img, int Lp, float scale,
+                                                              const int* __restrict__ ntok) {
     __shared__ __attribute__((aligned(16))) bf16_t sK[SM_KB][SM_KP];
     __shared__ __attribute__((aligned(16))) bf16_t sVt[64][SM_VP];
     __shared__ __attribute__((aligned(16))) bf16_t sP[4][16][SM_VP];
@@ -254,8 +256,9 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
     const int ld3 = 3 * d;
     const size_t row_base = (size_t)q * Lp;
     const int img = image_of[q];
+    const int n_i = ntok ? ntok[img] : N_img;        // the image's keys (ragged batches); N_img = row stride of its block
     const int j_last = min(Lp, j0 + 64) - 1;
-    const int n_keys = N_img + j_last + 1;
+    const int n_keys = n_i + j_last + 1;
     // Q fragments (A operand): row = query jw + c (clamped), dims kk * 32 + 8 g ..
     bf16x8_t qf[2];
     {
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
             const int key = k0 + sk;
             uint4 kv = make_uint4(0, 0, 0, 0), vv = kv;
             if (key < n_keys) {
-                const bf16_t* src = key < N_img ? img_kv + ((size_t)img * N_img + key) * ld3 : qkv + (row_base + (key - N_img)) * ld3;
+                const bf16_t* src = key < n_i ? img_kv + ((size_t)img * N_img + key) * ld3 : qkv + (row_base + (key - n_i)) * ld3;
                 kv = *reinterpret_cast<const uint4*>(src + d + h * 64 + sc);
                 vv = *reinterpret_cast<const uint4*>(src + 2 * d + h * 64 + sc);
             }
@@ -303,7 +306,7 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
                 const int key = k0 + blk * 16 + c;
-                const bool ok = key < n_keys && (key < N_img || key - N_img <= j);
+                const bool ok = key < n_keys && (key < n_i || key - n_i <= j);
                 x[blk] = ok ? sfr[blk][i] * scale : -INFINITY;
             }
             const float mx = xor16_max(fmaxf(x[0], x[1]));
@@ -338,15 +341,15 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
 }
 
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
-                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s) {
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok) {
     if (d != H * 64 || Q < 1 || Lp < 1 || N_img < 1) return hipErrorInvalidValue;
     const dim3 grid(Q, H, (Lp + 63) / 64);
     if (is_f32)
         hipLaunchKernelGGL(score_attn_kernel<float>, grid, dim3(64), 0, s, (const float*)qkv, (const float*)img_kv, image_of,
-                           (float*)out, d, N_img, Lp, scale);
+                           (float*)out, d, N_img, Lp, scale, ntok);
     else
         hipLaunchKernelGGL(score_attn_mfma_kernel, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv,
-                           image_of, (bf16_t*)out, d, N_img, Lp, scale);
+                           image_of, (bf16_t*)out, d, N_img, Lp, scale, ntok);
     return hipGetLastError();
 }
 

@@ -77,6 +77,27 @@ hipError_t launch_layernorm(const float* x, int ldx, const float* gamma, const f
 hipError_t launch_im2col(const float* img, void* out, bool out_f32, int B, int H, int W, int p, int K, int Kpad,
                          hipStream_t s);
 hipError_t launch_pos_bicubic(const float* pos, float* out, int g, int gh, int gw, int D, hipStream_t s);
+// ---- ragged image batches (kernels_norm.hip) ----
+// Input buffer: int32 desc[B][4] = {h, w, offset, 0} (the block padded to 256 bytes), then fp32 [3, h, w] planes at
+// src + offset (floats, offset % 4 == 0).  ragged_stage validates every entry, copies the planes of the valid images to
+// dst + b * slot (slot = 3 * max_pixels floats) and writes meta[b] = {h, w, ntok, bad}; a rejected image (bad = 1) becomes a
+// one-token image (its class token only) whose planes are never read.
+hipError_t launch_ragged_stage(const float* src, float* dst, size_t slot, int4* meta, int* ntok, int B, int p, size_t max_pixels,
+                               int Nmax, hipStream_t s);
+// patches[b][t][Kpad] for t < Nmax - 1: image b's patch t (t < gh * gw) or zeros
+hipError_t launch_im2col_ragged(const float* stage, size_t slot, const int4* meta, void* out, bool out_f32, int B, int Nmax,
+                                int p, int K, int Kpad, hipStream_t s);
+// token row (b, t) of the [B, Nmax] block: class token / patch_out[b * (Nmax - 1) + t - 1] + the positional embedding resized
+// to image b's grid (the arithmetic of launch_pos_bicubic; the stored table itself on the native grid), ln_pre; rows
+// t >= ntok[b] are zeros (part: zero partials)
+hipError_t launch_vit_assemble_ragged(const float* patch_out, const float* cls, const float* pos, int g, const int4* meta,
+                                      const float* gamma, const float* beta, float eps, void* X, bool x_f16, int B, int Nmax,
+                                      int p, int D, float2* part, hipStream_t s);
+// zero rows t >= ntok[b] of a [B, Nmax, ld] feature tensor (fp32 or 16-bit elements)
+hipError_t launch_zero_pad_rows(void* x, bool is_f32, int ld, const int* ntok, int B, int Nmax, hipStream_t s);
+// sentences whose image was rejected: log-prob NaN, counted in info[3] (logprob [Q * nout_per] fp32; image_of nullptr: q)
+hipError_t launch_ragged_report(const int4* meta, const int* image_of, int Q, int nout_per, float* logprob, int* info,
+                                int* bad, hipStream_t s);
 hipError_t launch_vit_assemble_ln(const float* patch_out, const float* cls, const float* pos, const float* gamma,
                                   const float* beta, float eps, void* X, bool x_f16, int B, int N, int D, float2* part,
                                   int nparts, hipStream_t s);   // part: row partials for the folded ln_1 of the first block (or nullptr)
@@ -97,8 +118,11 @@ hipError_t launch_fill_i32(int* dst, int value, int n, hipStream_t s);
 struct AttnFullArgs {
     const void* q; const void* k; const void* v; void* out;
     int ldq, ldk, ldv, ldo;
-    int N, H;
+    int N, H;            // N = rows per image (the row stride of an image's block)
     float scale;
+    // ragged batches (gitmi_set_image_shape(e, 0, 0)): image b has ntok[b] <= N real rows; keys past it are never read as
+    // keys, query rows past it are written as zeros.  nullptr: every image has N rows (the uniform path, unchanged).
+    const int* ntok;
 };
 hipError_t launch_attn_full(const AttnFullArgs& a, int B, bool is_f32, int impl, hipStream_t s);
 
@@ -120,6 +144,8 @@ struct AttnDecodeArgs {
                          // many workgroups -- each wave walks its share of the pairs; 0: the register kernels above
     int n_pairs;         // set by the launcher
     int waves_per_pair;  // MFMA kernel: 0 / 1 = one wave walks all key steps of a pair (default); 2 = two waves split them (A/B)
+    const int* ntok;     // ragged batches: image keys of every image ([B images] <= N_img; N_img stays the row stride); nullptr:
+                         // all N_img.  The streaming kernel does not serve ragged batches (stream_wgs must be 0).
 };
 hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, bool is_f32, hipStream_t s);
 size_t attn_decode_lds_bytes(int beams, int N_img, int pos);
@@ -204,8 +230,9 @@ hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp,
                                  const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
                                  int D, int vocab, int max_pos, hipStream_t s);
 // qkv [Q * Lp][3d] text rows, img_kv [B * N_img][3d] prefill rows of the same layer, image_of [Q] -> out [Q * Lp][d]
+// ntok (ragged batches): image keys of every image (<= N_img, the row stride of an image's block); nullptr: N_img each
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
-                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s);
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok = nullptr);
 int score_head_tiles(int V);      // 128-column tiles of the fused head
 // part [M][score_head_tiles(V)] = (max, sum exp, sum z), zt [M] = z at tgt[row] (tgt < 0: none); 16-bit A [M][lda], W [V][K]
 hipError_t launch_score_head(const void* A, int lda, const void* W, const float* bias, const int* tgt, int M, int V, int K,

@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
 # libgitmi_exp.so only (include/gitmi_experiment.h): schedules that measured slower than the default, debug hooks
 EXPERIMENT_SYMBOLS = [
     "gitmi_debug_import_stage", "gitmi_debug_head_from", "gitmi_debug_set_gemm_impl", "gitmi_debug_set_dgemm",
-    "gitmi_debug_score_attn", "gitmi_debug_score_head",
+    "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
 ]
 
 
@@ -145,6 +145,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_set_dgemm.argtypes = [i32]
         lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        lib.gitmi_debug_attention_ragged.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands == "exp" else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -186,6 +188,58 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _torch_dtype_code(t: torch.Tensor) -> int:
     return {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}[t.dtype]
+
+
+RAGGED_DESC_BYTES = 256    # the descriptor block of a ragged input is padded to this size (include/gitmi.h)
+
+
+class RaggedImages:
+    """B images of their own sizes in ONE device buffer: the input of a ragged engine call (gitmi_set_image_shape(e, 0, 0),
+    include/gitmi.h).  buffer: fp32 [n] = int32 descriptor [B][4] = {h, w, offset, 0} padded to 256 bytes, then the [3, h, w]
+    planes of every image at `offset` floats (a multiple of 4: 16-byte aligned).  shapes: [(h, w)] per image.  Built by
+    Engine.pack_images; pass it wherever the engine takes frames (encode, generate, generate_prefixed, score)."""
+
+    def __init__(self, buffer: torch.Tensor, shapes: Sequence[Tuple[int, int]]):
+        self.buffer, self.shapes = buffer, [tuple(int(v) for v in hw) for hw in shapes]
+
+    def __len__(self) -> int:
+        return len(self.shapes)
+
+
+def pack_ragged(images: Sequence[torch.Tensor], patch: int, max_pixels: int, max_tokens: int, max_batch: int,
+                device=None) -> RaggedImages:
+    """Pack fp32 [3, h, w] images of any sizes into the ragged input buffer, validating every shape on the host first
+    (the engine checks again on the device): h, w >= patch, h * w <= max_pixels, (h // patch) * (w // patch) + 1 <=
+    max_tokens, 1 <= B <= max_batch.  device: where the buffer lives (default: the first image's device)."""
+    images = list(images)
+    B = len(images)
+    if not 1 <= B <= max_batch:
+        raise ValueError(f"{B} images: a ragged call takes 1 .. max_batch={max_batch}")
+    shapes = []
+    for b, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or im.dim() != 3 or int(im.shape[0]) != 3:
+            raise ValueError(f"image {b}: expected a [3, h, w] tensor, got {getattr(im, 'shape', type(im))}")
+        h, w = int(im.shape[1]), int(im.shape[2])
+        if h < patch or w < patch:
+            raise ValueError(f"image {b}: {h}x{w} is smaller than one {patch}-pixel patch")
+        if h * w > max_pixels:
+            raise ValueError(f"image {b}: {h}x{w} exceeds the max_image_pixels capacity ({max_pixels})")
+        if (h // patch) * (w // patch) + 1 > max_tokens:
+            raise ValueError(f"image {b}: a {h // patch}x{w // patch} token grid exceeds the max_image_tokens capacity "
+                             f"({max_tokens})")
+        shapes.append((h, w))
+    desc_floats = (B * 16 + RAGGED_DESC_BYTES - 1) // RAGGED_DESC_BYTES * (RAGGED_DESC_BYTES // 4)
+    offsets, off = [], desc_floats
+    for h, w in shapes:
+        offsets.append(off)
+        off += (3 * h * w + 3) // 4 * 4
+    dev = torch.device(device) if device is not None else images[0].device
+    buf = torch.zeros(off, dtype=torch.float32, device=dev)
+    desc = torch.tensor([[h, w, o, 0] for (h, w), o in zip(shapes, offsets)], dtype=torch.int32)
+    buf[:4 * B].view(torch.int32).copy_(desc.reshape(-1))
+    for im, (h, w), o in zip(images, shapes, offsets):
+        buf[o:o + 3 * h * w].copy_(im.detach().to(dtype=torch.float32).reshape(-1))
+    return RaggedImages(buf, shapes)
 
 
 class Engine:
@@ -277,7 +331,37 @@ class Engine:
             self._hw = (int(H), int(W))
             self.n_tok = (H // self.c.patch) * (W // self.c.patch) + 1
 
-    def _frames_arg(self, frames: Sequence[torch.Tensor]) -> Tuple[C.Array, List[torch.Tensor], int]:
+    # -- ragged batches: every image of a call at its own size ------------------------------------------------------
+    @property
+    def max_pixels(self) -> int:
+        return max(int(self.c.image_size) ** 2, int(self.c.max_image_pixels))
+
+    @property
+    def max_tokens(self) -> int:
+        """Nmax: token rows every image owns in a ragged call (the capacity grid, class token included)."""
+        return max((int(self.c.image_size) // int(self.c.patch)) ** 2 + 1, int(self.c.max_image_tokens))
+
+    def pack_images(self, images: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+        """fp32 [3, h, w] images of any sizes -> (buffer, shapes): the ragged input of one engine call on this engine's
+        device (include/gitmi.h), shapes validated against the engine's capacity here.  RaggedImages(buffer, shapes) -- or
+        ragged() -- is what encode / generate / generate_prefixed / score take."""
+        r = self.ragged(images)
+        return r.buffer, r.shapes
+
+    def ragged(self, images: Sequence[torch.Tensor]) -> RaggedImages:
+        return pack_ragged(images, int(self.c.patch), self.max_pixels, self.max_tokens, int(self.c.max_batch),
+                           device=f"cuda:{self.device}")
+
+    def _frames_arg(self, frames) -> Tuple[C.Array, List[torch.Tensor], int]:
+        if isinstance(frames, RaggedImages):
+            if self._hw != (0, 0):
+                self._ck(self.lib.gitmi_set_image_shape(self._h, 0, 0, _stream()))
+                self._hw = (0, 0)
+                self.n_tok = self.max_tokens
+            buf = frames.buffer
+            if buf.device != torch.device(f"cuda:{self.device}") or buf.dtype != torch.float32:
+                raise ValueError("a ragged input buffer must be fp32 on the engine's device (Engine.pack_images)")
+            return (C.c_void_p * 1)(buf.data_ptr()), [buf], len(frames)
         keep = [f.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous() for f in frames]
         B, _, H, W = keep[0].shape
         for f in keep:
@@ -726,6 +810,30 @@ def op_attn_decode(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, 
     _ck(lib.gitmi_op_attn_decode(qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(),
                                  kv_src.data_ptr(), out.data_ptr(), B, H, N_img, T_max, pos, beams, _torch_dtype_code(qkv),
                                  dbg, _stream()), lib)
+    return out
+
+
+def op_attention_ragged(qkv: torch.Tensor, ntok, B: int, N: int, H: int, impl: int) -> torch.Tensor:
+    """op_attention with per-image row counts ntok [B] (measurement build): keys past ntok[b] unused, their queries zeros."""
+    lib = load_library()
+    nt = torch.as_tensor(ntok, dtype=torch.int32).to(qkv.device)
+    out = torch.empty(B * N, H * 64, device=qkv.device, dtype=qkv.dtype)
+    _ck(_experiment_only(lib, "gitmi_debug_attention_ragged")(qkv.data_ptr(), out.data_ptr(), nt.data_ptr(), B, N, H,
+                                                              _torch_dtype_code(qkv), impl, _stream()), lib)
+    return out
+
+
+def op_attn_decode_ragged(qkv, img_k, img_v, txt_k, txt_v, kv_src, ntok, B, H, N_img, T_max, pos, beams):
+    """op_attn_decode with per-image key counts ntok [B] (measurement build)."""
+    lib = load_library()
+    R, d = B * beams, H * 64
+    nt = torch.as_tensor(ntok, dtype=torch.int32).to(qkv.device)
+    out = torch.empty(R, d, device=qkv.device, dtype=qkv.dtype)
+    if qkv.dtype != torch.float32 and img_k.dim() == 4:
+        img_k, img_v = kv_repack(img_k, img_v)
+    _ck(_experiment_only(lib, "gitmi_debug_attn_decode_ragged")(qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(),
+                                                                txt_v.data_ptr(), kv_src.data_ptr(), out.data_ptr(), nt.data_ptr(), B,
+                                                                H, N_img, T_max, pos, beams, _torch_dtype_code(qkv), _stream()), lib)
     return out
 
 

@@ -381,7 +381,7 @@ def run_tsv_inference(image_tsv: str, question_tsv: Optional[str], out_tsv: str,
                       answer_questions, batch_size: int, rank: Optional[int] = None, world: Optional[int] = None,
                       poll_s: float = 0.2, decode=None, decode_threads: int = 0, submit_captions=None, submit_answers=None,
                       in_flight: int = 1, stats: Optional[dict] = None, batch_source=None,
-                      max_questions: Optional[int] = None) -> None:
+                      max_questions: Optional[int] = None, mixed_shapes: bool = False) -> None:
     """Everything of test_git_inference_single_tsv (inference.py:134-225) except the model: shard the rows by
     rank (:165-169), write this rank's rows, and deliver the complete, ordered `out_tsv` on rank 0 --
     through ONE RCCL gather when a process group exists or can be formed, else through the reference's
@@ -397,6 +397,7 @@ def run_tsv_inference(image_tsv: str, question_tsv: Optional[str], out_tsv: str,
       submit_answers (optional): (list of same-shape images, list of question lists) -> handle whose .result() is one answer
       list per image; images are bucketed BY SHAPE (aspect-preserving resize: a COCO-style set has two or three shapes) up to
       `batch_size` images or questions per call instead of one call per image; rows are written in input order.
+      mixed_shapes: one bucket for all shapes (submit_answers then takes images of different sizes in one call).
       batch_source (optional, captioning only): callable(start, end) -> iterator of (keys, device batch) in input order,
       replacing the decode / transform loop of this function (pooled_caption_batches: worker processes + batched GPU transform).
     Row formats are the reference's: `key \t json_dump([{"caption": ...}])` (:212) and the ONE-column
@@ -496,7 +497,7 @@ def run_tsv_inference(image_tsv: str, question_tsv: Optional[str], out_tsv: str,
         if submit_answers is None:
             answers[i] = answer_questions(img, qs)
             continue
-        shape = tuple(img.shape)
+        shape = "mixed" if mixed_shapes else tuple(img.shape)
         b = buckets.get(shape)
         if b is not None and (len(b[0]) + 1 > batch_size or sum(len(q) for q in b[2]) + len(qs) > (max_questions or batch_size)):
             vqa_flush(shape)
@@ -632,7 +633,7 @@ class _Mapped:
 
 
 def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, *, checkpoint=None,
-                                  batch_size=64, precision="f16", contexts=4, stats=None):
+                                  batch_size=64, precision="f16", contexts=4, stats=None, mixed_shapes=False):
     """inference.py:134-225.  image_tsv rows: key \\t base64(jpeg).  question_tsv (optional) rows:
     key \\t json list of {'question', 'question_id'}.  Writes out_tsv rows
     key \\t [{"caption": ...}]   or the one-column   {"answer": ..., "question_id": ...}.
@@ -643,7 +644,10 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
     contexts: requests kept in flight on the device (CaptioningModel.set_pipeline: clones on their own HIP streams, two image
     encoders at a time) while host threads decode the next batches; 1 = the serial loop of the reference.
     Models with test_respect_ratio_max (VQAv2 / TextVQA) batch images of EQUAL resized shape into one engine call
-    (gitmi_generate_prefixed takes ragged questions about several images) instead of one call per image."""
+    (gitmi_generate_prefixed takes ragged questions about several images) instead of one call per image.
+    mixed_shapes: VQA question files are batched ACROSS shapes instead -- up to batch_size images or max_batch questions per
+    call, every image at its own size in one ragged engine call (CaptioningModel.submit_ragged); answers are those of the
+    per-shape calls.  The default path is unchanged."""
     import time
     t_build = time.perf_counter()
     param, from_file = _task_param(model_name, "output")                    # inference.py:135-137
@@ -695,8 +699,6 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
                 prefixes.append(_prefix_ids(tokenizer, q))
                 image_of.append(b)
         counts = [len(qs) for qs in qss]
-        with torch.no_grad():
-            h = model.submit_answers(torch.stack(list(imgs)).cuda(), prefixes, image_of)
 
         def split(preds):
             texts, out, lo = decode_ids(preds), [], 0
@@ -704,6 +706,12 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
                 out.append(texts[lo:lo + n])
                 lo += n
             return out
+        if mixed_shapes:        # images of any sizes in one ragged engine call
+            with torch.no_grad():
+                h = model.submit_ragged([im.cuda() for im in imgs], prefixes=prefixes, image_of=image_of)
+            return _Mapped(h, lambda res: split(res["predictions"]))
+        with torch.no_grad():
+            h = model.submit_answers(torch.stack(list(imgs)).cuda(), prefixes, image_of)
         return _Mapped(h, split)
 
     # JPEG decoding on a few host threads ahead of the GPU (GIT_DECODE_THREADS, default min(16, cores); 0 = serial as in
@@ -733,7 +741,8 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
                           transform=transforms, caption_batch=caption_batch, answer_questions=answer_questions,
                           batch_size=batch_size, submit_captions=submit_captions if pipelined else None,
                           submit_answers=submit_answers if (can_batch_vqa and is_vqa) else None,
-                          in_flight=contexts if pipelined else 1, stats=stats, batch_source=batch_source, max_questions=max_batch)
+                          in_flight=contexts if pipelined else 1, stats=stats, batch_source=batch_source, max_questions=max_batch,
+                          mixed_shapes=bool(mixed_shapes) and is_vqa and can_batch_vqa and hasattr(model, "submit_ragged"))
     if stats is not None:
         if "t_first_batch" in stats and stats.get("images", 0) > batch_size:
             # rate once the workers are up: everything after the first batch became ready

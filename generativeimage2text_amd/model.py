@@ -550,9 +550,15 @@ class CaptioningModel:
             captions = tab
         tokens = captions.detach().cpu().long()
         is_list = isinstance(images, (list, tuple))
-        frames = list(images) if is_list else [images]
-        self.engine.set_temporal_embedding(is_list)                          # decoder.py:845-857: list branch only
-        out = self.engine.score(frames, tokens, image_of=image_of).cpu()
+        if is_list and len(images) and all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in images):
+            # a list of [3, h, w] images of their own sizes: one ragged engine call (a list of [B, 3, H, W] means frames)
+            self._check_ragged()
+            self.engine.set_temporal_embedding(False)
+            out = self.engine.score(self.engine.ragged(images), tokens, image_of=image_of).cpu()
+        else:
+            frames = list(images) if is_list else [images]
+            self.engine.set_temporal_embedding(is_list)                      # decoder.py:845-857: list branch only
+            out = self.engine.score(frames, tokens, image_of=image_of).cpu()
         lp, mean_lp = out[..., 0], out[..., 1]
         if need_predict is None:
             need_predict = (tokens != 0).long()
@@ -564,6 +570,80 @@ class CaptioningModel:
         n = sel.sum(1)
         return {"logprobs": lp, "mean_logprobs": mean_lp, "sum": total,
                 "mean": total / n.clamp(min=1).to(total.dtype)}
+
+    def _check_ragged(self) -> None:
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if self.cfg.num_frames != 0:
+            raise ValueError("images of different sizes in one call: only models without temporal image embeddings "
+                             "(num_image_with_embedding = 0) take a list of [3, h, w] images")
+
+    def submit_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
+                      image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None) -> "Pending":
+        """Images of DIFFERENT sizes in one engine call (the aspect-preserving VQA models: MinMaxResizeForTest gives every
+        image its own shape).  images: list of fp32 [3, h, w]; every image gets exactly what a call with that image alone
+        gets.  prefixes None: captioning, `.result()` is submit({'image': image}).result()'s dict over the B images.
+        prefixes given: question q (token ids starting with [CLS]) about image image_of[q] (default: q <-> image q);
+        `.result()` is {'predictions': [ids of each answer, the prefix removed], 'logprobs': fp32 [Q, 1]}."""
+        self._check_ragged()
+        images = list(images)
+        eng, stream = self._context()
+        self._prepare(eng, False)
+        packed = eng.ragged(images)                                        # host-side shape checks, then one upload
+        search = self._search_struct(search_param)
+        if int((search_param or {}).get("num_return_sequences", 1)) != 1:
+            raise NotImplementedError("num_return_sequences with images of different sizes")
+        kind = self.decoder.kind
+        host = stream is not None
+        if prefixes is None:
+            def launch():
+                return eng.generate(packed, search, sync=False, host_out=host)
+
+            def finish(out):
+                tokens, logprobs, info = out
+                info_h = info.tolist()
+                eng.check_finite(info_h)
+                seq_len, early, _, _ = info_h
+                if kind in ("autoregressive", "trie"):
+                    if early:
+                        return {"predictions": tokens[:, 1:2], "logprobs": logprobs[:, None]}
+                    return {"predictions": tokens[:, :seq_len], "logprobs": logprobs}
+                return {"predictions": tokens, "logprobs": logprobs if logprobs.dim() > 1 else logprobs[:, None]}
+            return Pending(stream, launch, finish, keep=(packed,))
+        Q = len(prefixes)
+        image_of = list(range(Q)) if image_of is None else [int(i) for i in image_of]
+        if Q > eng.c.max_batch:
+            raise ValueError(f"{Q} questions exceed max_batch={eng.c.max_batch}")
+        if len(image_of) != Q or any(i < 0 or i >= len(images) for i in image_of):
+            raise ValueError(f"image_of must name one of the {len(images)} images for each of the {Q} questions")
+
+        def launch():
+            return eng.generate_prefixed(packed, search, prefixes, image_of=image_of, sync=False, host_out=host)
+
+        def finish(out):
+            tokens, logprobs, sent, info = out
+            eng.check_finite(info.tolist())
+            tokens, sent = tokens.cpu(), sent.cpu()
+            res = []
+            for q, p in enumerate(prefixes):
+                P = len(p)
+                L, early = int(sent[q, 0]), int(sent[q, 1])
+                if kind in ("autoregressive", "trie"):
+                    row = (tokens[q, P:P + 1] if early else tokens[q, :L])[P:]
+                else:
+                    row = tokens[q, P:]
+                res.append(row.tolist())
+            return {"predictions": res, "logprobs": logprobs.cpu().reshape(Q, -1)}
+        return Pending(stream, launch, finish, keep=(packed,))
+
+    def generate_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
+                        image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None):
+        """submit_ragged(...).result() on context 0 and the caller's stream."""
+        saved, self._ctxs = getattr(self, "_ctxs", None), None
+        try:
+            return self.submit_ragged(images, prefixes, image_of, search_param).result()
+        finally:
+            self._ctxs = saved
 
     def submit_answers(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
                        image_of: Optional[Sequence[int]] = None) -> "Pending":

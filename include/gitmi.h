@@ -183,6 +183,21 @@ int  gitmi_set_ln_fold(gitmi_engine* e, int on);
  * torch's bicubic (align_corners=False) kernel, class row kept.  H*W and the token count must fit the
  * max_image_pixels / max_image_tokens capacities given at gitmi_create(). */
 int  gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream);
+/* ---- ragged input: gitmi_set_image_shape(e, 0, 0, stream) makes every image of the following calls carry its own size
+ * (the aspect-preserving MinMaxResizeForTest models); any valid H, W returns to uniform input.  In ragged mode the calls
+ * that take frames (gitmi_encode_frames, gitmi_generate, gitmi_generate_prefixed incl. GITMI_SEARCH_SCORE) need F == 1, and
+ * frames[0] points to ONE device buffer:
+ *     int32 desc[B][4] = { h, w, offset, 0 }, the block padded to 256 bytes;
+ *     then the fp32 [3, h, w] plane of image b at (float*)buffer + offset (offset in floats, a multiple of 4: 16-byte aligned).
+ * Image b owns token rows [b * Nmax, b * Nmax + n_b) of the encoder / feature / prefill blocks, n_b = (h/p)(w/p) + 1 and
+ * Nmax = the max_image_tokens capacity; feats_out is [B, Nmax, vit_width] with zeros in the rows past n_b.  The shapes are
+ * read and checked ON THE DEVICE (one captured graph serves every mix of shapes): an entry with h or w below one patch,
+ * h * w above max_image_pixels, a grid above max_image_tokens, an offset inside the descriptor block or not a multiple of 4
+ * is not read; its sentences come back with a NaN log-prob and are counted in info_out[3] (score: counted in info_out[3]),
+ * the other images are unaffected.  The call has no buffer size to check against: the CALLER guarantees that frames[0] is
+ * 16-byte aligned (the descriptor is read as int4) and that offset + 3*h*w floats of every entry lie inside its buffer --
+ * an entry that passes the checks above is copied whole.
+ * Each image gets what a call with that image alone gets (bit for bit in the f32 mode). */
 
 /* ---- image encoder: replaces model.image_encoder(x) + the multi-frame branch of
  * CaptioningModel.forward_one (CLIP/model.py:240-274, decoder.py:845-857).

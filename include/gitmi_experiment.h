@@ -46,6 +46,16 @@ int  gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* imag
 int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K, int dtype,
                             float* out, void* stream);
 
+/* op hooks of the ragged-batch attention (gitmi_set_image_shape(e, 0, 0); tests/test_gpu_ragged_ops.py).  ntok: int32 [B] on the
+ * device, the rows of image b (<= N / N_img, which stay the row stride of an image's block); keys past ntok[b] are never used.
+ *   attention_ragged: gitmi_op_attention's layout and impl; query rows past ntok[b] are written as zeros.
+ *   attn_decode_ragged: gitmi_op_attn_decode's layouts (bf16: the kv_repack operand layouts, N_pad = round_up(N_img, 32));
+ *                       the ragged decode kernel is the two-wave MFMA form (16-bit) / the VALU form (f32). */
+int  gitmi_debug_attention_ragged(const void* qkv, void* out, const int* ntok, int B, int N, int H, int dtype, int impl, void* stream);
+int  gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                    const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max, int pos,
+                                    int beams, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
