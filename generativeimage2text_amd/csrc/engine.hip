@@ -19,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 using namespace gitmi;
@@ -77,6 +78,19 @@ struct DecLayerW {
 
 struct TimedSpan { hipEvent_t a, b; int tag; double flops; };
 enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM_OTHER = 11, TAG_STEP = 20 };
+
+// hipGraph cache key of gitmi_generate / gitmi_generate_prefixed: everything the captured launch sequence depends on
+struct GraphKey {
+    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb; double lp;
+    int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
+    static GraphKey of(int B, int Q, int F, int P, int H, int W, bool prefixed, bool ident, bool temb, const gitmi_search& sp) {
+        return {B, Q, F, P, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, H, W, prefixed ? 1 : 0, ident ? 1 : 0,
+                temb ? 1 : 0, sp.length_penalty, sp.do_sample, sp.top_k, sp.num_keep_best > 1 ? sp.num_keep_best : 1, sp.top_p,
+                sp.temperature, sp.repetition_penalty, sp.seed};
+    }
+    auto fields() const { return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, lp, smp, top_k, nh, top_p, temp, rp, seed); }
+    bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
+};
 
 struct gitmi_engine {
     gitmi_config cfg{};
@@ -142,13 +156,12 @@ struct gitmi_engine {
     int vocab_cols = 128, vocab_nparts = 1;
     // search
     SearchState ss{};
-    int ss_cur = 0, ss_len = 0, ss_minP = 1;
+    int ss_cur = 0, ss_len = 0;
     long long* start_dev = nullptr;     // [max_batch][max_text_len] start tokens of every sentence
     int *plen_dev = nullptr, *img_of_dev = nullptr;
     bool img_identity = true;           // sentence b attends to image b
     // token trie of trie-constrained greedy decoding (gitmi_set_trie; trie_decoder.py) + one cursor per sentence
     int *trie_off = nullptr, *trie_tok = nullptr, *trie_child = nullptr, *trie_cursor = nullptr;
-    int trie_nodes = 0;
     bool trie_search = false;           // the current search is GITMI_SEARCH_TRIE
     gitmi_search sample{};              // sampling parameters of the current search (do_sample, top_k, top_p, temperature, seed)
     int attn_dbg = 0, dgemm_dbg = 0;    // timing experiments (GITMI_ATTN_DBG, GITMI_DGEMM_DBG)
@@ -166,7 +179,6 @@ struct gitmi_engine {
                                         // out -- 1 attention, 2 QKV / FFN1 GEMMs, 4 out-proj / FFN2 GEMMs, 8 vocabulary head (ids are garbage)
     bool use_temb = true;               // add img_temperal_embedding[i] to frame i (the reference does so only for a LIST of frames)
     std::vector<int> plen_host, img_of_host;
-    const float* const* frames_dummy = nullptr;
 
     // state of the current batch
     int cur_B = 0, cur_F = 0, cur_Nimg = 0;
@@ -206,14 +218,6 @@ struct gitmi_engine {
     bool use_graph = true;
 
     // hipGraph cache for gitmi_generate
-    struct GraphKey {
-        int B, Q, F, P, kind, k, pn, T, H, W, ragged, ident, temb; double lp;
-        int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
-        bool operator==(const GraphKey& o) const {
-            return rp == o.rp && nh == o.nh && smp == o.smp && top_k == o.top_k && top_p == o.top_p && temp == o.temp && seed == o.seed && B == o.B && Q == o.Q && F == o.F && P == o.P && kind == o.kind && k == o.k && pn == o.pn && T == o.T &&
-                   H == o.H && W == o.W && ragged == o.ragged && ident == o.ident && temb == o.temb && lp == o.lp;
-        }
-    };
     bool graph_valid = false;
     GraphKey graph_key{};
     hipGraph_t graph = nullptr;
@@ -1325,8 +1329,6 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
     const bool trie = ids != nullptr && e->trie_search;
     if ((sampling || trie) && !logits_out) { logits_out = e->logits; ldl = e->ldl; }     // the filter / the trie need the whole row
     if (chain) {
-        const DecLayerW& L = e->dec[c.dec_layers - 1];
-        (void)L;
         VocabArgs v{};
         v.A = (const unsigned short*)e->xo_b; v.lda = d; v.W = (const unsigned short*)e->out_w_f; v.bias = e->out_b_f; v.colsum = e->cs_out;
         v.stats_in = e->stats_o; v.strips_in = d / 16; v.inv_d = 1.0f / (float)d; v.eps_in = 1e-12f;
@@ -1383,11 +1385,17 @@ static int ragged_prepare(gitmi_engine* e, const float* const* frames, int F, in
     return 0;
 }
 
+// the input checks every entry point that encodes images shares; `who` names it in the error text
+static int check_frames(const gitmi_engine* e, const char* who, const float* const* frames, int F, int B) {
+    if (!frames || F < 1 || F > e->cfg.max_frames) return fail("%s: F=%d outside [1,%d]", who, F, e->cfg.max_frames);
+    if (B < 1 || B > e->cfg.max_batch) return fail("%s: B=%d outside [1,%d]", who, B, e->cfg.max_batch);
+    return 0;
+}
+
 extern "C" int gitmi_encode_frames(gitmi_engine* e, const float* const* frames, int F, int B, float* feats_out,
                                    void* stream) {
     RCK(check_ready(e));
-    if (!frames || F < 1 || F > e->cfg.max_frames) return fail("encode_frames: F=%d outside [1,%d]", F, e->cfg.max_frames);
-    if (B < 1 || B > e->cfg.max_batch) return fail("encode_frames: B=%d outside [1,%d]", B, e->cfg.max_batch);
+    RCK(check_frames(e, "encode_frames", frames, F, B));
     RCK(ragged_prepare(e, frames, F, B, (hipStream_t)stream));
     return encode_frames_impl(e, frames, F, B, feats_out, (hipStream_t)stream);
 }
@@ -1426,7 +1434,7 @@ extern "C" int gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, 
 
 // ---- search seam -----------------------------------------------------------------------
 // `start_dev` / `plen_dev` (/ `img_of_dev`) must already describe the B sentences of the call
-static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int minP, int maxP, int V, bool ragged,
+static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int minP, int maxP, int V, bool prefixed,
                              hipStream_t s) {
     const gitmi_config& c = e->cfg;
     if (!sp) return fail("search: null config");
@@ -1465,12 +1473,12 @@ static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int
     st.T = sp->max_steps;           // max_length of the search AND the row stride of ids/kv_src/hyp_tok
     // the trie search shares AutoRegressiveBeamSearch's bookkeeping (beam 1): only the candidate selection differs
     st.V = V; st.eos = c.eos; st.kind = e->trie_search ? GITMI_SEARCH_AUTOREGRESSIVE : sp->kind; st.length_penalty = sp->length_penalty;
-    st.ragged = ragged ? 1 : 0;
+    st.prefixed = prefixed ? 1 : 0;
     st.nh = sp->num_keep_best > 1 ? sp->num_keep_best : 1;
     st.sampled = sp->do_sample ? 1 : 0;
     e->sample = *sp;
     st.start = e->start_dev; st.ld_start = c.max_text_len; st.plen = e->plen_dev;
-    e->ss_cur = 0; e->ss_len = minP; e->ss_minP = minP;
+    e->ss_cur = 0; e->ss_len = minP;
     HIPCK(launch_search_init(st, s));
     if (e->trie_search) HIPCK(launch_fill_i32(e->trie_cursor, 0, B, s));      // TokenTrie.reset(): every cursor at the root
     return 0;
@@ -1564,7 +1572,6 @@ extern "C" int gitmi_set_trie(gitmi_engine* e, int n_nodes, const int32_t* child
     }
     if (e->trie_off) { hipFree(e->trie_off); hipFree(e->trie_tok); hipFree(e->trie_child); }
     e->trie_off = n_off; e->trie_tok = n_tok; e->trie_child = n_child;
-    e->trie_nodes = n_nodes > 0 ? n_nodes : 0;
     return 0;
 }
 
@@ -1639,11 +1646,11 @@ static int generate_encode(gitmi_engine* e, const float* const* frames, int F, i
 
 // search over the text positions (teacher-forced prefix positions, then searched ones) + result formatting.
 // Q sentences (start_dev / plen_dev / img_of_dev describe them), prefix lengths in [minP, maxP].
-static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool ragged, const gitmi_search* sp,
+static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool prefixed, const gitmi_search* sp,
                            long long* tokens_out, float* logprob_out, int32_t* info_out, int32_t* sent_out, hipStream_t s,
                            bool allow_poll) {
     const gitmi_config& c = e->cfg;
-    RCK(search_begin_impl(e, sp, Q, minP, maxP, c.vocab, ragged, s));
+    RCK(search_begin_impl(e, sp, Q, minP, maxP, c.vocab, prefixed, s));
     const int T = sp->max_steps;
     const SearchState& st = e->ss;
     const int k = sp->beam_size, R = Q * k;
@@ -1686,23 +1693,23 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool ragg
     return 0;
 }
 
-static int generate_body(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool ragged,
+static int generate_body(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool prefixed,
                          const gitmi_search* sp, long long* tokens_out, float* logprob_out, int32_t* info_out,
                          int32_t* sent_out, hipStream_t s, bool allow_poll) {
     SpanGuard total(e, s, 99, 0);
     RCK(generate_encode(e, frames, F, B, s));
-    return generate_decode(e, Q, minP, maxP, ragged, sp, tokens_out, logprob_out, info_out, sent_out, s, allow_poll);
+    return generate_decode(e, Q, minP, maxP, prefixed, sp, tokens_out, logprob_out, info_out, sent_out, s, allow_poll);
 }
 
 // common tail of gitmi_generate / gitmi_generate_prefixed: start_dev / plen_dev / img_of_dev are already enqueued on `s`
-static int generate_run(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool ragged,
+static int generate_run(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool prefixed,
                         const gitmi_search* sp, int64_t* tokens_out, float* logprob_out, int32_t* info_out,
                         int32_t* sent_out, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const bool long_budget = sp->max_steps - minP > 32;
     const bool graph = e->use_graph && !e->profiling && !long_budget;
     if (!graph)
-        return generate_body(e, frames, F, B, Q, minP, maxP, ragged, sp, (long long*)tokens_out, logprob_out, info_out,
+        return generate_body(e, frames, F, B, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
                              sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
 
     // ---- hipGraph path: the launch sequence only depends on (B,Q,F,minP,search); inputs and outputs are
@@ -1718,12 +1725,7 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
     if (!e->ragged)     // ragged: ragged_prepare staged the images already
     for (int f = 0; f < F_eff; ++f)
         HIPCK(hipMemcpyAsync(e->frame_stage[f], frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
-    gitmi_engine::GraphKey key{};
-    key.B = B; key.Q = Q; key.F = F_eff; key.P = minP; key.kind = sp->kind; key.k = sp->beam_size; key.pn = sp->per_node_beam_size;
-    key.T = sp->max_steps; key.H = e->H; key.W = e->W; key.lp = sp->length_penalty;
-    key.ragged = ragged ? 1 : 0; key.ident = e->img_identity ? 1 : 0; key.temb = e->use_temb ? 1 : 0;
-    key.smp = sp->do_sample; key.top_k = sp->top_k; key.top_p = sp->top_p; key.temp = sp->temperature; key.seed = sp->seed;
-    key.rp = sp->repetition_penalty; key.nh = sp->num_keep_best > 1 ? sp->num_keep_best : 1;
+    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->use_temb, *sp);
     // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
     // enc_done record other contexts wait for
     const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
@@ -1734,10 +1736,10 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
         auto capture = [&](int part, hipGraph_t* gr_out) -> int {       // part 0: whole call, 1: encode + prefill, 2: decode
             HIPCK(hipStreamBeginCapture(x, hipStreamCaptureModeThreadLocal));
             int rc = 0;
-            if (part == 0) rc = generate_body(e, fp.data(), F_eff, B, Q, minP, maxP, ragged, sp, e->out_tokens, e->out_lp,
+            if (part == 0) rc = generate_body(e, fp.data(), F_eff, B, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp,
                                               e->out_info, e->out_sent, x, false);
             else if (part == 1) rc = generate_encode(e, fp.data(), F_eff, B, x);
-            else rc = generate_decode(e, Q, minP, maxP, ragged, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
+            else rc = generate_decode(e, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
             hipGraph_t gr = nullptr;
             hipError_t ce = hipStreamEndCapture(x, &gr);
             if (rc != 0) { if (gr) hipGraphDestroy(gr); return rc; }
@@ -1805,8 +1807,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     const gitmi_config& c = e->cfg;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
     if (!frames || !sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
-    if (F < 1 || F > c.max_frames) return fail("generate: F=%d outside [1,%d]", F, c.max_frames);
-    if (B < 1 || B > c.max_batch) return fail("generate: B=%d outside [1,%d]", B, c.max_batch);
+    RCK(check_frames(e, "generate", frames, F, B));
     if (!prefix) P = 1;
     if (P < 1 || P > c.max_text_len) return fail("generate: prefix length %d outside [1,%d]", P, c.max_text_len);
     if (sp->max_steps < P || sp->max_steps > c.max_text_len) return fail("generate: max_steps %d outside [P,%d]", sp->max_steps, c.max_text_len);
@@ -1907,70 +1908,68 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
     return 0;
 }
 
-// Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V).
+// Sentence tables of gitmi_generate_prefixed (both kinds): read_sentences checks Q <= Qmax (`cap` names it), lengths in
+// [1, ld] and images in [0, B) into plen_host / img_of_host; upload_sentences copies them to the caller's device tables.
+struct SentenceSpan { int minP, maxP; bool ident; };
+static int read_sentences(gitmi_engine* e, const char* who, const int32_t* plen, const int32_t* image_of, int ld, int B, int Q,
+                          int Qmax, const char* cap, SentenceSpan* span) {
+    if (Q < 1 || Q > Qmax) return fail("%s: Q=%d sentences outside [1,%d] (%s)", who, Q, Qmax, cap);
+    if (!image_of && Q != B) return fail("%s: without image_of, Q must equal B", who);
+    *span = {1 << 30, 0, true};
+    e->plen_host.assign(plen, plen + Q);
+    e->img_of_host.resize(Q);
+    for (int q = 0; q < Q; ++q) {
+        const int p = plen[q];
+        if (p < 1 || p > ld) return fail("%s: length %d of sentence %d outside [1,%d]", who, p, q, ld);
+        span->minP = std::min(span->minP, p); span->maxP = std::max(span->maxP, p);
+        const int im = image_of ? image_of[q] : q;
+        if (im < 0 || im >= B) return fail("%s: sentence %d names image %d of %d", who, q, im, B);
+        e->img_of_host[q] = im;
+        span->ident = span->ident && im == q;
+    }
+    return 0;
+}
+// staged synchronously (the previous call's work on `s` may still read them): this serves the VQA loop, not the benchmark
+static int upload_sentences(gitmi_engine* e, int* plen_dst, int* img_dst, hipStream_t s) {
+    const size_t bytes = e->plen_host.size() * sizeof(int);
+    HIPCK(hipStreamSynchronize(s));
+    HIPCK(hipMemcpy(plen_dst, e->plen_host.data(), bytes, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(img_dst, e->img_of_host.data(), bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V)
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
                                        const gitmi_search* sp, int64_t* tokens_out, float* logprob_out,
                                        int32_t* sent_out, int32_t* info_out, void* stream) {
     RCK(check_ready(e));
     const gitmi_config& c = e->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    SentenceSpan span;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) {
         if (!frames || !logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("score: null argument");
-        if (F < 1 || F > c.max_frames) return fail("score: F=%d outside [1,%d]", F, c.max_frames);
-        if (B < 1 || B > c.max_batch) return fail("score: B=%d outside [1,%d]", B, c.max_batch);
-        if (Q < 1 || Q > c.max_batch * c.max_beams)
-            return fail("score: Q=%d sentences outside [1,%d] (max_batch x max_beams)", Q, c.max_batch * c.max_beams);
-        if (!image_of_host && Q != B) return fail("score: without image_of, Q must equal B");
+        RCK(check_frames(e, "score", frames, F, B));
         if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("score: ld=%d outside [1,%d] (max_text_len)", ld_prefix, c.max_text_len);
-        int maxlen = 0;
-        e->plen_host.assign(prefix_len_host, prefix_len_host + Q);
-        e->img_of_host.resize(Q);
-        for (int q = 0; q < Q; ++q) {
-            const int p = prefix_len_host[q];
-            if (p < 1 || p > ld_prefix) return fail("score: length %d of sentence %d outside [1,%d]", p, q, ld_prefix);
-            maxlen = std::max(maxlen, p);
-            const int im = image_of_host ? image_of_host[q] : q;
-            if (im < 0 || im >= B) return fail("score: sentence %d names image %d of %d", q, im, B);
-            e->img_of_host[q] = im;
-        }
-        hipStream_t s = (hipStream_t)stream;
-        HIPCK(hipStreamSynchronize(s));
-        RCK(score_alloc(e, (size_t)Q * round_up(maxlen, 16)));
-        HIPCK(hipMemcpy(e->sc_lens, e->plen_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(e->sc_img, e->img_of_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
+        RCK(read_sentences(e, "score", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch * c.max_beams,
+                           "max_batch x max_beams", &span));
+        RCK(score_alloc(e, (size_t)Q * round_up(span.maxP, 16)));
+        RCK(upload_sentences(e, e->sc_lens, e->sc_img, s));
         RCK(ragged_prepare(e, frames, F, B, s));
-        return score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, maxlen, logprob_out, info_out, s);
+        return score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, span.maxP, logprob_out, info_out, s);
     }
     if (!frames || !sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
         return fail("generate_prefixed: null argument");
-    if (F < 1 || F > c.max_frames) return fail("generate_prefixed: F=%d outside [1,%d]", F, c.max_frames);
-    if (B < 1 || B > c.max_batch) return fail("generate_prefixed: B=%d outside [1,%d]", B, c.max_batch);
-    if (Q < 1 || Q > c.max_batch) return fail("generate_prefixed: Q=%d sentences outside [1,%d]", Q, c.max_batch);
-    if (!image_of_host && Q != B) return fail("generate_prefixed: without image_of, Q must equal B");
-    int minP = 1 << 30, maxP = 0;
-    e->plen_host.assign(prefix_len_host, prefix_len_host + Q);
-    e->img_of_host.resize(Q);
-    bool ident = true;
-    for (int q = 0; q < Q; ++q) {
-        const int p = prefix_len_host[q];
-        if (p < 1 || p > ld_prefix) return fail("generate_prefixed: prefix length %d of sentence %d outside [1,%d]", p, q, ld_prefix);
-        minP = std::min(minP, p); maxP = std::max(maxP, p);
-        const int im = image_of_host ? image_of_host[q] : q;
-        if (im < 0 || im >= B) return fail("generate_prefixed: sentence %d names image %d of %d", q, im, B);
-        e->img_of_host[q] = im;
-        ident = ident && im == q;
-    }
-    if (sp->max_steps < maxP || sp->max_steps > c.max_text_len) return fail("generate_prefixed: max_steps %d outside [%d,%d]", sp->max_steps, maxP, c.max_text_len);
-    hipStream_t s = (hipStream_t)stream;
-    // the (tiny) host tables are staged synchronously: this entry point serves the VQA task loop, not the benchmark
-    HIPCK(hipStreamSynchronize(s));
-    HIPCK(hipMemcpy(e->plen_dev, e->plen_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
-    HIPCK(hipMemcpy(e->img_of_dev, e->img_of_host.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice));
+    RCK(check_frames(e, "generate_prefixed", frames, F, B));
+    RCK(read_sentences(e, "generate_prefixed", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch, "max_batch", &span));
+    if (sp->max_steps < span.maxP || sp->max_steps > c.max_text_len)
+        return fail("generate_prefixed: max_steps %d outside [%d,%d]", sp->max_steps, span.maxP, c.max_text_len);
+    RCK(upload_sentences(e, e->plen_dev, e->img_of_dev, s));
     HIPCK(hipMemcpy2D(e->start_dev, (size_t)c.max_text_len * sizeof(long long), prefixes, (size_t)ld_prefix * sizeof(long long),
-                      (size_t)maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
-    e->img_identity = ident;
+                      (size_t)span.maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
+    e->img_identity = span.ident;
     RCK(ragged_prepare(e, frames, F, B, s));
-    return generate_run(e, frames, F, B, Q, minP, maxP, true, sp, tokens_out, logprob_out, info_out, sent_out, s);
+    return generate_run(e, frames, F, B, Q, span.minP, span.maxP, true, sp, tokens_out, logprob_out, info_out, sent_out, s);
 }
 
 // ---- profiling --------------------------------------------------------------------------

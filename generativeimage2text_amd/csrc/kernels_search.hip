@@ -712,9 +712,9 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
             }
             if (nb < k) {
                 // done sentence, or every candidate finished (cur_len + 1 == max_length): pad the batch with
-                // (score 0, EOS, row 0 of the call)  -- decoder.py:1189, 1219-1220.  A sentence of a batched ragged call
+                // (score 0, EOS, row 0 of the call)  -- decoder.py:1189, 1219-1220.  A sentence of a batched prefixed call
                 // stands for its own batch-1 reference call, whose row 0 is the sentence's own first row.
-                const int pad_row = st.ragged ? b * k : 0;
+                const int pad_row = st.prefixed ? b * k : 0;
                 for (int j = 0; j < k; ++j) { sel_score[j] = 0.f; sel_word[j] = st.eos; sel_src[j] = pad_row; }
             }
         }

@@ -158,7 +158,7 @@ hipError_t attn_decode_configure();
 constexpr int SS_NHMAX = 8;            // num_keep_best supported by the device search
 struct SearchState {
     int B, k, pn, T, V, eos, kind;      // B sentences of k beams; T = max_steps = row stride of ids / kv_src / hyp_tok
-    int ragged;                         // 1: every sentence stands for its own batch-1 reference call (own prefix)
+    int prefixed;                       // 1: every sentence has its own prefix and stands for its own batch-1 reference call
     int sampled;                        // GENERATOR sampling branch: candidates arrive as per_node draws per beam, in draw order
     double length_penalty;
     double* len_norm;                   // [T_max + 1] ((5 + len) / 6) ** length_penalty, filled by search_init

@@ -193,6 +193,20 @@ def _torch_dtype_code(t: torch.Tensor) -> int:
 RAGGED_DESC_BYTES = 256    # the descriptor block of a ragged input is padded to this size (include/gitmi.h)
 
 
+def id_table(rows: Sequence[Sequence[int]]) -> torch.Tensor:
+    """Id lists of any lengths -> int64 [len(rows), longest] on the CPU, zero-padded past each row's end."""
+    table = torch.zeros(len(rows), max(len(r) for r in rows), dtype=torch.int64)
+    for q, r in enumerate(rows):
+        table[q, :len(r)] = torch.as_tensor(list(r), dtype=torch.int64)
+    return table
+
+
+def _sentence_tables(lens: Sequence[int], image_of: Optional[Sequence[int]]):
+    """(prefix_len_host, image_of_host) of gitmi_generate_prefixed as int32 arrays (image_of None: sentence q <-> image q)."""
+    Q = len(lens)
+    return (C.c_int32 * Q)(*lens), None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
+
+
 class RaggedImages:
     """B images of their own sizes in ONE device buffer: the input of a ragged engine call (gitmi_set_image_shape(e, 0, 0),
     include/gitmi.h).  buffer: fp32 [n] = int32 descriptor [B][4] = {h, w, offset, 0} padded to 256 bytes, then the [3, h, w]
@@ -276,8 +290,6 @@ class Engine:
         self._h = C.c_void_p()
         self._ck(self.lib.gitmi_create(C.byref(c), self.device, C.byref(self._h)))
         self._finalized = False
-        self._cur_B = 0
-        self._cur_F = 0
 
     # -- lifecycle ---------------------------------------------------------------------------
     def _ck(self, rc: int) -> None:
@@ -293,7 +305,7 @@ class Engine:
         other._hw = (int(self.c.image_size), int(self.c.image_size))
         other._h = C.c_void_p()
         self._ck(self.lib.gitmi_clone(self._h, C.byref(other._h)))
-        other._finalized, other._cur_B, other._cur_F = True, 0, 0
+        other._finalized = True
         other._parent = self
         return other
 
@@ -378,7 +390,6 @@ class Engine:
         if return_features:
             out = torch.empty(B, F_eff * self.n_tok, self.c.vit_width, device=keep[0].device, dtype=torch.float32)
         self._ck(self.lib.gitmi_encode_frames(self._h, arr, F, B, _ptr(out), _stream()))
-        self._cur_B, self._cur_F = B, F_eff
         return out
 
     def prefill(self) -> None:
@@ -408,34 +419,40 @@ class Engine:
         return s
 
     @staticmethod
-    def _out(n_sent: int, search: GitmiSearch, dev, host: bool = False):
-        """Output buffers of a search over n_sent sentences: [n, T] / [n], or [n, num_keep_best, T] / [n, num_keep_best]
-        when GeneratorWithBeamSearch keeps more than one hypothesis (decoder.py:1283-1290).  host: page-locked host tensors."""
+    def _empty(shape, dtype, dev, host: bool = False) -> torch.Tensor:
+        """An output buffer on `dev`, or with host a PAGE-LOCKED host tensor that the request itself fills (valid once the
+        stream has reached the end of the call): a server with other requests in flight reads it without a read-back."""
+        return torch.empty(shape, dtype=dtype, pin_memory=True) if host else torch.empty(shape, dtype=dtype, device=dev)
+
+    @classmethod
+    def _out(cls, n_sent: int, search: GitmiSearch, dev, host: bool = False):
+        """Output buffers of a search over n_sent sentences: tokens [n, T] / logprobs [n], or [n, num_keep_best, T] /
+        [n, num_keep_best] when GeneratorWithBeamSearch keeps more than one hypothesis (decoder.py:1283-1290); info [4]."""
         nh = max(1, int(search.num_keep_best))
         shape = (n_sent,) if nh == 1 else (n_sent, nh)
-        kw = dict(pin_memory=True) if host else dict(device=dev)
-        return (torch.empty(*shape, search.max_steps, dtype=torch.int64, **kw),
-                torch.empty(*shape, dtype=torch.float32, **kw))
+        return (cls._empty((*shape, search.max_steps), torch.int64, dev, host), cls._empty(shape, torch.float32, dev, host),
+                cls._empty(4, torch.int32, dev, host))
+
+    def _done(self, rc: int, info, sync: bool) -> None:
+        """The tail every request shares: raise on a failed call; with sync, wait for the stream and check info[3]."""
+        self._ck(rc)
+        if sync:
+            torch.cuda.current_stream().synchronize()
+            self.check_finite(info)
 
     def generate(self, frames: Sequence[torch.Tensor], search: GitmiSearch,
                  prefix: Optional[torch.Tensor] = None, sync: bool = True, host_out: bool = False):
         """-> (tokens int64 [B, max_steps] incl. start tokens / EOS padded, logprobs fp32 [B], info int32 [4]).
-        host_out: the three come back as PAGE-LOCKED HOST tensors, filled by the request itself (valid once the stream has reached
-        the end of the call): a server with other requests in flight reads them without enqueueing a read-back."""
+        host_out: the three come back as page-locked host tensors (_empty)."""
         arr, keep, B = self._frames_arg(frames)
         dev = keep[0].device
-        tokens, logprobs = self._out(B, search, dev, host_out)
-        info = torch.empty(4, dtype=torch.int32, pin_memory=True) if host_out else torch.empty(4, device=dev, dtype=torch.int32)
+        tokens, logprobs, info = self._out(B, search, dev, host_out)
         P, pfx = 1, None
         if prefix is not None:
             pfx = prefix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
             P = int(pfx.numel())
-        self._ck(self.lib.gitmi_generate(self._h, arr, len(keep), B, _ptr(pfx), P, C.byref(search), tokens.data_ptr(),
-                                    logprobs.data_ptr(), info.data_ptr(), _stream()))
-        self._cur_B = B
-        if sync:
-            torch.cuda.current_stream().synchronize()
-            self.check_finite(info)
+        self._done(self.lib.gitmi_generate(self._h, arr, len(keep), B, _ptr(pfx), P, C.byref(search), tokens.data_ptr(),
+                                           logprobs.data_ptr(), info.data_ptr(), _stream()), info, sync)
         return tokens, logprobs, info
 
     def check_finite(self, info) -> None:
@@ -477,24 +494,13 @@ class Engine:
         dev = keep[0].device
         Q = len(prefixes)
         lens = [len(p) for p in prefixes]
-        ld = max(lens)
-        table = torch.zeros(Q, ld, dtype=torch.int64)
-        for q, p in enumerate(prefixes):
-            table[q, :len(p)] = torch.as_tensor(list(p), dtype=torch.int64)
-        table = table.to(dev)
-        tokens, logprobs = self._out(Q, search, dev, host_out)
-        hk = dict(pin_memory=True) if host_out else dict(device=dev)
-        sent = torch.empty(Q, 2, dtype=torch.int32, **hk)
-        info = torch.empty(4, dtype=torch.int32, **hk)
-        lens_c = (C.c_int32 * Q)(*lens)
-        img_c = None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
-        self._ck(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, table.data_ptr(), ld, lens_c, img_c, Q,
-                                             C.byref(search), tokens.data_ptr(), logprobs.data_ptr(), sent.data_ptr(),
-                                             info.data_ptr(), _stream()))
-        self._cur_B = B
-        if sync:
-            torch.cuda.current_stream().synchronize()
-            self.check_finite(info)
+        table = id_table(prefixes).to(dev)
+        tokens, logprobs, info = self._out(Q, search, dev, host_out)
+        sent = self._empty((Q, 2), torch.int32, dev, host_out)
+        self._done(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, table.data_ptr(), table.shape[1],
+                                                    *_sentence_tables(lens, image_of), Q, C.byref(search), tokens.data_ptr(),
+                                                    logprobs.data_ptr(), sent.data_ptr(), info.data_ptr(), _stream()),
+                   info, sync)
         return tokens, logprobs, sent, info
 
     def score(self, frames: Sequence[torch.Tensor], tokens, lengths: Optional[Sequence[int]] = None,
@@ -527,18 +533,13 @@ class Engine:
             raise ValueError(f"{Q} sentences over {B} images: image_of is required")
         if image_of is not None and len(image_of) != Q:
             raise ValueError(f"image_of has {len(image_of)} entries for {Q} sentences")
-        out = torch.empty(Q, L, 2, device=dev, dtype=torch.float32)
-        info = torch.empty(4, device=dev, dtype=torch.int32)
+        out = self._empty((Q, L, 2), torch.float32, dev)
+        info = self._empty(4, torch.int32, dev)
         search = GitmiSearch()
         search.kind = SEARCH_SCORE
-        lens_c = (C.c_int32 * Q)(*lens)
-        img_c = None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
-        self._ck(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, tok.data_ptr(), L, lens_c, img_c, Q,
-                                                  C.byref(search), None, out.data_ptr(), None, info.data_ptr(), _stream()))
-        self._cur_B = B
-        self._cur_F = min(len(keep), self.c.num_frames) if self.c.num_frames > 0 else len(keep)
-        torch.cuda.current_stream().synchronize()
-        self.check_finite(info)
+        self._done(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, tok.data_ptr(), L, *_sentence_tables(lens, image_of),
+                                                    Q, C.byref(search), None, out.data_ptr(), None, info.data_ptr(), _stream()),
+                   info, True)
         return out
 
     # -- search seam ---------------------------------------------------------------------------
@@ -580,7 +581,6 @@ class Engine:
         """Take the image features (stage 1) or features + image K/V of every decoder layer (stage 2) from `src`, a
         context of the same model in the other precision; step_logits() then continues from there."""
         self._ck(_experiment_only(self.lib, "gitmi_debug_import_stage")(self._h, src._h, int(stage), _stream()))
-        self._cur_B = src._cur_B
 
     def debug_head_from(self, src: "Engine", R: int) -> torch.Tensor:
         """This (bf16) context's fused vocabulary head on the last hidden state of src's (fp32) latest step_logits."""
@@ -597,8 +597,7 @@ class Engine:
 
     def search_finish(self):
         dev = f"cuda:{self.device}"
-        tokens, logprobs = self._out(self._search_B, self._search_cfg, dev)
-        info = torch.empty(4, device=dev, dtype=torch.int32)
+        tokens, logprobs, info = self._out(self._search_B, self._search_cfg, dev)
         self._ck(self.lib.gitmi_search_finish(self._h, tokens.data_ptr(), logprobs.data_ptr(), info.data_ptr(), _stream()))
         torch.cuda.current_stream().synchronize()
         return tokens, logprobs, info

@@ -18,7 +18,7 @@ from typing import Dict, Mapping, Optional, Sequence, Union
 import torch
 
 from .configs import GitModelConfig, config_from_param
-from .engine import Engine
+from .engine import Engine, id_table
 
 
 # ---- decoder.search(start_predictions, step): the reference's search seam as a method ----------------------------
@@ -327,6 +327,51 @@ def caption_loss(lp, mean_lp, tokens, need_predict, loss_type: Optional[str] = "
     return float(per.mean())
 
 
+def format_predictions(tokens, logprobs, sent, prefix, kind: str):
+    """What the caller of a search gets from its raw output (tokens incl. the start tokens, logprobs): the early-EOS rule
+    of the autoregressive searches (decoder.py:279-291 / trie_decoder.py:76-83), then the prefix removed (decoder.py:1004-1006,
+    along dim 1 whatever it is).  Pure: launches no device work.
+      prefix None or an int P (one prefix for the whole batch; None: [CLS] alone, nothing removed): sent = (seq_len, early) of
+        the call (info[:2]) -> (predictions tensor, logprobs [B] / [B, 1] / [B, num_keep_best]) as model(batch) returns them;
+      prefix a list of per-sentence lengths: sent [Q, 2] = (length, early) of every sentence -> ([ids of each sentence],
+        logprobs [Q, 1] / [Q, num_keep_best])."""
+    autoregressive = kind in ("autoregressive", "trie")
+    if isinstance(prefix, (list, tuple)):
+        preds = []
+        for q, P in enumerate(prefix):
+            L, early = int(sent[q][0]), int(sent[q][1])
+            row = tokens[q]
+            if autoregressive:
+                row = row[P:P + 1] if early else row[:L]
+            preds.append(row[P:].tolist())
+        return preds, logprobs.reshape(len(prefix), -1)
+    P = 1 if prefix is None else int(prefix)
+    seq_len, early = int(sent[0]), int(sent[1])
+    if autoregressive:
+        if early:
+            tokens, logprobs = tokens[:, P:P + 1], logprobs[:, None]
+        else:
+            tokens = tokens[:, :seq_len]
+    elif logprobs.dim() == 1:
+        logprobs = logprobs[:, None]                                    # [B, num_keep_best]
+    return (tokens if prefix is None else tokens[:, P:]), logprobs
+
+
+def _finish_batch(eng, out, prefix, kind: str):
+    """Pending.finish of a batch-uniform request (model(batch), captioning ragged batches)."""
+    tokens, logprobs, info = out
+    info_h = info.tolist()                                              # ONE small read-back for the four fields
+    eng.check_finite(info_h)
+    predictions, logprobs = format_predictions(tokens, logprobs, info_h[:2], prefix, kind)
+    return {"predictions": predictions, "logprobs": logprobs}
+
+
+def _is_image_list(images) -> bool:
+    """A list of [3, h, w] images of their own sizes (one ragged engine call); a list of [B, 3, H, W] tensors means frames."""
+    return isinstance(images, (list, tuple)) and len(images) > 0 and \
+        all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in images)
+
+
 class CaptioningModel:
     """Callable like the reference model: ``model(batch) -> {'predictions', 'logprobs'}``.
 
@@ -465,7 +510,7 @@ class CaptioningModel:
         if prefix is not None:
             assert len(prefix) == 1, "not supported"                       # decoder.py:988
         search = self._search_struct(search_param)
-        P = 1 if prefix is None else int(prefix.numel())
+        P = None if prefix is None else int(prefix.numel())
         nret = int((search_param or {}).get("num_return_sequences", 1))
         kind = self.decoder.kind
 
@@ -485,36 +530,13 @@ class CaptioningModel:
                 tokens, logprobs, info = eng.generate(frames, search, prefix=prefix, sync=False, host_out=stream is not None)
             return tokens, logprobs, info
 
-        def finish(out):
-            tokens, logprobs, info = out
-            info_h = info.tolist()                                              # ONE small read-back for the four fields
-            eng.check_finite(info_h)
-            seq_len, early, _, _ = info_h
-            if kind in ("autoregressive", "trie"):
-                if early:                                                       # decoder.py:279-291 / trie_decoder.py:76-83
-                    predictions = tokens[:, P:P + 1]
-                    logprobs = logprobs[:, None]
-                else:
-                    predictions = tokens[:, :seq_len]
-            else:
-                predictions = tokens                                            # [B, T], or [B, num_keep_best, T]
-                if logprobs.dim() == 1:
-                    logprobs = logprobs[:, None]                                # [B, num_keep_best]
-            if prefix is not None:
-                predictions = predictions[:, P:]                                # decoder.py:1004-1006 (dim 1, whatever it is)
-            return {"predictions": predictions, "logprobs": logprobs}
-
-        return Pending(stream, launch, finish, keep=(frames, prefix))
+        return Pending(stream, launch, lambda out: _finish_batch(eng, out, P, kind), keep=(frames, prefix))
 
     def forward(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
                 search_param: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         if self.training:
             return self._loss_forward(batch)
-        saved, self._ctxs = getattr(self, "_ctxs", None), None              # model(batch): context 0, the caller's stream
-        try:
-            return self.submit(batch, search_param).result()
-        finally:
-            self._ctxs = saved
+        return self._on_context0(lambda: self.submit(batch, search_param))
 
     __call__ = forward
 
@@ -543,15 +565,10 @@ class CaptioningModel:
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
         if not isinstance(captions, torch.Tensor):
-            L = max(len(c) for c in captions)
-            tab = torch.zeros(len(captions), L, dtype=torch.int64)
-            for q, c in enumerate(captions):
-                tab[q, :len(c)] = torch.as_tensor(list(c), dtype=torch.int64)
-            captions = tab
+            captions = id_table(captions)
         tokens = captions.detach().cpu().long()
         is_list = isinstance(images, (list, tuple))
-        if is_list and len(images) and all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in images):
-            # a list of [3, h, w] images of their own sizes: one ragged engine call (a list of [B, 3, H, W] means frames)
+        if _is_image_list(images):
             self._check_ragged()
             self.engine.set_temporal_embedding(False)
             out = self.engine.score(self.engine.ragged(images), tokens, image_of=image_of).cpu()
@@ -587,63 +604,29 @@ class CaptioningModel:
         `.result()` is {'predictions': [ids of each answer, the prefix removed], 'logprobs': fp32 [Q, 1]}."""
         self._check_ragged()
         images = list(images)
+        if not _is_image_list(images):
+            raise ValueError("submit_ragged takes a non-empty list of [3, h, w] images")
         eng, stream = self._context()
         self._prepare(eng, False)
         packed = eng.ragged(images)                                        # host-side shape checks, then one upload
         search = self._search_struct(search_param)
         if int((search_param or {}).get("num_return_sequences", 1)) != 1:
             raise NotImplementedError("num_return_sequences with images of different sizes")
-        kind = self.decoder.kind
-        host = stream is not None
         if prefixes is None:
-            def launch():
-                return eng.generate(packed, search, sync=False, host_out=host)
-
-            def finish(out):
-                tokens, logprobs, info = out
-                info_h = info.tolist()
-                eng.check_finite(info_h)
-                seq_len, early, _, _ = info_h
-                if kind in ("autoregressive", "trie"):
-                    if early:
-                        return {"predictions": tokens[:, 1:2], "logprobs": logprobs[:, None]}
-                    return {"predictions": tokens[:, :seq_len], "logprobs": logprobs}
-                return {"predictions": tokens, "logprobs": logprobs if logprobs.dim() > 1 else logprobs[:, None]}
-            return Pending(stream, launch, finish, keep=(packed,))
+            return Pending(stream, lambda: eng.generate(packed, search, sync=False, host_out=stream is not None),
+                           lambda out: _finish_batch(eng, out, None, self.decoder.kind), keep=(packed,))
         Q = len(prefixes)
         image_of = list(range(Q)) if image_of is None else [int(i) for i in image_of]
         if Q > eng.c.max_batch:
             raise ValueError(f"{Q} questions exceed max_batch={eng.c.max_batch}")
         if len(image_of) != Q or any(i < 0 or i >= len(images) for i in image_of):
             raise ValueError(f"image_of must name one of the {len(images)} images for each of the {Q} questions")
-
-        def launch():
-            return eng.generate_prefixed(packed, search, prefixes, image_of=image_of, sync=False, host_out=host)
-
-        def finish(out):
-            tokens, logprobs, sent, info = out
-            eng.check_finite(info.tolist())
-            tokens, sent = tokens.cpu(), sent.cpu()
-            res = []
-            for q, p in enumerate(prefixes):
-                P = len(p)
-                L, early = int(sent[q, 0]), int(sent[q, 1])
-                if kind in ("autoregressive", "trie"):
-                    row = (tokens[q, P:P + 1] if early else tokens[q, :L])[P:]
-                else:
-                    row = tokens[q, P:]
-                res.append(row.tolist())
-            return {"predictions": res, "logprobs": logprobs.cpu().reshape(Q, -1)}
-        return Pending(stream, launch, finish, keep=(packed,))
+        return self._submit_prefixed(eng, stream, packed, prefixes, image_of, search, as_dict=True)
 
     def generate_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
                         image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None):
         """submit_ragged(...).result() on context 0 and the caller's stream."""
-        saved, self._ctxs = getattr(self, "_ctxs", None), None
-        try:
-            return self.submit_ragged(images, prefixes, image_of, search_param).result()
-        finally:
-            self._ctxs = saved
+        return self._on_context0(lambda: self.submit_ragged(images, prefixes, image_of, search_param))
 
     def submit_answers(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
                        image_of: Optional[Sequence[int]] = None) -> "Pending":
@@ -662,7 +645,11 @@ class CaptioningModel:
         if Q > eng.c.max_batch or int(frames[0].shape[0]) > eng.c.max_batch:
             raise ValueError(f"{Q} questions / {int(frames[0].shape[0])} images exceed max_batch={eng.c.max_batch}")
         self._prepare(eng, is_list)
-        search = self._search_struct()
+        return self._submit_prefixed(eng, stream, frames, prefixes, image_of, self._search_struct(), as_dict=False)
+
+    def _submit_prefixed(self, eng, stream, frames, prefixes, image_of, search, as_dict: bool) -> "Pending":
+        """submit_answers / submit_ragged with questions: one generate_prefixed call on `eng` (frames: a stacked batch or
+        RaggedImages).  .result(): the answers' id lists, and with as_dict {'predictions': them, 'logprobs' [Q, 1]}."""
         kind = self.decoder.kind
 
         def launch():
@@ -671,17 +658,8 @@ class CaptioningModel:
         def finish(out):
             tokens, logprobs, sent, info = out
             eng.check_finite(info.tolist())
-            tokens, sent = tokens.cpu(), sent.cpu()
-            res = []
-            for q, p in enumerate(prefixes):
-                P = len(p)
-                L, early = int(sent[q, 0]), int(sent[q, 1])
-                if kind in ("autoregressive", "trie"):
-                    row = (tokens[q, P:P + 1] if early else tokens[q, :L])[P:]     # decoder.py:279-291, then :1004-1006
-                else:
-                    row = tokens[q, P:]
-                res.append(row.tolist())
-            return res
+            preds, logprobs = format_predictions(tokens.cpu(), logprobs, sent.cpu(), [len(p) for p in prefixes], kind)
+            return {"predictions": preds, "logprobs": logprobs.cpu()} if as_dict else preds
 
         return Pending(stream, launch, finish, keep=(frames,))
 
@@ -689,11 +667,24 @@ class CaptioningModel:
         """Several questions about ONE image in one engine call: submit_answers(...).result() on context 0."""
         frames = list(image) if isinstance(image, (list, tuple)) else [image]
         assert frames[0].shape[0] == 1, "answer() takes one image (or one clip)"
-        saved, self._ctxs = getattr(self, "_ctxs", None), None
+        return self._on_context0(lambda: self.submit_answers(image, prefixes))
+
+    def _on_context0(self, submit):
+        """submit().result() on context 0 and the caller's stream (model(batch), answer, generate_ragged).  With set_pipeline
+        active, context 0 may still have a submission in flight on its own stream: the caller's stream waits for it, and
+        context 0's stream then waits for this call, so the context's workspaces are never in use on two streams at once."""
+        ctxs = getattr(self, "_ctxs", None)
+        if not ctxs:
+            return submit().result()
+        cur, own = torch.cuda.current_stream(), self._streams[0]
+        cur.wait_stream(own)
+        self._ctxs = None                                               # _context() -> (self.engine, None)
         try:
-            return self.submit_answers(image, prefixes).result()
+            pending = submit()
         finally:
-            self._ctxs = saved
+            self._ctxs = ctxs
+            own.wait_stream(cur)
+        return pending.result()
 
 
 class Pending:

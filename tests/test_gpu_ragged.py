@@ -325,3 +325,31 @@ def test_tsv_mixed_shapes_answers_equal_per_shape_answers(tmp_path):
     assert outs[True] == outs[False]
     assert outs[True].count(b"\n") == sum(1 + i % 2 for i in range(len(shapes)))
     m.close()
+
+
+def test_context0_calls_while_pipelined_requests_are_in_flight():
+    """model(batch) and answer() run on context 0 and the caller's stream while set_pipeline submissions are still in
+    flight, one of them on context 0's own stream: every result equals the same call made with no pipeline."""
+    from generativeimage2text_amd.model import CaptioningModel, AutoRegressiveBeamSearch
+    dec = AutoRegressiveBeamSearch(CFG.eos, max_steps=T, beam_size=1, fix_missing_prefix=True)
+    m = CaptioningModel(CFG, dec, precision="f32", max_batch=4)
+    m.engine.close()
+    m.engine = _engine("f32", 4)
+    m._loaded = True
+    g = torch.Generator().manual_seed(43)
+    batches = [torch.randn(3, 3, CFG.image_size, CFG.image_size, generator=g).cuda() for _ in range(5)]
+    qs = [[CFG.sos, 7], [CFG.sos, 8, 9], [CFG.sos, 5]]
+
+    def cpu(out):
+        return {k: v.cpu() for k, v in out.items()}
+    ref = [cpu(m({"image": b})) for b in batches]
+    ref_ans = m.answer(batches[1][:1], qs)
+    m.set_pipeline(4)
+    pending = [m.submit({"image": b}) for b in batches]              # the fifth goes to context 0 behind the first
+    fwd = cpu(m({"image": batches[2]}))
+    ans = m.answer(batches[1][:1], qs)
+    got = [cpu(p.result()) for p in pending]
+    for want, have in zip(ref + [ref[2]], got + [fwd]):
+        assert torch.equal(want["predictions"], have["predictions"]) and torch.equal(want["logprobs"], have["logprobs"])
+    assert ans == ref_ans
+    m.close()

@@ -862,3 +862,42 @@ def test_decode_pool_writes_the_pixels_pil_decodes(tmp_path):
             pool.next_result(timeout=60)
     finally:
         pool.close()
+
+
+def test_format_predictions_batch_prefix():
+    """The batch-uniform form (model(batch)): early-EOS rule, then the prefix stripped along dim 1."""
+    fmt = model.format_predictions
+    tok = torch.tensor([[101, 5, 6, 102, 102], [101, 7, 102, 102, 102]])
+    lp = torch.tensor([-1.0, -2.0])
+    p, l = fmt(tok, lp, (3, 0), None, "autoregressive")              # [CLS] only, nothing stripped
+    assert p.tolist() == [[101, 5, 6], [101, 7, 102]] and l.tolist() == [-1.0, -2.0]
+    p, l = fmt(tok, lp, (5, 1), None, "trie")                        # early EOS: the token after [CLS], logprobs [B, 1]
+    assert p.tolist() == [[5], [7]] and l.tolist() == [[-1.0], [-2.0]]
+    p, l = fmt(tok, lp, (5, 0), 2, "autoregressive")                 # full length, two-token prefix removed
+    assert p.tolist() == [[6, 102, 102], [102, 102, 102]] and l.tolist() == [-1.0, -2.0]
+    p, l = fmt(tok, lp, (4, 1), 2, "autoregressive")                 # early EOS behind a prefix: nothing left
+    assert p.shape == (2, 0) and l.tolist() == [[-1.0], [-2.0]]
+    p, l = fmt(tok, lp, (3, 0), 2, "generator")                      # generator: every position, logprobs [B, 1]
+    assert p.tolist() == [[6, 102, 102], [102, 102, 102]] and l.tolist() == [[-1.0], [-2.0]]
+    nk = torch.tensor([[[101, 1, 102], [101, 2, 102], [101, 3, 102]], [[101, 4, 102], [101, 5, 102], [101, 6, 102]]])
+    nl = torch.tensor([[-1.0, -2.0, -3.0], [-4.0, -5.0, -6.0]])
+    p, l = fmt(nk, nl, (3, 0), None, "generator")                    # num_keep_best = 3
+    assert torch.equal(p, nk) and torch.equal(l, nl)
+    p, l = fmt(nk, nl, (3, 0), 2, "generator")                       # the strip takes dim 1, the hypotheses
+    assert p.tolist() == [[[101, 3, 102]], [[101, 6, 102]]] and torch.equal(l, nl)
+
+
+def test_format_predictions_per_sentence_prefixes():
+    """The per-sentence form (answers, ragged questions): each sentence's own (length, early) and prefix."""
+    fmt = model.format_predictions
+    tok = torch.tensor([[101, 9, 4, 6, 102], [101, 8, 102, 102, 102], [101, 7, 6, 5, 3]])
+    lp = torch.tensor([-1.0, -2.0, -3.0])
+    sent = torch.tensor([[4, 0], [5, 1], [5, 0]])
+    p, l = fmt(tok, lp, sent, [3, 2, 1], "autoregressive")
+    assert p == [[6], [], [7, 6, 5, 3]] and l.tolist() == [[-1.0], [-2.0], [-3.0]]
+    p, l = fmt(tok, lp, sent, [3, 2, 1], "generator")                # the generator keeps every position
+    assert p == [[6, 102], [102, 102, 102], [7, 6, 5, 3]] and l.tolist() == [[-1.0], [-2.0], [-3.0]]
+    nk = torch.tensor([[[101, 1, 102], [101, 2, 102]], [[101, 3, 4], [101, 5, 102]]])
+    nl = torch.tensor([[-1.0, -2.0], [-3.0, -4.0]])
+    p, l = fmt(nk, nl, torch.tensor([[3, 0], [3, 0]]), [1, 2], "generator")    # num_keep_best = 2: dim 1 again
+    assert p == [[[101, 2, 102]], []] and l.tolist() == [[-1.0, -2.0], [-3.0, -4.0]]
