@@ -18,17 +18,32 @@ using namespace gitmi;
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+extern "C" int gitmi_operand_dtype(void);
+static const char* dtype_name(int dtype) {
+    return dtype == GITMI_DTYPE_F32 ? "fp32" : dtype == GITMI_DTYPE_BF16 ? "bf16" : dtype == GITMI_DTYPE_F16 ? "fp16" : "unknown";
+}
+// a dtype argument of a gitmi_op_* hook: fp32, or the 16-bit operand type of THIS build -- the other 16-bit code would make the
+// kernels read every element with the wrong encoding
+static int check_dtype(const char* op, const char* arg, int dtype) {
+    if (dtype == GITMI_DTYPE_F32 || dtype == gitmi_operand_dtype()) return 0;
+    return fail("%s: %s is %s (%d), but this library's 16-bit operands are %s (libgitmi%s.so)", op, arg, dtype_name(dtype), dtype,
+                dtype_name(gitmi_operand_dtype()), gitmi_operand_dtype() == GITMI_DTYPE_F16 ? "_f16" : "");
+}
+
 // ---- single-kernel entry points ------------------------------------------------------------
 extern "C" int gitmi_op_gemm(const void* A, const void* W, const float* bias, const float* residual, void* C, int M,
                              int N, int K, int lda, int ldc, int in_dtype, int out_dtype, int act, void* stream) {
     GemmArgs g{};
     g.A = A; g.W = W; g.bias = bias; g.res = residual; g.C = C;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldc; g.act = act;
+    RCK(check_dtype("op_gemm", "in_dtype", in_dtype));
     const bool in_f32 = in_dtype == GITMI_DTYPE_F32;
     if ((in_f32 && K % 16) || (!in_f32 && K % 64)) return fail("op_gemm: K must be a multiple of %d", in_f32 ? 16 : 64);
-    if (out_dtype == GITMI_DTYPE_F16) {      // fp16 rows out (a branch output / residual-stream rows of the bf16 engine mode)
-        if (in_f32) return fail("op_gemm: fp16 output needs bf16 operands");
+    if (out_dtype == GITMI_DTYPE_F16_STREAM) {      // fp16 residual-stream rows out, fp16 residual rows in (both builds)
+        if (in_f32) return fail("op_gemm: fp16 stream rows need 16-bit operands");
         g.out_f16 = 1;
+    } else {
+        RCK(check_dtype("op_gemm", "out_dtype", out_dtype));
     }
     HIPCK(launch_gemm(g, in_f32, out_dtype == GITMI_DTYPE_F32, (hipStream_t)stream));
     return 0;
@@ -63,11 +78,13 @@ extern "C" int gitmi_op_gemm_ln(const void* A, const void* W, const float* bias,
 }
 extern "C" int gitmi_op_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* y_t,
                                   float* y_f32, int rows, int D, int out_dtype, void* stream) {
+    if (y_t) RCK(check_dtype("op_layernorm", "out_dtype", out_dtype));
     HIPCK(launch_layernorm(x, D, gamma, beta, eps, nullptr, y_t, D, out_dtype == GITMI_DTYPE_F32, y_f32, D, rows, D, 0, 0,
                            0, (hipStream_t)stream));
     return 0;
 }
 extern "C" int gitmi_op_attention(const void* qkv, void* out, int B, int N, int H, int dtype, int impl, void* stream) {
+    RCK(check_dtype("op_attention", "dtype", dtype));
     const size_t esz = dtype == GITMI_DTYPE_F32 ? 4 : 2;
     const int D = H * 64;
     AttnFullArgs a{};
@@ -166,6 +183,7 @@ GITMI_EXP_EXPORT int gitmi_debug_set_gemm_impl(int impl) {
 extern "C" int gitmi_op_attn_decode(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
                                     const int* kv_src, void* out, int B, int H, int N_img, int T_max, int pos, int beams,
                                     int dtype, int dbg, void* stream) {
+    RCK(check_dtype("op_attn_decode", "dtype", dtype));
     AttnDecodeArgs a{};
     a.qkv = qkv; a.img_k = img_k; a.img_v = img_v; a.txt_k = txt_k; a.txt_v = txt_v; a.out = out;
     a.kv_src = kv_src; a.ld_src = T_max; a.d = H * 64; a.N_img = N_img; a.T_max = T_max; a.pos = pos; a.beams = beams;
@@ -176,12 +194,12 @@ extern "C" int gitmi_op_attn_decode(const void* qkv, const void* img_k, const vo
         HIPCK(launch_attn_decode(a, B, H, true, (hipStream_t)stream));
         return 0;
     }
-    // bf16: img_k / img_v are the MFMA operand layouts written by gitmi_op_kv_repack (keys padded to 32)
+    // 16-bit: img_k / img_v are the MFMA operand layouts written by gitmi_op_kv_repack (keys padded to 32)
     a.N_pad = round_up(N_img, 32);
     HIPCK(launch_attn_decode_mfma(a, B, H, (hipStream_t)stream));
     return 0;
 }
-// image-row K/V of the prefill ([B*N, 3*H*64] packed q|k|v, bf16) -> the decode layouts of kernels_attn_decode.hip:
+// image-row K/V of the prefill ([B*N, 3*H*64] packed q|k|v, 16-bit operands) -> the decode layouts of kernels_attn_decode.hip:
 // kf, vt: [B][H][round_up(N, 32)][64] each
 extern "C" int gitmi_op_kv_repack(const void* qkv_rows, void* kf, void* vt, int B, int N, int H, void* stream) {
     HIPCK(launch_kv_repack_frag(qkv_rows, kf, vt, B, N, round_up(N, 32), H, H * 64, (hipStream_t)stream));

@@ -19,6 +19,7 @@ LIB_PATH_EXP = os.path.join(_HERE, "libgitmi_exp.so")         # measurement buil
 
 PREC_BF16, PREC_F32 = 0, 1
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
+DTYPE_F16_STREAM = 3      # gitmi_op_gemm's out_dtype only: fp16 residual-stream rows, fp16 residual rows in
 SEARCH_AUTOREGRESSIVE, SEARCH_GENERATOR, SEARCH_TRIE = 0, 1, 2
 SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given sentences (Engine.score)
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
@@ -188,6 +189,21 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _torch_dtype_code(t: torch.Tensor) -> int:
     return {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}[t.dtype]
+
+
+_OPERAND_LIBS = {torch.bfloat16: "bf16", torch.float16: "f16"}
+
+
+def _op_library(*dtypes: torch.dtype, fp32_ok: bool = False) -> C.CDLL:
+    """The library of a gitmi_op_* call, picked by the dtype of its 16-bit tensors: fp16 -> libgitmi_f16.so, bf16 ->
+    libgitmi.so (or the measurement build, use_experiment_build).  They must share one dtype; fp32 ones are skipped, and an
+    all-fp32 call (fp32_ok) goes to libgitmi.so."""
+    dts = set(dtypes) - {torch.float32}
+    if not dts and fp32_ok:
+        return load_library()
+    if len(dts) != 1 or next(iter(dts)) not in _OPERAND_LIBS:
+        raise GitmiError(f"operands must all be bf16 or all fp16, got {sorted(str(d) for d in dts) or ['float32']}")
+    return load_library(_OPERAND_LIBS[dts.pop()])
 
 
 RAGGED_DESC_BYTES = 256    # the descriptor block of a ragged input is padded to this size (include/gitmi.h)
@@ -640,14 +656,28 @@ class Engine:
 # ---- single-kernel entry points (unit parity tests) -----------------------------------------------
 def op_gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
             residual: Optional[torch.Tensor] = None, act: int = ACT_NONE,
-            out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    lib = load_library()
+            out_dtype: torch.dtype = torch.float32, stream_rows: bool = False) -> torch.Tensor:
+    """C = act(A W^T + bias) + residual in one of three epilogues: fp32 (out_dtype float32), the operands' 16-bit type
+    (out_dtype = A.dtype), or fp16 residual-stream rows (stream_rows=True: C fp16 and the residual fp16 [M, N] rows).
+    fp16 operands run in libgitmi_f16.so, bf16 ones in libgitmi.so; fp32 A / W with a 16-bit out_dtype run in that type's
+    library."""
     assert A.is_cuda and W.is_cuda and A.dtype == W.dtype and A.is_contiguous() and W.is_contiguous()
     M, K = A.shape
     N = W.shape[0]
+    if stream_rows:
+        if A.dtype == torch.float32:
+            raise GitmiError("op_gemm: fp16 stream rows need 16-bit operands")
+        if residual is not None and (residual.dtype != torch.float16 or residual.shape != (M, N) or not residual.is_contiguous()):
+            raise GitmiError("op_gemm: the stream form's residual is contiguous fp16 [M, N] rows")
+        lib, out_code, out_dtype = _op_library(A.dtype), DTYPE_F16_STREAM, torch.float16
+    else:
+        if residual is not None and residual.dtype != torch.float32:
+            raise GitmiError("op_gemm: the residual is fp32 (fp16 rows: stream_rows=True)")
+        lib = _op_library(A.dtype, out_dtype, fp32_ok=True)
+        out_code = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}[out_dtype]
     out = torch.empty(M, N, device=A.device, dtype=out_dtype)
     _ck(lib.gitmi_op_gemm(A.data_ptr(), W.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, K, N,
-                          _torch_dtype_code(A), _torch_dtype_code(out), act, _stream()), lib)
+                          _torch_dtype_code(A), out_code, act, _stream()), lib)
     return out
 
 
@@ -671,7 +701,8 @@ def op_gemm_ln(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], *
 
 def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
                  out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    lib = load_library()
+    """y = LayerNorm(x) of fp32 rows, written in out_dtype: fp32, or a 16-bit type (run in that type's library)."""
+    lib = _op_library(out_dtype, fp32_ok=True)
     rows, D = x.shape
     out = torch.empty(rows, D, device=x.device, dtype=out_dtype)
     _ck(lib.gitmi_op_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), None, rows, D,
@@ -680,7 +711,7 @@ def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
 
 
 def op_attention(qkv: torch.Tensor, B: int, N: int, H: int, impl: int) -> torch.Tensor:
-    lib = load_library()
+    lib = _op_library(qkv.dtype, fp32_ok=True)
     assert qkv.is_cuda and qkv.is_contiguous() and qkv.shape == (B * N, 3 * H * 64)
     out = torch.empty(B * N, H * 64, device=qkv.device, dtype=qkv.dtype)
     _ck(lib.gitmi_op_attention(qkv.data_ptr(), out.data_ptr(), B, N, H, _torch_dtype_code(qkv), impl, _stream()), lib)
@@ -723,11 +754,12 @@ def _pad_vec(v: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
 def op_dgemm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, colsum: Optional[torch.Tensor] = None,
              stats: Optional[torch.Tensor] = None, eps: float = 1e-12, act: int = ACT_NONE,
              frag_out: bool = False, packed: bool = False, strips_per_wg: int = 0) -> torch.Tensor:
-    """Decode-chain GEMM, QKV / FFN1 form (kernels_dgemm.hip): bf16 A [M,K], W [N,K] -> bf16 [M,N].
+    """Decode-chain GEMM, QKV / FFN1 form (kernels_dgemm.hip): 16-bit A [M,K], W [N,K] -> [M,N] in the same type (bf16:
+    libgitmi.so, fp16: libgitmi_f16.so).
     With `stats` ([K/16][M][2] strip partials of the raw rows behind A) the LayerNorm in front of the GEMM is folded:
     out = rstd * (A W^T - mean * colsum) + bias.  Operands are given row-major and packed here (packed=True: A, W are
     already fragment-major and M, N are taken from bias / stats)."""
-    lib = load_library()
+    lib = _op_library(A.dtype, W.dtype)
     if packed:
         Af, Wf, M, N, K = A, W, int(A.shape[0]), int(bias.numel()), int(A.shape[1])
         if stats is not None:
@@ -736,7 +768,7 @@ def op_dgemm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, colsum: Optio
         M, K = A.shape
         N = W.shape[0]
         Af, Wf = to_frag(A, 64), to_frag(W)
-    out = torch.empty((M + 15) // 16 * 16 if frag_out else M, N, device=A.device, dtype=torch.bfloat16)
+    out = torch.empty((M + 15) // 16 * 16 if frag_out else M, N, device=A.device, dtype=A.dtype)
     strips = 0 if stats is None else int(stats.shape[0])
     _ck(lib.gitmi_op_dgemm(Af.data_ptr(), Wf.data_ptr(), bias.data_ptr(), _ptr(colsum), _ptr(stats), strips, eps,
                            out.data_ptr(), 1 if frag_out else 0, M, N, K, act, int(strips_per_wg), _stream()), lib)
@@ -747,13 +779,13 @@ def op_dgemm_res(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, res_x: to
                  res_stats: Optional[torch.Tensor] = None, res_gamma: Optional[torch.Tensor] = None,
                  res_beta: Optional[torch.Tensor] = None, res_eps: float = 1e-12, packed: bool = False):
     """Decode-chain GEMM, N = hidden form: x = A W^T + bias + residual, where the residual is `res_x` itself or
-    LayerNorm(res_x) rebuilt from its strip partials.  -> (x fp32 [M,N], bf16 copy, strip partials of x)."""
-    lib = load_library()
+    LayerNorm(res_x) rebuilt from its strip partials.  -> (x fp32 [M,N], copy in A's 16-bit type, strip partials of x)."""
+    lib = _op_library(A.dtype, W.dtype)
     M, N = res_x.shape
     K = A.shape[1]
     Af, Wf = (A, W) if packed else (to_frag(A, 64), to_frag(W))
     x = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    xb = torch.empty((M + 15) // 16 * 16, N, device=A.device, dtype=torch.bfloat16)
+    xb = torch.empty((M + 15) // 16 * 16, N, device=A.device, dtype=A.dtype)
     st = torch.empty(N // 16, M, 2, device=A.device, dtype=torch.float32)
     strips = 0 if res_stats is None else int(res_stats.shape[0])
     _ck(lib.gitmi_op_dgemm_res(Af.data_ptr(), Wf.data_ptr(), bias.data_ptr(), res_x.data_ptr(), _ptr(res_stats), strips,
@@ -768,8 +800,9 @@ def op_vocab_topm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mtop: in
                   rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0):
     """Vocabulary head with the fused running top-M / log-sum-exp: -> (part_val [M, nparts, slots], part_idx,
     part_lse [M, nparts, 2] = (max, sum exp), logits [M, V] or None).  packed=True: A / W fragment-major (W rows and
-    bias / colsum padded to a multiple of cols_per_wg), `rows` = M, `V` = vocabulary size."""
-    lib = load_library()
+    bias / colsum padded to a multiple of cols_per_wg), `rows` = M, `V` = vocabulary size.  A / W: bf16 or fp16 (that
+    type's library)."""
+    lib = _op_library(A.dtype, W.dtype)
     K = A.shape[1]
     V = int(bias.numel()) if V is None else int(V)
     if packed:
@@ -799,11 +832,12 @@ def set_gemm_impl(impl: int) -> None:
 
 
 def op_attn_decode(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, pos, beams, dbg=0):
-    """qkv [R,3d]; img_k/img_v [B,H,N_img,64]; txt_k/txt_v [R,T_max,d] (position pos gets appended); kv_src int32 [R,T_max]."""
-    lib = load_library()
+    """qkv [R,3d]; img_k/img_v [B,H,N_img,64]; txt_k/txt_v [R,T_max,d] (position pos gets appended); kv_src int32 [R,T_max].
+    All fp32, or all in one 16-bit type (that type's library; image K/V head-major or already in kv_repack's layouts)."""
+    lib = _op_library(qkv.dtype, img_k.dtype, img_v.dtype, txt_k.dtype, txt_v.dtype, fp32_ok=True)
     R, d = B * beams, H * 64
     out = torch.empty(R, d, device=qkv.device, dtype=qkv.dtype)
-    if qkv.dtype == torch.bfloat16 and img_k.dim() == 4:
+    if qkv.dtype != torch.float32 and img_k.dim() == 4:
         # head-major [B,H,N,64] given: build the prefill-layout rows and repack into the matrix-core layouts
         img_k, img_v = kv_repack(img_k, img_v)
     _ck(lib.gitmi_op_attn_decode(qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(),
@@ -878,16 +912,17 @@ def op_sample_rows(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 
 
 
 def kv_repack(img_k: torch.Tensor, img_v: torch.Tensor):
-    """Head-major bf16 image K/V [B,H,N,64] -> the decode layouts of kernels_attn_decode.hip (flat [B*H*Npad*64] each)."""
-    lib = load_library()
+    """Head-major 16-bit image K/V [B,H,N,64] -> the decode layouts of kernels_attn_decode.hip (flat [B*H*Npad*64] each, same
+    dtype; bf16: libgitmi.so, fp16: libgitmi_f16.so)."""
+    lib = _op_library(img_k.dtype, img_v.dtype)
     B, H, N, _ = img_k.shape
     d = H * 64
-    rows = torch.zeros(B * N, 3 * d, device=img_k.device, dtype=torch.bfloat16)
+    rows = torch.zeros(B * N, 3 * d, device=img_k.device, dtype=img_k.dtype)
     rows[:, d:2 * d] = img_k.permute(0, 2, 1, 3).reshape(B * N, d)
     rows[:, 2 * d:] = img_v.permute(0, 2, 1, 3).reshape(B * N, d)
     Np = (N + 31) // 32 * 32
-    kf = torch.empty(B * H * Np * 64, device=img_k.device, dtype=torch.bfloat16)
-    vt = torch.empty(B * H * Np * 64, device=img_k.device, dtype=torch.bfloat16)
+    kf = torch.empty(B * H * Np * 64, device=img_k.device, dtype=img_k.dtype)
+    vt = torch.empty(B * H * Np * 64, device=img_k.device, dtype=img_k.dtype)
     _ck(lib.gitmi_op_kv_repack(rows.data_ptr(), kf.data_ptr(), vt.data_ptr(), B, N, H, _stream()), lib)
     return kf, vt
 

@@ -39,6 +39,8 @@ extern "C" {
 #define GITMI_DTYPE_F32  0
 #define GITMI_DTYPE_BF16 1
 #define GITMI_DTYPE_F16  2
+/* gitmi_op_gemm's out_dtype only: fp16 residual-stream rows (C fp16 [M, ldc]; the residual, if any, is fp16 rows too) */
+#define GITMI_DTYPE_F16_STREAM 3
 
 /* search strategies (layers/decoder.py) */
 #define GITMI_SEARCH_AUTOREGRESSIVE 0  /* AutoRegressiveBeamSearch   decoder.py:208-440  */
@@ -309,9 +311,13 @@ int  gitmi_profile_read(gitmi_engine* e, gitmi_profile* out);   /* synchronises 
 int  gitmi_set_graph(gitmi_engine* e, int on);
 
 /* ---- single-kernel entry points (unit parity tests through the C ABI).
- * dtype arguments are GITMI_DTYPE_F32 / GITMI_DTYPE_BF16. ------------------------------- */
+ * dtype arguments are GITMI_DTYPE_F32 or the library's 16-bit operand type, gitmi_operand_dtype(): GITMI_DTYPE_BF16 in
+ * libgitmi.so, GITMI_DTYPE_F16 in libgitmi_f16.so.  The other 16-bit code is refused (the call fails, gitmi_last_error names
+ * it).  16-bit tensors of the hooks without a dtype argument (dgemm, dgemm_res, vocab_topm, kv_repack) are in the
+ * operand type. ------------------------------- */
 /* C[M,N] = act(A[M,K] * W[N,K]^T + bias) (+ residual);  act: 0 none, 1 QuickGELU, 2 erf-GELU.
- * A, W in `in_dtype`; bias/residual fp32 (may be NULL); C in `out_dtype`. K % 64 == 0. */
+ * A, W in `in_dtype`; bias fp32 (may be NULL); C in `out_dtype`. K % 64 == 0.  The residual (may be NULL) is fp32 rows,
+ * except with out_dtype GITMI_DTYPE_F16_STREAM (16-bit operands, either library): C and the residual are fp16 rows. */
 int  gitmi_op_gemm(const void* A, const void* W, const float* bias, const float* residual,
                    void* C, int M, int N, int K, int lda, int ldc, int in_dtype, int out_dtype,
                    int act, void* stream);
@@ -332,11 +338,11 @@ int  gitmi_op_layernorm(const float* x, const float* gamma, const float* beta, f
                         void* y_t, float* y_f32, int rows, int D, int out_dtype, void* stream);
 
 /* full (unmasked) multi-head attention over packed qkv [B*N, 3*D] (q|k|v, head h = cols h*64..);
- * out [B*N, D].  impl: 0 = reference VALU kernel, 1 = MFMA flash kernel (bf16 only). */
+ * out [B*N, D].  impl: 0 = reference VALU kernel, 1 = MFMA flash kernel (16-bit operands only). */
 int  gitmi_op_attention(const void* qkv, void* out, int B, int N, int H, int dtype, int impl,
                         void* stream);
 
-/* decode-step GEMM chain (kernels_dgemm.hip; bf16 A [M,K], W [N,K], K % 32 == 0).  BOTH operands are FRAGMENT-MAJOR:
+/* decode-step GEMM chain (kernels_dgemm.hip; 16-bit operand A [M,K], W [N,K], K % 32 == 0).  BOTH operands are FRAGMENT-MAJOR:
  * 16-row x 32-k tiles in MFMA operand order, element (row, k) at
  *     (((row/16)*(K/32) + k/32)*64 + ((k%32)/8)*16 + row%16)*8 + k%8,   rows padded to a multiple of 16
  * (weights: zero rows; bias / colsum of the vocabulary head padded to a multiple of cols_per_wg), so that every
@@ -345,10 +351,11 @@ int  gitmi_op_attention(const void* qkv, void* out, int B, int N, int H, int dty
  * (modeling_bert.py:171-178, 243-250) runs WITHOUT LayerNorm launches: the N = hidden GEMMs emit the pre-LayerNorm
  * sum and per-16-column-strip row partials (sum, sum of squares), the consumer GEMM folds the LayerNorm.
  * stats layout: fp32 [strips][M][2].
- *   gitmi_op_dgemm     : C bf16 [M,N] = act( LN_fold(A) W^T + bias ); stats == NULL: plain A W^T + bias.
- *                        With stats: W must be bf16(W . gamma), bias = beta W^T + b, colsum[n] = sum_k W'[n][k].
+ *   gitmi_op_dgemm     : C 16-bit [M,N] = act( LN_fold(A) W^T + bias ); stats == NULL: plain A W^T + bias.
+ *                        With stats: W must be W . gamma rounded to the operand type, bias = beta W^T + b,
+ *                        colsum[n] = sum_k W'[n][k].
  *   gitmi_op_dgemm_res : x = A W^T + bias + r,  r = res_x (res_stats == NULL) or LayerNorm(res_x; res_gamma, res_beta)
- *                        rebuilt from res_stats; writes x fp32, its bf16 copy and stats_out [N/16][M][2].  N % 16 == 0.
+ *                        rebuilt from res_stats; writes x fp32, its 16-bit copy and stats_out [N/16][M][2].  N % 16 == 0.
  *                        strips_per_wg (QKV / FFN1 form, 33..64 rows): 16-column strips a workgroup computes one after
  *                        the other -- 0 / 1 (one workgroup per strip), 2, 4 or 6; results do not depend on it. */
 int  gitmi_op_dgemm(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
@@ -373,12 +380,12 @@ int  gitmi_op_vocab_topm(const void* A, const void* W, const float* bias, const 
 /* decode attention for one new text position (unit parity / timing): qkv [R,3d] (R = B*beams), text caches
  * [R][T_max][d] (position `pos` is appended), kv_src int32 [R][T_max], out [R,d].
  *   fp32 : image K/V head-major [B][H][N_img][64] (scalar kernel);
- *   bf16 : image K/V in the matrix-core operand layouts written by gitmi_op_kv_repack (keys padded to 32).
+ *   16-bit: image K/V in the matrix-core operand layouts written by gitmi_op_kv_repack (keys padded to 32).
  * dbg: 0, or timing-experiment bits of the fp32 kernel (results undefined). */
 int  gitmi_op_attn_decode(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
                           const int* kv_src, void* out, int B, int H, int N_img, int T_max, int pos, int beams,
                           int dtype, int dbg, void* stream);
-/* bf16 image-row K/V of the decoder prefill ([B*N, 3*H*64] packed q|k|v) -> decode layouts kf / vt, each
+/* 16-bit image-row K/V of the decoder prefill ([B*N, 3*H*64] packed q|k|v) -> decode layouts kf / vt, each
  * [B][H][round_up(N,32)][64]: K fragment-major (a wave's MFMA operand is one contiguous 1-KiB read), V transposed with
  * the key slots ordered so that softmax probabilities feed the P V product without leaving their registers. */
 int  gitmi_op_kv_repack(const void* qkv_rows, void* kf, void* vt, int B, int N, int H, void* stream);

@@ -292,6 +292,18 @@ def test_vocab_head_fused_topm(M, V, K, mtop, fold):
     lg = lg.cpu()
     tol = (2.5e-2 if fold else 2e-4) * max(1.0, ref.abs().max().item())
     assert (lg.double() - ref).abs().max().item() < tol
+    if fold:
+        _check_vocab_lists(lambda **kw: E.op_vocab_topm(x.bfloat16().cuda(), Wf.cuda(), bf.cuda(), mtop, cols, cs.cuda(),
+                                                        E.strip_stats(x.cuda()), 1e-12, sup.cuda(), **kw), lg, pv, pi, pl, sup, mtop, cols)
+    else:
+        _check_vocab_lists(lambda **kw: E.op_vocab_topm(x.bfloat16().cuda(), W.bfloat16().cuda(), bias.cuda(), mtop, cols,
+                                                        suppress_tok=sup.cuda(), **kw), lg, pv, pi, pl, sup, mtop, cols)
+
+
+def _check_vocab_lists(head, lg, pv, pi, pl, sup, mtop, cols):
+    """The per-column-block lists and log-sum-exp of a logits-materialising head call (pv, pi, pl, logits lg on the host)
+    against those logits, then the lists of head(want_logits=False, max_wgs=n) -- the decode-loop kernels -- bit for bit."""
+    M = lg.shape[0]
     # the lists: built from the suppressed logits (decoder.py:330)
     sl = lg.clone()
     sl[torch.arange(M), sup.long()] = -10000.0
@@ -312,12 +324,7 @@ def test_vocab_head_fused_topm(M, V, K, mtop, fold):
     assert (got - lse).abs().max().item() < 1e-4
     # the decode-loop kernels (no logits output), every grid size
     for max_wgs in (0, 1000, (nparts + 2) // 3, max(1, nparts - 1), (nparts + 7) // 8, 60):
-        if fold:
-            qv, qi, ql, _ = E.op_vocab_topm(x.bfloat16().cuda(), Wf.cuda(), bf.cuda(), mtop, cols, cs.cuda(), E.strip_stats(x.cuda()),
-                                            1e-12, sup.cuda(), False, max_wgs=max_wgs)
-        else:
-            qv, qi, ql, _ = E.op_vocab_topm(x.bfloat16().cuda(), W.bfloat16().cuda(), bias.cuda(), mtop, cols, suppress_tok=sup.cuda(),
-                                            want_logits=False, max_wgs=max_wgs)
+        qv, qi, ql, _ = head(want_logits=False, max_wgs=max_wgs)
         k = min(mtop, cols)
         assert torch.equal(qv.cpu()[:, :, :k], pv[:, :, :k]), max_wgs
         assert torch.equal(qi.cpu().long()[:, :, :k], pi[:, :, :k]), max_wgs
@@ -331,6 +338,10 @@ def test_vocab_head_topm_tie_order(M, mtop):
     positional insertion (kernels_dgemm.hip: topm_insert; round 5) must share with the bubble insertion it replaced and with
     the 4-lane merge -- in all three kernel forms (logits-materialising, one-row-block, row-block-walking) and for walked
     column blocks.  Integer-valued operands make the logits exact integers with hundreds of ties per 128-column block."""
+    _check_tie_order(M, mtop, torch.bfloat16)
+
+
+def _check_tie_order(M, mtop, dtype):
     from generativeimage2text_amd import engine as E
     V, K, cols = 1000, 768, 128
     g = torch.Generator().manual_seed(7)
@@ -341,7 +352,7 @@ def test_vocab_head_topm_tie_order(M, mtop):
     assert max(r.unique().numel() for r in ref) < V // 4               # every row: plenty of ties
     order = torch.sort(ref, dim=1, descending=True, stable=True)       # stable: the lower column first among equals
     for want_logits, max_wgs in ((True, 0), (False, 0), (False, 3), (False, 60)):
-        pv, pi, pl, lg = E.op_vocab_topm(x.bfloat16().cuda(), W.bfloat16().cuda(), bias.cuda(), mtop, cols, want_logits=want_logits,
+        pv, pi, pl, lg = E.op_vocab_topm(x.to(dtype).cuda(), W.to(dtype).cuda(), bias.cuda(), mtop, cols, want_logits=want_logits,
                                          max_wgs=max_wgs)
         if want_logits:
             assert torch.equal(lg.cpu().double(), ref)
