@@ -1,4 +1,4 @@
-// Error reporting shared by the translation units that implement the C ABI (engine.hip, abi_ops.hip).
+// Error reporting shared by the translation units that implement the C ABI (engine.hip, engine_weights.hip, abi_ops.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

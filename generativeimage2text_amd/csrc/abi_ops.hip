@@ -1,6 +1,6 @@
 // Unit entry points of the C ABI (include/gitmi.h: gitmi_op_*, gitmi_preprocess_*): ONE launch each on caller-supplied
 // buffers -- what the GPU op tests and tools/ call -- plus the kernel-selection hooks of the measurement build.  No engine
-// state: everything that needs a gitmi_engine lives in engine.hip.
+// state: everything that needs a gitmi_engine lives in engine.hip / engine_weights.hip.
 #include "../../include/gitmi.h"
 #include "abi_common.h"
 #include "launchers.h"
@@ -281,4 +281,53 @@ extern "C" int gitmi_preprocess_image_to(const uint8_t* rgb_hwc, int H, int W, i
         return fail("preprocess: workspace must hold H * %d * 3 bytes", out_w);
     HIPCK(launch_resize_crop_norm(rgb_hwc, H, W, out_h, out_w, 0, 0, out_h, out_w, tmp, out_chw, (hipStream_t)stream));
     return 0;
+}
+
+// ---- op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py) -----------------------
+// attention: qkv [Q * Lp][3 H 64] text rows, img_kv [B * N_img][3 H 64] prefill rows, image_of int32 [Q] -> out [Q * Lp][H 64]
+// (dtype GITMI_DTYPE_F32: the fp32 kernel of the parity mode; the build's 16-bit operand dtype: the MFMA kernel)
+GITMI_EXP_EXPORT int gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H,
+                                            int N_img, int Lp, int dtype, void* stream) {
+    if (!qkv || !img_kv || !image_of || !out) return fail("debug_score_attn: null argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_attn: dtype %d not served by this build", dtype);
+    HIPCK(launch_score_attn(qkv, img_kv, image_of, out, Q, H, H * 64, N_img, Lp, 0.125f, dtype == GITMI_DTYPE_F32,
+                            (hipStream_t)stream));
+    return 0;
+}
+// head + combine: logits z = A [M][K] W [V][K]^T + bias (never stored in the 16-bit form) -> out fp32 [M][2] =
+// (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) for rows with tgt[m] >= 0, 0 elsewhere.  Synchronises the stream.
+GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K,
+                                            int dtype, float* out, void* stream) {
+    if (!A || !W || !bias || !tgt || !out || M < 1 || V < 2 || K < 32 || K % 32) return fail("debug_score_head: bad argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_head: dtype %d not served by this build", dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const bool f32 = dtype == GITMI_DTYPE_F32;
+    const int ntiles = f32 ? 1 : score_head_tiles(V);
+    const int ldl = round_up(V, 8);
+    float4* part = nullptr; float* zt = nullptr; float2* o2 = nullptr; int* bad = nullptr; float* logits = nullptr;
+    int rc = 0;
+    auto body = [&]() -> int {
+        HIPCK(hipMalloc(&part, (size_t)M * ntiles * sizeof(float4)));
+        HIPCK(hipMalloc(&zt, (size_t)M * sizeof(float)));
+        HIPCK(hipMalloc(&o2, (size_t)(M + 1) * sizeof(float2)));
+        HIPCK(hipMalloc(&bad, (size_t)M * sizeof(int)));
+        if (f32) {
+            HIPCK(hipMalloc(&logits, (size_t)M * ldl * sizeof(float)));
+            GemmArgs g{};
+            g.A = A; g.W = W; g.bias = bias; g.C = logits; g.M = M; g.N = V; g.K = K; g.lda = K; g.ldc = ldl;
+            HIPCK(launch_gemm(g, true, true, s));
+            HIPCK(launch_score_rowstats(logits, ldl, V, tgt, 0, M, part, zt, s));
+        } else {
+            HIPCK(launch_score_head(A, K, W, bias, tgt, M, V, K, part, zt, s));
+        }
+        HIPCK(hipMemsetAsync(o2, 0, (size_t)(M + 1) * sizeof(float2), s));
+        // one position per "sentence" (Lp = ld = 1): row m lands in o2[m + 1]
+        HIPCK(launch_score_combine(part, ntiles, zt, tgt, M, 1, 1, V, o2, bad, s));
+        HIPCK(hipMemcpyAsync(out, o2 + 1, (size_t)M * sizeof(float2), hipMemcpyDefault, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    rc = body();
+    hipFree(part); hipFree(zt); hipFree(o2); hipFree(bad); hipFree(logits);
+    return rc;
 }

@@ -1,26 +1,19 @@
-// Host side of the GIT engine: weight ingest/repack, workspaces, the forward schedule
-// (ViT encode -> decoder prefill over image tokens -> KV-cached decode steps -> device search)
-// and the C ABI of include/gitmi.h.
+// Host side of the GIT engine: the forward schedule (ViT encode -> decoder prefill over image tokens -> KV-cached
+// decode steps -> device search), generate / graph, scoring, setters, profiling and the C ABI of include/gitmi.h.
+// The state lives in engine_state.h; weight ingest/repack, clones and workspaces in engine_weights.hip.
 //
 // Schedule vs. the reference (SURVEY.md headline facts 2/3): the reference re-runs the visual
 // projection and all decoder layers over [image | text] tokens at every decode step and for every
 // beam copy.  Image rows never attend to text (mask top-right = -inf) and text is causal, so
 // computing the image rows once per image and caching K/V is exact; this engine does that.
 #include "../../include/gitmi.h"
-#include "abi_common.h"
-#include "launchers.h"
-
-#include <hip/hip_runtime.h>
+#include "engine_state.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <string>
-#include <tuple>
-#include <vector>
 
 using namespace gitmi;
 
@@ -41,215 +34,6 @@ int gitmi::fail(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return 1;
-}
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-struct HostTensor {
-    std::vector<float> data;
-    std::vector<int64_t> shape;
-    float amax = 0.f;                   // max |value| (gitmi_load_tensor; every value is finite)
-    size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
-
-struct VitLayerW {
-    void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
-    float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
-    float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr;
-    // LayerNorm folded into the consumer GEMM (fp16-operand build, kernels_gemm10.hip LNF): row-major f16(W . gamma),
-    // beta W^T + bias, column sums of the rounded matrix
-    void *wqkv_f = nullptr; float *bqkv_f = nullptr, *cs_qkv = nullptr;   // ln_1
-    void *w1_f = nullptr;   float *b1_f = nullptr,   *cs_1 = nullptr;     // ln_2
-};
-struct DecLayerW {
-    void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
-    float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
-    float *lnag = nullptr, *lnab = nullptr, *lnog = nullptr, *lnob = nullptr;
-    // decode chain (bf16 mode): the LayerNorm in front of a GEMM folded into its weights (kernels_dgemm.hip):
-    // W' = bf16(W . gamma), folded constant beta W^T + bias, column sums of W'
-    // All decode-chain matrices are fragment-major copies (gitmi_common.h frag_offset), rows padded to 16.
-    void *wqkv_f = nullptr; float *bqkv_f = nullptr, *cs_qkv = nullptr;   // previous layer's output LayerNorm (layer 0: plain, cs_qkv == nullptr)
-    void *w1_f = nullptr;   float *b1_f = nullptr,   *cs_1 = nullptr;     // this layer's attention-output LayerNorm
-    void *wo_p = nullptr, *w2_p = nullptr;                                 // plain, packed
-    // prefill (image rows, large M): the same two folds in ROW-MAJOR layout for gemm_p8_kernel (layer 0: the visual projection's LayerNorm)
-    void *wqkv_pf = nullptr; float *bqkv_pf = nullptr, *cs_qkv_p = nullptr;
-    void *w1_pf = nullptr;   float *b1_pf = nullptr,   *cs_1_p = nullptr;
-};
-
-struct TimedSpan { hipEvent_t a, b; int tag; double flops; };
-enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM_OTHER = 11, TAG_STEP = 20 };
-
-// hipGraph cache key of gitmi_generate / gitmi_generate_prefixed: everything the captured launch sequence depends on
-struct GraphKey {
-    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb; double lp;
-    int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
-    static GraphKey of(int B, int Q, int F, int P, int H, int W, bool prefixed, bool ident, bool temb, const gitmi_search& sp) {
-        return {B, Q, F, P, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, H, W, prefixed ? 1 : 0, ident ? 1 : 0,
-                temb ? 1 : 0, sp.length_penalty, sp.do_sample, sp.top_k, sp.num_keep_best > 1 ? sp.num_keep_best : 1, sp.top_p,
-                sp.temperature, sp.repetition_penalty, sp.seed};
-    }
-    auto fields() const { return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, lp, smp, top_k, nh, top_p, temp, rp, seed); }
-    bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
-};
-
-struct gitmi_engine {
-    gitmi_config cfg{};
-    int device = 0;
-    bool f32 = false;
-    size_t esz = 2;
-    bool finalized = false;
-    gitmi_engine* parent = nullptr;   // clone: packed weights are borrowed from this engine
-    int attn_impl = 1;          // 1 = MFMA flash kernel for full attention (bf16), 0 = VALU kernel
-
-    std::map<std::string, HostTensor> host_w;
-    std::vector<void*> allocs;
-
-    // derived dims: N/gh/gw/H/W describe the CURRENT input resolution (gitmi_set_image_shape); *_nat the stored grid
-    int N = 0, gh = 0, gw = 0, H = 0, W = 0, Kp = 0, Kp_pad = 0;
-    int N_nat = 0, g_nat = 0, Nmax = 0;
-    size_t max_pixels = 0;
-    float* pos_var = nullptr;          // [Nmax, D] positional table resized to the current grid
-    const float* pos_cur = nullptr;    // pos (native grid) or pos_var
-    // ragged batches (gitmi_set_image_shape(e, 0, 0)): every image of a call has its own size, read from the input's
-    // descriptor on the device; image b owns rows [b * Nmax, b * Nmax + ntok[b]) of the encoder / prefill blocks (N = Nmax)
-    bool ragged = false;
-    int4* rg_meta = nullptr;           // [max_batch] {h, w, ntok, rejected} of the staged call
-    int* rg_ntok = nullptr;            // [max_batch] token rows of every image (class token included)
-
-    // packed weights
-    void* conv_w = nullptr;
-    float *cls = nullptr, *pos = nullptr, *lnpre_g = nullptr, *lnpre_b = nullptr, *lnpost_g = nullptr, *lnpost_b = nullptr;
-    std::vector<VitLayerW> vit;
-    std::vector<float*> temb;
-    void* vp_w = nullptr;
-    float *vp_b = nullptr, *vp_lng = nullptr, *vp_lnb = nullptr;
-    float *words_f = nullptr, *positions_f = nullptr, *emb_lng = nullptr, *emb_lnb = nullptr;
-    std::vector<DecLayerW> dec;
-    void* out_w = nullptr;
-    float* out_b = nullptr;
-    void* out_w_f = nullptr;            // vocabulary head folded with the last layer's output LayerNorm (bf16 mode)
-    float *out_b_f = nullptr, *cs_out = nullptr;
-    double dec_weight_bytes = 0;
-
-    // ViT workspaces (one frame of max_batch images at a time)
-    void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;
-    float *patch_out = nullptr, *v_x = nullptr;
-    // visual features [B, F*N, vfs]
-    void* feats = nullptr;
-    // prefill workspaces
-    float *p_y = nullptr, *p_hf = nullptr;
-    void *p_ht = nullptr, *p_ctx = nullptr, *p_u = nullptr;
-    std::vector<void*> img_kv;      // per layer [B*N_img, 3d] (prefill layout)
-    std::vector<void*> img_kh, img_vh;   // per layer head-major [B][H][N_img][64] (decode layout)
-    // decode workspaces
-    float *d_y = nullptr, *d_hf = nullptr, *logits = nullptr;
-    void *d_ht = nullptr, *d_qkv = nullptr, *d_ctx = nullptr, *d_u = nullptr;
-    std::vector<void*> txt_k, txt_v;   // per layer [R_max, T_max, d]
-    int ldl = 0;
-    bool skinny = true;                 // bf16 decode steps through the folded-LayerNorm GEMM chain (kernels_dgemm.hip)
-    // decode chain workspaces: pre-LayerNorm sums of the two N = d GEMMs of a layer (fp32 + bf16) and their strip partials
-    float *xa_f = nullptr, *xo_f = nullptr;
-    void *xa_b = nullptr, *xo_b = nullptr;
-    float2 *stats_a = nullptr, *stats_o = nullptr;
-    // per-step candidate lists [R][nparts][slots] (+ (max, sum exp) per part)
-    float* part_val = nullptr; int* part_idx = nullptr; float2* part_lse = nullptr;
-    int vocab_cols = 128, vocab_nparts = 1;
-    // search
-    SearchState ss{};
-    int ss_cur = 0, ss_len = 0;
-    long long* start_dev = nullptr;     // [max_batch][max_text_len] start tokens of every sentence
-    int *plen_dev = nullptr, *img_of_dev = nullptr;
-    bool img_identity = true;           // sentence b attends to image b
-    // token trie of trie-constrained greedy decoding (gitmi_set_trie; trie_decoder.py) + one cursor per sentence
-    int *trie_off = nullptr, *trie_tok = nullptr, *trie_child = nullptr, *trie_cursor = nullptr;
-    bool trie_search = false;           // the current search is GITMI_SEARCH_TRIE
-    gitmi_search sample{};              // sampling parameters of the current search (do_sample, top_k, top_p, temperature, seed)
-    int attn_dbg = 0, dgemm_dbg = 0;    // timing experiments (GITMI_ATTN_DBG, GITMI_DGEMM_DBG)
-    int attn_pw = 0;                    // (sentence, head) pairs per workgroup of the decode attention (GITMI_ATTN_PW; 0 = by policy)
-    int attn_nh = 0;                    // waves per (sentence, head) pair of the decode attention (GITMI_ATTN_NH: 1 / 2)
-    int attn_ppw = 0;                   // pairs a wave of the packed one-wave decode attention serves one after the other (0 = by policy)
-    int attn_stream = -1;               // workgroups of the streaming decode attention (0 = register kernels; -1 = by policy)
-    bool shared_device = false;         // gitmi_set_shared_device: other contexts run beside this one
-    int dgemm_no_row_walk = -1;         // A/B (GITMI_DGEMM_NO_ROW_WALK=0|1; -1 = by policy)
-    int dgemm_strips = -1;              // 16-column strips per workgroup of the wide chain GEMMs at <= 64 rows (1, 2, 4, 6; -1 = by policy)
-    int vocab_wgs = -1;                 // workgroups of the vocabulary head (each walks ceil(239 / n) column blocks; 0 = one per block; -1 = by policy)
-    int gemm_tall = 1;                  // serving policy: encoder GEMMs always on 256-row tiles (1) or on the modelled height (0; GITMI_GEMM_TALL)
-    int dgemm_rows = 0;                 // rows per workgroup of the N = 768 chain GEMMs (GITMI_DGEMM_ROWS: 16 / 32 / 64; 0 = by policy)
-    int decode_skip = 0;                // MEASUREMENT BUILDS ONLY (GITMI_EXPERIMENT, GITMI_DECODE_SKIP): launches of the decode chain left
-                                        // out -- 1 attention, 2 QKV / FFN1 GEMMs, 4 out-proj / FFN2 GEMMs, 8 vocabulary head (ids are garbage)
-    bool use_temb = true;               // add img_temperal_embedding[i] to frame i (the reference does so only for a LIST of frames)
-    std::vector<int> plen_host, img_of_host;
-
-    // state of the current batch
-    int cur_B = 0, cur_F = 0, cur_Nimg = 0;
-    bool have_feats = false, have_prefill = false;
-
-    // profiling: 1 = eager launches with HIP events around phases, decode steps and every GEMM;
-    //            2 = hipGraph replays, the call split into an encode graph and a decode graph with events between them
-    //                (what the production path costs: no per-launch host work, no event records inside the chain)
-    int profile_mode = 0;
-    bool profiling = false;             // profile_mode == 1
-    hipGraph_t graph_b = nullptr;
-    hipGraphExec_t graph_exec_b = nullptr;
-    bool graph_is_split = false;
-    // residual streams of the image encoder and the prefill (v_x, p_y, p_hf) stored in fp16 instead of fp32 (bf16 mode
-    // only, the default there; GITMI_STREAM_F16=0 keeps fp32): half the bytes of their read-modify-writes at 2^-11 relative
-    // rounding.  Measured (profiles/r03_a_bench_f16_*.json, interleaved A/B): encode + prefill 5.31 -> 5.03 ms,
-    // 9.48k -> 9.82k captions/s, logit error 0.01118 -> 0.01094, the same 50 of 64 rows identical to the reference.
-    bool stream_f16 = false;
-    // LayerNorm folding in the encoder and the prefill (round 6; fp16-operand build only: the fp16 stream rows are the
-    // consumer GEMM's A operand as they are).  Row partials (sum, sumsq) per 256-column tile: [rows][4], ping-pong for
-    // the post-norm prefill (a producer tile reads the previous partials of a row while another tile writes the new ones).
-    bool ln_fold = false;
-    bool ln_fold_ready = false;         // folded matrices and partial buffers exist (decided at gitmi_create; gitmi_set_ln_fold switches the use)
-    float2 *v_part = nullptr, *p_part[2] = {nullptr, nullptr};
-    hipEvent_t gev[3] = {nullptr, nullptr, nullptr};
-    // serving schedule: this context's image encoder starts only after `enc_after`'s has finished (at most one encoder
-    // in flight on the device; decode chains of the other contexts fill in beside it)
-    gitmi_engine* enc_after = nullptr;
-    std::vector<gitmi_engine*> enc_watchers;   // contexts whose enc_after is this one (they wait on enc_done)
-    hipEvent_t enc_done = nullptr;
-    double split_encode_ms = 0, split_decode_ms = 0;
-    int split_calls = 0, split_steps = 0;
-    std::vector<TimedSpan> spans;
-    std::vector<hipEvent_t> event_pool;
-    size_t event_next = 0;
-    double last_decode_step_bytes = 0;
-    bool use_graph = true;
-
-    // hipGraph cache for gitmi_generate
-    bool graph_valid = false;
-    GraphKey graph_key{};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    std::vector<float*> frame_stage;   // engine-owned copies of the input frames (graph inputs)
-    long long* out_tokens = nullptr;   // graph outputs, copied to the caller's buffers after the launch
-    float* out_lp = nullptr;
-    int* out_info = nullptr;
-    int* out_sent = nullptr;           // [max_batch][2] per-sentence (length, early) of the last generate
-    hipStream_t own_stream = nullptr;  // used when the caller passes the (uncapturable) null stream
-    hipEvent_t fence_in = nullptr, fence_out = nullptr;
-
-    // caption scoring (GITMI_SEARCH_SCORE, kernels_score.hip): workspaces of the text pass over (sentence, position) rows,
-    // allocated by the first score call and grown to the rows of a larger call (score_alloc)
-    size_t sc_rows = 0;                 // rows the current workspaces hold (0: none)
-    std::vector<void*> sc_allocs;
-    float *sc_hf = nullptr, *sc_y = nullptr, *sc_zt = nullptr;
-    void *sc_ht = nullptr, *sc_qkv = nullptr, *sc_ctx = nullptr, *sc_u = nullptr;
-    float4* sc_part = nullptr;
-    int *sc_tgt = nullptr, *sc_lens = nullptr, *sc_img = nullptr, *sc_bad = nullptr, *sc_info = nullptr;
-    float2* sc_out = nullptr;
-};
-
-// ---------------------------------------------------------------------------------------
-static int dev_alloc(gitmi_engine* e, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    HIPCK(hipMalloc(p, bytes));
-    e->allocs.push_back(*p);
-    return 0;
-}
-template <typename T> static int dev_alloc_t(gitmi_engine* e, T** p, size_t count) {
-    return dev_alloc(e, reinterpret_cast<void**>(p), count * sizeof(T));
 }
 
 static hipEvent_t get_event(gitmi_engine* e) {
@@ -276,83 +60,103 @@ struct SpanGuard {
 // fill, because other contexts' kernels fill the CUs a partial round leaves idle.  gemm_tall (measurement builds): 1 always,
 // 0 never (the modelled height, as for a context alone), 2 only for the wide GEMMs (N >= 2048), 3 only for the N < 2048 ones
 static bool gemm_tall_tiles(const gitmi_engine* e, int N) {
-    if (!e->shared_device) return false;
-    return e->gemm_tall == 1 || (e->gemm_tall == 2 && N >= 2048) || (e->gemm_tall == 3 && N < 2048);
+    if (!e->pol.shared_device) return false;
+    return e->pol.gemm_tall == 1 || (e->pol.gemm_tall == 2 && N >= 2048) || (e->pol.gemm_tall == 3 && N < 2048);
 }
 
-// GEMM wrapper: C = act(A W^T + bias) (+ res)
-static int gemm(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
-                const float* res, int ldr, void* C, int ldc, bool out_f32, int M, int N, int K, int act, int tag) {
+static double gemm_flops(int M, int N, int K) { return 2.0 * (double)M * (double)N * (double)K; }
+// ---- the schedule's large-M GEMMs: C = act(A W^T + bias) (+ res).  gemm_args fills what every form shares, gemm_run adds
+// the tile policy and the profiling span and launches; the forms below differ in a few fields of the arguments
+static GemmArgs gemm_args(const void* A, int lda, const void* W, const float* bias, const void* res, int ldr, void* C, int ldc,
+                          int M, int N, int K, int act) {
     GemmArgs g{};
-    g.A = A; g.W = W; g.bias = bias; g.res = res; g.C = C;
+    g.A = A; g.W = W; g.bias = bias; g.res = (const float*)res; g.C = C;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.act = act;
-    g.shared = gemm_tall_tiles(e, N) ? 1 : 0;
-    SpanGuard sp(e, s, tag, 2.0 * (double)M * (double)N * (double)K);
-    HIPCK(launch_gemm(g, e->f32, out_f32, s));
+    return g;
+}
+static int gemm_run(gitmi_engine* e, hipStream_t s, GemmArgs g, bool in_f32, bool out_f32, int tag) {
+    g.shared = gemm_tall_tiles(e, g.N) ? 1 : 0;
+    SpanGuard sp(e, s, tag, gemm_flops(g.M, g.N, g.K));
+    HIPCK(launch_gemm(g, in_f32, out_f32, s));
     return 0;
 }
-
+static int gemm(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
+                const float* res, int ldr, void* C, int ldc, bool out_f32, int M, int N, int K, int act, int tag) {
+    return gemm_run(e, s, gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, act), e->pol.f32, out_f32, tag);
+}
 // GEMM whose output (and residual, if any) are rows of a residual stream: fp32, or fp16 with stream_f16
 static int gemm_stream(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
                        const void* res, int ldr, void* C, int ldc, int M, int N, int K, int tag) {
-    GemmArgs g{};
-    g.A = A; g.W = W; g.bias = bias; g.res = (const float*)res; g.C = C;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.act = 0;
-    g.out_f16 = e->stream_f16 ? 1 : 0;
-    g.shared = gemm_tall_tiles(e, N) ? 1 : 0;
-    SpanGuard sp(e, s, tag, 2.0 * (double)M * (double)N * (double)K);
-    HIPCK(launch_gemm(g, e->f32, !e->stream_f16, s));
-    return 0;
+    GemmArgs g = gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, 0);
+    g.out_f16 = e->pol.stream_f16 ? 1 : 0;
+    return gemm_run(e, s, g, e->pol.f32, !e->pol.stream_f16, tag);
 }
-// ---- folded LayerNorm (e->ln_fold): what a GEMM needs to know about the LayerNorm in front of it / of its residual
+// ---- folded LayerNorm (e->pol.ln_fold): what a GEMM needs to know about the LayerNorm in front of it / of its residual
 struct LnRef {
     const float2* part = nullptr; int nparts = 0; int D = 0; float eps = 0.f;
     const float* gamma = nullptr; const float* beta = nullptr;       // residual form only
 };
-// consumer: C = act(LayerNorm(x) W^T + b) with x the raw stream rows, W / bias / colsum the folded set
-static int gemm_ln(gitmi_engine* e, hipStream_t s, const void* x, int ldx, const void* Wf, const float* bias_f, const float* colsum,
-                   const LnRef& ln, void* C, int ldc, int M, int N, int K, int act, int tag) {
-    GemmArgs g{};
-    g.A = x; g.W = Wf; g.bias = bias_f; g.C = C;
-    g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldc = ldc; g.act = act;
-    g.ln_part = ln.part; g.ln_nparts = ln.nparts; g.ln_colsum = colsum; g.ln_inv_d = 1.0f / (float)ln.D; g.ln_eps = ln.eps;
-    g.shared = gemm_tall_tiles(e, N) ? 1 : 0;
-    SpanGuard sp(e, s, tag, 2.0 * (double)M * (double)N * (double)K);
-    HIPCK(launch_gemm(g, false, false, s));
-    return 0;
+// consumer: C = act(LayerNorm(x) W^T + b) with x the raw stream rows, f the folded set of W
+static int gemm_ln(gitmi_engine* e, hipStream_t s, const void* x, int ldx, const Folded& f, const LnRef& ln, void* C, int ldc,
+                   int M, int N, int K, int act, int tag) {
+    GemmArgs g = gemm_args(x, ldx, f.w, f.bias, nullptr, 0, C, ldc, M, N, K, act);
+    g.ln_part = ln.part; g.ln_nparts = ln.nparts; g.ln_colsum = f.colsum; g.ln_inv_d = 1.0f / (float)ln.D; g.ln_eps = ln.eps;
+    return gemm_run(e, s, g, false, false, tag);
 }
 // producer: stream rows C = A W^T + b (+ res, or + LayerNorm(res) when res_ln is given) and their row partials
 static int gemm_stream_part(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
                             const void* res, int ldr, const LnRef* res_ln, void* C, int ldc, float2* part_out, int M, int N, int K,
                             int tag) {
-    GemmArgs g{};
-    g.A = A; g.W = W; g.bias = bias; g.res = (const float*)res; g.C = C;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = ldr; g.act = 0;
+    GemmArgs g = gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, 0);
     g.out_f16 = 1;
     g.part_out = part_out;
     if (res_ln) {
         g.res_part = res_ln->part; g.res_nparts = res_ln->nparts; g.res_gamma = res_ln->gamma; g.res_beta = res_ln->beta;
         g.res_inv_d = 1.0f / (float)res_ln->D; g.res_eps = res_ln->eps;
     }
-    g.shared = gemm_tall_tiles(e, N) ? 1 : 0;
-    SpanGuard sp(e, s, tag, 2.0 * (double)M * (double)N * (double)K);
-    HIPCK(launch_gemm(g, false, false, s));
-    return 0;
+    return gemm_run(e, s, g, false, false, tag);
 }
 // does a 16-bit GEMM of this shape run on gemm_p8_kernel (the only kernel with the folded epilogues)?
 static bool on_p8(const void* A, int lda, const void* W, const void* C, int ldc, int M, int N, int K, bool stream_out) {
-    GemmArgs g{};
-    g.A = A; g.W = W; g.C = const_cast<void*>(C); g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.out_f16 = stream_out ? 1 : 0;
+    GemmArgs g = gemm_args(A, lda, W, nullptr, nullptr, 0, const_cast<void*>(C), ldc, M, N, K, 0);
+    g.out_f16 = stream_out ? 1 : 0;
     return gemm_uses_p8(g, false, false);
 }
 // LayerNorm of stream rows x -> operand copy y_t (compute dtype) [+ stream copy y_s]
 static int ln_stream(gitmi_engine* e, hipStream_t s, const void* x, int ldx, const float* gamma, const float* beta, float eps,
                      void* y_t, int ld_t, void* y_s, int ld_s, int rows, int D) {
-    if (e->stream_f16)
+    if (e->pol.stream_f16)
         HIPCK(launch_layernorm_s16(x, ldx, gamma, beta, eps, nullptr, y_t, ld_t, false, y_s, ld_s, rows, D, 0, 0, 0, s));
     else
-        HIPCK(launch_layernorm((const float*)x, ldx, gamma, beta, eps, nullptr, y_t, ld_t, e->f32, (float*)y_s, ld_s, rows, D,
+        HIPCK(launch_layernorm((const float*)x, ldx, gamma, beta, eps, nullptr, y_t, ld_t, e->pol.f32, (float*)y_s, ld_s, rows, D,
                                0, 0, 0, s));
+    return 0;
+}
+// full attention over packed q|k|v rows [batch * N][3 * width] -> out [batch * N][width]
+static int attn_full_packed(gitmi_engine* e, const void* qkv, void* out, int width, int heads, int N, int batch, hipStream_t s) {
+    AttnFullArgs a{};
+    a.q = qkv;
+    a.k = (const char*)qkv + (size_t)width * e->pol.esz;
+    a.v = (const char*)qkv + (size_t)2 * width * e->pol.esz;
+    a.out = out;
+    a.ldq = a.ldk = a.ldv = 3 * width;
+    a.ldo = width;
+    a.N = N; a.H = heads; a.scale = 0.125f;
+    a.ntok = e->ragged ? e->rg_ntok : nullptr;
+    HIPCK(launch_attn_full(a, batch, e->pol.f32, e->pol.attn_impl, s));
+    return 0;
+}
+// generic post-norm tail of a decoder layer over M rows (decode steps outside the chain, caption scoring): out-proj + residual,
+// LayerNorm, FFN1, FFN2 + residual, LayerNorm.  ctx: the attention output; hf / ht: the layer's input rows (fp32 / compute
+// dtype), replaced by its output rows; y: the pre-LayerNorm sums; u: the FFN's inner rows
+static int dec_layer_tail(gitmi_engine* e, hipStream_t s, const DecLayerW& L, const void* ctx, float* hf, void* ht, float* y, void* u,
+                          int M) {
+    const int d = e->cfg.dec_hidden, ffn = e->cfg.dec_ffn;
+    RCK(gemm(e, s, ctx, d, L.wo, L.bo, hf, d, y, d, true, M, d, d, 0, TAG_GEMM_OTHER));
+    HIPCK(launch_layernorm(y, d, L.lnag, L.lnab, 1e-12f, nullptr, ht, d, e->pol.f32, hf, d, M, d, 0, 0, 0, s));
+    RCK(gemm(e, s, ht, d, L.w1, L.b1, nullptr, 0, u, ffn, e->pol.f32, M, ffn, d, 2, TAG_GEMM_OTHER));
+    RCK(gemm(e, s, u, ffn, L.w2, L.b2, hf, d, y, d, true, M, d, ffn, 0, TAG_GEMM_OTHER));
+    HIPCK(launch_layernorm(y, d, L.lnog, L.lnob, 1e-12f, nullptr, ht, d, e->pol.f32, hf, d, M, d, 0, 0, 0, s));
     return 0;
 }
 
@@ -395,43 +199,37 @@ extern "C" int gitmi_create(const gitmi_config* cfg, int device, gitmi_engine** 
     gitmi_engine* e = new gitmi_engine();
     e->cfg = c;
     e->device = device;
-    e->f32 = c.precision == GITMI_PREC_F32;
-    e->esz = e->f32 ? 4 : 2;
-    e->attn_impl = e->f32 ? 0 : 1;
-    e->g_nat = e->gh = e->gw = c.image_size / c.patch;
-    e->N_nat = e->N = e->g_nat * e->g_nat + 1;
-    e->H = e->W = c.image_size;
-    e->Nmax = std::max(e->N_nat, c.max_image_tokens);
-    e->max_pixels = std::max((size_t)c.image_size * c.image_size, (size_t)c.max_image_pixels);
-    e->Kp = 3 * c.patch * c.patch;
-    e->Kp_pad = round_up(e->Kp, 64);
-    e->stream_f16 = !e->f32;
+    e->pol.f32 = c.precision == GITMI_PREC_F32;
+    e->pol.esz = e->pol.f32 ? 4 : 2;
+    e->pol.attn_impl = e->pol.f32 ? 0 : 1;
+    init_geometry(e);
+    e->pol.stream_f16 = !e->pol.f32;
 #ifdef GITMI_OPS_F16
-    e->ln_fold = !e->f32 && c.vit_width % 256 == 0 && c.dec_hidden % 256 == 0;
+    e->pol.ln_fold = !e->pol.f32 && c.vit_width % 256 == 0 && c.dec_hidden % 256 == 0;
 #endif
 #ifdef GITMI_EXPERIMENT
     // measurement builds only (libgitmi_exp.so, `make exp`): kernel-shape overrides and work-skipping switches for A/B runs
     // and timing decompositions.  The product libraries read no environment.
-    if (const char* env = getenv("GITMI_ATTN_IMPL")) e->attn_impl = e->f32 ? 0 : atoi(env);
-    if (const char* env = getenv("GITMI_GRAPH")) e->use_graph = atoi(env) != 0;
-    if (const char* env = getenv("GITMI_ATTN_DBG")) e->attn_dbg = atoi(env);
-    if (const char* env = getenv("GITMI_ATTN_PW")) e->attn_pw = atoi(env);
-    if (const char* env = getenv("GITMI_ATTN_NH")) e->attn_nh = atoi(env);
-    if (const char* env = getenv("GITMI_ATTN_PPW")) e->attn_ppw = atoi(env);
-    if (const char* env = getenv("GITMI_ATTN_STREAM")) e->attn_stream = atoi(env);
-    if (const char* env = getenv("GITMI_DECODE_SKIP")) e->decode_skip = atoi(env);
-    if (const char* env = getenv("GITMI_GEMM_TALL")) e->gemm_tall = atoi(env);
-    if (const char* env = getenv("GITMI_DGEMM_ROWS")) e->dgemm_rows = atoi(env);
-    if (const char* env = getenv("GITMI_DGEMM_STRIPS")) e->dgemm_strips = atoi(env);
-    if (const char* env = getenv("GITMI_DGEMM_NO_ROW_WALK")) e->dgemm_no_row_walk = atoi(env);
-    if (const char* env = getenv("GITMI_DGEMM_DBG")) e->dgemm_dbg = atoi(env);
-    if (const char* env = getenv("GITMI_VOCAB_WGS")) e->vocab_wgs = atoi(env);
-    if (const char* env = getenv("GITMI_SKINNY")) e->skinny = atoi(env) != 0;
-    if (const char* env = getenv("GITMI_STREAM_F16")) e->stream_f16 = !e->f32 && atoi(env) != 0;
+    if (const char* env = getenv("GITMI_ATTN_IMPL")) e->pol.attn_impl = e->pol.f32 ? 0 : atoi(env);
+    if (const char* env = getenv("GITMI_GRAPH")) e->pol.use_graph = atoi(env) != 0;
+    if (const char* env = getenv("GITMI_ATTN_DBG")) e->pol.attn_dbg = atoi(env);
+    if (const char* env = getenv("GITMI_ATTN_PW")) e->pol.attn_pw = atoi(env);
+    if (const char* env = getenv("GITMI_ATTN_NH")) e->pol.attn_nh = atoi(env);
+    if (const char* env = getenv("GITMI_ATTN_PPW")) e->pol.attn_ppw = atoi(env);
+    if (const char* env = getenv("GITMI_ATTN_STREAM")) e->pol.attn_stream = atoi(env);
+    if (const char* env = getenv("GITMI_DECODE_SKIP")) e->pol.decode_skip = atoi(env);
+    if (const char* env = getenv("GITMI_GEMM_TALL")) e->pol.gemm_tall = atoi(env);
+    if (const char* env = getenv("GITMI_DGEMM_ROWS")) e->pol.dgemm_rows = atoi(env);
+    if (const char* env = getenv("GITMI_DGEMM_STRIPS")) e->pol.dgemm_strips = atoi(env);
+    if (const char* env = getenv("GITMI_DGEMM_NO_ROW_WALK")) e->pol.dgemm_no_row_walk = atoi(env);
+    if (const char* env = getenv("GITMI_DGEMM_DBG")) e->pol.dgemm_dbg = atoi(env);
+    if (const char* env = getenv("GITMI_VOCAB_WGS")) e->pol.vocab_wgs = atoi(env);
+    if (const char* env = getenv("GITMI_SKINNY")) e->pol.skinny = atoi(env) != 0;
+    if (const char* env = getenv("GITMI_STREAM_F16")) e->pol.stream_f16 = !e->pol.f32 && atoi(env) != 0;
     if (const char* env = getenv("GITMI_GEMM_IMPL")) set_gemm_impl(atoi(env));
 #endif
-    e->ln_fold = e->ln_fold && e->stream_f16;
-    e->ln_fold_ready = e->ln_fold;
+    e->pol.ln_fold = e->pol.ln_fold && e->pol.stream_f16;
+    e->pol.ln_fold_ready = e->pol.ln_fold;
     if (attn_decode_configure() != hipSuccess) { delete e; return fail("hipFuncSetAttribute failed"); }
     *out = e;
     return 0;
@@ -473,509 +271,6 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     delete e;
 }
 
-// ---------------------------------------------------------------------------------------
-static float half_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000) << 16;
-    uint32_t exp = (h >> 10) & 0x1f, man = h & 0x3ff, out;
-    if (exp == 0) {
-        if (man == 0) out = sign;
-        else {
-            exp = 127 - 15 + 1;
-            while (!(man & 0x400)) { man <<= 1; --exp; }
-            man &= 0x3ff;
-            out = sign | (exp << 23) | (man << 13);
-        }
-    } else if (exp == 31) out = sign | 0x7f800000u | (man << 13);
-    else out = sign | ((exp + 127 - 15) << 23) | (man << 13);
-    float f;
-    memcpy(&f, &out, 4);
-    return f;
-}
-
-extern "C" int gitmi_load_tensor(gitmi_engine* e, const char* key, const void* data_host, const int64_t* shape,
-                                 int ndim, int dtype) {
-    if (!e || !key || !data_host || (ndim > 0 && !shape)) return fail("gitmi_load_tensor: null argument");
-    if (e->finalized) return fail("gitmi_load_tensor: weights already finalized");
-    std::string k(key);
-    if (k.rfind("module.", 0) == 0) k = k.substr(7);          // torch_common.py:95-99 strips DataParallel prefixes
-    if (k == "image_encoder.proj") return 0;                   // unused with output_grid=True
-    const bool known = k.rfind("image_encoder.", 0) == 0 || k.rfind("textual.", 0) == 0 ||
-                       k.rfind("img_temperal_embedding.", 0) == 0;
-    if (!known) return fail("gitmi_load_tensor: unknown key '%s'", key);
-    HostTensor t;
-    t.shape.assign(shape, shape + ndim);
-    const size_t n = t.numel();
-    t.data.resize(n);
-    if (dtype == GITMI_DTYPE_F32) memcpy(t.data.data(), data_host, n * 4);
-    else if (dtype == GITMI_DTYPE_BF16) {
-        const uint16_t* p = (const uint16_t*)data_host;
-        for (size_t i = 0; i < n; ++i) { uint32_t u = (uint32_t)p[i] << 16; memcpy(&t.data[i], &u, 4); }
-    } else if (dtype == GITMI_DTYPE_F16) {
-        const uint16_t* p = (const uint16_t*)data_host;
-        for (size_t i = 0; i < n; ++i) t.data[i] = half_to_float(p[i]);
-    } else return fail("gitmi_load_tensor: bad dtype %d", dtype);
-    // a checkpoint with inf / NaN in it fails here, by name, not as garbage ids later
-    float amax = 0.f;
-    for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(t.data[i])) return fail("gitmi_load_tensor: '%s' holds a non-finite value at element %zu", key, i);
-        amax = std::max(amax, std::fabs(t.data[i]));
-    }
-    t.amax = amax;
-    e->host_w[k] = std::move(t);
-    return 0;
-}
-
-static int get_w(gitmi_engine* e, const std::string& key, std::initializer_list<int64_t> shape, const HostTensor** out) {
-    auto it = e->host_w.find(key);
-    if (it == e->host_w.end()) return fail("missing weight '%s'", key.c_str());
-    size_t want = 1;
-    for (auto s : shape) want *= (size_t)s;
-    if (it->second.numel() != want) return fail("weight '%s' has %zu elements, expected %zu", key.c_str(), it->second.numel(), want);
-    *out = &it->second;
-    return 0;
-}
-// fp32 vector / table on device
-static int up_f32(gitmi_engine* e, const std::string& key, std::initializer_list<int64_t> shape, float** dst) {
-    const HostTensor* t;
-    RCK(get_w(e, key, shape, &t));
-    RCK(dev_alloc_t(e, dst, t->numel()));
-    HIPCK(hipMemcpy(*dst, t->data.data(), t->numel() * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-// a MATRIX that becomes an MFMA operand must fit the operand format: fp16 tops out at 65504 (bf16 and f32 share fp32's exponent)
-static int operand_range_check(gitmi_engine* e, const char* what, float amax) {
-#ifdef GITMI_OPS_F16
-    if (!e->f32 && amax > 65504.f)
-        return fail("'%s': max |w| = %g is outside the fp16 operand range (65504): load this checkpoint with precision "
-                    "\"bf16\" or \"f32\"", what, (double)amax);
-#endif
-    (void)e; (void)what; (void)amax;
-    return 0;
-}
-// matrix [rows, K] -> compute dtype [rows, Kpad] written at dst + row_off rows
-static int up_mat_into(gitmi_engine* e, const std::string& key, int64_t rows, int K, int Kpad, void* dst, size_t row_off) {
-    const HostTensor* t;
-    RCK(get_w(e, key, {rows, (int64_t)K}, &t));
-    RCK(operand_range_check(e, key.c_str(), t->amax));
-    float* tmp = nullptr;
-    HIPCK(hipMalloc((void**)&tmp, t->numel() * 4));
-    hipError_t err = hipMemcpy(tmp, t->data.data(), t->numel() * 4, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = launch_convert_pad(tmp, (char*)dst + row_off * (size_t)Kpad * e->esz, e->f32, (size_t)rows, K, Kpad, 0);
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    hipFree(tmp);
-    HIPCK(err);
-    return 0;
-}
-static int up_mat(gitmi_engine* e, const std::string& key, int64_t rows, int K, int Kpad, void** dst) {
-    RCK(dev_alloc(e, dst, (size_t)rows * Kpad * e->esz));
-    return up_mat_into(e, key, rows, K, Kpad, *dst, 0);
-}
-static int up_f32_into(gitmi_engine* e, const std::string& key, int64_t n, float* dst, size_t off) {
-    const HostTensor* t;
-    RCK(get_w(e, key, {n}, &t));
-    HIPCK(hipMemcpy(dst + off, t->data.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-
-static int alloc_workspaces(gitmi_engine* e) {
-    const gitmi_config& c = e->cfg;
-    const size_t esz = e->esz;
-    const int D = c.vit_width, d = c.dec_hidden;
-    const size_t Mv = (size_t)c.max_batch * c.max_frames * e->Nmax;  // ViT rows: all frames of a call in one pass
-    const size_t Mp = (size_t)c.max_batch * c.max_frames * e->Nmax;  // prefill rows
-    // fragment-major operand buffers hold whole 16-row tiles, and the wide chain GEMMs / the vocabulary head load their
-    // activations four tiles (64 rows) at a time whatever M is: every row-sized buffer is padded to 64 rows
-    const size_t R = (size_t)round_up(c.max_batch * c.max_beams, 64);
-    const int T = c.max_text_len;
-    RCK(dev_alloc(e, &e->patches, (size_t)c.max_batch * c.max_frames * (e->Nmax - 1) * e->Kp_pad * esz));
-    RCK(dev_alloc_t(e, &e->patch_out, (size_t)c.max_batch * c.max_frames * (e->Nmax - 1) * D));
-    RCK(dev_alloc_t(e, &e->pos_var, (size_t)e->Nmax * D));
-    RCK(dev_alloc_t(e, &e->v_x, Mv * D));
-    RCK(dev_alloc(e, &e->v_h, Mv * D * esz));
-    RCK(dev_alloc(e, &e->v_qkv, Mv * 3 * D * esz));
-    RCK(dev_alloc(e, &e->v_ctx, Mv * D * esz));
-    RCK(dev_alloc(e, &e->v_u, Mv * 4 * D * esz));
-    RCK(dev_alloc(e, &e->feats, Mp * D * esz));
-    if (e->ln_fold_ready) {
-        // [row][4] (sum, sumsq) per 256-column tile; slots past the row width stay zero for ever
-        RCK(dev_alloc_t(e, &e->v_part, Mv * 4));
-        RCK(dev_alloc_t(e, &e->p_part[0], Mp * 4));
-        RCK(dev_alloc_t(e, &e->p_part[1], Mp * 4));
-        HIPCK(hipMemset(e->v_part, 0, Mv * 4 * sizeof(float2)));
-        HIPCK(hipMemset(e->p_part[0], 0, Mp * 4 * sizeof(float2)));
-        HIPCK(hipMemset(e->p_part[1], 0, Mp * 4 * sizeof(float2)));
-    }
-    RCK(dev_alloc_t(e, &e->p_y, Mp * d));
-    RCK(dev_alloc_t(e, &e->p_hf, Mp * d));
-    RCK(dev_alloc(e, &e->p_ht, Mp * d * esz));
-    RCK(dev_alloc(e, &e->p_ctx, Mp * d * esz));
-    RCK(dev_alloc(e, &e->p_u, Mp * c.dec_ffn * esz));
-    e->img_kv.resize(c.dec_layers);
-    e->img_kh.resize(c.dec_layers);
-    e->img_vh.resize(c.dec_layers);
-    e->txt_k.resize(c.dec_layers);
-    e->txt_v.resize(c.dec_layers);
-    for (int l = 0; l < c.dec_layers; ++l) {
-        RCK(dev_alloc(e, &e->img_kv[l], Mp * 3 * d * esz));
-        // decode layout; bf16: per (image, head) keys padded to a multiple of 32 (kernels_attn_decode.hip)
-        const size_t Mkv = (size_t)c.max_batch * round_up(c.max_frames * e->Nmax, 32);
-        RCK(dev_alloc(e, &e->img_kh[l], Mkv * d * esz));
-        RCK(dev_alloc(e, &e->img_vh[l], Mkv * d * esz));
-        RCK(dev_alloc(e, &e->txt_k[l], R * T * d * esz));
-        RCK(dev_alloc(e, &e->txt_v[l], R * T * d * esz));
-    }
-    RCK(dev_alloc_t(e, &e->d_y, R * d));
-    RCK(dev_alloc_t(e, &e->d_hf, R * d));
-    RCK(dev_alloc(e, &e->d_ht, R * d * esz));
-    RCK(dev_alloc(e, &e->d_qkv, R * 3 * d * esz));
-    RCK(dev_alloc(e, &e->d_ctx, R * d * esz));
-    RCK(dev_alloc(e, &e->d_u, R * c.dec_ffn * esz));
-    RCK(dev_alloc_t(e, &e->xa_f, R * d));
-    RCK(dev_alloc_t(e, &e->xo_f, R * d));
-    RCK(dev_alloc(e, &e->xa_b, R * d * 2));
-    RCK(dev_alloc(e, &e->xo_b, R * d * 2));
-    RCK(dev_alloc_t(e, &e->stats_a, R * (size_t)(d / 16)));
-    RCK(dev_alloc_t(e, &e->stats_o, R * (size_t)(d / 16)));
-    e->ldl = round_up(c.vocab, 8);
-    RCK(dev_alloc_t(e, &e->logits, R * e->ldl));
-    // candidate lists of a step: the fused vocabulary head writes one list per (row, 128-column workgroup)
-    e->vocab_cols = 128;                  // columns per workgroup of the fused head (239 workgroups for the 30522-token vocabulary)
-    // only the bf16 decode chain uses the fused head (finalize_weights turns the chain off for vocabularies above 32768
-    // tokens); f32 engines and search-only contexts get ONE list per row from row_topm / sample_rows
-    e->vocab_nparts = (e->skinny && !e->f32) ? vocab_parts(c.vocab, e->vocab_cols) : 1;
-    RCK(dev_alloc_t(e, &e->part_val, R * (size_t)e->vocab_nparts * 16));
-    RCK(dev_alloc_t(e, &e->part_idx, R * (size_t)e->vocab_nparts * 16));
-    RCK(dev_alloc_t(e, &e->part_lse, R * (size_t)e->vocab_nparts));
-    // search state
-    SearchState& s = e->ss;
-    for (int i = 0; i < 2; ++i) {
-        RCK(dev_alloc_t(e, &s.ids[i], R * T));
-        RCK(dev_alloc_t(e, &s.kv_src[i], R * T));
-        RCK(dev_alloc_t(e, &s.score[i], R));
-    }
-    RCK(dev_alloc_t(e, &s.done, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.hyp_n, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.hyp_cnt, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.hyp_worst, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.hyp_score, (size_t)c.max_batch * SS_NHMAX));
-    RCK(dev_alloc_t(e, &s.hyp_len, (size_t)c.max_batch * SS_NHMAX));
-    RCK(dev_alloc_t(e, &s.hyp_seq, (size_t)c.max_batch * SS_NHMAX));
-    RCK(dev_alloc_t(e, &s.hyp_tok, (size_t)c.max_batch * SS_NHMAX * T));
-    RCK(dev_alloc_t(e, &s.stop, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.early, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &s.info, 4));
-    RCK(dev_alloc_t(e, &s.len_norm, (size_t)T + 1));
-    RCK(dev_alloc_t(e, &e->start_dev, (size_t)c.max_batch * T));
-    RCK(dev_alloc_t(e, &e->plen_dev, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &e->img_of_dev, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &e->trie_cursor, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &e->out_tokens, (size_t)c.max_batch * SS_NHMAX * T));
-    RCK(dev_alloc_t(e, &e->out_lp, (size_t)c.max_batch * SS_NHMAX));
-    RCK(dev_alloc_t(e, &e->out_info, 4));
-    RCK(dev_alloc_t(e, &e->out_sent, (size_t)c.max_batch * 2));
-    HIPCK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    HIPCK(hipEventCreateWithFlags(&e->fence_in, hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&e->fence_out, hipEventDisableTiming));
-    e->frame_stage.resize(c.max_frames);
-    for (int f = 0; f < c.max_frames; ++f)
-        RCK(dev_alloc_t(e, &e->frame_stage[f], (size_t)c.max_batch * 3 * e->max_pixels));
-    RCK(dev_alloc_t(e, &e->rg_meta, (size_t)c.max_batch));
-    RCK(dev_alloc_t(e, &e->rg_ntok, (size_t)c.max_batch));
-    return 0;
-}
-
-// ---- LayerNorm folding for the decode chain (kernels_dgemm.hip) ------------------------------------------------
-// An fp32 value rounded to the 16-bit operand type of this build (round-to-nearest-even, as the device conversions do
-// it): the column sums of a folded LayerNorm must be taken over exactly the values the MFMA will see.
-#ifdef GITMI_OPS_F16
-static inline float bf16_round(float f) { return (float)(_Float16)f; }
-#else
-static inline float bf16_round(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return f;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    u &= 0xffff0000u;
-    memcpy(&f, &u, 4);
-    return f;
-}
-#endif
-// W [rows, K], bias [rows], LayerNorm (gamma, beta) [K] in front of it  ->  device W' (bf16), folded bias, column sums
-// frag: fragment-major packing for the decode chain; else row-major for gemm_p8_kernel
-static int fold_layernorm(gitmi_engine* e, const std::vector<float>& W, const std::vector<float>& bias,
-                          const std::vector<float>& gamma, const std::vector<float>& beta, int64_t rows, int K,
-                          void** Wf, float** bf, float** cs, bool frag = true) {
-    std::vector<float> wf((size_t)rows * K), b2((size_t)rows), c2((size_t)rows);
-    float amax = 0.f;
-    for (int64_t n = 0; n < rows; ++n) {
-        double sum = 0.0, cst = bias[n];
-        const float* w = &W[(size_t)n * K];
-        float* o = &wf[(size_t)n * K];
-        for (int k = 0; k < K; ++k) {
-            amax = std::max(amax, std::fabs(w[k] * gamma[k]));
-            o[k] = bf16_round(w[k] * gamma[k]);
-            sum += (double)o[k];
-            cst += (double)beta[k] * (double)w[k];
-        }
-        c2[n] = (float)sum;
-        b2[n] = (float)cst;
-    }
-    RCK(operand_range_check(e, "a matrix with the LayerNorm gain in front of it folded in (W . gamma)", amax));
-    const int64_t rows_pad = (rows + 127) / 128 * 128;       // the vocabulary head reads bias / colsum a workgroup (128 columns) at a time
-    RCK(dev_alloc(e, Wf, (size_t)rows_pad * K * 2));
-    float* tmp = nullptr;
-    void* tmp_b = nullptr;
-    HIPCK(hipMalloc((void**)&tmp, wf.size() * 4));
-    hipError_t err = hipSuccess;
-    if (frag) err = hipMalloc(&tmp_b, wf.size() * 2);
-    if (err == hipSuccess) err = hipMemcpy(tmp, wf.data(), wf.size() * 4, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = launch_convert_pad(tmp, frag ? tmp_b : *Wf, false, (size_t)rows, K, K, 0);
-    if (err == hipSuccess && frag) err = launch_frag_pack(tmp_b, *Wf, (int)rows, (int)rows_pad, K, 0);
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-    hipFree(tmp);
-    if (tmp_b) hipFree(tmp_b);
-    HIPCK(err);
-    b2.resize((size_t)rows_pad, 0.f);
-    c2.resize((size_t)rows_pad, 0.f);
-    RCK(dev_alloc_t(e, bf, (size_t)rows_pad));
-    RCK(dev_alloc_t(e, cs, (size_t)rows_pad));
-    HIPCK(hipMemcpy(*bf, b2.data(), (size_t)rows_pad * 4, hipMemcpyHostToDevice));
-    HIPCK(hipMemcpy(*cs, c2.data(), (size_t)rows_pad * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-// fragment-major copy of an already packed row-major bf16 matrix [rows, K]
-static int pack_frag(gitmi_engine* e, const void* src, int64_t rows, int K, void** dst) {
-    const int64_t rows_pad = (rows + 15) / 16 * 16;
-    RCK(dev_alloc(e, dst, (size_t)rows_pad * K * 2));
-    HIPCK(launch_frag_pack(src, *dst, (int)rows, (int)rows_pad, K, 0));
-    HIPCK(hipDeviceSynchronize());
-    return 0;
-}
-static int host_vec(gitmi_engine* e, const std::string& key, size_t n, const std::vector<float>** out) {
-    auto it = e->host_w.find(key);
-    if (it == e->host_w.end()) return fail("missing weight '%s'", key.c_str());
-    if (it->second.numel() != n) return fail("weight '%s' has %zu elements, expected %zu", key.c_str(), it->second.numel(), n);
-    *out = &it->second.data;
-    return 0;
-}
-static int fold_decoder(gitmi_engine* e) {
-    const gitmi_config& c = e->cfg;
-    const int d = c.dec_hidden, f = c.dec_ffn, V = c.vocab;
-    const std::string base = "textual.transformer.encoder.layer.";
-    for (int i = 0; i < c.dec_layers; ++i) {
-        const std::string pre = base + std::to_string(i) + ".";
-        DecLayerW& L = e->dec[i];
-        const std::vector<float>*g, *b, *w, *bi;
-        if (i > 0) {      // QKV behind the previous layer's output LayerNorm
-            const std::string prev = base + std::to_string(i - 1) + ".";
-            RCK(host_vec(e, prev + "output.LayerNorm.weight", d, &g));
-            RCK(host_vec(e, prev + "output.LayerNorm.bias", d, &b));
-            std::vector<float> wq((size_t)3 * d * d), bq((size_t)3 * d);
-            const char* names[3] = {"query", "key", "value"};
-            for (int j = 0; j < 3; ++j) {
-                RCK(host_vec(e, pre + "attention.self." + names[j] + ".weight", (size_t)d * d, &w));
-                RCK(host_vec(e, pre + "attention.self." + names[j] + ".bias", d, &bi));
-                std::copy(w->begin(), w->end(), wq.begin() + (size_t)j * d * d);
-                std::copy(bi->begin(), bi->end(), bq.begin() + (size_t)j * d);
-            }
-            RCK(fold_layernorm(e, wq, bq, *g, *b, 3 * d, d, &L.wqkv_f, &L.bqkv_f, &L.cs_qkv));
-        } else {          // layer 0 consumes the embedding LayerNorm's output directly: plain weights, packed
-            RCK(pack_frag(e, L.wqkv, 3 * d, d, &L.wqkv_f));
-            L.bqkv_f = L.bqkv;
-        }
-        RCK(pack_frag(e, L.wo, d, d, &L.wo_p));
-        RCK(pack_frag(e, L.w2, d, f, &L.w2_p));
-        RCK(host_vec(e, pre + "attention.output.LayerNorm.weight", d, &g));
-        RCK(host_vec(e, pre + "attention.output.LayerNorm.bias", d, &b));
-        RCK(host_vec(e, pre + "intermediate.dense.weight", (size_t)f * d, &w));
-        RCK(host_vec(e, pre + "intermediate.dense.bias", f, &bi));
-        RCK(fold_layernorm(e, *w, *bi, *g, *b, f, d, &L.w1_f, &L.b1_f, &L.cs_1));
-    }
-    const std::string last = base + std::to_string(c.dec_layers - 1) + ".";
-    const std::vector<float>*g, *b, *w, *bi;
-    RCK(host_vec(e, last + "output.LayerNorm.weight", d, &g));
-    RCK(host_vec(e, last + "output.LayerNorm.bias", d, &b));
-    RCK(host_vec(e, "textual.output.weight", (size_t)V * d, &w));
-    RCK(host_vec(e, "textual.output.bias", V, &bi));
-    RCK(fold_layernorm(e, *w, *bi, *g, *b, V, d, &e->out_w_f, &e->out_b_f, &e->cs_out));
-    return 0;
-}
-
-// encoder and prefill GEMMs behind a LayerNorm (e->ln_fold): row-major folded copies next to the plain ones (small batches and
-// shapes outside gemm_p8_kernel's rules keep the LayerNorm launches and the plain matrices)
-static int fold_encoder_prefill(gitmi_engine* e) {
-    const gitmi_config& c = e->cfg;
-    const int D = c.vit_width, d = c.dec_hidden, f = c.dec_ffn;
-    const std::vector<float>*g, *b, *w, *bi;
-    for (int i = 0; i < c.vit_layers; ++i) {
-        const std::string pre = "image_encoder.transformer.resblocks." + std::to_string(i) + ".";
-        VitLayerW& L = e->vit[i];
-        RCK(host_vec(e, pre + "ln_1.weight", D, &g));
-        RCK(host_vec(e, pre + "ln_1.bias", D, &b));
-        RCK(host_vec(e, pre + "attn.in_proj_weight", (size_t)3 * D * D, &w));
-        RCK(host_vec(e, pre + "attn.in_proj_bias", (size_t)3 * D, &bi));
-        RCK(fold_layernorm(e, *w, *bi, *g, *b, 3 * D, D, &L.wqkv_f, &L.bqkv_f, &L.cs_qkv, false));
-        RCK(host_vec(e, pre + "ln_2.weight", D, &g));
-        RCK(host_vec(e, pre + "ln_2.bias", D, &b));
-        RCK(host_vec(e, pre + "mlp.c_fc.weight", (size_t)4 * D * D, &w));
-        RCK(host_vec(e, pre + "mlp.c_fc.bias", (size_t)4 * D, &bi));
-        RCK(fold_layernorm(e, *w, *bi, *g, *b, 4 * D, D, &L.w1_f, &L.b1_f, &L.cs_1, false));
-    }
-    const std::string base = "textual.transformer.encoder.layer.";
-    for (int i = 0; i < c.dec_layers; ++i) {
-        const std::string pre = base + std::to_string(i) + ".";
-        DecLayerW& L = e->dec[i];
-        if (i == 0) {
-            RCK(host_vec(e, "textual.visual_projection.1.weight", d, &g));
-            RCK(host_vec(e, "textual.visual_projection.1.bias", d, &b));
-        } else {
-            const std::string prev = base + std::to_string(i - 1) + ".";
-            RCK(host_vec(e, prev + "output.LayerNorm.weight", d, &g));
-            RCK(host_vec(e, prev + "output.LayerNorm.bias", d, &b));
-        }
-        std::vector<float> wq((size_t)3 * d * d), bq((size_t)3 * d);
-        const char* names[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            RCK(host_vec(e, pre + "attention.self." + names[j] + ".weight", (size_t)d * d, &w));
-            RCK(host_vec(e, pre + "attention.self." + names[j] + ".bias", d, &bi));
-            std::copy(w->begin(), w->end(), wq.begin() + (size_t)j * d * d);
-            std::copy(bi->begin(), bi->end(), bq.begin() + (size_t)j * d);
-        }
-        RCK(fold_layernorm(e, wq, bq, *g, *b, 3 * d, d, &L.wqkv_pf, &L.bqkv_pf, &L.cs_qkv_p, false));
-        if (i + 1 == c.dec_layers) break;            // the last layer's image rows stop at K / V
-        RCK(host_vec(e, pre + "attention.output.LayerNorm.weight", d, &g));
-        RCK(host_vec(e, pre + "attention.output.LayerNorm.bias", d, &b));
-        RCK(host_vec(e, pre + "intermediate.dense.weight", (size_t)f * d, &w));
-        RCK(host_vec(e, pre + "intermediate.dense.bias", f, &bi));
-        RCK(fold_layernorm(e, *w, *bi, *g, *b, f, d, &L.w1_pf, &L.b1_pf, &L.cs_1_p, false));
-    }
-    return 0;
-}
-
-extern "C" int gitmi_finalize_weights(gitmi_engine* e) {
-    if (!e) return fail("null engine");
-    if (e->finalized) return 0;
-    HIPCK(hipSetDevice(e->device));
-    const gitmi_config& c = e->cfg;
-    const int D = c.vit_width, F4 = 4 * D, d = c.dec_hidden, f = c.dec_ffn, V = c.vocab;
-    const int64_t p = c.patch;
-    // ---- image encoder -----------------------------------------------------------------
-    {
-        const HostTensor* t;
-        RCK(get_w(e, "image_encoder.conv1.weight", {D, 3, p, p}, &t));
-        e->host_w["image_encoder.conv1.weight"].shape = {D, (int64_t)e->Kp};
-        RCK(up_mat(e, "image_encoder.conv1.weight", D, e->Kp, e->Kp_pad, &e->conv_w));
-    }
-    RCK(up_f32(e, "image_encoder.class_embedding", {D}, &e->cls));
-    RCK(up_f32(e, "image_encoder.positional_embedding", {e->N_nat, D}, &e->pos));
-    e->pos_cur = e->pos;
-    RCK(up_f32(e, "image_encoder.ln_pre.weight", {D}, &e->lnpre_g));
-    RCK(up_f32(e, "image_encoder.ln_pre.bias", {D}, &e->lnpre_b));
-    RCK(up_f32(e, "image_encoder.ln_post.weight", {D}, &e->lnpost_g));
-    RCK(up_f32(e, "image_encoder.ln_post.bias", {D}, &e->lnpost_b));
-    e->vit.resize(c.vit_layers);
-    for (int i = 0; i < c.vit_layers; ++i) {
-        const std::string pre = "image_encoder.transformer.resblocks." + std::to_string(i) + ".";
-        VitLayerW& L = e->vit[i];
-        RCK(up_mat(e, pre + "attn.in_proj_weight", 3 * D, D, D, &L.wqkv));
-        RCK(up_f32(e, pre + "attn.in_proj_bias", {3 * D}, &L.bqkv));
-        RCK(up_mat(e, pre + "attn.out_proj.weight", D, D, D, &L.wo));
-        RCK(up_f32(e, pre + "attn.out_proj.bias", {D}, &L.bo));
-        RCK(up_f32(e, pre + "ln_1.weight", {D}, &L.ln1g));
-        RCK(up_f32(e, pre + "ln_1.bias", {D}, &L.ln1b));
-        RCK(up_mat(e, pre + "mlp.c_fc.weight", F4, D, D, &L.w1));
-        RCK(up_f32(e, pre + "mlp.c_fc.bias", {F4}, &L.b1));
-        RCK(up_mat(e, pre + "mlp.c_proj.weight", D, F4, F4, &L.w2));
-        RCK(up_f32(e, pre + "mlp.c_proj.bias", {D}, &L.b2));
-        RCK(up_f32(e, pre + "ln_2.weight", {D}, &L.ln2g));
-        RCK(up_f32(e, pre + "ln_2.bias", {D}, &L.ln2b));
-    }
-    e->temb.resize(c.num_frames);
-    for (int i = 0; i < c.num_frames; ++i)
-        RCK(up_f32(e, "img_temperal_embedding." + std::to_string(i), {1, 1, D}, &e->temb[i]));
-    // ---- text decoder ------------------------------------------------------------------
-    RCK(up_mat(e, "textual.visual_projection.0.weight", d, D, D, &e->vp_w));
-    RCK(up_f32(e, "textual.visual_projection.0.bias", {d}, &e->vp_b));
-    RCK(up_f32(e, "textual.visual_projection.1.weight", {d}, &e->vp_lng));
-    RCK(up_f32(e, "textual.visual_projection.1.bias", {d}, &e->vp_lnb));
-    RCK(up_f32(e, "textual.embedding.words.weight", {V, d}, &e->words_f));
-    RCK(up_f32(e, "textual.embedding.positions.weight", {c.max_pos, d}, &e->positions_f));
-    RCK(up_f32(e, "textual.embedding.layer_norm.weight", {d}, &e->emb_lng));
-    RCK(up_f32(e, "textual.embedding.layer_norm.bias", {d}, &e->emb_lnb));
-    e->dec.resize(c.dec_layers);
-    double wbytes = 0;
-    for (int i = 0; i < c.dec_layers; ++i) {
-        const std::string pre = "textual.transformer.encoder.layer." + std::to_string(i) + ".";
-        DecLayerW& L = e->dec[i];
-        // fused [Wq; Wk; Wv] so that one GEMM produces the packed q|k|v rows the attention kernels read
-        RCK(dev_alloc(e, &L.wqkv, (size_t)3 * d * d * e->esz));
-        RCK(dev_alloc_t(e, &L.bqkv, (size_t)3 * d));
-        const char* names[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            RCK(up_mat_into(e, pre + "attention.self." + names[j] + ".weight", d, d, d, L.wqkv, (size_t)j * d));
-            RCK(up_f32_into(e, pre + "attention.self." + names[j] + ".bias", d, L.bqkv, (size_t)j * d));
-        }
-        RCK(up_mat(e, pre + "attention.output.dense.weight", d, d, d, &L.wo));
-        RCK(up_f32(e, pre + "attention.output.dense.bias", {d}, &L.bo));
-        RCK(up_f32(e, pre + "attention.output.LayerNorm.weight", {d}, &L.lnag));
-        RCK(up_f32(e, pre + "attention.output.LayerNorm.bias", {d}, &L.lnab));
-        RCK(up_mat(e, pre + "intermediate.dense.weight", f, d, d, &L.w1));
-        RCK(up_f32(e, pre + "intermediate.dense.bias", {f}, &L.b1));
-        RCK(up_mat(e, pre + "output.dense.weight", d, f, f, &L.w2));
-        RCK(up_f32(e, pre + "output.dense.bias", {d}, &L.b2));
-        RCK(up_f32(e, pre + "output.LayerNorm.weight", {d}, &L.lnog));
-        RCK(up_f32(e, pre + "output.LayerNorm.bias", {d}, &L.lnob));
-        wbytes += ((double)4 * d * d + (double)2 * d * f) * e->esz;
-    }
-    if (e->host_w.find("textual.output.weight") == e->host_w.end())   // tied (decoder.py:503-505)
-        e->host_w["textual.output.weight"] = e->host_w["textual.embedding.words.weight"];
-    RCK(up_mat(e, "textual.output.weight", V, d, d, &e->out_w));
-    RCK(up_f32(e, "textual.output.bias", {V}, &e->out_b));
-    wbytes += (double)V * d * e->esz;
-    e->dec_weight_bytes = wbytes;
-    if (!e->f32 && d % 32 == 0 && f % 32 == 0 && d <= 768 && V <= 32768) RCK(fold_decoder(e));      // the bf16 decode chain (else: generic GEMM + LayerNorm launches)
-    else e->skinny = false;
-    if (e->ln_fold_ready) RCK(fold_encoder_prefill(e));
-    e->host_w.clear();
-    RCK(alloc_workspaces(e));
-    HIPCK(hipDeviceSynchronize());
-    e->finalized = true;
-    return 0;
-}
-
-// A second execution context on the same device that BORROWS the packed weights of `src` (its own
-// workspaces, KV caches, search state, streams and graph).  Lets a server keep several batches in
-// flight on different HIP streams: the latency-bound decode steps of one batch overlap the
-// MFMA-bound encoder of the next.  `src` must outlive the clone.
-extern "C" int gitmi_clone(gitmi_engine* src, gitmi_engine** out) {
-    if (!src || !out) return fail("gitmi_clone: null argument");
-    if (!src->finalized) return fail("gitmi_clone: source weights not finalized");
-    HIPCK(hipSetDevice(src->device));
-    gitmi_engine* e = new gitmi_engine();
-    e->cfg = src->cfg; e->device = src->device; e->f32 = src->f32; e->esz = src->esz; e->stream_f16 = src->stream_f16; e->ln_fold = src->ln_fold; e->ln_fold_ready = src->ln_fold_ready;
-    e->attn_impl = src->attn_impl; e->Kp = src->Kp; e->Kp_pad = src->Kp_pad;
-    // a clone starts at the native resolution (its own gitmi_set_image_shape state and resized table)
-    e->N_nat = e->N = src->N_nat; e->g_nat = e->gh = e->gw = src->g_nat; e->H = e->W = src->cfg.image_size;
-    e->Nmax = src->Nmax; e->max_pixels = src->max_pixels;
-    e->use_graph = src->use_graph; e->skinny = src->skinny; e->use_temb = src->use_temb;
-    e->attn_dbg = src->attn_dbg; e->dgemm_dbg = src->dgemm_dbg; e->attn_pw = src->attn_pw; e->attn_nh = src->attn_nh; e->attn_ppw = src->attn_ppw; e->attn_stream = src->attn_stream; e->decode_skip = src->decode_skip;
-    e->shared_device = src->shared_device; e->gemm_tall = src->gemm_tall; e->dgemm_rows = src->dgemm_rows; e->dgemm_strips = src->dgemm_strips; e->vocab_wgs = src->vocab_wgs; e->dgemm_no_row_walk = src->dgemm_no_row_walk;
-    e->parent = src->parent ? src->parent : src;
-    e->conv_w = src->conv_w; e->cls = src->cls; e->pos = src->pos; e->pos_cur = src->pos;
-    e->lnpre_g = src->lnpre_g; e->lnpre_b = src->lnpre_b; e->lnpost_g = src->lnpost_g; e->lnpost_b = src->lnpost_b;
-    e->vit = src->vit; e->temb = src->temb;
-    e->vp_w = src->vp_w; e->vp_b = src->vp_b; e->vp_lng = src->vp_lng; e->vp_lnb = src->vp_lnb;
-    e->words_f = src->words_f; e->positions_f = src->positions_f; e->emb_lng = src->emb_lng; e->emb_lnb = src->emb_lnb;
-    e->dec = src->dec; e->out_w = src->out_w; e->out_b = src->out_b; e->dec_weight_bytes = src->dec_weight_bytes;
-    e->out_w_f = src->out_w_f; e->out_b_f = src->out_b_f; e->cs_out = src->cs_out;
-    int rc = alloc_workspaces(e);
-    if (rc != 0) { gitmi_destroy(e); return rc; }
-    HIPCK(hipDeviceSynchronize());
-    e->finalized = true;
-    *out = e;
-    return 0;
-}
 // ---- input resolution (CLIP/model.py:243-251) ---------------------------------------------
 extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream) {
     if (!e) return fail("null engine");
@@ -1000,9 +295,9 @@ extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream
     e->ragged = false;
     HIPCK(hipSetDevice(e->device));
     if (gh == e->g_nat && gw == e->g_nat) {
-        e->pos_cur = e->pos;
+        e->pos_cur = e->w.pos;
     } else {
-        HIPCK(launch_pos_bicubic(e->pos, e->pos_var, e->g_nat, gh, gw, c.vit_width, (hipStream_t)stream));
+        HIPCK(launch_pos_bicubic(e->w.pos, e->pos_var, e->g_nat, gh, gw, c.vit_width, (hipStream_t)stream));
         e->pos_cur = e->pos_var;
     }
     e->H = H; e->W = W; e->gh = gh; e->gw = gw; e->N = gh * gw + 1;
@@ -1025,73 +320,64 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
     const int g2 = N - 1;                    // patch rows per image (ragged: the capacity grid, zeros past each image's own)
     const size_t slot = (size_t)3 * e->max_pixels;
     if (e->ragged)      // F == 1; the images were staged by ragged_stage (the `frames` pointer is not read)
-        HIPCK(launch_im2col_ragged(e->frame_stage[0], slot, e->rg_meta, e->patches, e->f32, B, N, c.patch, e->Kp, e->Kp_pad, s));
+        HIPCK(launch_im2col_ragged(e->frame_stage[0], slot, e->rg_meta, e->patches, e->pol.f32, B, N, c.patch, e->Kp, e->Kp_pad, s));
     else
     for (int fr = 0; fr < F_eff; ++fr)
-        HIPCK(launch_im2col(frames[fr], (char*)e->patches + (size_t)fr * B * g2 * e->Kp_pad * e->esz, e->f32, B,
+        HIPCK(launch_im2col(frames[fr], (char*)e->patches + (size_t)fr * B * g2 * e->Kp_pad * e->pol.esz, e->pol.f32, B,
                             e->H, e->W, c.patch, e->Kp, e->Kp_pad, s));
-    RCK(gemm(e, s, e->patches, e->Kp_pad, e->conv_w, nullptr, nullptr, 0, e->patch_out, D, true, BI * g2, D, e->Kp_pad, 0,
+    RCK(gemm(e, s, e->patches, e->Kp_pad, e->w.conv_w, nullptr, nullptr, 0, e->patch_out, D, true, BI * g2, D, e->Kp_pad, 0,
              TAG_GEMM_VIT));
     // LayerNorm folding (fp16-operand build): ln_1 / ln_2 disappear into the GEMMs either side of them when every GEMM of the
     // pass runs on gemm_p8_kernel (more than 512 rows); the stream rows v_x are then the QKV / c_fc GEMMs' A operand as they are
-    const bool fold = e->ln_fold && on_p8(e->v_x, D, e->vit[0].wqkv_f, e->v_qkv, 3 * D, M, 3 * D, D, false) &&
-                      on_p8(e->v_x, D, e->vit[0].w1_f, e->v_u, 4 * D, M, 4 * D, D, false) &&
-                      on_p8(e->v_ctx, D, e->vit[0].wo, e->v_x, D, M, D, D, true) && on_p8(e->v_u, 4 * D, e->vit[0].w2, e->v_x, D, M, D, 4 * D, true);
+    const bool fold = e->pol.ln_fold && on_p8(e->v_x, D, e->w.vit[0].qkv_f.w, e->v_qkv, 3 * D, M, 3 * D, D, false) &&
+                      on_p8(e->v_x, D, e->w.vit[0].ffn1_f.w, e->v_u, 4 * D, M, 4 * D, D, false) &&
+                      on_p8(e->v_ctx, D, e->w.vit[0].wo, e->v_x, D, M, D, D, true) && on_p8(e->v_u, 4 * D, e->w.vit[0].w2, e->v_x, D, M, D, 4 * D, true);
     LnRef vln;
     vln.part = e->v_part; vln.nparts = D / 256; vln.D = D; vln.eps = 1e-5f;
     if (e->ragged)
-        HIPCK(launch_vit_assemble_ragged(e->patch_out, e->cls, e->pos, e->g_nat, e->rg_meta, e->lnpre_g, e->lnpre_b, 1e-5f, e->v_x,
-                                         e->stream_f16, BI, N, c.patch, D, fold ? e->v_part : nullptr, s));
+        HIPCK(launch_vit_assemble_ragged(e->patch_out, e->w.cls, e->w.pos, e->g_nat, e->rg_meta, e->w.lnpre_g, e->w.lnpre_b, 1e-5f, e->v_x,
+                                         e->pol.stream_f16, BI, N, c.patch, D, fold ? e->v_part : nullptr, s));
     else
-    HIPCK(launch_vit_assemble_ln(e->patch_out, e->cls, e->pos_cur, e->lnpre_g, e->lnpre_b, 1e-5f, e->v_x, e->stream_f16, BI, N, D,
+    HIPCK(launch_vit_assemble_ln(e->patch_out, e->w.cls, e->pos_cur, e->w.lnpre_g, e->w.lnpre_b, 1e-5f, e->v_x, e->pol.stream_f16, BI, N, D,
                                  fold ? e->v_part : nullptr, D / 256, s));
     for (int l = 0; l < c.vit_layers; ++l) {
-        const VitLayerW& L = e->vit[l];
+        const VitLayerW& L = e->w.vit[l];
         if (fold) {
-            RCK(gemm_ln(e, s, e->v_x, D, L.wqkv_f, L.bqkv_f, L.cs_qkv, vln, e->v_qkv, 3 * D, M, 3 * D, D, 0, TAG_GEMM_VIT));
+            RCK(gemm_ln(e, s, e->v_x, D, L.qkv_f, vln, e->v_qkv, 3 * D, M, 3 * D, D, 0, TAG_GEMM_VIT));
         } else {
             RCK(ln_stream(e, s, e->v_x, D, L.ln1g, L.ln1b, 1e-5f, e->v_h, D, nullptr, 0, M, D));
-            RCK(gemm(e, s, e->v_h, D, L.wqkv, L.bqkv, nullptr, 0, e->v_qkv, 3 * D, e->f32, M, 3 * D, D, 0, TAG_GEMM_VIT));
+            RCK(gemm(e, s, e->v_h, D, L.wqkv, L.bqkv, nullptr, 0, e->v_qkv, 3 * D, e->pol.f32, M, 3 * D, D, 0, TAG_GEMM_VIT));
         }
-        AttnFullArgs a{};
-        a.q = e->v_qkv;
-        a.k = (char*)e->v_qkv + (size_t)D * e->esz;
-        a.v = (char*)e->v_qkv + (size_t)2 * D * e->esz;
-        a.out = e->v_ctx;
-        a.ldq = a.ldk = a.ldv = 3 * D;
-        a.ldo = D;
-        a.N = N; a.H = c.vit_heads; a.scale = 0.125f;
-        a.ntok = e->ragged ? e->rg_ntok : nullptr;
-        HIPCK(launch_attn_full(a, BI, e->f32, e->attn_impl, s));
+        RCK(attn_full_packed(e, e->v_qkv, e->v_ctx, D, c.vit_heads, N, BI, s));
         if (fold) {     // pre-norm blocks: the residual is the raw stream; every producer leaves the partials of its rows
             RCK(gemm_stream_part(e, s, e->v_ctx, D, L.wo, L.bo, e->v_x, D, nullptr, e->v_x, D, e->v_part, M, D, D, TAG_GEMM_VIT));
-            RCK(gemm_ln(e, s, e->v_x, D, L.w1_f, L.b1_f, L.cs_1, vln, e->v_u, 4 * D, M, 4 * D, D, 1, TAG_GEMM_VIT));
+            RCK(gemm_ln(e, s, e->v_x, D, L.ffn1_f, vln, e->v_u, 4 * D, M, 4 * D, D, 1, TAG_GEMM_VIT));
             RCK(gemm_stream_part(e, s, e->v_u, 4 * D, L.w2, L.b2, e->v_x, D, nullptr, e->v_x, D, l + 1 < c.vit_layers ? e->v_part : nullptr,
                                  M, D, 4 * D, TAG_GEMM_VIT));
             continue;
         }
         RCK(gemm_stream(e, s, e->v_ctx, D, L.wo, L.bo, e->v_x, D, e->v_x, D, M, D, D, TAG_GEMM_VIT));
         RCK(ln_stream(e, s, e->v_x, D, L.ln2g, L.ln2b, 1e-5f, e->v_h, D, nullptr, 0, M, D));
-        RCK(gemm(e, s, e->v_h, D, L.w1, L.b1, nullptr, 0, e->v_u, 4 * D, e->f32, M, 4 * D, D, 1, TAG_GEMM_VIT));
+        RCK(gemm(e, s, e->v_h, D, L.w1, L.b1, nullptr, 0, e->v_u, 4 * D, e->pol.f32, M, 4 * D, D, 1, TAG_GEMM_VIT));
         RCK(gemm_stream(e, s, e->v_u, 4 * D, L.w2, L.b2, e->v_x, D, e->v_x, D, M, D, 4 * D, TAG_GEMM_VIT));
     }
     // ln_post (+ temporal embedding of the frame), scattered into the concatenated [B, F*N, D] feature tensor
     for (int fr = 0; fr < F_eff; ++fr) {
-        const float* te = (c.num_frames > 0 && e->use_temb) ? e->temb[fr] : nullptr;
-        if (e->stream_f16) {
+        const float* te = (c.num_frames > 0 && e->pol.use_temb) ? e->w.temb[fr] : nullptr;
+        if (e->pol.stream_f16) {
             const char* xs = (const char*)e->v_x + (size_t)fr * B * N * D * 2;      // fp16 rows
-            HIPCK(launch_layernorm_s16(xs, D, e->lnpost_g, e->lnpost_b, 1e-5f, te, e->feats, D, false, nullptr, 0, B * N, D, N,
+            HIPCK(launch_layernorm_s16(xs, D, e->w.lnpost_g, e->w.lnpost_b, 1e-5f, te, e->feats, D, false, nullptr, 0, B * N, D, N,
                                        Nimg, fr * N, s));
             if (feats_out)      // parity hook: the fp32 copy of the features comes from a second pass over the same rows
-                HIPCK(launch_layernorm_s16(xs, D, e->lnpost_g, e->lnpost_b, 1e-5f, te, feats_out, D, true, nullptr, 0, B * N, D,
+                HIPCK(launch_layernorm_s16(xs, D, e->w.lnpost_g, e->w.lnpost_b, 1e-5f, te, feats_out, D, true, nullptr, 0, B * N, D,
                                            N, Nimg, fr * N, s));
         } else {
-            HIPCK(launch_layernorm(e->v_x + (size_t)fr * B * N * D, D, e->lnpost_g, e->lnpost_b, 1e-5f, te, e->feats, D, e->f32,
+            HIPCK(launch_layernorm(e->v_x + (size_t)fr * B * N * D, D, e->w.lnpost_g, e->w.lnpost_b, 1e-5f, te, e->feats, D, e->pol.f32,
                                    feats_out, D, B * N, D, N, Nimg, fr * N, s));
         }
     }
     if (e->ragged) {    // padding rows of the features are zeros (prefill rows past an image stay finite and are never keys)
-        HIPCK(launch_zero_pad_rows(e->feats, e->f32, D, e->rg_ntok, B, N, s));
+        HIPCK(launch_zero_pad_rows(e->feats, e->pol.f32, D, e->rg_ntok, B, N, s));
         if (feats_out) HIPCK(launch_zero_pad_rows(feats_out, true, D, e->rg_ntok, B, N, s));
     }
 
@@ -1106,7 +392,7 @@ static int kv_repack(gitmi_engine* e, int l, int B, int Nimg, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     void* kh = e->img_kh[l];
     void* vh = e->img_vh[l];
-    if (e->f32) HIPCK(launch_kv_repack(e->img_kv[l], kh, vh, B, Nimg, c.dec_heads, c.dec_hidden, true, s));
+    if (e->pol.f32) HIPCK(launch_kv_repack(e->img_kv[l], kh, vh, B, Nimg, c.dec_heads, c.dec_hidden, true, s));
     else HIPCK(launch_kv_repack_frag(e->img_kv[l], kh, vh, B, Nimg, round_up(Nimg, 32), c.dec_heads, c.dec_hidden, s));
     return 0;
 }
@@ -1116,12 +402,12 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
     const int d = c.dec_hidden, ffn = c.dec_ffn, D = c.vit_width;
     const int B = e->cur_B, Nimg = e->cur_Nimg, M = B * Nimg;
     SpanGuard phase(e, s, TAG_PREFILL, 0);
-    const bool fold = e->ln_fold && on_p8(e->feats, D, e->vp_w, e->p_y, d, M, d, D, true) &&
-                      on_p8(e->p_y, d, e->dec[0].wqkv_pf, e->img_kv[0], 3 * d, M, 3 * d, d, false) &&
-                      on_p8(e->p_y, d, e->dec[0].wqkv_pf, e->img_kv[0], 3 * d, M, 2 * d, d, false) &&
-                      (c.dec_layers < 2 || (on_p8(e->p_y, d, e->dec[0].w1_pf, e->p_u, ffn, M, ffn, d, false) &&
-                                            on_p8(e->p_ctx, d, e->dec[0].wo, e->p_y, d, M, d, d, true) &&
-                                            on_p8(e->p_u, ffn, e->dec[0].w2, e->p_y, d, M, d, ffn, true)));
+    const bool fold = e->pol.ln_fold && on_p8(e->feats, D, e->w.vp_w, e->p_y, d, M, d, D, true) &&
+                      on_p8(e->p_y, d, e->w.dec[0].qkv_pf.w, e->img_kv[0], 3 * d, M, 3 * d, d, false) &&
+                      on_p8(e->p_y, d, e->w.dec[0].qkv_pf.w, e->img_kv[0], 3 * d, M, 2 * d, d, false) &&
+                      (c.dec_layers < 2 || (on_p8(e->p_y, d, e->w.dec[0].ffn1_pf.w, e->p_u, ffn, M, ffn, d, false) &&
+                                            on_p8(e->p_ctx, d, e->w.dec[0].wo, e->p_y, d, M, d, d, true) &&
+                                            on_p8(e->p_u, ffn, e->w.dec[0].w2, e->p_y, d, M, d, ffn, true)));
     if (fold) {
         // Post-norm layers with every LayerNorm folded: p_y holds the RAW sums (dense + residual) in place, the consumer GEMMs
         // read it as their A operand, and the residual LayerNorm(previous raw row) is rebuilt inside the next producer's
@@ -1129,32 +415,23 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
         int cur = 0;
         LnRef ln;                   // the LayerNorm that stands between p_y and its consumers right now
         ln.nparts = d / 256; ln.D = d;
-        RCK(gemm_stream_part(e, s, e->feats, D, e->vp_w, e->vp_b, nullptr, 0, nullptr, e->p_y, d, e->p_part[cur], M, d, D, TAG_GEMM_OTHER));
-        ln.part = e->p_part[cur]; ln.eps = 1e-5f; ln.gamma = e->vp_lng; ln.beta = e->vp_lnb;
+        RCK(gemm_stream_part(e, s, e->feats, D, e->w.vp_w, e->w.vp_b, nullptr, 0, nullptr, e->p_y, d, e->p_part[cur], M, d, D, TAG_GEMM_OTHER));
+        ln.part = e->p_part[cur]; ln.eps = 1e-5f; ln.gamma = e->w.vp_lng; ln.beta = e->w.vp_lnb;
         for (int l = 0; l < c.dec_layers; ++l) {
-            const DecLayerW& L = e->dec[l];
+            const DecLayerW& L = e->w.dec[l];
             if (l + 1 == c.dec_layers) {      // only K and V of the last layer's image rows are ever read
-                RCK(gemm_ln(e, s, e->p_y, d, (char*)L.wqkv_pf + (size_t)d * d * e->esz, L.bqkv_pf + d, L.cs_qkv_p + d, ln,
-                            (char*)e->img_kv[l] + (size_t)d * e->esz, 3 * d, M, 2 * d, d, 0, TAG_GEMM_OTHER));
+                const Folded kv{(char*)L.qkv_pf.w + (size_t)d * d * e->pol.esz, L.qkv_pf.bias + d, L.qkv_pf.colsum + d};
+                RCK(gemm_ln(e, s, e->p_y, d, kv, ln, (char*)e->img_kv[l] + (size_t)d * e->pol.esz, 3 * d, M, 2 * d, d, 0, TAG_GEMM_OTHER));
                 RCK(kv_repack(e, l, B, Nimg, s));
                 break;
             }
-            RCK(gemm_ln(e, s, e->p_y, d, L.wqkv_pf, L.bqkv_pf, L.cs_qkv_p, ln, e->img_kv[l], 3 * d, M, 3 * d, d, 0, TAG_GEMM_OTHER));
+            RCK(gemm_ln(e, s, e->p_y, d, L.qkv_pf, ln, e->img_kv[l], 3 * d, M, 3 * d, d, 0, TAG_GEMM_OTHER));
             RCK(kv_repack(e, l, B, Nimg, s));
-            AttnFullArgs a{};
-            a.q = e->img_kv[l];
-            a.k = (char*)e->img_kv[l] + (size_t)d * e->esz;
-            a.v = (char*)e->img_kv[l] + (size_t)2 * d * e->esz;
-            a.out = e->p_ctx;
-            a.ldq = a.ldk = a.ldv = 3 * d;
-            a.ldo = d;
-            a.N = Nimg; a.H = c.dec_heads; a.scale = 0.125f;
-            a.ntok = e->ragged ? e->rg_ntok : nullptr;
-            HIPCK(launch_attn_full(a, B, e->f32, e->attn_impl, s));
+            RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, s));
             RCK(gemm_stream_part(e, s, e->p_ctx, d, L.wo, L.bo, e->p_y, d, &ln, e->p_y, d, e->p_part[cur ^ 1], M, d, d, TAG_GEMM_OTHER));
             cur ^= 1;
             ln.part = e->p_part[cur]; ln.eps = 1e-12f; ln.gamma = L.lnag; ln.beta = L.lnab;
-            RCK(gemm_ln(e, s, e->p_y, d, L.w1_pf, L.b1_pf, L.cs_1_p, ln, e->p_u, ffn, M, ffn, d, 2, TAG_GEMM_OTHER));
+            RCK(gemm_ln(e, s, e->p_y, d, L.ffn1_pf, ln, e->p_u, ffn, M, ffn, d, 2, TAG_GEMM_OTHER));
             RCK(gemm_stream_part(e, s, e->p_u, ffn, L.w2, L.b2, e->p_y, d, &ln, e->p_y, d, e->p_part[cur ^ 1], M, d, ffn, TAG_GEMM_OTHER));
             cur ^= 1;
             ln.part = e->p_part[cur]; ln.eps = 1e-12f; ln.gamma = L.lnog; ln.beta = L.lnob;
@@ -1162,34 +439,25 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
         e->have_prefill = true;
         return 0;
     }
-    RCK(gemm_stream(e, s, e->feats, D, e->vp_w, e->vp_b, nullptr, 0, e->p_y, d, M, d, D, TAG_GEMM_OTHER));
-    RCK(ln_stream(e, s, e->p_y, d, e->vp_lng, e->vp_lnb, 1e-5f, e->p_ht, d, e->p_hf, d, M, d));
+    RCK(gemm_stream(e, s, e->feats, D, e->w.vp_w, e->w.vp_b, nullptr, 0, e->p_y, d, M, d, D, TAG_GEMM_OTHER));
+    RCK(ln_stream(e, s, e->p_y, d, e->w.vp_lng, e->w.vp_lnb, 1e-5f, e->p_ht, d, e->p_hf, d, M, d));
     for (int l = 0; l < c.dec_layers; ++l) {
-        const DecLayerW& L = e->dec[l];
+        const DecLayerW& L = e->w.dec[l];
         const bool last = l + 1 == c.dec_layers;
         if (!last) {
-            RCK(gemm(e, s, e->p_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->img_kv[l], 3 * d, e->f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
+            RCK(gemm(e, s, e->p_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->img_kv[l], 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
             RCK(kv_repack(e, l, B, Nimg, s));
         } else {
             // the last layer's image-row outputs are never consumed: only its K and V are needed
-            RCK(gemm(e, s, e->p_ht, d, (char*)L.wqkv + (size_t)d * d * e->esz, L.bqkv + d, nullptr, 0,
-                     (char*)e->img_kv[l] + (size_t)d * e->esz, 3 * d, e->f32, M, 2 * d, d, 0, TAG_GEMM_OTHER));
+            RCK(gemm(e, s, e->p_ht, d, (char*)L.wqkv + (size_t)d * d * e->pol.esz, L.bqkv + d, nullptr, 0,
+                     (char*)e->img_kv[l] + (size_t)d * e->pol.esz, 3 * d, e->pol.f32, M, 2 * d, d, 0, TAG_GEMM_OTHER));
             RCK(kv_repack(e, l, B, Nimg, s));
             break;
         }
-        AttnFullArgs a{};
-        a.q = e->img_kv[l];
-        a.k = (char*)e->img_kv[l] + (size_t)d * e->esz;
-        a.v = (char*)e->img_kv[l] + (size_t)2 * d * e->esz;
-        a.out = e->p_ctx;
-        a.ldq = a.ldk = a.ldv = 3 * d;
-        a.ldo = d;
-        a.N = Nimg; a.H = c.dec_heads; a.scale = 0.125f;
-        a.ntok = e->ragged ? e->rg_ntok : nullptr;
-        HIPCK(launch_attn_full(a, B, e->f32, e->attn_impl, s));
+        RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, s));
         RCK(gemm_stream(e, s, e->p_ctx, d, L.wo, L.bo, e->p_hf, d, e->p_y, d, M, d, d, TAG_GEMM_OTHER));
         RCK(ln_stream(e, s, e->p_y, d, L.lnag, L.lnab, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
-        RCK(gemm(e, s, e->p_ht, d, L.w1, L.b1, nullptr, 0, e->p_u, ffn, e->f32, M, ffn, d, 2, TAG_GEMM_OTHER));
+        RCK(gemm(e, s, e->p_ht, d, L.w1, L.b1, nullptr, 0, e->p_u, ffn, e->pol.f32, M, ffn, d, 2, TAG_GEMM_OTHER));
         RCK(gemm_stream(e, s, e->p_u, ffn, L.w2, L.b2, e->p_hf, d, e->p_y, d, M, d, ffn, TAG_GEMM_OTHER));
         RCK(ln_stream(e, s, e->p_y, d, L.lnog, L.lnob, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
     }
@@ -1200,7 +468,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
 // work-skipping for timing decompositions exists in measurement builds only: the product libraries cannot be told to
 // return wrong answers faster
 #ifdef GITMI_EXPERIMENT
-#define GITMI_SKIPPED(e, bit) (((e)->decode_skip & (bit)) != 0)
+#define GITMI_SKIPPED(e, bit) (((e)->pol.decode_skip & (bit)) != 0)
 #else
 #define GITMI_SKIPPED(e, bit) false
 #endif
@@ -1214,7 +482,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
 // search step.  logits_out != nullptr additionally materialises the logits [R, ldl] (teacher-forced parity hook).
 static int dgemm(gitmi_engine* e, hipStream_t s, const DGemmArgs& g_in) {
     DGemmArgs g = g_in;
-    g.dbg = e->dgemm_dbg;
+    g.dbg = e->pol.dgemm_dbg;
     // N = 768 GEMMs of the chain: 64 rows per workgroup (one pass over the weight strip, a quarter of the workgroups) for
     // beam batches -- faster even alone (R = 256: 0.466 -> 0.461 ms per step) -- and whenever other contexts share the
     // device: the launch is 2.8 us longer on its own but closes far fewer CUs to the encoder's GEMM workgroups
@@ -1222,16 +490,16 @@ static int dgemm(gitmi_engine* e, hipStream_t s, const DGemmArgs& g_in) {
     // wide GEMMs over > 64 rows (beam batches, decode groups): one workgroup per strip walks the row blocks with its weight
     // fragments in registers when other contexts share the device (beam-4: 7.18k -> 7.30k captions/s in the mixed schedule,
     // profiles/r03_zzz_ab_bench_lines.txt); alone, one workgroup per (strip, row block) is 3.5 us faster per launch
-    g.no_row_walk = e->dgemm_no_row_walk >= 0 ? e->dgemm_no_row_walk : e->shared_device ? 0 : 1;
-    g.strips_per_wg = e->dgemm_strips >= 0 ? e->dgemm_strips : e->shared_device ? 2 : 1;
+    g.no_row_walk = e->pol.dgemm_no_row_walk >= 0 ? e->pol.dgemm_no_row_walk : e->pol.shared_device ? 0 : 1;
+    g.strips_per_wg = e->pol.dgemm_strips >= 0 ? e->pol.dgemm_strips : e->pol.shared_device ? 2 : 1;
     // rows per workgroup of the N = 768 chain GEMMs: 16 alone (48 strips x R/16 workgroups, shortest launch); next to other
     // contexts 32 -- half the workgroups for +1 us per launch.  Round 3 took 64 there (a quarter of the workgroups, +5 us:
     // +1.5 % captions/s with the kernels of the time); with the walking vocabulary head and the two-strip wide GEMMs in place
     // 32 gives the same throughput and a 7 % shorter decode step (profiles/r04_k_policy_components_bench_lines.txt:
     // 16 / 32 / 64 rows = 11.18k / 11.24k / 11.20k captions/s at 0.297 / 0.310 / 0.333 ms per step).  > 64 rows (beam
     // batches): 64, faster alone too.
-    g.rows_per_wg = e->dgemm_rows > 0 ? e->dgemm_rows : g.M > 64 ? 64 : e->shared_device ? 32 : 16;
-    SpanGuard sp(e, s, TAG_GEMM_OTHER, 2.0 * (double)g.M * (double)g.N * (double)g.K);
+    g.rows_per_wg = e->pol.dgemm_rows > 0 ? e->pol.dgemm_rows : g.M > 64 ? 64 : e->pol.shared_device ? 32 : 16;
+    SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(g.M, g.N, g.K));
     HIPCK(launch_dgemm(g, s));
     return 0;
 }
@@ -1240,22 +508,22 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, ffn = c.dec_ffn;
     const int B = R / beams;
-    const bool chain = e->skinny && !e->f32;
+    const bool chain = e->pol.skinny && !e->pol.f32;
     const int strips = d / 16;
     const float inv_d = 1.0f / (float)d;
     for (int l = 0; l < c.dec_layers; ++l) {
-        const DecLayerW& L = e->dec[l];
-        const DecLayerW* Lp = l > 0 ? &e->dec[l - 1] : nullptr;
+        const DecLayerW& L = e->w.dec[l];
+        const DecLayerW* Lp = l > 0 ? &e->w.dec[l - 1] : nullptr;
         if (chain) {
             DGemmArgs q{};
             q.A = (const unsigned short*)(l == 0 ? e->d_ht : e->xo_b); q.lda = d;
-            q.W = (const unsigned short*)L.wqkv_f;
-            q.bias = L.bqkv_f;
-            if (l > 0) { q.colsum = L.cs_qkv; q.stats_in = e->stats_o; q.strips_in = strips; q.inv_d = inv_d; q.eps_in = 1e-12f; }
+            q.W = (const unsigned short*)L.qkv_f.w;
+            q.bias = L.qkv_f.bias;
+            if (l > 0) { q.colsum = L.qkv_f.colsum; q.stats_in = e->stats_o; q.strips_in = strips; q.inv_d = inv_d; q.eps_in = 1e-12f; }
             q.C = e->d_qkv; q.ldc = 3 * d; q.act = 0; q.M = R; q.N = 3 * d; q.K = d;
             if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, q));
         } else {
-            RCK(gemm(e, s, e->d_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->d_qkv, 3 * d, e->f32, R, 3 * d, d, 0, TAG_GEMM_OTHER));
+            RCK(gemm(e, s, e->d_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->d_qkv, 3 * d, e->pol.f32, R, 3 * d, d, 0, TAG_GEMM_OTHER));
         }
         AttnDecodeArgs a{};
         a.qkv = e->d_qkv; a.img_k = e->img_kh[l]; a.img_v = e->img_vh[l]; a.txt_k = e->txt_k[l]; a.txt_v = e->txt_v[l]; a.out = e->d_ctx;
@@ -1264,20 +532,20 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         a.pos = pos; a.beams = beams; a.scale = 0.125f;
         a.out_frag = chain ? 1 : 0;
         a.N_pad = round_up(e->cur_Nimg, 32);
-        a.dbg = e->attn_dbg;
-        a.waves_per_pair = e->attn_nh;
-        a.pairs_per_wg = e->attn_pw > 0 ? e->attn_pw : e->shared_device ? 8 : 4;
-        a.pairs_per_wave = e->attn_ppw > 0 ? e->attn_ppw : 1;
+        a.dbg = e->pol.attn_dbg;
+        a.waves_per_pair = e->pol.attn_nh;
+        a.pairs_per_wg = e->pol.attn_pw > 0 ? e->pol.attn_pw : e->pol.shared_device ? 8 : 4;
+        a.pairs_per_wave = e->pol.attn_ppw > 0 ? e->pol.attn_ppw : 1;
         // a context that has the device to itself streams the image K/V through LDS rings (kernels_attn_decode.hip: all of a
         // pair's first 36 KiB requested at once, no second memory round trip): 11.7 instead of 15.6 us per launch on 192
         // workgroups.  Same arithmetic as the one-wave register kernel, every fused multiply-add written out in both, so the
         // two agree bit for bit and gitmi_set_shared_device stays bitwise neutral.  Next to other contexts the register kernel
         // packed 8 pairs per workgroup stays: a CU streams ~24 GB/s from HBM whatever the kernel form, and fewer workgroups
         // of the streaming kernel only stretch the launch (profiles/r04_f_*)
-        const bool stream_ok = !e->shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->attn_nh != 2;
-        a.stream_wgs = e->attn_stream >= 0 ? e->attn_stream : stream_ok ? 192 : 0;
+        const bool stream_ok = !e->pol.shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->pol.attn_nh != 2;
+        a.stream_wgs = e->pol.attn_stream >= 0 ? e->pol.attn_stream : stream_ok ? 192 : 0;
         if (e->ragged) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }      // per-image key counts: the register kernels
-        if (e->f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, true, s));
+        if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, true, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
             DGemmArgs o{};
@@ -1288,7 +556,7 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
             o.M = R; o.N = d; o.K = d;
             if (!GITMI_SKIPPED(e, 4)) RCK(dgemm(e, s, o));
             DGemmArgs f1{};
-            f1.A = (const unsigned short*)e->xa_b; f1.lda = d; f1.W = (const unsigned short*)L.w1_f; f1.bias = L.b1_f; f1.colsum = L.cs_1;
+            f1.A = (const unsigned short*)e->xa_b; f1.lda = d; f1.W = (const unsigned short*)L.ffn1_f.w; f1.bias = L.ffn1_f.bias; f1.colsum = L.ffn1_f.colsum;
             f1.stats_in = e->stats_a; f1.strips_in = strips; f1.inv_d = inv_d; f1.eps_in = 1e-12f;
             f1.C = e->d_u; f1.ldc = ffn; f1.c_frag = 1; f1.act = 2; f1.M = R; f1.N = ffn; f1.K = d;
             if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, f1));
@@ -1300,11 +568,7 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
             f2.M = R; f2.N = d; f2.K = ffn;
             if (!GITMI_SKIPPED(e, 4)) RCK(dgemm(e, s, f2));
         } else {
-            RCK(gemm(e, s, e->d_ctx, d, L.wo, L.bo, e->d_hf, d, e->d_y, d, true, R, d, d, 0, TAG_GEMM_OTHER));
-            HIPCK(launch_layernorm(e->d_y, d, L.lnag, L.lnab, 1e-12f, nullptr, e->d_ht, d, e->f32, e->d_hf, d, R, d, 0, 0, 0, s));
-            RCK(gemm(e, s, e->d_ht, d, L.w1, L.b1, nullptr, 0, e->d_u, ffn, e->f32, R, ffn, d, 2, TAG_GEMM_OTHER));
-            RCK(gemm(e, s, e->d_u, ffn, L.w2, L.b2, e->d_hf, d, e->d_y, d, true, R, d, ffn, 0, TAG_GEMM_OTHER));
-            HIPCK(launch_layernorm(e->d_y, d, L.lnog, L.lnob, 1e-12f, nullptr, e->d_ht, d, e->f32, e->d_hf, d, R, d, 0, 0, 0, s));
+            RCK(dec_layer_tail(e, s, L, e->d_ctx, e->d_hf, e->d_ht, e->d_y, e->d_u, R));
         }
     }
     return 0;
@@ -1323,14 +587,14 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
                             int M, float* logits_out, int ldl, hipStream_t s, StepCands* cands) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden;
-    const bool chain = e->skinny && !e->f32;
+    const bool chain = e->pol.skinny && !e->pol.f32;
     cands->part_val = e->part_val; cands->part_idx = e->part_idx; cands->part_lse = e->part_lse;
     const bool sampling = ids != nullptr && e->ss.sampled;
     const bool trie = ids != nullptr && e->trie_search;
     if ((sampling || trie) && !logits_out) { logits_out = e->logits; ldl = e->ldl; }     // the filter / the trie need the whole row
     if (chain) {
         VocabArgs v{};
-        v.A = (const unsigned short*)e->xo_b; v.lda = d; v.W = (const unsigned short*)e->out_w_f; v.bias = e->out_b_f; v.colsum = e->cs_out;
+        v.A = (const unsigned short*)e->xo_b; v.lda = d; v.W = (const unsigned short*)e->w.out_f.w; v.bias = e->w.out_f.bias; v.colsum = e->w.out_f.colsum;
         v.stats_in = e->stats_o; v.strips_in = d / 16; v.inv_d = 1.0f / (float)d; v.eps_in = 1e-12f;
         v.M = R; v.N = c.vocab; v.K = d; v.cols_per_wg = e->vocab_cols;
         // workgroups of the head: by default one per column block (one HBM round trip; fastest alone); when other contexts
@@ -1340,20 +604,20 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
         // (beam batches, R > 64 rows: one column block per workgroup in either policy -- the walking form re-reads the rows of
         // four row blocks per column block and takes 186 instead of 56 us, and the mix measures the same captions/s with either:
         // profiles/r05_m_beam_head_wgs_ab_bench_lines.txt; the shorter launch takes 0.17 ms off every beam step)
-        v.max_wgs = e->vocab_wgs >= 0 ? e->vocab_wgs : (e->shared_device && R <= 64) ? 60 : 0;
+        v.max_wgs = e->pol.vocab_wgs >= 0 ? e->pol.vocab_wgs : (e->pol.shared_device && R <= 64) ? 60 : 0;
         v.ids = ids; v.ld_ids = ld_ids; v.cur_len = cur_len; v.plen = e->plen_dev; v.beams = beams; v.suppress_kind = suppress_kind;
         v.rep_penalty = ids ? rep_penalty_of(e) : 0.f;
         v.part_val = e->part_val; v.part_idx = e->part_idx; v.part_lse = e->part_lse;
         v.logits_out = logits_out; v.ld_logits = ldl;
         {
-            SpanGuard sp(e, s, TAG_GEMM_OTHER, 2.0 * (double)R * (double)c.vocab * (double)d);
+            SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(R, c.vocab, d));
             if (!GITMI_SKIPPED(e, 8)) HIPCK(launch_vocab_topm(v, M, s));
         }
         cands->nparts = e->vocab_nparts; cands->slots = vocab_mtop_slots(M);
         if (sampling) RCK(sample_candidates(e, logits_out, ldl, R, cur_len, s, cands));
         if (trie) RCK(trie_candidates(e, logits_out, ldl, cur_len, s, cands));
     } else {
-        RCK(gemm(e, s, e->d_ht, d, e->out_w, e->out_b, nullptr, 0, e->logits, e->ldl, true, R, c.vocab, d, 0, TAG_GEMM_OTHER));
+        RCK(gemm(e, s, e->d_ht, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, R, c.vocab, d, 0, TAG_GEMM_OTHER));
         cands->nparts = 1; cands->slots = row_topm_slots(M);
         if (sampling) RCK(sample_candidates(e, e->logits, e->ldl, R, cur_len, s, cands));
         else if (trie) RCK(trie_candidates(e, e->logits, e->ldl, cur_len, s, cands));
@@ -1424,8 +688,8 @@ extern "C" int gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, 
     StepCands cands{};
     for (int pos = 0; pos < t; ++pos) {
         SpanGuard step(e, s, TAG_STEP, 0);
-        HIPCK(launch_embed_ln(e->ss.ids[0], T, pos, e->words_f, e->positions_f, e->emb_lng, e->emb_lnb, 1e-8f, e->d_hf,
-                              e->d_ht, e->f32, R, c.dec_hidden, c.vocab, e->skinny && !e->f32, s));
+        HIPCK(launch_embed_ln(e->ss.ids[0], T, pos, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->d_hf,
+                              e->d_ht, e->pol.f32, R, c.dec_hidden, c.vocab, e->pol.skinny && !e->pol.f32, s));
         RCK(decode_layers_impl(e, e->ss.kv_src[0], T, pos, R, beams, s));
         if (pos == t - 1) RCK(decode_head_impl(e, nullptr, T, t, R, beams, 0, 1, logits_out, c.vocab, s, &cands));
     }
@@ -1474,7 +738,7 @@ static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int
     // the trie search shares AutoRegressiveBeamSearch's bookkeeping (beam 1): only the candidate selection differs
     st.V = V; st.eos = c.eos; st.kind = e->trie_search ? GITMI_SEARCH_AUTOREGRESSIVE : sp->kind; st.length_penalty = sp->length_penalty;
     st.prefixed = prefixed ? 1 : 0;
-    st.nh = sp->num_keep_best > 1 ? sp->num_keep_best : 1;
+    st.nh = keep_best(*sp);
     st.sampled = sp->do_sample ? 1 : 0;
     e->sample = *sp;
     st.start = e->start_dev; st.ld_start = c.max_text_len; st.plen = e->plen_dev;
@@ -1514,9 +778,9 @@ static int trie_candidates(gitmi_engine* e, const float* logits, int ldl, int cu
 static EmbedArgs embed_args(gitmi_engine* e, bool on) {
     EmbedArgs em{};
     if (!on) return em;
-    em.words = e->words_f; em.positions = e->positions_f; em.gamma = e->emb_lng; em.beta = e->emb_lnb; em.eps = 1e-8f;
+    em.words = e->w.words_f; em.positions = e->w.positions_f; em.gamma = e->w.emb_lng; em.beta = e->w.emb_lnb; em.eps = 1e-8f;
     em.h_f = e->d_hf; em.h_t = e->d_ht; em.D = e->cfg.dec_hidden; em.vocab = e->cfg.vocab;
-    em.frag = (e->skinny && !e->f32) ? 1 : 0;
+    em.frag = (e->pol.skinny && !e->pol.f32) ? 1 : 0;
     return em;
 }
 
@@ -1525,7 +789,7 @@ static int search_step_impl(gitmi_engine* e, const StepCands& cands, bool embed,
     const SearchState& st = e->ss;
     const int cur_len = e->ss_len;
     if (cur_len >= st.T) return fail("search_advance: sequence already at max_steps");
-    HIPCK(launch_search_step(st, e->ss_cur, cur_len, cands, embed_args(e, embed), e->f32, s));
+    HIPCK(launch_search_step(st, e->ss_cur, cur_len, cands, embed_args(e, embed), e->pol.f32, s));
     e->ss_cur ^= 1;
     e->ss_len = cur_len + 1;
     return 0;
@@ -1659,8 +923,8 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool pref
     {
         SpanGuard phase(e, s, TAG_DECODE, 0);
         // position 0 is embedded here; every later position by the search step that appends its token
-        HIPCK(launch_embed_ln(st.ids[0], T, 0, e->words_f, e->positions_f, e->emb_lng, e->emb_lnb, 1e-8f, e->d_hf, e->d_ht,
-                              e->f32, R, c.dec_hidden, c.vocab, e->skinny && !e->f32, s));
+        HIPCK(launch_embed_ln(st.ids[0], T, 0, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->d_hf, e->d_ht,
+                              e->pol.f32, R, c.dec_hidden, c.vocab, e->pol.skinny && !e->pol.f32, s));
         e->ss_len = 1;
         StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, 1};
         while (e->ss_len < T) {
@@ -1684,12 +948,12 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool pref
     }
     HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, tokens_out, logprob_out, info_out, sent_out, s));
     if (e->ragged)      // sentences over a rejected image: NaN log-probs, counted with the non-finite ones (info[3])
-        HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q,
-                                   sp->num_keep_best > 1 ? sp->num_keep_best : 1, logprob_out, info_out, nullptr, s));
+        HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q, keep_best(*sp), logprob_out, info_out,
+                                   nullptr, s));
     // algorithmic bytes of one decode step: all decoder weights once +
     // per sentence the K/V of every layer (image part shared by beams, text part per beam)
-    const double kv = (double)Q * c.dec_layers * 2.0 * ((double)e->cur_Nimg + k * 0.5 * (minP + T)) * c.dec_hidden * e->esz;
-    e->last_decode_step_bytes = e->dec_weight_bytes + kv;
+    const double kv = (double)Q * c.dec_layers * 2.0 * ((double)e->cur_Nimg + k * 0.5 * (minP + T)) * c.dec_hidden * e->pol.esz;
+    e->last_decode_step_bytes = e->w.dec_weight_bytes + kv;
     return 0;
 }
 
@@ -1707,7 +971,7 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
                         int32_t* sent_out, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const bool long_budget = sp->max_steps - minP > 32;
-    const bool graph = e->use_graph && !e->profiling && !long_budget;
+    const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
     if (!graph)
         return generate_body(e, frames, F, B, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
                              sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
@@ -1725,7 +989,7 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
     if (!e->ragged)     // ragged: ragged_prepare staged the images already
     for (int f = 0; f < F_eff; ++f)
         HIPCK(hipMemcpyAsync(e->frame_stage[f], frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
-    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->use_temb, *sp);
+    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->pol.use_temb, *sp);
     // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
     // enc_done record other contexts wait for
     const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
@@ -1785,7 +1049,7 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
         HIPCK(hipEventElapsedTime(&b, e->gev[1], e->gev[2]));
         e->split_encode_ms += a; e->split_decode_ms += b; e->split_calls += 1; e->split_steps += sp->max_steps - 1;
     }
-    const size_t nout = (size_t)Q * (size_t)(sp->num_keep_best > 1 ? sp->num_keep_best : 1);      // sequences returned
+    const size_t nout = (size_t)Q * (size_t)keep_best(*sp);      // sequences returned
     // the caller's buffers: device memory or PAGE-LOCKED host memory (hipMemcpyDefault: the results then arrive on the host as part
     // of the request itself -- a server reads them after the stream's event without enqueueing anything more, which matters when
     // its other streams keep the device's queues full: a separate small read-back waits milliseconds for a queue slot)
@@ -1834,7 +1098,7 @@ static int score_alloc(gitmi_engine* e, size_t rows_needed) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden;
     const size_t Qmax = (size_t)c.max_batch * c.max_beams;
-    const size_t esz = e->esz;
+    const size_t esz = e->pol.esz;
     auto alloc = [&](auto** p, size_t bytes) -> bool {
         void* q = nullptr;
         if (hipMalloc(&q, bytes) != hipSuccess) return false;
@@ -1845,7 +1109,7 @@ static int score_alloc(gitmi_engine* e, size_t rows_needed) {
     const bool ok = alloc(&e->sc_hf, rows * d * 4) && alloc(&e->sc_y, rows * d * 4) && alloc(&e->sc_ht, rows * d * esz) &&
                     alloc(&e->sc_qkv, rows * 3 * d * esz) && alloc(&e->sc_ctx, rows * d * esz) &&
                     alloc(&e->sc_u, rows * c.dec_ffn * esz) &&
-                    alloc(&e->sc_part, rows * (size_t)(e->f32 ? 1 : score_head_tiles(c.vocab)) * sizeof(float4)) &&
+                    alloc(&e->sc_part, rows * (size_t)(e->pol.f32 ? 1 : score_head_tiles(c.vocab)) * sizeof(float4)) &&
                     alloc(&e->sc_zt, rows * 4) && alloc(&e->sc_tgt, rows * 4) && alloc(&e->sc_lens, Qmax * 4) &&
                     alloc(&e->sc_img, Qmax * 4) && alloc(&e->sc_bad, Qmax * 4) && alloc(&e->sc_info, 16) &&
                     alloc(&e->sc_out, Qmax * (size_t)c.max_text_len * sizeof(float2));
@@ -1869,34 +1133,30 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
     RCK(generate_encode(e, frames, F, B, s));
     const int Lp = round_up(maxlen, 16), M = Q * Lp;
     SpanGuard phase(e, s, TAG_DECODE, 0);
-    HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->words_f, e->positions_f, e->emb_lng, e->emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
-                                e->f32, d, V, c.max_pos, s));
+    HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
+                                e->pol.f32, d, V, c.max_pos, s));
     for (int l = 0; l < c.dec_layers; ++l) {
-        const DecLayerW& L = e->dec[l];
-        RCK(gemm(e, s, e->sc_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
-        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->f32, s,
+        const DecLayerW& L = e->w.dec[l];
+        RCK(gemm(e, s, e->sc_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
+        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->pol.f32, s,
                                 e->ragged ? e->rg_ntok : nullptr));
-        RCK(gemm(e, s, e->sc_ctx, d, L.wo, L.bo, e->sc_hf, d, e->sc_y, d, true, M, d, d, 0, TAG_GEMM_OTHER));
-        HIPCK(launch_layernorm(e->sc_y, d, L.lnag, L.lnab, 1e-12f, nullptr, e->sc_ht, d, e->f32, e->sc_hf, d, M, d, 0, 0, 0, s));
-        RCK(gemm(e, s, e->sc_ht, d, L.w1, L.b1, nullptr, 0, e->sc_u, ffn, e->f32, M, ffn, d, 2, TAG_GEMM_OTHER));
-        RCK(gemm(e, s, e->sc_u, ffn, L.w2, L.b2, e->sc_hf, d, e->sc_y, d, true, M, d, ffn, 0, TAG_GEMM_OTHER));
-        HIPCK(launch_layernorm(e->sc_y, d, L.lnog, L.lnob, 1e-12f, nullptr, e->sc_ht, d, e->f32, e->sc_hf, d, M, d, 0, 0, 0, s));
+        RCK(dec_layer_tail(e, s, L, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
     }
     HIPCK(launch_score_targets(tokens, ld, Lp, e->sc_lens, V, M, e->sc_tgt, s));
     int ntiles = 1;
-    if (e->f32) {
+    if (e->pol.f32) {
         // parity mode: logits in chunks of the decode workspace's rows, then one statistics row each
         const int chunk = round_up(c.max_batch * c.max_beams, 64);
         for (int r0 = 0; r0 < M; r0 += chunk) {
             const int rows = std::min(chunk, M - r0);
-            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->out_w, e->out_b, nullptr, 0, e->logits, e->ldl, true, rows,
+            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, rows,
                      V, d, 0, TAG_GEMM_OTHER));
             HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
         }
     } else {
-        SpanGuard sp(e, s, TAG_GEMM_OTHER, 2.0 * (double)M * (double)V * (double)d);
+        SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
         ntiles = score_head_tiles(V);
-        HIPCK(launch_score_head(e->sc_ht, d, e->out_w, e->out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
+        HIPCK(launch_score_head(e->sc_ht, d, e->w.out_w, e->w.out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
     }
     HIPCK(hipMemsetAsync(e->sc_out, 0, (size_t)Q * ld * sizeof(float2), s));
     HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
@@ -2009,7 +1269,7 @@ extern "C" int gitmi_set_encode_after(gitmi_engine* e, gitmi_engine* after) {
 // (decoder.py:845-857); a bare tensor goes through image_encoder alone, also on a video model.
 extern "C" int gitmi_set_temporal_embedding(gitmi_engine* e, int on) {
     if (!e) return fail("null engine");
-    if ((on != 0) != e->use_temb) { e->use_temb = on != 0; e->have_feats = e->have_prefill = false; }
+    if ((on != 0) != e->pol.use_temb) { e->pol.use_temb = on != 0; e->have_feats = e->have_prefill = false; }
     return 0;
 }
 // Serving policy: other contexts keep the device busy beside this one.  Kernel shapes are then chosen for what they cost
@@ -2018,10 +1278,10 @@ extern "C" int gitmi_set_temporal_embedding(gitmi_engine* e, int on) {
 // workgroup, the decode attention packs 8 (sentence, head) pairs per workgroup.  Results are bit-identical either way.
 extern "C" int gitmi_set_shared_device(gitmi_engine* e, int on) {
     if (!e) return fail("null engine");
-    if ((on != 0) != e->shared_device) {
+    if ((on != 0) != e->pol.shared_device) {
         HIPCK(hipSetDevice(e->device));
         HIPCK(hipDeviceSynchronize());
-        e->shared_device = on != 0;
+        e->pol.shared_device = on != 0;
         destroy_graph(e);
     }
     return 0;
@@ -2031,12 +1291,12 @@ extern "C" int gitmi_set_shared_device(gitmi_engine* e, int on) {
 // rows less with the fold); the switch exists for A/B timing and for the parity tests that hold both forms to the same bound.
 extern "C" int gitmi_set_ln_fold(gitmi_engine* e, int on) {
     if (!e) return fail("null engine");
-    if (on && !e->ln_fold_ready)
+    if (on && !e->pol.ln_fold_ready)
         return fail("gitmi_set_ln_fold: not available (needs the fp16-operand library, the 16-bit engine mode and hidden sizes that are multiples of 256)");
-    if ((on != 0) != e->ln_fold) {
+    if ((on != 0) != e->pol.ln_fold) {
         HIPCK(hipSetDevice(e->device));
         HIPCK(hipDeviceSynchronize());
-        e->ln_fold = on != 0;
+        e->pol.ln_fold = on != 0;
         e->have_feats = e->have_prefill = false;
         destroy_graph(e);
     }
@@ -2044,7 +1304,7 @@ extern "C" int gitmi_set_ln_fold(gitmi_engine* e, int on) {
 }
 extern "C" int gitmi_set_graph(gitmi_engine* e, int on) {
     if (!e) return fail("null engine");
-    e->use_graph = on != 0;
+    e->pol.use_graph = on != 0;
     return 0;
 }
 extern "C" int gitmi_profile_read(gitmi_engine* e, gitmi_profile* out) {
@@ -2105,12 +1365,12 @@ GITMI_EXP_EXPORT int gitmi_debug_import_stage(gitmi_engine* dst, gitmi_engine* s
     if (src->cur_B > a.max_batch || src->cur_F > a.max_frames || src->N != dst->N) return fail("debug_import_stage: capacity / resolution mismatch");
     hipStream_t s = (hipStream_t)stream;
     const size_t M = (size_t)src->cur_B * src->cur_Nimg;
-    HIPCK(launch_convert(src->feats, src->f32, dst->feats, dst->f32, M * a.vit_width, s));
+    HIPCK(launch_convert(src->feats, src->pol.f32, dst->feats, dst->pol.f32, M * a.vit_width, s));
     dst->cur_B = src->cur_B; dst->cur_F = src->cur_F; dst->cur_Nimg = src->cur_Nimg;
     dst->have_feats = true; dst->have_prefill = false;
     if (stage == 2) {
         for (int l = 0; l < a.dec_layers; ++l) {
-            HIPCK(launch_convert(src->img_kv[l], src->f32, dst->img_kv[l], dst->f32, M * 3 * a.dec_hidden, s));
+            HIPCK(launch_convert(src->img_kv[l], src->pol.f32, dst->img_kv[l], dst->pol.f32, M * 3 * a.dec_hidden, s));
             RCK(kv_repack(dst, l, dst->cur_B, dst->cur_Nimg, s));
         }
         dst->have_prefill = true;
@@ -2121,8 +1381,8 @@ GITMI_EXP_EXPORT int gitmi_debug_import_stage(gitmi_engine* dst, gitmi_engine* s
 // (an fp32 context) computed in its most recent gitmi_step_logits over R rows: logits_out fp32 [R, vocab] (device)
 GITMI_EXP_EXPORT int gitmi_debug_head_from(gitmi_engine* dst, gitmi_engine* src, int R, float* logits_out, void* stream) {
     RCK(check_ready(dst));
-    if (!src || !src->f32 || !logits_out) return fail("debug_head_from: the source must be an fp32 context");
-    if (dst->f32 || !dst->skinny) return fail("debug_head_from: the destination must run the bf16 decode chain");
+    if (!src || !src->pol.f32 || !logits_out) return fail("debug_head_from: the source must be an fp32 context");
+    if (dst->pol.f32 || !dst->pol.skinny) return fail("debug_head_from: the destination must run the bf16 decode chain");
     const gitmi_config& c = dst->cfg;
     if (c.dec_hidden != src->cfg.dec_hidden || c.vocab != src->cfg.vocab) return fail("debug_head_from: different models");
     if (R < 1 || R > c.max_batch * c.max_beams) return fail("debug_head_from: R outside the capacity");
@@ -2130,53 +1390,4 @@ GITMI_EXP_EXPORT int gitmi_debug_head_from(gitmi_engine* dst, gitmi_engine* src,
     HIPCK(launch_chain_input(src->d_y, dst->xo_b, dst->stats_o, R, c.dec_hidden, s));   // d_y: pre-LayerNorm sum of the last layer
     StepCands cands{};
     return decode_head_impl(dst, nullptr, c.max_text_len, 1, R, 1, 0, 1, logits_out, c.vocab, s, &cands);
-}
-
-// ---- op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py) -----------------------
-// attention: qkv [Q * Lp][3 H 64] text rows, img_kv [B * N_img][3 H 64] prefill rows, image_of int32 [Q] -> out [Q * Lp][H 64]
-// (dtype GITMI_DTYPE_F32: the fp32 kernel of the parity mode; the build's 16-bit operand dtype: the MFMA kernel)
-GITMI_EXP_EXPORT int gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H,
-                                            int N_img, int Lp, int dtype, void* stream) {
-    if (!qkv || !img_kv || !image_of || !out) return fail("debug_score_attn: null argument");
-    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_attn: dtype %d not served by this build", dtype);
-    HIPCK(launch_score_attn(qkv, img_kv, image_of, out, Q, H, H * 64, N_img, Lp, 0.125f, dtype == GITMI_DTYPE_F32,
-                            (hipStream_t)stream));
-    return 0;
-}
-// head + combine: logits z = A [M][K] W [V][K]^T + bias (never stored in the 16-bit form) -> out fp32 [M][2] =
-// (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) for rows with tgt[m] >= 0, 0 elsewhere.  Synchronises the stream.
-GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K,
-                                            int dtype, float* out, void* stream) {
-    if (!A || !W || !bias || !tgt || !out || M < 1 || V < 2 || K < 32 || K % 32) return fail("debug_score_head: bad argument");
-    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_head: dtype %d not served by this build", dtype);
-    hipStream_t s = (hipStream_t)stream;
-    const bool f32 = dtype == GITMI_DTYPE_F32;
-    const int ntiles = f32 ? 1 : score_head_tiles(V);
-    const int ldl = round_up(V, 8);
-    float4* part = nullptr; float* zt = nullptr; float2* o2 = nullptr; int* bad = nullptr; float* logits = nullptr;
-    int rc = 0;
-    auto body = [&]() -> int {
-        HIPCK(hipMalloc(&part, (size_t)M * ntiles * sizeof(float4)));
-        HIPCK(hipMalloc(&zt, (size_t)M * sizeof(float)));
-        HIPCK(hipMalloc(&o2, (size_t)(M + 1) * sizeof(float2)));
-        HIPCK(hipMalloc(&bad, (size_t)M * sizeof(int)));
-        if (f32) {
-            HIPCK(hipMalloc(&logits, (size_t)M * ldl * sizeof(float)));
-            GemmArgs g{};
-            g.A = A; g.W = W; g.bias = bias; g.C = logits; g.M = M; g.N = V; g.K = K; g.lda = K; g.ldc = ldl;
-            HIPCK(launch_gemm(g, true, true, s));
-            HIPCK(launch_score_rowstats(logits, ldl, V, tgt, 0, M, part, zt, s));
-        } else {
-            HIPCK(launch_score_head(A, K, W, bias, tgt, M, V, K, part, zt, s));
-        }
-        HIPCK(hipMemsetAsync(o2, 0, (size_t)(M + 1) * sizeof(float2), s));
-        // one position per "sentence" (Lp = ld = 1): row m lands in o2[m + 1]
-        HIPCK(launch_score_combine(part, ntiles, zt, tgt, M, 1, 1, V, o2, bad, s));
-        HIPCK(hipMemcpyAsync(out, o2 + 1, (size_t)M * sizeof(float2), hipMemcpyDefault, s));
-        HIPCK(hipStreamSynchronize(s));
-        return 0;
-    };
-    rc = body();
-    hipFree(part); hipFree(zt); hipFree(o2); hipFree(bad); hipFree(logits);
-    return rc;
 }

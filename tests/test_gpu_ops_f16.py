@@ -327,7 +327,7 @@ def test_kv_repack_moves_each_block(dtype, B, H, N):
 
 # ---- decode-step GEMM chain (kernels_dgemm.hip) -------------------------------------------------------------------
 def _fold16(W, bias, gamma, beta):
-    """gitmi_finalize_weights of the fp16 library for a GEMM behind a LayerNorm: W' = fp16(W . gamma) (engine.hip's
+    """gitmi_finalize_weights of the fp16 library for a GEMM behind a LayerNorm: W' = fp16(W . gamma) (engine_weights.hip's
     bf16_round rounds to the build's operand type), beta W^T + b, colsum(W')."""
     Wf = (W * gamma[None, :]).half()
     return Wf, (bias.double() + W.double() @ beta.double()).float(), Wf.double().sum(1).float()

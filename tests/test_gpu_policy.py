@@ -1,4 +1,5 @@
-"""GPU: the kernel-shape policy of gitmi_set_shared_device never changes results (include/gitmi.h)."""
+"""GPU: the kernel-shape policy of gitmi_set_shared_device never changes results (include/gitmi.h); a clone inherits the
+current policy of its source."""
 import pytest
 import torch
 
@@ -34,3 +35,38 @@ def test_shared_device_policy_is_bitwise_neutral(precision):
         assert torch.equal(out[False][1], out[True][1]) and torch.equal(out[False][2], out[True][2])
         assert torch.equal(tok_c, out[True][1]) and torch.equal(lp_c, out[True][2])
     eng.close()
+
+
+def test_clone_inherits_the_current_switches_of_its_source():
+    """A clone takes the CURRENT gitmi_set_ln_fold / gitmi_set_shared_device / gitmi_set_temporal_embedding state of its
+    source, not the defaults of a fresh context: after the three setters, features, ids and log-probs of the clone are
+    bit-identical to the source's.  The folded and the unfolded encoder differ by rounding (B x 197 > 512 rows, so the fold is
+    live), and a video model's features differ with and without the temporal embedding, so equality holds only if the clone
+    really took the switches; both discriminations are asserted."""
+    from generativeimage2text_amd.configs import config_for_model
+    from generativeimage2text_amd.engine import Engine
+    from generativeimage2text_amd.synthetic import random_frames, random_state_dict
+    search = Engine.make_search("greedy", 20, 1, 1)
+    for model, B, F in (("GIT_BASE", 4, 1), ("GIT_BASE_VATEX", 3, 2)):
+        cfg = config_for_model(model)
+        eng = Engine(cfg, precision="f16", max_batch=B, max_beams=1, max_frames=F, max_text_len=20)
+        eng.load_state_dict(random_state_dict(cfg, seed=1234))
+        frames = random_frames(cfg, B, F, seed=0)
+        feats = {}
+        for fold, temb in ((False, False), (True, False), (True, True)):
+            eng.set_ln_fold(fold)
+            eng.set_shared_device(True)
+            eng.set_temporal_embedding(temb)
+            f = eng.encode(frames, return_features=True).clone()
+            tok, lp, _ = eng.generate(frames, search)
+            clone = eng.clone()
+            f_c = clone.encode(frames, return_features=True).clone()
+            tok_c, lp_c, _ = clone.generate(frames, search)
+            clone.close()
+            assert torch.equal(f_c, f), (model, fold, temb)
+            assert torch.equal(tok_c, tok) and torch.equal(lp_c, lp), (model, fold, temb)
+            feats[fold, temb] = f
+        assert not torch.equal(feats[False, False], feats[True, False]), model        # the fold switch changes the rounding
+        if cfg.num_frames:
+            assert not torch.equal(feats[True, False], feats[True, True]), model      # the embedding switch changes the features
+        eng.close()
