@@ -235,7 +235,8 @@ extern "C" int gitmi_create(const gitmi_config* cfg, int device, gitmi_engine** 
     return 0;
 }
 
-static void destroy_graph(gitmi_engine* e) {
+// the two hipGraph slots: full calls (one graph, or encode + prefill | decode) and follow-up calls (decode alone)
+static void destroy_full_graph(gitmi_engine* e) {
     if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
     if (e->graph) hipGraphDestroy(e->graph);
     if (e->graph_exec_b) hipGraphExecDestroy(e->graph_exec_b);
@@ -244,6 +245,19 @@ static void destroy_graph(gitmi_engine* e) {
     e->graph = e->graph_b = nullptr;
     e->graph_valid = false;
 }
+static void destroy_followup_graph(gitmi_engine* e) {
+    if (e->graph_exec_r) hipGraphExecDestroy(e->graph_exec_r);
+    if (e->graph_r) hipGraphDestroy(e->graph_r);
+    e->graph_exec_r = nullptr;
+    e->graph_r = nullptr;
+    e->graph_r_valid = false;
+}
+static void destroy_graph(gitmi_engine* e) {
+    destroy_full_graph(e);
+    destroy_followup_graph(e);
+}
+// the engine's images stop being resident: an encode starts (or failed), or a setter changed what an encode would produce
+static void drop_resident(gitmi_engine* e) { e->have_feats = e->have_prefill = false; }
 
 extern "C" void gitmi_destroy(gitmi_engine* e) {
     if (!e) return;
@@ -281,7 +295,7 @@ extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream
             e->ragged = true;
             e->H = e->W = e->gh = e->gw = 0;
             e->N = e->Nmax;
-            e->have_feats = e->have_prefill = false;
+            drop_resident(e);
         }
         return 0;
     }
@@ -301,7 +315,7 @@ extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream
         e->pos_cur = e->pos_var;
     }
     e->H = H; e->W = W; e->gh = gh; e->gw = gw; e->N = gh * gw + 1;
-    e->have_feats = e->have_prefill = false;
+    drop_resident(e);
     return 0;
 }
 
@@ -312,6 +326,7 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
     const int D = c.vit_width, N = e->N;
     const int F_eff = c.num_frames > 0 ? std::min(F, c.num_frames) : F;   // zip() truncation, decoder.py:849
     const int Nimg = F_eff * N;
+    drop_resident(e);           // the workspaces are overwritten from here on: resident again once the whole pass is enqueued
     SpanGuard phase(e, s, TAG_VIT, 0);
     // all frames of the call go through the encoder as ONE batch of F*B images (the reference encodes frame by
     // frame, decoder.py:847; per-image results are identical, the GEMMs just see M = F*B*197 rows)
@@ -401,6 +416,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, ffn = c.dec_ffn, D = c.vit_width;
     const int B = e->cur_B, Nimg = e->cur_Nimg, M = B * Nimg;
+    e->have_prefill = false;
     SpanGuard phase(e, s, TAG_PREFILL, 0);
     const bool fold = e->pol.ln_fold && on_p8(e->feats, D, e->w.vp_w, e->p_y, d, M, d, D, true) &&
                       on_p8(e->p_y, d, e->w.dec[0].qkv_pf.w, e->img_kv[0], 3 * d, M, 3 * d, d, false) &&
@@ -644,6 +660,7 @@ static int check_ready(gitmi_engine* e) {
 static int ragged_prepare(gitmi_engine* e, const float* const* frames, int F, int B, hipStream_t s) {
     if (!e->ragged) return 0;
     if (F != 1 || !frames[0]) return fail("ragged input (gitmi_set_image_shape(e, 0, 0)): F must be 1, frames[0] the descriptor buffer");
+    drop_resident(e);           // rg_meta / rg_ntok of the resident batch are overwritten
     HIPCK(launch_ragged_stage(frames[0], e->frame_stage[0], (size_t)3 * e->max_pixels, e->rg_meta, e->rg_ntok, B, e->cfg.patch,
                               e->max_pixels, e->Nmax, s));
     return 0;
@@ -653,6 +670,16 @@ static int ragged_prepare(gitmi_engine* e, const float* const* frames, int F, in
 static int check_frames(const gitmi_engine* e, const char* who, const float* const* frames, int F, int B) {
     if (!frames || F < 1 || F > e->cfg.max_frames) return fail("%s: F=%d outside [1,%d]", who, F, e->cfg.max_frames);
     if (B < 1 || B > e->cfg.max_batch) return fail("%s: B=%d outside [1,%d]", who, B, e->cfg.max_batch);
+    return 0;
+}
+
+// follow-up calls (frames == NULL, include/gitmi.h): the images of the engine's last encode, `B` of them
+static int check_resident(const gitmi_engine* e, const char* who, int B) {
+    if (!e->have_feats)
+        return fail("%s: frames == NULL is a follow-up call, but the engine holds no resident images (encode some with a call "
+                    "that takes frames; a change of the image shape or mode, of the temporal embedding or of the LayerNorm "
+                    "folding, and a failed call, drop them)", who);
+    if (B != e->cur_B) return fail("%s: follow-up call with B=%d, but %d images are resident (B must equal that count)", who, B, e->cur_B);
     return 0;
 }
 
@@ -970,11 +997,21 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
                         const gitmi_search* sp, int64_t* tokens_out, float* logprob_out, int32_t* info_out,
                         int32_t* sent_out, hipStream_t s) {
     const gitmi_config& c = e->cfg;
+    const bool resident = frames == nullptr;        // follow-up call: the decode part alone (+ the prefill if it is not current)
     const bool long_budget = sp->max_steps - minP > 32;
     const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
-    if (!graph)
-        return generate_body(e, frames, F, B, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
-                             sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
+    if (!graph) {
+        if (resident) {
+            SpanGuard total(e, s, 99, 0);
+            if (!e->have_prefill) RCK(prefill_impl(e, s));
+            return generate_decode(e, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
+                                   sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
+        }
+        const int rc = generate_body(e, frames, F, B, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
+                                     sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
+        if (rc != 0) drop_resident(e);
+        return rc;
+    }
 
     // ---- hipGraph path: the launch sequence only depends on (B,Q,F,minP,search); inputs and outputs are
     // staged through engine-owned buffers so the captured pointers stay valid across calls.
@@ -985,16 +1022,46 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
         HIPCK(hipStreamWaitEvent(x, e->fence_in, 0));
     }
     const size_t frame_bytes = (size_t)B * 3 * e->H * e->W * sizeof(float);
-    const int F_eff = c.num_frames > 0 ? std::min(F, c.num_frames) : F;
-    if (!e->ragged)     // ragged: ragged_prepare staged the images already
+    const int F_eff = resident ? e->cur_F : c.num_frames > 0 ? std::min(F, c.num_frames) : F;
+    if (!e->ragged && !resident)    // ragged: ragged_prepare staged the images already; follow-up: no frames
     for (int f = 0; f < F_eff; ++f)
         HIPCK(hipMemcpyAsync(e->frame_stage[f], frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
-    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->pol.use_temb, *sp);
+    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->pol.use_temb, resident, *sp);
     // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
     // enc_done record other contexts wait for
     const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
-    if (!e->graph_valid || !(key == e->graph_key) || split != e->graph_is_split) {
-        destroy_graph(e);
+    if (resident) {
+        // the decode graph alone, in its own slot.  No encoder runs: the call neither waits for enc_after's encoder nor
+        // records enc_done (watchers keep waiting for the most recent real encoder)
+        if (!e->have_prefill) RCK(prefill_impl(e, x));          // after gitmi_encode_frames alone; outside the graph
+        if (!e->graph_r_valid || !(key == e->graph_r_key)) {
+            destroy_followup_graph(e);
+            HIPCK(hipStreamBeginCapture(x, hipStreamCaptureModeThreadLocal));
+            const int rc = generate_decode(e, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
+            hipGraph_t gr = nullptr;
+            const hipError_t ce = hipStreamEndCapture(x, &gr);
+            if (rc != 0) { if (gr) hipGraphDestroy(gr); return rc; }
+            HIPCK(ce);
+            e->graph_r = gr;
+            HIPCK(hipGraphInstantiate(&e->graph_exec_r, e->graph_r, nullptr, nullptr, 0));
+            e->graph_r_key = key;
+            e->graph_r_valid = true;
+        }
+        if (e->profile_mode != 2) {
+            HIPCK(hipGraphLaunch(e->graph_exec_r, x));
+        } else {            // the decode graph timed as in a full call; nothing is added to the encode side
+            for (auto& ev : e->gev)
+                if (!ev) HIPCK(hipEventCreate(&ev));
+            HIPCK(hipEventRecord(e->gev[1], x));
+            HIPCK(hipGraphLaunch(e->graph_exec_r, x));
+            HIPCK(hipEventRecord(e->gev[2], x));
+            HIPCK(hipStreamSynchronize(x));
+            float b = 0;
+            HIPCK(hipEventElapsedTime(&b, e->gev[1], e->gev[2]));
+            e->split_decode_ms += b; e->split_calls += 1; e->split_steps += sp->max_steps - 1;
+        }
+    } else if (!e->graph_valid || !(key == e->graph_key) || split != e->graph_is_split) {
+        destroy_full_graph(e);
         std::vector<const float*> fp(F_eff);
         for (int f = 0; f < F_eff; ++f) fp[f] = e->frame_stage[f];
         auto capture = [&](int part, hipGraph_t* gr_out) -> int {       // part 0: whole call, 1: encode + prefill, 2: decode
@@ -1006,7 +1073,8 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
             else rc = generate_decode(e, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
             hipGraph_t gr = nullptr;
             hipError_t ce = hipStreamEndCapture(x, &gr);
-            if (rc != 0) { if (gr) hipGraphDestroy(gr); return rc; }
+            // a failed capture ran the host side of the encode (cur_B, have_feats) but nothing on the device
+            if (rc != 0) { if (gr) hipGraphDestroy(gr); drop_resident(e); return rc; }
             HIPCK(ce);
             *gr_out = gr;
             return 0;
@@ -1028,7 +1096,9 @@ static int generate_run(gitmi_engine* e, const float* const* frames, int F, int 
         e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = F_eff * e->N;
         e->have_feats = e->have_prefill = true;
     }
-    if (!split) {
+    if (resident) {
+        // launched above
+    } else if (!split) {
         HIPCK(hipGraphLaunch(e->graph_exec, x));
     } else if (e->profile_mode != 2) {
         if (e->enc_after && e->enc_after->enc_done) HIPCK(hipStreamWaitEvent(x, e->enc_after->enc_done, 0));
@@ -1070,13 +1140,15 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     RCK(check_ready(e));
     const gitmi_config& c = e->cfg;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
-    if (!frames || !sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
-    RCK(check_frames(e, "generate", frames, F, B));
+    // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
+    if (!frames) RCK(check_resident(e, "generate", B));
+    if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
+    if (frames) RCK(check_frames(e, "generate", frames, F, B));
     if (!prefix) P = 1;
     if (P < 1 || P > c.max_text_len) return fail("generate: prefix length %d outside [1,%d]", P, c.max_text_len);
     if (sp->max_steps < P || sp->max_steps > c.max_text_len) return fail("generate: max_steps %d outside [P,%d]", sp->max_steps, c.max_text_len);
     hipStream_t s = (hipStream_t)stream;
-    RCK(ragged_prepare(e, frames, F, B, s));
+    if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     // start tokens [B, P] on device (shared prefix, or [CLS]) -- filled by a kernel, no host copy
     RCK(fill_uniform_sentences(e, B, (const long long*)prefix, P, s));
     return generate_run(e, frames, F, B, B, P, P, false, sp, tokens_out, logprob_out, info_out, nullptr, s);
@@ -1130,7 +1202,8 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
                       float* out, int32_t* info_out, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, ffn = c.dec_ffn, V = c.vocab;
-    RCK(generate_encode(e, frames, F, B, s));
+    if (frames) RCK(generate_encode(e, frames, F, B, s));
+    else if (!e->have_prefill) RCK(prefill_impl(e, s));     // follow-up call: the resident images' K/V
     const int Lp = round_up(maxlen, 16), M = Q * Lp;
     SpanGuard phase(e, s, TAG_DECODE, 0);
     HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
@@ -1208,19 +1281,23 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     hipStream_t s = (hipStream_t)stream;
     SentenceSpan span;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) {
-        if (!frames || !logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("score: null argument");
-        RCK(check_frames(e, "score", frames, F, B));
+        if (!frames) RCK(check_resident(e, "score", B));
+        if (!logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("score: null argument");
+        if (frames) RCK(check_frames(e, "score", frames, F, B));
         if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("score: ld=%d outside [1,%d] (max_text_len)", ld_prefix, c.max_text_len);
         RCK(read_sentences(e, "score", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch * c.max_beams,
                            "max_batch x max_beams", &span));
         RCK(score_alloc(e, (size_t)Q * round_up(span.maxP, 16)));
         RCK(upload_sentences(e, e->sc_lens, e->sc_img, s));
-        RCK(ragged_prepare(e, frames, F, B, s));
-        return score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, span.maxP, logprob_out, info_out, s);
+        if (frames) RCK(ragged_prepare(e, frames, F, B, s));
+        const int rc = score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, span.maxP, logprob_out, info_out, s);
+        if (rc != 0 && frames) drop_resident(e);
+        return rc;
     }
-    if (!frames || !sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
+    if (!frames) RCK(check_resident(e, "generate_prefixed", B));
+    if (!sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
         return fail("generate_prefixed: null argument");
-    RCK(check_frames(e, "generate_prefixed", frames, F, B));
+    if (frames) RCK(check_frames(e, "generate_prefixed", frames, F, B));
     RCK(read_sentences(e, "generate_prefixed", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch, "max_batch", &span));
     if (sp->max_steps < span.maxP || sp->max_steps > c.max_text_len)
         return fail("generate_prefixed: max_steps %d outside [%d,%d]", sp->max_steps, span.maxP, c.max_text_len);
@@ -1228,7 +1305,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     HIPCK(hipMemcpy2D(e->start_dev, (size_t)c.max_text_len * sizeof(long long), prefixes, (size_t)ld_prefix * sizeof(long long),
                       (size_t)span.maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
     e->img_identity = span.ident;
-    RCK(ragged_prepare(e, frames, F, B, s));
+    if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     return generate_run(e, frames, F, B, Q, span.minP, span.maxP, true, sp, tokens_out, logprob_out, info_out, sent_out, s);
 }
 
@@ -1269,7 +1346,7 @@ extern "C" int gitmi_set_encode_after(gitmi_engine* e, gitmi_engine* after) {
 // (decoder.py:845-857); a bare tensor goes through image_encoder alone, also on a video model.
 extern "C" int gitmi_set_temporal_embedding(gitmi_engine* e, int on) {
     if (!e) return fail("null engine");
-    if ((on != 0) != e->pol.use_temb) { e->pol.use_temb = on != 0; e->have_feats = e->have_prefill = false; }
+    if ((on != 0) != e->pol.use_temb) { e->pol.use_temb = on != 0; drop_resident(e); }
     return 0;
 }
 // Serving policy: other contexts keep the device busy beside this one.  Kernel shapes are then chosen for what they cost
@@ -1297,7 +1374,7 @@ extern "C" int gitmi_set_ln_fold(gitmi_engine* e, int on) {
         HIPCK(hipSetDevice(e->device));
         HIPCK(hipDeviceSynchronize());
         e->pol.ln_fold = on != 0;
-        e->have_feats = e->have_prefill = false;
+        drop_resident(e);
         destroy_graph(e);
     }
     return 0;

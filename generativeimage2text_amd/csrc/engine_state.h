@@ -54,14 +54,18 @@ enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM
 
 // hipGraph cache key of gitmi_generate / gitmi_generate_prefixed: everything the captured launch sequence depends on
 struct GraphKey {
-    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb; double lp;
+    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident; double lp;
     int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
-    static GraphKey of(int B, int Q, int F, int P, int H, int W, bool prefixed, bool ident, bool temb, const gitmi_search& sp) {
+    // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds
+    static GraphKey of(int B, int Q, int F, int P, int H, int W, bool prefixed, bool ident, bool temb, bool resident,
+                       const gitmi_search& sp) {
         return {B, Q, F, P, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, H, W, prefixed ? 1 : 0, ident ? 1 : 0,
-                temb ? 1 : 0, sp.length_penalty, sp.do_sample, sp.top_k, keep_best(sp), sp.top_p,
+                temb ? 1 : 0, resident ? 1 : 0, sp.length_penalty, sp.do_sample, sp.top_k, keep_best(sp), sp.top_p,
                 sp.temperature, sp.repetition_penalty, sp.seed};
     }
-    auto fields() const { return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, lp, smp, top_k, nh, top_p, temp, rp, seed); }
+    auto fields() const {
+        return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, lp, smp, top_k, nh, top_p, temp, rp, seed);
+    }
     bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
 
@@ -170,7 +174,9 @@ struct gitmi_engine {
     gitmi_search sample{};              // sampling parameters of the current search (do_sample, top_k, top_p, temperature, seed)
     std::vector<int> plen_host, img_of_host;
 
-    // state of the current batch
+    // state of the current batch.  have_feats also means "these images are RESIDENT": a follow-up call (frames == NULL,
+    // include/gitmi.h) searches or scores over them without encoding.  Set at the end of an encode, cleared when an encode
+    // starts (so a call that fails half-way leaves none) and by every setter that changes what an encode would produce.
     int cur_B = 0, cur_F = 0, cur_Nimg = 0;
     bool have_feats = false, have_prefill = false;
 
@@ -203,6 +209,12 @@ struct gitmi_engine {
     GraphKey graph_key{};
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
+    // ... and the slot beside it for follow-up calls: the decode part alone (GraphKey::resident), so that full and follow-up
+    // calls with unchanged arguments alternate without re-capturing either
+    bool graph_r_valid = false;
+    GraphKey graph_r_key{};
+    hipGraph_t graph_r = nullptr;
+    hipGraphExec_t graph_exec_r = nullptr;
     std::vector<float*> frame_stage;   // engine-owned copies of the input frames (graph inputs)
     long long* out_tokens = nullptr;   // graph outputs, copied to the caller's buffers after the launch
     float* out_lp = nullptr;

@@ -306,6 +306,10 @@ class Engine:
         self._h = C.c_void_p()
         self._ck(self.lib.gitmi_create(C.byref(c), self.device, C.byref(self._h)))
         self._finalized = False
+        self._init_resident()
+        # host mirror of the two switches whose flip drops the resident images (gitmi_create's defaults)
+        self._temb = True
+        self._ln_fold = precision in ("f16", "fp16") and c.vit_width % 256 == 0 and c.dec_hidden % 256 == 0
 
     # -- lifecycle ---------------------------------------------------------------------------
     def _ck(self, rc: int) -> None:
@@ -323,7 +327,56 @@ class Engine:
         self._ck(self.lib.gitmi_clone(self._h, C.byref(other._h)))
         other._finalized = True
         other._parent = self
+        other._init_resident()                                  # every context has its own resident set; a clone starts with none
+        other._temb, other._ln_fold = self._temb, self._ln_fold  # clones inherit the switches
         return other
+
+    # -- resident images: what follow-up calls (frames=None) run over ---------------------------------------------------------
+    def _init_resident(self) -> None:
+        self._resident: Optional[int] = None
+        self._generation = 0
+
+    @property
+    def resident(self) -> Optional[int]:
+        """Number of images a follow-up call (generate / generate_prefixed / score with frames=None) would run over, or None:
+        the host mirror of include/gitmi.h's residency rules -- set by every call that encodes images, dropped by a change of
+        the image shape or mode, of the temporal embedding or of the LayerNorm folding."""
+        return self._resident
+
+    @property
+    def generation(self) -> int:
+        """Counts the changes of the resident set (a new encode, a drop): a handle that remembers it can tell whether the
+        images it was issued for are still the ones this context holds (model.Pending)."""
+        return self._generation
+
+    def _drop_resident(self) -> None:
+        self._resident = None
+        self._generation += 1
+
+    def _encoded(self, rc: int, B: int) -> None:
+        """The tail of a call that takes frames: B images are resident if it succeeded.  If it failed, the images of before
+        are still resident exactly when the error was found before the first launch; the library is asked (a follow-up call
+        whose only fault is an empty prefix fails on that prefix if, and only if, they are), then the call's error is raised."""
+        old = self._resident
+        self._generation += 1
+        if rc == 0:
+            self._resident = int(B)
+            return
+        msg = (self.lib.gitmi_last_error() or b"").decode("utf-8", "replace")
+        if old is not None:
+            s = GitmiSearch()
+            s.max_steps = 1
+            dummy = (C.c_int64 * 4)()
+            self.lib.gitmi_generate(self._h, None, 0, old, dummy, 0, C.byref(s), dummy, dummy, dummy, None)
+            still = b"prefix length" in (self.lib.gitmi_last_error() or b"")
+            self._resident = old if still else None
+        raise GitmiError(msg or "gitmi call failed")
+
+    def _call(self, frames, rc: int, B: int) -> int:
+        """rc of an entry point that was given `frames` (None: a follow-up call, which changes nothing about residency)."""
+        if frames is not None:
+            self._encoded(rc, B)
+        return rc
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -357,6 +410,7 @@ class Engine:
         if (H, W) != self._hw:
             self._ck(self.lib.gitmi_set_image_shape(self._h, int(H), int(W), _stream()))
             self._hw = (int(H), int(W))
+            self._drop_resident()
             self.n_tok = (H // self.c.patch) * (W // self.c.patch) + 1
 
     # -- ragged batches: every image of a call at its own size ------------------------------------------------------
@@ -380,12 +434,17 @@ class Engine:
         return pack_ragged(images, int(self.c.patch), self.max_pixels, self.max_tokens, int(self.c.max_batch),
                            device=f"cuda:{self.device}")
 
-    def _frames_arg(self, frames) -> Tuple[C.Array, List[torch.Tensor], int]:
+    def _frames_arg(self, frames) -> Tuple[Optional[C.Array], List[torch.Tensor], int]:
+        """-> (the `frames` argument of the C call, the tensors to keep alive, B).  frames None: a follow-up call over the
+        resident images (NULL, no tensors, their count -- 0 when there are none, which the library refuses by name)."""
+        if frames is None:
+            return None, [], int(self._resident or 0)
         if isinstance(frames, RaggedImages):
             if self._hw != (0, 0):
                 self._ck(self.lib.gitmi_set_image_shape(self._h, 0, 0, _stream()))
                 self._hw = (0, 0)
                 self.n_tok = self.max_tokens
+                self._drop_resident()
             buf = frames.buffer
             if buf.device != torch.device(f"cuda:{self.device}") or buf.dtype != torch.float32:
                 raise ValueError("a ragged input buffer must be fp32 on the engine's device (Engine.pack_images)")
@@ -405,7 +464,7 @@ class Engine:
         out = None
         if return_features:
             out = torch.empty(B, F_eff * self.n_tok, self.c.vit_width, device=keep[0].device, dtype=torch.float32)
-        self._ck(self.lib.gitmi_encode_frames(self._h, arr, F, B, _ptr(out), _stream()))
+        self._encoded(self.lib.gitmi_encode_frames(self._h, arr, F, B, _ptr(out), _stream()), B)
         return out
 
     def prefill(self) -> None:
@@ -456,19 +515,21 @@ class Engine:
             torch.cuda.current_stream().synchronize()
             self.check_finite(info)
 
-    def generate(self, frames: Sequence[torch.Tensor], search: GitmiSearch,
+    def generate(self, frames: Optional[Sequence[torch.Tensor]], search: GitmiSearch,
                  prefix: Optional[torch.Tensor] = None, sync: bool = True, host_out: bool = False):
         """-> (tokens int64 [B, max_steps] incl. start tokens / EOS padded, logprobs fp32 [B], info int32 [4]).
-        host_out: the three come back as page-locked host tensors (_empty)."""
+        host_out: the three come back as page-locked host tensors (_empty).
+        frames None: a follow-up call -- the search runs over the resident images (`resident`), nothing is encoded."""
         arr, keep, B = self._frames_arg(frames)
-        dev = keep[0].device
+        dev = torch.device(f"cuda:{self.device}")
         tokens, logprobs, info = self._out(B, search, dev, host_out)
         P, pfx = 1, None
         if prefix is not None:
             pfx = prefix.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
             P = int(pfx.numel())
-        self._done(self.lib.gitmi_generate(self._h, arr, len(keep), B, _ptr(pfx), P, C.byref(search), tokens.data_ptr(),
-                                           logprobs.data_ptr(), info.data_ptr(), _stream()), info, sync)
+        self._done(self._call(frames, self.lib.gitmi_generate(self._h, arr, len(keep), B, _ptr(pfx), P, C.byref(search),
+                                                              tokens.data_ptr(), logprobs.data_ptr(), info.data_ptr(), _stream()), B),
+                   info, sync)
         return tokens, logprobs, info
 
     def check_finite(self, info) -> None:
@@ -499,36 +560,37 @@ class Engine:
             lo += n
         return out, info
 
-    def generate_prefixed(self, frames: Sequence[torch.Tensor], search: GitmiSearch,
+    def generate_prefixed(self, frames: Optional[Sequence[torch.Tensor]], search: GitmiSearch,
                           prefixes: Sequence[Sequence[int]], image_of: Optional[Sequence[int]] = None, sync: bool = True,
                           host_out: bool = False):
         """Batched VQA: sentence q starts from its own prefix `prefixes[q]` (token ids incl. [CLS], any lengths) and
         attends to image `image_of[q]` of the encoded batch (default: sentence q <-> image q).  Every sentence gets
         exactly what a batch-1 reference call with that image and prefix returns (decoder.py:984-1006).
+        frames None: a follow-up call -- new questions (or another search) over the resident images, nothing is encoded.
         -> (tokens int64 [Q, max_steps], logprobs fp32 [Q], sent int32 [Q, 2] = (returned length, early), info int32 [4])"""
         arr, keep, B = self._frames_arg(frames)
-        dev = keep[0].device
+        dev = torch.device(f"cuda:{self.device}")
         Q = len(prefixes)
         lens = [len(p) for p in prefixes]
         table = id_table(prefixes).to(dev)
         tokens, logprobs, info = self._out(Q, search, dev, host_out)
         sent = self._empty((Q, 2), torch.int32, dev, host_out)
-        self._done(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, table.data_ptr(), table.shape[1],
-                                                    *_sentence_tables(lens, image_of), Q, C.byref(search), tokens.data_ptr(),
-                                                    logprobs.data_ptr(), sent.data_ptr(), info.data_ptr(), _stream()),
-                   info, sync)
+        self._done(self._call(frames, self.lib.gitmi_generate_prefixed(
+            self._h, arr, len(keep), B, table.data_ptr(), table.shape[1], *_sentence_tables(lens, image_of), Q, C.byref(search),
+            tokens.data_ptr(), logprobs.data_ptr(), sent.data_ptr(), info.data_ptr(), _stream()), B), info, sync)
         return tokens, logprobs, sent, info
 
-    def score(self, frames: Sequence[torch.Tensor], tokens, lengths: Optional[Sequence[int]] = None,
+    def score(self, frames: Optional[Sequence[torch.Tensor]], tokens, lengths: Optional[Sequence[int]] = None,
               image_of: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Per-token log-probabilities of given sentences (include/gitmi.h GITMI_SEARCH_SCORE; the textual head of
         CaptioningModel.forward_one_ce, decoder.py:916-972, run once over whole sequences).
         tokens: int [Q, L] (each row starts with [CLS]; entries past a row's length are ignored), lengths: [Q] (default L),
         image_of: [Q] image of the encoded batch every sentence belongs to (default: sentence q <-> image q, Q == B).
         -> fp32 [Q, L, 2] on the device: (lp, mean_lp) at position j = (log_softmax(z)[tokens[q, j]],
-        mean_c log_softmax(z)[c]) with z the logits at position j - 1; position 0 and positions >= length are 0."""
+        mean_c log_softmax(z)[c]) with z the logits at position j - 1; position 0 and positions >= length are 0.
+        frames None: a follow-up call -- the sentences are scored over the resident images, nothing is encoded."""
         arr, keep, B = self._frames_arg(frames)
-        dev = keep[0].device
+        dev = torch.device(f"cuda:{self.device}")
         tok = torch.as_tensor(tokens).detach().to("cpu", torch.int64)
         if tok.dim() != 2 or tok.shape[1] < 1:
             raise ValueError(f"tokens must be [Q, L], got {tuple(tok.shape)}")
@@ -553,9 +615,9 @@ class Engine:
         info = self._empty(4, torch.int32, dev)
         search = GitmiSearch()
         search.kind = SEARCH_SCORE
-        self._done(self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, tok.data_ptr(), L, *_sentence_tables(lens, image_of),
-                                                    Q, C.byref(search), None, out.data_ptr(), None, info.data_ptr(), _stream()),
-                   info, True)
+        self._done(self._call(frames, self.lib.gitmi_generate_prefixed(
+            self._h, arr, len(keep), B, tok.data_ptr(), L, *_sentence_tables(lens, image_of), Q, C.byref(search), None,
+            out.data_ptr(), None, info.data_ptr(), _stream()), B), info, True)
         return out
 
     # -- search seam ---------------------------------------------------------------------------
@@ -597,6 +659,8 @@ class Engine:
         """Take the image features (stage 1) or features + image K/V of every decoder layer (stage 2) from `src`, a
         context of the same model in the other precision; step_logits() then continues from there."""
         self._ck(_experiment_only(self.lib, "gitmi_debug_import_stage")(self._h, src._h, int(stage), _stream()))
+        self._resident = src._resident
+        self._generation += 1
 
     def debug_head_from(self, src: "Engine", R: int) -> torch.Tensor:
         """This (bf16) context's fused vocabulary head on the last hidden state of src's (fp32) latest step_logits."""
@@ -643,11 +707,17 @@ class Engine:
         """on (default): frames come as a list -> frame i gets img_temperal_embedding[i]; off: a bare image tensor
         (decoder.py:845-857 adds the embedding only in the list branch)."""
         self._ck(self.lib.gitmi_set_temporal_embedding(self._h, 1 if on else 0))
+        if bool(on) != self._temb:
+            self._temb = bool(on)
+            self._drop_resident()
 
     def set_ln_fold(self, on: bool) -> None:
         """fp16-operand library only: fold the encoder's / prefill's LayerNorms into the GEMMs either side of them (default
         there) or run one LayerNorm launch per module.  Raises if `on` is asked of an engine that cannot fold."""
         self._ck(self.lib.gitmi_set_ln_fold(self._h, 1 if on else 0))
+        if bool(on) != self._ln_fold:
+            self._ln_fold = bool(on)
+            self._drop_resident()
 
     def set_graph(self, on: bool) -> None:
         self._ck(self.lib.gitmi_set_graph(self._h, 1 if on else 0))

@@ -377,6 +377,10 @@ class CaptioningModel:
 
     batch['image']  : FloatTensor [B,3,H,W] or a list of such (video frames)   (decoder.py:845-857)
     batch['prefix'] : LongTensor [1,P] starting with [CLS] (VQA question)       (decoder.py:984-989)
+
+    A batch WITHOUT 'image' (the reference requires the key) is a follow-up request over the images the engine context
+    still holds from its last call -- no image encoder, no prefill: {'prefix' [1,P] or 'prefixes' [id lists], 'image_of' [Q]};
+    see submit_followup.
     """
 
     # precision: "f32" (reference-identical ids), "f16" (default 16-bit mode: fp16 operands, same MFMA rate as bf16 on gfx950,
@@ -479,24 +483,53 @@ class CaptioningModel:
     def _context(self):
         """-> (engine context, its stream or None) of the next submission"""
         if not getattr(self, "_ctxs", None):
+            self._last = self.engine
             return self.engine, None
         i = self._next % len(self._ctxs)
         self._next += 1
+        self._last = self._ctxs[i]
         return self._ctxs[i], self._streams[i]
 
-    def _prepare(self, eng, frames_is_list: bool):
-        eng.set_temporal_embedding(frames_is_list)                          # decoder.py:845-857: list branch only
+    def _followup_context(self, on=None):
+        """-> (engine context, its stream or None) of a follow-up request: the context that ran `on` (a Pending, or the result
+        it returned), else the context of the most recent call.  Raises when that context's images are no longer the ones
+        `on` was issued for: a follow-up must never answer about other images."""
+        on = getattr(on, "pending", on)
+        if on is not None and not isinstance(on, Pending):
+            raise TypeError("on= takes the Pending of the call that encoded the images, or the result it returned")
+        eng = on.engine if on is not None else getattr(self, "_last", None) or self.engine
+        if on is not None and eng.generation != on.generation:
+            raise StaleImagesError("the images of this handle are no longer resident on its context: another call has "
+                                   "replaced them (or a setter dropped them) since it was issued")
+        if eng.resident is None:
+            raise StaleImagesError("no resident images on this context: run a call with images first")
+        ctxs = getattr(self, "_ctxs", None)
+        if ctxs:        # every context of a pipeline owns a stream: the follow-up is ordered behind the context's own work
+            for c, st in zip(ctxs, self._streams):
+                if c is eng:
+                    return eng, st
+        return eng, None
+
+    def _prepare(self, eng, frames_is_list: Optional[bool]):
+        """frames_is_list None: a follow-up request (the temporal-embedding switch stays: flipping it drops the images)"""
+        if frames_is_list is not None:
+            eng.set_temporal_embedding(frames_is_list)                      # decoder.py:845-857: list branch only
         if self.decoder.kind == "trie" and getattr(eng, "_trie_loaded", None) is not self.decoder.trie:
             eng.set_trie(*self.decoder.trie.csr())
             eng._trie_loaded = self.decoder.trie
 
     def submit(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
-               search_param: Optional[dict] = None) -> "Pending":
+               search_param: Optional[dict] = None, on=None) -> "Pending":
         """Asynchronous model(batch): enqueue the request on the next context's stream and return at once; `.result()` waits
         for it and returns what model(batch) returns.  The batch's tensors must have been produced on the CURRENT stream (the
-        context's stream waits for it)."""
+        context's stream waits for it).  A batch without 'image' is a follow-up request (submit_followup; `on` names the call
+        whose images it is about)."""
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if "image" not in batch:
+            return self.submit_followup(batch, search_param, on=on)
+        if on is not None:
+            raise ValueError("on= belongs to follow-up requests (a batch without 'image')")
         image = batch["image"]
         is_list = isinstance(image, (list, tuple))
         frames = list(image) if is_list else [image]
@@ -530,12 +563,36 @@ class CaptioningModel:
                 tokens, logprobs, info = eng.generate(frames, search, prefix=prefix, sync=False, host_out=stream is not None)
             return tokens, logprobs, info
 
-        return Pending(stream, launch, lambda out: _finish_batch(eng, out, P, kind), keep=(frames, prefix))
+        return Pending(stream, launch, lambda out: _finish_batch(eng, out, P, kind), keep=(frames, prefix), engine=eng)
+
+    def submit_followup(self, batch: Mapping, search_param: Optional[dict] = None, on=None) -> "Pending":
+        """A request over RESIDENT images: the ones the context of `on` (default: of the most recent call) encoded in its
+        last call.  Only the decode steps run.  batch: {'prefix': [1, P] (one question for every sentence) or 'prefixes': [id
+        lists starting with [CLS]], 'image_of': [Q] image index of every sentence}; search_param as for submit (the search
+        may differ from the first call's: a beam pass after a greedy one, sampling, num_keep_best).
+        `.result()`: {'predictions': [ids of each sentence, the prefix removed], 'logprobs': fp32 [Q, 1 or num_keep_best]}."""
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if "image_of" not in batch or ("prefix" not in batch and "prefixes" not in batch):
+            raise ValueError("a batch without 'image' is a follow-up request: it needs 'image_of' and 'prefix' or 'prefixes'")
+        image_of = [int(i) for i in batch["image_of"]]
+        if "prefixes" in batch:
+            prefixes = [[int(t) for t in p] for p in batch["prefixes"]]
+        else:
+            prefix = torch.as_tensor(batch["prefix"])
+            assert len(prefix) == 1, "not supported"                       # decoder.py:988
+            prefixes = [[int(t) for t in prefix.reshape(-1).tolist()]] * len(image_of)
+        if int((search_param or {}).get("num_return_sequences", 1)) != 1:
+            raise NotImplementedError("num_return_sequences in a follow-up request: repeat the sentence in 'image_of'")
+        eng, stream = self._followup_context(on)
+        return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=True)
 
     def forward(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
-                search_param: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                search_param: Optional[dict] = None, on=None) -> Dict[str, torch.Tensor]:
         if self.training:
             return self._loss_forward(batch)
+        if "image" not in batch:
+            return self.submit(batch, search_param, on=on).result()
         return self._on_context0(lambda: self.submit(batch, search_param))
 
     __call__ = forward
@@ -554,12 +611,14 @@ class CaptioningModel:
                             self.label_smoothing, self.cfg.vocab)
         return {"vl_l_loss": torch.tensor(loss, dtype=torch.float32)}
 
-    def score(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], captions, image_of: Optional[Sequence[int]] = None,
-              need_predict=None) -> Dict[str, torch.Tensor]:
+    def score(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], captions,
+              image_of: Optional[Sequence[int]] = None, need_predict=None, on=None) -> Dict[str, torch.Tensor]:
         """Log-likelihood of given captions (validation loss / perplexity, reranking, retrieval, closed-set VQA).
         captions: int [Q, L] padded with 0 (or a list of id lists), each starting with [CLS]; caption q belongs to image
         image_of[q] of `images` (default: caption q <-> image q).  need_predict [Q, L] (default: the non-padding positions
         after [CLS]) selects the positions that count, e.g. 0 on a VQA question prefix.
+        images None: the captions are scored over the RESIDENT images of `on`'s context (default: of the most recent call),
+        e.g. the captions that call just generated; nothing is encoded.
         -> {'logprobs' [Q, L] (lp of tokens[:, j], 0 at position 0), 'mean_logprobs' [Q, L] (mean log-prob over the
             vocabulary at that position), 'sum' [Q], 'mean' [Q] (over the counted positions)}, all fp32 on the CPU."""
         if not self._loaded:
@@ -568,14 +627,24 @@ class CaptioningModel:
             captions = id_table(captions)
         tokens = captions.detach().cpu().long()
         is_list = isinstance(images, (list, tuple))
-        if _is_image_list(images):
+        if images is None:
+            eng, stream = self._followup_context(on)
+            if stream is None:
+                out = eng.score(None, tokens, image_of=image_of).cpu()
+            else:
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    out = eng.score(None, tokens, image_of=image_of).cpu()
+        elif _is_image_list(images):
             self._check_ragged()
             self.engine.set_temporal_embedding(False)
             out = self.engine.score(self.engine.ragged(images), tokens, image_of=image_of).cpu()
+            self._last = self.engine
         else:
             frames = list(images) if is_list else [images]
             self.engine.set_temporal_embedding(is_list)                      # decoder.py:845-857: list branch only
             out = self.engine.score(frames, tokens, image_of=image_of).cpu()
+            self._last = self.engine
         lp, mean_lp = out[..., 0], out[..., 1]
         if need_predict is None:
             need_predict = (tokens != 0).long()
@@ -595,13 +664,18 @@ class CaptioningModel:
             raise ValueError("images of different sizes in one call: only models without temporal image embeddings "
                              "(num_image_with_embedding = 0) take a list of [3, h, w] images")
 
-    def submit_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
-                      image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None) -> "Pending":
+    def submit_ragged(self, images: Optional[Sequence[torch.Tensor]], prefixes: Optional[Sequence[Sequence[int]]] = None,
+                      image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None, on=None) -> "Pending":
         """Images of DIFFERENT sizes in one engine call (the aspect-preserving VQA models: MinMaxResizeForTest gives every
         image its own shape).  images: list of fp32 [3, h, w]; every image gets exactly what a call with that image alone
         gets.  prefixes None: captioning, `.result()` is submit({'image': image}).result()'s dict over the B images.
         prefixes given: question q (token ids starting with [CLS]) about image image_of[q] (default: q <-> image q);
-        `.result()` is {'predictions': [ids of each answer, the prefix removed], 'logprobs': fp32 [Q, 1]}."""
+        `.result()` is {'predictions': [ids of each answer, the prefix removed], 'logprobs': fp32 [Q, 1]}.
+        images None: a follow-up request over the resident images (submit_followup)."""
+        if images is None:
+            if prefixes is None or image_of is None:
+                raise ValueError("a follow-up request (images=None) needs prefixes and image_of")
+            return self.submit_followup({"prefixes": prefixes, "image_of": image_of}, search_param, on=on)
         self._check_ragged()
         images = list(images)
         if not _is_image_list(images):
@@ -614,7 +688,7 @@ class CaptioningModel:
             raise NotImplementedError("num_return_sequences with images of different sizes")
         if prefixes is None:
             return Pending(stream, lambda: eng.generate(packed, search, sync=False, host_out=stream is not None),
-                           lambda out: _finish_batch(eng, out, None, self.decoder.kind), keep=(packed,))
+                           lambda out: _finish_batch(eng, out, None, self.decoder.kind), keep=(packed,), engine=eng)
         Q = len(prefixes)
         image_of = list(range(Q)) if image_of is None else [int(i) for i in image_of]
         if Q > eng.c.max_batch:
@@ -628,15 +702,21 @@ class CaptioningModel:
         """submit_ragged(...).result() on context 0 and the caller's stream."""
         return self._on_context0(lambda: self.submit_ragged(images, prefixes, image_of, search_param))
 
-    def submit_answers(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
-                       image_of: Optional[Sequence[int]] = None) -> "Pending":
+    def submit_answers(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
+                       image_of: Optional[Sequence[int]] = None, on=None) -> "Pending":
         """Questions about SEVERAL images of one resolution in one engine call (batched ragged prefixes): `images` [B,3,H,W]
         (or a list of frames of that shape), question q = token ids starting with [CLS], about image image_of[q] (default: all
         about image 0).  `.result()` returns, per question, the list of predicted token ids exactly as
         ``model({'image': image, 'prefix': [prefix]})['predictions'][0]`` gives them for that image alone -- the reference loop
-        of inference.py:172-199 without re-encoding an image per question and without one call per image."""
+        of inference.py:172-199 without re-encoding an image per question and without one call per image.
+        images None: further questions about the RESIDENT images of `on`'s context (default: of the most recent call)."""
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if images is None:
+            image_of = [0] * len(prefixes) if image_of is None else [int(i) for i in image_of]
+            eng, stream = self._followup_context(on)
+            self._prepare(eng, None)
+            return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(), as_dict=False)
         is_list = isinstance(images, (list, tuple))
         frames = list(images) if is_list else [images]
         Q = len(prefixes)
@@ -651,6 +731,13 @@ class CaptioningModel:
         """submit_answers / submit_ragged with questions: one generate_prefixed call on `eng` (frames: a stacked batch or
         RaggedImages).  .result(): the answers' id lists, and with as_dict {'predictions': them, 'logprobs' [Q, 1]}."""
         kind = self.decoder.kind
+        if frames is None:
+            self._prepare(eng, None)
+            if len(prefixes) > eng.c.max_batch:
+                raise ValueError(f"{len(prefixes)} questions exceed max_batch={eng.c.max_batch}")
+            if any(i < 0 or i >= eng.resident for i in image_of) or len(image_of) != len(prefixes):
+                raise ValueError(f"image_of must name one of the {eng.resident} resident images for each of the "
+                                 f"{len(prefixes)} sentences")
 
         def launch():
             return eng.generate_prefixed(frames, search, prefixes, image_of=image_of, sync=False, host_out=stream is not None)
@@ -661,7 +748,7 @@ class CaptioningModel:
             preds, logprobs = format_predictions(tokens.cpu(), logprobs, sent.cpu(), [len(p) for p in prefixes], kind)
             return {"predictions": preds, "logprobs": logprobs.cpu()} if as_dict else preds
 
-        return Pending(stream, launch, finish, keep=(frames,))
+        return Pending(stream, launch, finish, keep=(frames,), engine=eng)
 
     def answer(self, image: Union[torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]]):
         """Several questions about ONE image in one engine call: submit_answers(...).result() on context 0."""
@@ -687,11 +774,28 @@ class CaptioningModel:
         return pending.result()
 
 
-class Pending:
-    """A request enqueued on a context's stream (CaptioningModel.submit / submit_answers)."""
+class StaleImagesError(RuntimeError):
+    """A follow-up request names images that its context no longer holds."""
 
-    def __init__(self, stream, launch, finish, keep=()):
+
+class _ResultDict(dict):
+    """What Pending.result() returns for dict results: the dict, plus `.pending` so that it can be passed as on=."""
+    pending = None
+
+
+class _ResultList(list):
+    pending = None
+
+
+class Pending:
+    """A request enqueued on a context's stream (CaptioningModel.submit / submit_answers).  It records the engine context
+    that ran it and that context's image generation after the launch (Engine.generation): a follow-up request issued with
+    on=<this> (or with the result it returned) runs on the same context and stream, and is refused once another call has
+    replaced the images there."""
+
+    def __init__(self, stream, launch, finish, keep=(), engine=None):
         self._finish, self._keep, self._done, self._value, self._stream = finish, keep, False, None, stream
+        self.engine = engine
         if stream is None:
             self._out = launch()
             self._event = None
@@ -701,6 +805,7 @@ class Pending:
                 self._out = launch()
                 self._event = torch.cuda.Event()
                 self._event.record()
+        self.generation = engine.generation if engine is not None else None
 
     wait_s = 0.0            # class-wide: seconds spent waiting for the device in result() (diagnostics of the TSV task)
 
@@ -713,7 +818,14 @@ class Pending:
             else:
                 torch.cuda.current_stream().synchronize()
             Pending.wait_s += time.perf_counter() - t0
-            self._value = self._finish(self._out)
+            value = self._finish(self._out)
+            if type(value) is dict:
+                value = _ResultDict(value)
+            elif type(value) is list:
+                value = _ResultList(value)
+            if isinstance(value, (_ResultDict, _ResultList)):
+                value.pending = self
+            self._value = value
             self._done, self._out, self._keep = True, None, ()
         return self._value
 

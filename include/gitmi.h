@@ -225,6 +225,7 @@ int  gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, int t,
 
 /* ---- whole hot path: replaces model({'image':..., 'prefix':...})
  * (CaptioningModel.forward/infer, decoder.py:838-877, 977-1011) incl. the search loop.
+ *   frames       : F device pointers as for gitmi_encode_frames, or NULL: a follow-up call over the resident images (below);
  *   prefix       : int64 [P] starting with [CLS], or NULL for captioning (P ignored);
  *                  the reference requires B==1 with a prefix (decoder.py:988) -- here a
  *                  single prefix is shared by all B images.
@@ -243,6 +244,28 @@ int  gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, int t,
  *                  operand format (fp16: 65504) somewhere upstream -- the ids of such a call are meaningless and the
  *                  caller must treat it as an error (the Python binding raises).  Weights are range-checked when they
  *                  are loaded (gitmi_load_tensor / gitmi_finalize_weights fail by name). */
+/* ---- follow-up calls on resident images: frames == NULL.
+ * gitmi_generate(e, frames = NULL, ...) and gitmi_generate_prefixed(e, frames = NULL, ...) -- every search kind and
+ * GITMI_SEARCH_SCORE -- run over the images the engine already holds: no image encoder and, when the prefill is current, no
+ * prefill; only the decode chain (or the score pass) runs.  A second question about the same images, a beam-4 pass after a
+ * greedy one, the log-probs of the captions just generated, reranking of an n-best list.
+ *   F is ignored.  B must equal the number of resident images (the B of the call that encoded them); anything else fails
+ *   with a message naming both numbers.  Everything else keeps its meaning and its checks: prefixes, image_of_host (any
+ *   subset, order or repetition of [0, B)), Q, the whole gitmi_search, the trie, the output buffers.
+ * Residency: the images of a call are resident from the end of any call that encoded them -- gitmi_generate,
+ * gitmi_generate_prefixed (score included), gitmi_encode_frames -- until something changes what an encode would produce: a
+ * gitmi_set_image_shape that changes the shape or the mode, a gitmi_set_temporal_embedding or gitmi_set_ln_fold flip.
+ * Decode steps and score passes write text caches only.  After gitmi_encode_frames alone the follow-up runs the prefill
+ * first (as gitmi_step_logits does).  Without resident images the call fails before any launch.  An argument error found
+ * before the first launch of any call leaves residency as it was; a call that fails after it started encoding clears it.
+ * Every context has its own resident set; a clone starts with none.
+ * Ragged mode: the shapes, token counts and rejected entries of the resident batch are used (no descriptor is read);
+ * sentences over a rejected entry still come back NaN and are counted in info_out[3].
+ * hipGraph: a follow-up captures and replays the decode part alone, in a slot of its own beside the full call's graph:
+ * full, follow-up, full, follow-up with unchanged arguments replays both and re-captures neither.  Score follow-ups run
+ * eagerly, as score does.  Serving schedule (gitmi_set_encode_after): a follow-up has no encoder -- it neither waits for
+ * `after`'s encoder nor signals its own watchers, who keep waiting for the most recent real encoder.
+ * Profiling: vit_ms, prefill_ms and vit_gemm_* of a follow-up are 0, decode_* as usual. */
 int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
                     const int64_t* prefix, int P, const gitmi_search* search,
                     int64_t* tokens_out, float* logprob_out, int32_t* info_out, void* stream);
@@ -268,8 +291,9 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  *   logprob_out     : fp32 [Q, ld, 2] = (lp, mean_lp), device or page-locked host buffer
  *   tokens_out, sent_out: ignored (may be NULL); info_out = { ld, 0, 0, sentences with a non-finite value }
  *   the other gitmi_search fields are ignored.  gitmi_generate and gitmi_search_begin refuse this kind.
- * Like a generate call it replaces the engine's encoded images and prefill; its workspaces are allocated by the first
- * score call (engines that never score keep their footprint). */
+ * Like a generate call it replaces the engine's encoded images and prefill (with frames == NULL it scores over the resident
+ * images instead: follow-up calls, above gitmi_generate); its workspaces are allocated by the first score call (engines that
+ * never score keep their footprint). */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,
