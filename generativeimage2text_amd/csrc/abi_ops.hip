@@ -3,6 +3,7 @@
 // state: everything that needs a gitmi_engine lives in engine.hip / engine_weights.hip.
 #include "../../include/gitmi.h"
 #include "abi_common.h"
+#include "gitmi_common.h"
 #include "launchers.h"
 
 #include <hip/hip_runtime.h>
@@ -136,15 +137,24 @@ extern "C" int gitmi_op_dgemm_res(const void* A, const void* W, const float* bia
     HIPCK(launch_dgemm(g, (hipStream_t)stream));
     return 0;
 }
-extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
-                                   int strips, float eps, int M, int V, int K, int cols_per_wg, int mtop,
-                                   const int* suppress_tok, float* part_val, int* part_idx, float* part_lse,
-                                   float* logits_out, int max_wgs, void* stream) {
+// the VocabArgs fields gitmi_op_vocab_topm and gitmi_debug_vocab_topm_rules share (everything but the rule inputs)
+static VocabArgs vocab_op_args(const void* A, const void* W, const float* bias, const float* colsum, const float* stats, int strips,
+                               float eps, int M, int V, int K, int cols_per_wg, float* part_val, int* part_idx, float* part_lse,
+                               float* logits_out, int max_wgs) {
     VocabArgs v{};
     v.max_wgs = max_wgs;
     v.A = (const unsigned short*)A; v.lda = K; v.W = (const unsigned short*)W; v.bias = bias;
     if (stats) { v.colsum = colsum; v.stats_in = (const float2*)stats; v.strips_in = strips; v.inv_d = 1.0f / (float)K; v.eps_in = eps; }
     v.M = M; v.N = V; v.K = K; v.cols_per_wg = cols_per_wg;
+    v.part_val = part_val; v.part_idx = part_idx; v.part_lse = (float2*)part_lse;
+    v.logits_out = logits_out; v.ld_logits = V;
+    return v;
+}
+extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
+                                   int strips, float eps, int M, int V, int K, int cols_per_wg, int mtop,
+                                   const int* suppress_tok, float* part_val, int* part_idx, float* part_lse,
+                                   float* logits_out, int max_wgs, void* stream) {
+    VocabArgs v = vocab_op_args(A, W, bias, colsum, stats, strips, eps, M, V, K, cols_per_wg, part_val, part_idx, part_lse, logits_out, max_wgs);
     if (cols_per_wg != 128) return fail("op_vocab_topm: cols_per_wg must be 128");
     // the rule is driven through the search tables in the engine; the unit entry point takes one token per row
     // (ids [M][1], cur_len 1, prefix length 0 => "past the first step")
@@ -154,8 +164,33 @@ extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bi
         if (M > 4096) return fail("op_vocab_topm: at most 4096 rows with suppress_tok");
         v.ids = suppress_tok; v.ld_ids = 1; v.cur_len = 1; v.plen = zero_plen; v.beams = 1; v.suppress_kind = 1;
     }
-    v.part_val = part_val; v.part_idx = part_idx; v.part_lse = (float2*)part_lse;
-    v.logits_out = logits_out; v.ld_logits = V;
+    HIPCK(launch_vocab_topm(v, mtop, (hipStream_t)stream));
+    return 0;
+}
+
+// the fused head with the REAL rule inputs of a search step (tests/test_gpu_search_ops.py): VocabArgs exactly as the engine's
+// decode_head_impl fills them -- ids int32 [M][ld_ids] (DEVICE) the rows' histories, cur_len tokens each, plen int32 [M / beams]
+// (DEVICE) the sentences' prefix lengths, suppress_kind 1 = the no-immediate-repeat rule on rows with cur_len > plen,
+// rep_penalty the GENERATOR repetition penalty over ids[row][0..cur_len) (0 or 1: off).  ids == NULL: no rules.  A penalty over
+// more than HIST_SLOTS / 2 tokens is refused HERE, as search_begin_impl refuses it for the engine (the row_topm / sample_rows
+// launchers hold the history as a set of that capacity; launch_vocab_topm walks the ids and has no such check of its own).
+GITMI_EXP_EXPORT int gitmi_debug_vocab_topm_rules(const void* A, const void* W, const float* bias, const float* colsum,
+                                                  const float* stats, int strips, float eps, int M, int V, int K, int cols_per_wg,
+                                                  int mtop, const int* ids, int ld_ids, int cur_len, const int* plen, int beams,
+                                                  int suppress_kind, float rep_penalty, float* part_val, int* part_idx,
+                                                  float* part_lse, float* logits_out, int max_wgs, void* stream) {
+    if (!A || !W || !bias || !part_val || !part_idx || !part_lse) return fail("debug_vocab_topm_rules: null argument");
+    if (cols_per_wg != 128) return fail("debug_vocab_topm_rules: cols_per_wg must be 128");
+    VocabArgs v = vocab_op_args(A, W, bias, colsum, stats, strips, eps, M, V, K, cols_per_wg, part_val, part_idx, part_lse, logits_out, max_wgs);
+    if (ids) {
+        if (!plen) return fail("debug_vocab_topm_rules: ids without plen");
+        if (beams < 1 || M % beams) return fail("debug_vocab_topm_rules: M=%d is not a multiple of beams=%d", M, beams);
+        if (cur_len < 1 || cur_len > ld_ids) return fail("debug_vocab_topm_rules: cur_len=%d outside [1, ld_ids=%d]", cur_len, ld_ids);
+        if (rep_penalty != 0.f && rep_penalty != 1.f && cur_len > HIST_SLOTS / 2)
+            return fail("debug_vocab_topm_rules: the repetition penalty supports histories up to %d tokens (cur_len=%d)", HIST_SLOTS / 2, cur_len);
+        v.ids = ids; v.ld_ids = ld_ids; v.cur_len = cur_len; v.plen = plen; v.beams = beams; v.suppress_kind = suppress_kind;
+        v.rep_penalty = rep_penalty;
+    }
     HIPCK(launch_vocab_topm(v, mtop, (hipStream_t)stream));
     return 0;
 }

@@ -866,21 +866,37 @@ extern "C" int gitmi_set_trie(gitmi_engine* e, int n_nodes, const int32_t* child
     return 0;
 }
 
+// start_host int64 [B][ld] and the prefix lengths (plen_host int32 [B], or NULL: all `ld`) -> the engine's start / plen tables,
+// then search_begin_impl.  `who` names the entry point in the error text.
+static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_search* sp, int B, const int64_t* start_host, int ld,
+                             const int32_t* plen_host, int vocab, void* stream) {
+    RCK(check_ready(e));
+    if (!start_host) return fail("%s: null start", who);
+    if (B < 1 || B > e->cfg.max_batch || ld < 1 || ld > e->cfg.max_text_len) return fail("%s: bad B/P", who);
+    if (vocab < 2) return fail("%s: bad vocab", who);
+    if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("%s: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)", who);
+    int minP = ld, maxP = ld;
+    if (plen_host) {
+        maxP = 1;
+        for (int b = 0; b < B; ++b) {
+            if (plen_host[b] < 1 || plen_host[b] > ld) return fail("%s: prefix length %d of sentence %d outside [1,%d]", who, plen_host[b], b, ld);
+            minP = std::min(minP, (int)plen_host[b]); maxP = std::max(maxP, (int)plen_host[b]);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // one row per sentence, written into the engine's [B, max_text_len] start table
+    HIPCK(hipMemcpy2DAsync(e->start_dev, (size_t)e->cfg.max_text_len * sizeof(long long), start_host,
+                           (size_t)ld * sizeof(long long), (size_t)ld * sizeof(long long), (size_t)B, hipMemcpyHostToDevice, s));
+    if (plen_host) HIPCK(hipMemcpyAsync(e->plen_dev, plen_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCK(hipStreamSynchronize(s));
+    if (!plen_host) HIPCK(launch_fill_i32(e->plen_dev, ld, B, s));
+    e->img_identity = true;
+    return search_begin_impl(e, sp, B, minP, maxP, vocab, plen_host != nullptr, s);
+}
+
 extern "C" int gitmi_search_begin(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host, int P,
                                   int vocab, void* stream) {
-    RCK(check_ready(e));
-    if (!start_host) return fail("search_begin: null start");
-    if (B < 1 || B > e->cfg.max_batch || P < 1 || P > e->cfg.max_text_len) return fail("search_begin: bad B/P");
-    if (vocab < 2) return fail("search_begin: bad vocab");
-    if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("search_begin: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)");
-    hipStream_t s = (hipStream_t)stream;
-    // start_host is [B, P]: one row per sentence, written into the engine's [B, max_text_len] start table
-    HIPCK(hipMemcpy2DAsync(e->start_dev, (size_t)e->cfg.max_text_len * sizeof(long long), start_host,
-                           (size_t)P * sizeof(long long), (size_t)P * sizeof(long long), (size_t)B, hipMemcpyHostToDevice, s));
-    HIPCK(hipStreamSynchronize(s));
-    HIPCK(launch_fill_i32(e->plen_dev, P, B, s));
-    e->img_identity = true;
-    return search_begin_impl(e, sp, B, P, P, vocab, false, s);
+    return search_begin_host(e, "search_begin", sp, B, start_host, P, nullptr, vocab, stream);
 }
 
 extern "C" int gitmi_search_rows(gitmi_engine* e, int64_t* tokens_out, int* R, int* t, void* stream) {
@@ -924,6 +940,51 @@ extern "C" int gitmi_search_finish(gitmi_engine* e, int64_t* tokens_out, float* 
     const SearchState& st = e->ss;
     HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, (long long*)tokens_out, logprob_out, info_out, nullptr,
                                (hipStream_t)stream));
+    return 0;
+}
+
+// ---- op hooks of the search step (measurement build; tests/test_gpu_search_ops.py) -------------------------------------------
+// gitmi_search_begin with a prefix of its own length per sentence: start_host int64 [B][ld], plen_host int32 [B] (1 .. ld).
+// Every sentence then stands for its own batch-1 reference call, as in gitmi_generate_prefixed; the search starts at the
+// shortest prefix length and appends the given tokens to the longer ones until their prefix ends.
+GITMI_EXP_EXPORT int gitmi_debug_search_begin_prefixed(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host,
+                                                       int ld, const int32_t* plen_host, int vocab, void* stream) {
+    if (!plen_host) return fail("debug_search_begin_prefixed: null prefix lengths");
+    return search_begin_host(e, "debug_search_begin_prefixed", sp, B, start_host, ld, plen_host, vocab, stream);
+}
+// gitmi_search_advance on caller-supplied candidate lists (DEVICE; the format of the fused vocabulary head: part_val / part_idx
+// [R][nparts][slots] sorted, unused entries (-inf, 0x7fffffff); part_lse [R][nparts] (max, sum exp)) in place of the row_topm
+// launch: the multi-part merge of search_step_kernel.  embed != 0: the step also embeds the appended tokens (engine weights).
+GITMI_EXP_EXPORT int gitmi_debug_search_advance_lists(gitmi_engine* e, const float* part_val, const int* part_idx,
+                                                      const float* part_lse, int nparts, int slots, int embed, void* stream) {
+    RCK(check_ready(e));
+    if (!part_val || !part_idx || !part_lse) return fail("debug_search_advance_lists: null argument");
+    const SearchState& st = e->ss;
+    if (st.B < 1 || st.T < 1) return fail("debug_search_advance_lists: no search has begun");
+    if (st.sampled || e->trie_search) return fail("debug_search_advance_lists: the sampling and trie searches select from whole logit rows");
+    if (nparts < 1 || nparts > 256) return fail("debug_search_advance_lists: nparts=%d outside [1,256]", nparts);
+    if (slots != 1 && slots != 2 && slots != 4 && slots != 8 && slots != 16)
+        return fail("debug_search_advance_lists: slots=%d is not one of 1, 2, 4, 8, 16", slots);
+    if (slots < search_mtop(st)) return fail("debug_search_advance_lists: slots=%d, but the step reads %d candidates per row", slots, search_mtop(st));
+    const StepCands cands{part_val, part_idx, (const float2*)part_lse, nparts, slots};
+    return search_step_impl(e, cands, embed != 0, (hipStream_t)stream);
+}
+// the embedded rows of the most recent step (embed_ln / the search step's fused embedding): hf_out fp32 [R][D]; ht_out
+// round_up(R, 16) * D elements of the engine's compute type exactly as stored, *ht_frag = 1 when that is the fragment-major
+// operand layout (gitmi_common.h frag_offset; the caller undoes it), *ht_dtype its GITMI_DTYPE_* code.  Synchronises.
+GITMI_EXP_EXPORT int gitmi_debug_read_hidden(gitmi_engine* e, int R, float* hf_out, void* ht_out, int* ht_frag, int* ht_dtype,
+                                             void* stream) {
+    RCK(check_ready(e));
+    const gitmi_config& c = e->cfg;
+    if (R < 1 || R > c.max_batch * c.max_beams) return fail("debug_read_hidden: R=%d outside the capacity", R);
+    if (!hf_out || !ht_out || !ht_frag || !ht_dtype) return fail("debug_read_hidden: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = (size_t)c.dec_hidden, Rp = (size_t)(R + 15) / 16 * 16;
+    HIPCK(hipMemcpyAsync(hf_out, e->d_hf, (size_t)R * D * sizeof(float), hipMemcpyDefault, s));
+    HIPCK(hipMemcpyAsync(ht_out, e->d_ht, Rp * D * e->pol.esz, hipMemcpyDefault, s));
+    HIPCK(hipStreamSynchronize(s));
+    *ht_frag = (e->pol.skinny && !e->pol.f32) ? 1 : 0;
+    *ht_dtype = e->pol.f32 ? GITMI_DTYPE_F32 : gitmi_operand_dtype();
     return 0;
 }
 

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
 EXPERIMENT_SYMBOLS = [
     "gitmi_debug_import_stage", "gitmi_debug_head_from", "gitmi_debug_set_gemm_impl", "gitmi_debug_set_dgemm",
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
+    "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
 ]
 
 
@@ -148,6 +149,11 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         lib.gitmi_debug_attention_ragged.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_vocab_topm_rules.argtypes = [vp, vp, vp, vp, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32,
+                                                     i32, C.c_float, vp, vp, vp, vp, i32, vp]
+        lib.gitmi_debug_search_begin_prefixed.argtypes = [vp, C.POINTER(GitmiSearch), i32, vp, i32, vp, i32, vp]
+        lib.gitmi_debug_search_advance_lists.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+        lib.gitmi_debug_read_hidden.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands == "exp" else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -669,6 +675,46 @@ class Engine:
         torch.cuda.current_stream().synchronize()
         return out
 
+    # -- op hooks of the search step (measurement build; tests/test_gpu_search_ops.py) ------------------------
+    def debug_search_begin_prefixed(self, search: GitmiSearch, prefixes: Sequence[Sequence[int]], vocab: int) -> None:
+        """search_begin with a prefix of its own length per sentence (every sentence = its own batch-1 reference call)."""
+        start = id_table(prefixes)
+        B, ld = start.shape
+        plen = torch.tensor([len(p) for p in prefixes], dtype=torch.int32)
+        self._ck(_experiment_only(self.lib, "gitmi_debug_search_begin_prefixed")(
+            self._h, C.byref(search), B, start.data_ptr(), ld, plen.data_ptr(), vocab, _stream()))
+        self._search_k, self._search_B, self._search_T, self._search_cfg = search.beam_size, B, search.max_steps, search
+
+    def debug_search_advance_lists(self, part_val: torch.Tensor, part_idx: torch.Tensor, part_lse: torch.Tensor,
+                                   embed: bool = False) -> None:
+        """search_advance on candidate lists in the fused head's format -- part_val fp32 / part_idx int32 [R, nparts, slots],
+        part_lse fp32 [R, nparts, 2] -- in place of logits: the multi-part merge of the search step."""
+        dev = f"cuda:{self.device}"
+        pv = part_val.to(device=dev, dtype=torch.float32).contiguous()
+        pi = part_idx.to(device=dev, dtype=torch.int32).contiguous()
+        pl = part_lse.to(device=dev, dtype=torch.float32).contiguous()
+        R, nparts, slots = pv.shape
+        if pi.shape != pv.shape or tuple(pl.shape) != (R, nparts, 2) or R != self._search_B * self._search_k:
+            raise ValueError(f"candidate lists {tuple(pv.shape)} / {tuple(pi.shape)} / {tuple(pl.shape)} do not describe the "
+                             f"{self._search_B * self._search_k} rows of the search")
+        self._keep_lists = (pv, pi, pl)
+        self._ck(_experiment_only(self.lib, "gitmi_debug_search_advance_lists")(
+            self._h, pv.data_ptr(), pi.data_ptr(), pl.data_ptr(), nparts, slots, 1 if embed else 0, _stream()))
+
+    def debug_read_hidden(self, R: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The embedded rows of the most recent step: (h_f fp32 [R, D], the compute-type copy [R, D] in row-major order)."""
+        D = int(self.c.dec_hidden)
+        dev = f"cuda:{self.device}"
+        Rp = (R + 15) // 16 * 16
+        hf = torch.empty(R, D, device=dev, dtype=torch.float32)
+        raw = torch.empty(Rp * D * 4, device=dev, dtype=torch.uint8)
+        frag, dt = C.c_int(), C.c_int()
+        self._ck(_experiment_only(self.lib, "gitmi_debug_read_hidden")(self._h, int(R), hf.data_ptr(), raw.data_ptr(),
+                                                                       C.byref(frag), C.byref(dt), _stream()))
+        tdt = {DTYPE_F32: torch.float32, DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16}[dt.value]
+        ht = raw.view(tdt)[:Rp * D].reshape(Rp, D)
+        return hf, (from_frag(ht, R) if frag.value else ht[:R].contiguous())
+
     def search_done_count(self) -> int:
         """Sentences of the running search that need no further step (synchronises the stream)."""
         n = C.c_int()
@@ -864,14 +910,9 @@ def op_dgemm_res(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, res_x: to
     return x, (xb if packed else from_frag(xb, M)), st
 
 
-def op_vocab_topm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mtop: int, cols_per_wg: int = 128,
-                  colsum: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, eps: float = 1e-12,
-                  suppress_tok: Optional[torch.Tensor] = None, want_logits: bool = False, packed: bool = False,
-                  rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0):
-    """Vocabulary head with the fused running top-M / log-sum-exp: -> (part_val [M, nparts, slots], part_idx,
-    part_lse [M, nparts, 2] = (max, sum exp), logits [M, V] or None).  packed=True: A / W fragment-major (W rows and
-    bias / colsum padded to a multiple of cols_per_wg), `rows` = M, `V` = vocabulary size.  A / W: bf16 or fp16 (that
-    type's library)."""
+def _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V):
+    """What op_vocab_topm and op_vocab_topm_rules share: the library of the operands' type, the packed operands and the
+    output buffers -> (lib, leading arguments (A .. mtop) of the C entry point, trailing arguments, outputs)."""
     lib = _op_library(A.dtype, W.dtype)
     K = A.shape[1]
     V = int(bias.numel()) if V is None else int(V)
@@ -888,10 +929,42 @@ def op_vocab_topm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mtop: in
     pl = torch.empty(M, nparts, 2, device=A.device, dtype=torch.float32)
     lg = torch.empty(M, V, device=A.device, dtype=torch.float32) if want_logits else None
     strips = 0 if stats is None else int(stats.shape[0])
-    _ck(lib.gitmi_op_vocab_topm(Af.data_ptr(), Wf.data_ptr(), bp.data_ptr(), _ptr(cp), _ptr(stats), strips, eps,
-                                M, V, K, cols_per_wg, mtop, _ptr(suppress_tok), pv.data_ptr(), pi.data_ptr(),
-                                pl.data_ptr(), _ptr(lg), int(max_wgs), _stream()), lib)
-    return pv, pi, pl, lg
+    keep = (Af, Wf, bp, cp)                                  # alive until the call has been enqueued
+    return lib, M, (Af.data_ptr(), Wf.data_ptr(), bp.data_ptr(), _ptr(cp), _ptr(stats), strips), (M, V, K, cols_per_wg, mtop), \
+        (pv.data_ptr(), pi.data_ptr(), pl.data_ptr(), _ptr(lg)), (pv, pi, pl, lg), keep
+
+
+def op_vocab_topm(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mtop: int, cols_per_wg: int = 128,
+                  colsum: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, eps: float = 1e-12,
+                  suppress_tok: Optional[torch.Tensor] = None, want_logits: bool = False, packed: bool = False,
+                  rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0):
+    """Vocabulary head with the fused running top-M / log-sum-exp: -> (part_val [M, nparts, slots], part_idx,
+    part_lse [M, nparts, 2] = (max, sum exp), logits [M, V] or None).  packed=True: A / W fragment-major (W rows and
+    bias / colsum padded to a multiple of cols_per_wg), `rows` = M, `V` = vocabulary size.  A / W: bf16 or fp16 (that
+    type's library)."""
+    lib, _, ops, shape, outs, result, keep = _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V)
+    _ck(lib.gitmi_op_vocab_topm(*ops, eps, *shape, _ptr(suppress_tok), *outs, int(max_wgs), _stream()), lib)
+    return result
+
+
+def op_vocab_topm_rules(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mtop: int, ids: Optional[torch.Tensor],
+                        cur_len: int, plen: Optional[torch.Tensor], beams: int = 1, suppress_kind: int = 0,
+                        rep_penalty: float = 0.0, cols_per_wg: int = 128, colsum: Optional[torch.Tensor] = None,
+                        stats: Optional[torch.Tensor] = None, eps: float = 1e-12, want_logits: bool = False, packed: bool = False,
+                        rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0):
+    """op_vocab_topm with the rule inputs of a real search step (measurement build): ids int32 [M, ld_ids] row histories of
+    cur_len tokens, plen int32 [M / beams] prefix lengths, suppress_kind (no immediate repeat on rows with cur_len > plen),
+    rep_penalty.  Same outputs; the materialised logits are taken before the rules."""
+    lib, M, ops, shape, outs, result, keep = _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V)
+    if ids is not None:
+        ids = ids.to(device=A.device, dtype=torch.int32).contiguous()
+        plen = plen.to(device=A.device, dtype=torch.int32).contiguous()
+        if ids.dim() != 2 or ids.shape[0] != M or plen.numel() * beams != M:
+            raise ValueError(f"ids {tuple(ids.shape)} / plen {tuple(plen.shape)} do not describe {M} rows of {beams} beams")
+    _ck(_experiment_only(lib, "gitmi_debug_vocab_topm_rules")(
+        *ops, eps, *shape, _ptr(ids), 0 if ids is None else int(ids.shape[1]), int(cur_len), _ptr(plen), int(beams),
+        int(suppress_kind), float(rep_penalty), *outs, int(max_wgs), _stream()), lib)
+    return result
 
 
 def set_gemm_impl(impl: int) -> None:

@@ -56,6 +56,29 @@ int  gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const vo
                                     const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max, int pos,
                                     int beams, int dtype, void* stream);
 
+/* op hooks of the fused decode step (kernels_dgemm.hip vocab_topm_kernel, kernels_search.hip search_step_kernel;
+ * tests/test_gpu_search_ops.py).  All list / id / plen pointers are DEVICE memory unless named _host.
+ *   vocab_topm_rules:      gitmi_op_vocab_topm with the rule inputs of a real search step in place of suppress_tok: ids int32
+ *                          [M][ld_ids] row histories (cur_len tokens each), plen int32 [M / beams] prefix lengths, suppress_kind
+ *                          (1: no immediate repeat on rows with cur_len > plen), rep_penalty (0 or 1: off).  ids NULL: no rules.
+ *   search_begin_prefixed: gitmi_search_begin with one prefix length per sentence (start_host int64 [B][ld], plen_host int32 [B]);
+ *                          every sentence stands for its own batch-1 reference call, as in gitmi_generate_prefixed.
+ *   search_advance_lists:  gitmi_search_advance on caller-supplied candidate lists in the fused head's format (part_val / part_idx
+ *                          [R][nparts][slots] sorted, unused entries (-inf, 0x7fffffff); part_lse [R][nparts][2] = (max, sum exp));
+ *                          nparts 1..256, slots one of 1 / 2 / 4 / 8 / 16 and at least what the step reads per row.  embed != 0:
+ *                          the step also embeds the appended tokens with the engine's weights (input of the next decode step).
+ *   read_hidden:           the embedded rows of the most recent step: hf_out fp32 [R][D]; ht_out round_up(R, 16) * D elements of the
+ *                          compute type as stored, *ht_frag = 1 when fragment-major (include/gitmi.h), *ht_dtype a GITMI_DTYPE_*. */
+int  gitmi_debug_vocab_topm_rules(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
+                                  int strips, float eps, int M, int V, int K, int cols_per_wg, int mtop, const int* ids, int ld_ids,
+                                  int cur_len, const int* plen, int beams, int suppress_kind, float rep_penalty, float* part_val,
+                                  int* part_idx, float* part_lse, float* logits_out, int max_wgs, void* stream);
+int  gitmi_debug_search_begin_prefixed(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host, int ld,
+                                       const int32_t* plen_host, int vocab, void* stream);
+int  gitmi_debug_search_advance_lists(gitmi_engine* e, const float* part_val, const int* part_idx, const float* part_lse,
+                                      int nparts, int slots, int embed, void* stream);
+int  gitmi_debug_read_hidden(gitmi_engine* e, int R, float* hf_out, void* ht_out, int* ht_frag, int* ht_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
