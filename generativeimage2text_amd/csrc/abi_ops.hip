@@ -366,3 +366,72 @@ GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const 
     hipFree(part); hipFree(zt); hipFree(o2); hipFree(bad); hipFree(logits);
     return rc;
 }
+
+// ---- op hooks of the image front end of the encoder (kernels_norm.hip; tests/test_gpu_frontend_ops.py) -----------------------
+// Each one is an argument check + the launcher encode_frames_impl calls, so the launcher's kernel selection is what runs.
+#ifdef GITMI_EXPERIMENT
+GITMI_EXP_EXPORT int gitmi_debug_im2col(const float* img, void* out, int out_dtype, int B, int H, int W, int p, int K, int Kpad,
+                                        void* stream) {
+    if (!img || !out) return fail("debug_im2col: null argument");
+    RCK(check_dtype("debug_im2col", "out_dtype", out_dtype));
+    if (B < 1 || p < 1 || H < p || W < p || K != 3 * p * p || Kpad < K) return fail("debug_im2col: bad shape");
+    HIPCK(launch_im2col(img, out, out_dtype == GITMI_DTYPE_F32, B, H, W, p, K, Kpad, (hipStream_t)stream));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_pos_resize(const float* pos, float* out, int g, int gh, int gw, int D, void* stream) {
+    if (!pos || !out || g < 1 || gh < 1 || gw < 1 || D < 1) return fail("debug_pos_resize: bad argument");
+    HIPCK(launch_pos_bicubic(pos, out, g, gh, gw, D, (hipStream_t)stream));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_vit_assemble(const float* patch_out, const float* cls, const float* pos, const float* gamma,
+                                              const float* beta, float eps, void* X, int x_f16, int B, int N, int D, float* part,
+                                              void* stream) {
+    if (!patch_out || !cls || !pos || !gamma || !beta || !X || B < 1 || N < 1 || D < 1) return fail("debug_vit_assemble: bad argument");
+    HIPCK(launch_vit_assemble_ln(patch_out, cls, pos, gamma, beta, eps, X, x_f16 != 0, B, N, D, (float2*)part, (D + 255) / 256,
+                                 (hipStream_t)stream));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_ragged_front(int stage, const float* src, float* slots, int* meta, int* ntok, void* patches,
+                                              int patches_dtype, const float* patch_out, const float* cls, const float* pos, int g,
+                                              const float* gamma, const float* beta, float eps, void* X, int x_f16, float* part,
+                                              int B, int p, long long max_pixels, int Nmax, int K, int Kpad, int D, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B < 1 || p < 1 || max_pixels < 1 || Nmax < 2 || !meta) return fail("debug_ragged_front: bad argument");
+    const size_t slot = (size_t)3 * (size_t)max_pixels;
+    if (stage == 0) {
+        if (!src || !slots || !ntok) return fail("debug_ragged_front: staging takes src, slots, meta and ntok");
+        HIPCK(launch_ragged_stage(src, slots, slot, (int4*)meta, ntok, B, p, (size_t)max_pixels, Nmax, s));
+    } else if (stage == 1) {
+        if (!slots || !patches || K != 3 * p * p || Kpad < K) return fail("debug_ragged_front: im2col takes slots, meta and patches");
+        RCK(check_dtype("debug_ragged_front", "patches_dtype", patches_dtype));
+        HIPCK(launch_im2col_ragged(slots, slot, (const int4*)meta, patches, patches_dtype == GITMI_DTYPE_F32, B, Nmax, p, K, Kpad, s));
+    } else if (stage == 2) {
+        if (!patch_out || !cls || !pos || !gamma || !beta || !X || g < 1 || D < 1) return fail("debug_ragged_front: assembly argument missing");
+        HIPCK(launch_vit_assemble_ragged(patch_out, cls, pos, g, (const int4*)meta, gamma, beta, eps, X, x_f16 != 0, B, Nmax, p, D,
+                                         (float2*)part, s));
+    } else {
+        return fail("debug_ragged_front: stage %d (0 staging, 1 im2col, 2 assembly)", stage);
+    }
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_zero_pad_rows(void* x, int is_f32, int ld, const int* ntok, int B, int Nmax, void* stream) {
+    if (!x || !ntok || B < 1 || Nmax < 1 || ld < 1) return fail("debug_zero_pad_rows: bad argument");
+    HIPCK(launch_zero_pad_rows(x, is_f32 != 0, ld, ntok, B, Nmax, (hipStream_t)stream));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_layernorm_map(const void* x, int src_f16, const float* gamma, const float* beta, float eps,
+                                               const float* add_after, void* y_t, int out_dtype, void* y_s, int rows, int D,
+                                               int map_n_in, int map_n_out, int map_off, void* stream) {
+    if (!x || !gamma || !beta || (!y_t && !y_s) || rows < 1 || D < 1) return fail("debug_layernorm_map: bad argument");
+    if (y_t) RCK(check_dtype("debug_layernorm_map", "out_dtype", out_dtype));
+    if (map_n_in > 0 && (map_off < 0 || map_off + map_n_in > map_n_out)) return fail("debug_layernorm_map: row map leaves its block");
+    const bool t_is_f32 = out_dtype == GITMI_DTYPE_F32;
+    if (src_f16)
+        HIPCK(launch_layernorm_s16(x, D, gamma, beta, eps, add_after, y_t, D, t_is_f32, y_s, D, rows, D, map_n_in, map_n_out, map_off,
+                                   (hipStream_t)stream));
+    else
+        HIPCK(launch_layernorm((const float*)x, D, gamma, beta, eps, add_after, y_t, D, t_is_f32, (float*)y_s, D, rows, D, map_n_in,
+                               map_n_out, map_off, (hipStream_t)stream));
+    return 0;
+}
+#endif

@@ -40,6 +40,8 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_import_stage", "gitmi_debug_head_from", "gitmi_debug_set_gemm_impl", "gitmi_debug_set_dgemm",
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
+    "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
+    "gitmi_debug_layernorm_map",
 ]
 
 
@@ -154,6 +156,13 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_search_begin_prefixed.argtypes = [vp, C.POINTER(GitmiSearch), i32, vp, i32, vp, i32, vp]
         lib.gitmi_debug_search_advance_lists.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
         lib.gitmi_debug_read_hidden.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+        lib.gitmi_debug_im2col.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_pos_resize.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_vit_assemble.argtypes = [vp, vp, vp, vp, vp, C.c_float, vp, i32, i32, i32, i32, vp, vp]
+        lib.gitmi_debug_ragged_front.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, C.c_float, vp, i32, vp, i32, i32,
+                                                 C.c_longlong, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_zero_pad_rows.argtypes = [vp, i32, i32, vp, i32, i32, vp]
+        lib.gitmi_debug_layernorm_map.argtypes = [vp, i32, vp, vp, C.c_float, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands == "exp" else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -1037,6 +1046,63 @@ def op_score_head(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tgt: tor
                                                         t.data_ptr(), M, V, K, _torch_dtype_code(A), out.data_ptr(),
                                                         _stream()), lib)
     return out
+
+
+# ---- op hooks of the encoder's image front end (measurement build; tests/test_gpu_frontend_ops.py).  Every output is a
+# caller-supplied device tensor (the tests put a sentinel-filled margin behind it); the launcher of encode_frames runs on it.
+def _front(name: str):
+    lib = load_library()
+    return lib, _experiment_only(lib, name)
+
+
+def op_im2col(img: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, p: int, Kpad: int) -> None:
+    """img fp32 [B, 3, H, W] (any 4-byte aligned view) -> out [B * (H // p) * (W // p), Kpad] patch rows, fp32 or the build's
+    16-bit operand type, zeros past K = 3 p p."""
+    lib, fn = _front("gitmi_debug_im2col")
+    _ck(fn(img.data_ptr(), out.data_ptr(), _torch_dtype_code(out), B, H, W, p, 3 * p * p, Kpad, _stream()), lib)
+
+
+def op_pos_resize(pos: torch.Tensor, out: torch.Tensor, g: int, gh: int, gw: int) -> None:
+    """pos fp32 [g * g + 1, D] -> out fp32 [gh * gw + 1, D]: bicubic resize of the grid rows, class row copied."""
+    lib, fn = _front("gitmi_debug_pos_resize")
+    _ck(fn(pos.data_ptr(), out.data_ptr(), g, gh, gw, int(pos.shape[1]), _stream()), lib)
+
+
+def op_vit_assemble(patch_out: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                    eps: float, X: torch.Tensor, B: int, N: int, part: Optional[torch.Tensor] = None) -> None:
+    """Class / patch rows + positional rows, ln_pre -> X [B * N, D] (fp32, or the fp16 stream when X is float16); part fp32
+    [B * N, 4, 2]: the folded-LayerNorm partials (fp16 stream only)."""
+    lib, fn = _front("gitmi_debug_vit_assemble")
+    _ck(fn(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, X.data_ptr(),
+           1 if X.dtype == torch.float16 else 0, B, N, int(cls.numel()), _ptr(part), _stream()), lib)
+
+
+def op_ragged_front(stage: int, B: int, p: int, max_pixels: int, Nmax: int, *, src=None, slots=None, meta=None, ntok=None,
+                    patches=None, Kpad: int = 0, patch_out=None, cls=None, pos=None, g: int = 0, gamma=None, beta=None,
+                    eps: float = 1e-5, X=None, part=None) -> None:
+    """One stage of a ragged batch's front end on caller-supplied buffers: 0 staging (src -> slots, meta, ntok), 1 patch gather
+    (slots, meta -> patches [B, Nmax - 1, Kpad]), 2 token assembly + ln_pre (patch_out, cls, pos, meta -> X [B * Nmax, D], part)."""
+    lib, fn = _front("gitmi_debug_ragged_front")
+    _ck(fn(int(stage), _ptr(src), _ptr(slots), _ptr(meta), _ptr(ntok), _ptr(patches),
+           DTYPE_F32 if patches is None else _torch_dtype_code(patches), _ptr(patch_out), _ptr(cls), _ptr(pos), int(g), _ptr(gamma),
+           _ptr(beta), eps, _ptr(X), 1 if X is not None and X.dtype == torch.float16 else 0, _ptr(part), B, p, int(max_pixels), Nmax,
+           3 * p * p, int(Kpad), 0 if cls is None else int(cls.numel()), _stream()), lib)
+
+
+def op_zero_pad_rows(x: torch.Tensor, ntok: torch.Tensor, B: int, Nmax: int, ld: int) -> None:
+    """Rows t >= ntok[b] of x [B, Nmax, ld] (fp32 or 16-bit elements) set to zero, in place."""
+    lib, fn = _front("gitmi_debug_zero_pad_rows")
+    _ck(fn(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, ld, ntok.data_ptr(), B, Nmax, _stream()), lib)
+
+
+def op_layernorm_map(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, add_after: Optional[torch.Tensor],
+                     y_t: Optional[torch.Tensor], y_s: Optional[torch.Tensor], rows: int, D: int, map_n_in: int = 0,
+                     map_n_out: int = 0, map_off: int = 0) -> None:
+    """LayerNorm of `rows` rows of x (fp32, or fp16 stream rows) + add_after, scattered by the row map of ln_post: y_t fp32 or
+    the build's 16-bit operand type, y_s the source's type (either may be None)."""
+    lib, fn = _front("gitmi_debug_layernorm_map")
+    _ck(fn(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, gamma.data_ptr(), beta.data_ptr(), eps, _ptr(add_after), _ptr(y_t),
+           DTYPE_F32 if y_t is None else _torch_dtype_code(y_t), _ptr(y_s), rows, D, map_n_in, map_n_out, map_off, _stream()), lib)
 
 
 def op_sample_rows(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, ndraw: int = 2,

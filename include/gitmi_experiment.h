@@ -79,6 +79,35 @@ int  gitmi_debug_search_advance_lists(gitmi_engine* e, const float* part_val, co
                                       int nparts, int slots, int embed, void* stream);
 int  gitmi_debug_read_hidden(gitmi_engine* e, int R, float* hf_out, void* ht_out, int* ht_frag, int* ht_dtype, void* stream);
 
+/* op hooks of the image front end of the encoder (kernels_norm.hip; tests/test_gpu_frontend_ops.py): an argument check + the
+ * launcher gitmi_encode_frames calls, so the launcher's kernel selection is part of what runs.  All pointers DEVICE memory;
+ * 16-bit dtypes: the build's operand type (gitmi_operand_dtype); x_f16 / src_f16: fp16 residual-stream rows.
+ *   im2col:        img fp32 [B][3][H][W] -> out [B * (H/p) * (W/p)][Kpad] (K = 3 p p, zeros past K).
+ *   pos_resize:    pos fp32 [g*g + 1][D] -> out fp32 [gh*gw + 1][D] (bicubic, align_corners = False; row 0 copied).
+ *   vit_assemble:  class row / patch_out [B * (N-1)][D] + pos [N][D], ln_pre -> X [B * N][D] (fp32, or fp16 with x_f16);
+ *                  part (x_f16 only, or NULL): fp32 [B * N][4][2] folded-LayerNorm partials of the rows as stored.
+ *   ragged_front:  one stage of a ragged batch (include/gitmi.h: int32 descriptors [B][4] = {h, w, offset, 0} padded to 256
+ *                  bytes, then the planes).  stage 0: src -> slots fp32 [B][3 * max_pixels], meta int32 [B][4] = {h, w, ntok, bad},
+ *                  ntok int32 [B].  stage 1: slots, meta -> patches [B][Nmax - 1][Kpad] (patches_dtype).  stage 2: patch_out
+ *                  [B * (Nmax-1)][D], cls, pos [g*g + 1][D], meta -> X [B * Nmax][D], part as in vit_assemble.  Arguments of the
+ *                  other stages are ignored.
+ *   zero_pad_rows: rows t >= ntok[b] of x [B][Nmax][ld] (fp32 or 16-bit elements) set to zero.
+ *   layernorm_map: LayerNorm of rows x [rows][D] (fp32, or fp16 with src_f16) + add_after [D] (or NULL) -> y_t (out_dtype, or
+ *                  NULL) and y_s (the source's type, or NULL), input row r written to output row
+ *                  (r / map_n_in) * map_n_out + map_off + r % map_n_in (map_n_in = 0: row r). */
+int  gitmi_debug_im2col(const float* img, void* out, int out_dtype, int B, int H, int W, int p, int K, int Kpad, void* stream);
+int  gitmi_debug_pos_resize(const float* pos, float* out, int g, int gh, int gw, int D, void* stream);
+int  gitmi_debug_vit_assemble(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta,
+                              float eps, void* X, int x_f16, int B, int N, int D, float* part, void* stream);
+int  gitmi_debug_ragged_front(int stage, const float* src, float* slots, int* meta, int* ntok, void* patches, int patches_dtype,
+                              const float* patch_out, const float* cls, const float* pos, int g, const float* gamma,
+                              const float* beta, float eps, void* X, int x_f16, float* part, int B, int p, long long max_pixels,
+                              int Nmax, int K, int Kpad, int D, void* stream);
+int  gitmi_debug_zero_pad_rows(void* x, int is_f32, int ld, const int* ntok, int B, int Nmax, void* stream);
+int  gitmi_debug_layernorm_map(const void* x, int src_f16, const float* gamma, const float* beta, float eps, const float* add_after,
+                               void* y_t, int out_dtype, void* y_s, int rows, int D, int map_n_in, int map_n_out, int map_off,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
