@@ -235,29 +235,40 @@ extern "C" int gitmi_create(const gitmi_config* cfg, int device, gitmi_engine** 
     return 0;
 }
 
-// the two hipGraph slots: full calls (one graph, or encode + prefill | decode) and follow-up calls (decode alone)
-static void destroy_full_graph(gitmi_engine* e) {
-    if (e->graph_exec) hipGraphExecDestroy(e->graph_exec);
-    if (e->graph) hipGraphDestroy(e->graph);
-    if (e->graph_exec_b) hipGraphExecDestroy(e->graph_exec_b);
-    if (e->graph_b) hipGraphDestroy(e->graph_b);
-    e->graph_exec = e->graph_exec_b = nullptr;
-    e->graph = e->graph_b = nullptr;
-    e->graph_valid = false;
+int CapturedGraph::capture(hipStream_t s, const std::function<int()>& fn) {
+    reset();
+    HIPCK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = fn();            // 0, or the code of a gitmi::fail: nothing has run on the device either way
+    const hipError_t ce = hipStreamEndCapture(s, &graph);
+    if (rc != 0 || ce != hipSuccess) reset();
+    RCK(rc);
+    HIPCK(ce);
+    HIPCK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    return 0;
 }
-static void destroy_followup_graph(gitmi_engine* e) {
-    if (e->graph_exec_r) hipGraphExecDestroy(e->graph_exec_r);
-    if (e->graph_r) hipGraphDestroy(e->graph_r);
-    e->graph_exec_r = nullptr;
-    e->graph_r = nullptr;
-    e->graph_r_valid = false;
-}
+// both hipGraph slots: full calls (one graph, or encode + prefill | decode) and follow-up calls (decode alone)
 static void destroy_graph(gitmi_engine* e) {
-    destroy_full_graph(e);
-    destroy_followup_graph(e);
+    for (CapturedGraph* g : {&e->graph_full, &e->graph_decode, &e->graph_follow}) g->reset();
+    e->full_slot.valid = e->follow_slot.valid = false;
 }
+// ---- residency (include/gitmi.h: what a follow-up call runs over): the only writers of cur_* / have_* ----
 // the engine's images stop being resident: an encode starts (or failed), or a setter changed what an encode would produce
 static void drop_resident(gitmi_engine* e) { e->have_feats = e->have_prefill = false; }
+// an encode of B images with F_eff frames each is enqueued (or replayed, or imported): they are resident, their K/V is not
+static void set_resident(gitmi_engine* e, int B, int F_eff) {
+    e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = F_eff * e->N;
+    e->have_feats = true; e->have_prefill = false;
+}
+static void set_prefilled(gitmi_engine* e) { e->have_prefill = true; }
+// The failure rule, for every call that runs over images (rc: what its launches returned):
+//   a call that was given frames and fails after its first launch or capture leaves NOTHING resident (the workspaces are
+//     partly overwritten, or -- a failed capture -- the host side of the encode ran and nothing on the device);
+//   a follow-up call (frames == NULL) that fails leaves what was resident: it writes text caches only;
+//   an argument error is found before any launch and never gets here: it leaves everything as it was.
+static int settle_residency(gitmi_engine* e, const Request& rq, int rc) {
+    if (rc != 0 && rq.frames) drop_resident(e);
+    return rc;
+}
 
 extern "C" void gitmi_destroy(gitmi_engine* e) {
     if (!e) return;
@@ -396,9 +407,7 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
         if (feats_out) HIPCK(launch_zero_pad_rows(feats_out, true, D, e->rg_ntok, B, N, s));
     }
 
-    e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = Nimg;
-    e->have_feats = true;
-    e->have_prefill = false;
+    set_resident(e, B, F_eff);      // cur_Nimg == Nimg: N is e->N, ragged (Nmax) or not
     return 0;
 }
 
@@ -452,7 +461,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
             cur ^= 1;
             ln.part = e->p_part[cur]; ln.eps = 1e-12f; ln.gamma = L.lnog; ln.beta = L.lnob;
         }
-        e->have_prefill = true;
+        set_prefilled(e);
         return 0;
     }
     RCK(gemm_stream(e, s, e->feats, D, e->w.vp_w, e->w.vp_b, nullptr, 0, e->p_y, d, M, d, D, TAG_GEMM_OTHER));
@@ -477,7 +486,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
         RCK(gemm_stream(e, s, e->p_u, ffn, L.w2, L.b2, e->p_hf, d, e->p_y, d, M, d, ffn, TAG_GEMM_OTHER));
         RCK(ln_stream(e, s, e->p_y, d, L.lnog, L.lnob, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
     }
-    e->have_prefill = true;
+    set_prefilled(e);
     return 0;
 }
 
@@ -724,10 +733,12 @@ extern "C" int gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, 
 }
 
 // ---- search seam -----------------------------------------------------------------------
-// `start_dev` / `plen_dev` (/ `img_of_dev`) must already describe the B sentences of the call
-static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int minP, int maxP, int V, bool prefixed,
-                             hipStream_t s) {
+// `start_dev` / `plen_dev` (/ `img_of_dev`) must already describe the rq.Q sentences of the call (of rq, the search and
+// the sentence counts are read; V: the vocabulary the search ranks)
+static int search_begin_impl(gitmi_engine* e, const Request& rq, int V, hipStream_t s) {
     const gitmi_config& c = e->cfg;
+    const gitmi_search* sp = rq.sp;
+    const int B = rq.Q, minP = rq.minP, maxP = rq.maxP;
     if (!sp) return fail("search: null config");
     if (sp->kind != GITMI_SEARCH_AUTOREGRESSIVE && sp->kind != GITMI_SEARCH_GENERATOR && sp->kind != GITMI_SEARCH_TRIE)
         return fail("search: bad kind");
@@ -764,7 +775,7 @@ static int search_begin_impl(gitmi_engine* e, const gitmi_search* sp, int B, int
     st.T = sp->max_steps;           // max_length of the search AND the row stride of ids/kv_src/hyp_tok
     // the trie search shares AutoRegressiveBeamSearch's bookkeeping (beam 1): only the candidate selection differs
     st.V = V; st.eos = c.eos; st.kind = e->trie_search ? GITMI_SEARCH_AUTOREGRESSIVE : sp->kind; st.length_penalty = sp->length_penalty;
-    st.prefixed = prefixed ? 1 : 0;
+    st.prefixed = rq.prefixed ? 1 : 0;
     st.nh = keep_best(*sp);
     st.sampled = sp->do_sample ? 1 : 0;
     e->sample = *sp;
@@ -891,7 +902,9 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     HIPCK(hipStreamSynchronize(s));
     if (!plen_host) HIPCK(launch_fill_i32(e->plen_dev, ld, B, s));
     e->img_identity = true;
-    return search_begin_impl(e, sp, B, minP, maxP, vocab, plen_host != nullptr, s);
+    Request rq{};
+    rq.Q = B; rq.minP = minP; rq.maxP = maxP; rq.prefixed = plen_host != nullptr; rq.sp = sp;
+    return search_begin_impl(e, rq, vocab, s);
 }
 
 extern "C" int gitmi_search_begin(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host, int P,
@@ -990,22 +1003,19 @@ GITMI_EXP_EXPORT int gitmi_debug_read_hidden(gitmi_engine* e, int R, float* hf_o
 
 // ---- the whole hot path ------------------------------------------------------------------
 // image encoder + decoder prefill over the image tokens
-static int generate_encode(gitmi_engine* e, const float* const* frames, int F, int B, hipStream_t s) {
-    RCK(encode_frames_impl(e, frames, F, B, nullptr, s));
-    RCK(prefill_impl(e, s));
-    return 0;
+static int generate_encode(gitmi_engine* e, const Request& rq, hipStream_t s) {
+    RCK(encode_frames_impl(e, rq.frames, rq.F, rq.B, nullptr, s));
+    return prefill_impl(e, s);
 }
 
 // search over the text positions (teacher-forced prefix positions, then searched ones) + result formatting.
-// Q sentences (start_dev / plen_dev / img_of_dev describe them), prefix lengths in [minP, maxP].
-static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool prefixed, const gitmi_search* sp,
-                           long long* tokens_out, float* logprob_out, int32_t* info_out, int32_t* sent_out, hipStream_t s,
-                           bool allow_poll) {
+// rq.Q sentences (start_dev / plen_dev / img_of_dev describe them), prefix lengths in [minP, maxP].
+static int generate_decode(gitmi_engine* e, const Request& rq, hipStream_t s, bool allow_poll) {
     const gitmi_config& c = e->cfg;
-    RCK(search_begin_impl(e, sp, Q, minP, maxP, c.vocab, prefixed, s));
-    const int T = sp->max_steps;
+    const gitmi_search* sp = rq.sp;
+    RCK(search_begin_impl(e, rq, c.vocab, s));
+    const int Q = rq.Q, minP = rq.minP, maxP = rq.maxP, T = sp->max_steps, k = sp->beam_size, R = Q * k;
     const SearchState& st = e->ss;
-    const int k = sp->beam_size, R = Q * k;
     const int M = search_mtop(st);
     const int suppress = sp->kind != GITMI_SEARCH_GENERATOR ? 1 : 0;
     {
@@ -1034,9 +1044,9 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool pref
             }
         }
     }
-    HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, tokens_out, logprob_out, info_out, sent_out, s));
+    HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, rq.tokens, rq.logprob, rq.info, rq.sent, s));
     if (e->ragged)      // sentences over a rejected image: NaN log-probs, counted with the non-finite ones (info[3])
-        HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q, keep_best(*sp), logprob_out, info_out,
+        HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q, keep_best(*sp), rq.logprob, rq.info,
                                    nullptr, s));
     // algorithmic bytes of one decode step: all decoder weights once +
     // per sentence the K/V of every layer (image part shared by beams, text part per beam)
@@ -1045,154 +1055,128 @@ static int generate_decode(gitmi_engine* e, int Q, int minP, int maxP, bool pref
     return 0;
 }
 
-static int generate_body(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool prefixed,
-                         const gitmi_search* sp, long long* tokens_out, float* logprob_out, int32_t* info_out,
-                         int32_t* sent_out, hipStream_t s, bool allow_poll) {
+// the whole call: encode + prefill of the frames (a follow-up: the prefill, if it is not current), then the search
+static int generate_body(gitmi_engine* e, const Request& rq, hipStream_t s, bool allow_poll) {
     SpanGuard total(e, s, 99, 0);
-    RCK(generate_encode(e, frames, F, B, s));
-    return generate_decode(e, Q, minP, maxP, prefixed, sp, tokens_out, logprob_out, info_out, sent_out, s, allow_poll);
+    if (rq.frames) RCK(generate_encode(e, rq, s));
+    else if (!e->have_prefill) RCK(prefill_impl(e, s));
+    return generate_decode(e, rq, s, allow_poll);
 }
 
-// common tail of gitmi_generate / gitmi_generate_prefixed: start_dev / plen_dev / img_of_dev are already enqueued on `s`
-static int generate_run(gitmi_engine* e, const float* const* frames, int F, int B, int Q, int minP, int maxP, bool prefixed,
-                        const gitmi_search* sp, int64_t* tokens_out, float* logprob_out, int32_t* info_out,
-                        int32_t* sent_out, hipStream_t s) {
-    const gitmi_config& c = e->cfg;
-    const bool resident = frames == nullptr;        // follow-up call: the decode part alone (+ the prefill if it is not current)
-    const bool long_budget = sp->max_steps - minP > 32;
-    const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
-    if (!graph) {
-        if (resident) {
-            SpanGuard total(e, s, 99, 0);
-            if (!e->have_prefill) RCK(prefill_impl(e, s));
-            return generate_decode(e, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
-                                   sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
-        }
-        const int rc = generate_body(e, frames, F, B, Q, minP, maxP, prefixed, sp, (long long*)tokens_out, logprob_out, info_out,
-                                     sent_out ? sent_out : e->out_sent, s, long_budget && !e->profiling);
-        if (rc != 0) drop_resident(e);
-        return rc;
-    }
+// hipGraph cache key of a call: everything the captured launch sequence depends on
+static GraphKey graph_key_of(const gitmi_engine* e, const Request& rq, int F_eff) {
+    const gitmi_search& sp = *rq.sp;
+    return {rq.B, rq.Q, F_eff, rq.minP, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, e->H, e->W,
+            rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, rq.frames ? 0 : 1, sp.length_penalty,
+            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed};
+}
 
-    // ---- hipGraph path: the launch sequence only depends on (B,Q,F,minP,search); inputs and outputs are
-    // staged through engine-owned buffers so the captured pointers stay valid across calls.
-    // The legacy null stream cannot be captured: run on the engine's own stream, fenced by events.
+// Launches the graphs of one call on `x`: `enc` (the whole call, or encode + prefill; nullptr in a follow-up), then `dec`
+// (the decode part; nullptr when `enc` is the whole call).  Between the two graphs of a split full call the serving schedule
+// has its say: the call waits for enc_after's encoder before `enc` and records enc_done after it for its watchers.  A
+// follow-up runs no encoder, so it neither waits nor records (watchers keep waiting for the most recent real encoder).
+// profile_mode 2 takes the place of the schedule: events around each graph, a synchronisation, the split_* sums; a
+// follow-up's graph is timed as the decode graph of a full call and adds nothing to the encode side.
+static int replay(gitmi_engine* e, const Request& rq, hipStream_t x, const CapturedGraph* enc, const CapturedGraph* dec) {
+    const bool timed = e->profile_mode == 2;
+    if (timed) {
+        for (auto& ev : e->gev)
+            if (!ev) HIPCK(hipEventCreate(&ev));
+        HIPCK(hipEventRecord(e->gev[enc ? 0 : 1], x));
+    } else if (enc && e->enc_after && e->enc_after->enc_done) {
+        HIPCK(hipStreamWaitEvent(x, e->enc_after->enc_done, 0));
+    }
+    if (enc) {
+        HIPCK(enc->launch(x));
+        if (timed) HIPCK(hipEventRecord(e->gev[1], x));
+        else if (e->enc_done && !e->enc_watchers.empty()) HIPCK(hipEventRecord(e->enc_done, x));
+    }
+    if (dec) HIPCK(dec->launch(x));
+    if (!timed) return 0;
+    HIPCK(hipEventRecord(e->gev[2], x));
+    HIPCK(hipStreamSynchronize(x));
+    float a = 0, b = 0;
+    if (enc) HIPCK(hipEventElapsedTime(&a, e->gev[0], e->gev[1]));
+    HIPCK(hipEventElapsedTime(&b, e->gev[1], e->gev[2]));
+    e->split_encode_ms += a; e->split_decode_ms += b; e->split_calls += 1; e->split_steps += rq.sp->max_steps - 1;
+    return 0;
+}
+
+// hipGraph path: the launch sequence only depends on (B,Q,F,minP,search); inputs and outputs are staged through
+// engine-owned buffers so the captured pointers stay valid across calls.
+static int generate_graphed(gitmi_engine* e, const Request& rq, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    const bool resident = rq.frames == nullptr;     // follow-up call: the decode part alone (+ the prefill if it is not current)
+    // the legacy null stream cannot be captured: run on the engine's own stream, fenced by events
     hipStream_t x = s ? s : e->own_stream;
     if (x != s) {
         HIPCK(hipEventRecord(e->fence_in, s));
         HIPCK(hipStreamWaitEvent(x, e->fence_in, 0));
     }
-    const size_t frame_bytes = (size_t)B * 3 * e->H * e->W * sizeof(float);
-    const int F_eff = resident ? e->cur_F : c.num_frames > 0 ? std::min(F, c.num_frames) : F;
-    if (!e->ragged && !resident)    // ragged: ragged_prepare staged the images already; follow-up: no frames
+    // ---- stage the inputs (ragged: ragged_prepare staged the images already; follow-up: no frames)
+    const size_t frame_bytes = (size_t)rq.B * 3 * e->H * e->W * sizeof(float);
+    const int F_eff = resident ? e->cur_F : c.num_frames > 0 ? std::min(rq.F, c.num_frames) : rq.F;
+    if (!e->ragged && !resident)
     for (int f = 0; f < F_eff; ++f)
-        HIPCK(hipMemcpyAsync(e->frame_stage[f], frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
-    const GraphKey key = GraphKey::of(B, Q, F_eff, minP, e->H, e->W, prefixed, e->img_identity, e->pol.use_temb, resident, *sp);
-    // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
-    // enc_done record other contexts wait for
-    const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
+        HIPCK(hipMemcpyAsync(e->frame_stage[f], rq.frames[f], frame_bytes, hipMemcpyDeviceToDevice, x));
+    // ---- look the graphs up, or capture them: the same call on the engine's own frames and output buffers
+    Request own = rq;
+    if (!resident) { own.frames = e->frame_stage.data(); own.F = F_eff; }
+    own.tokens = e->out_tokens; own.logprob = e->out_lp; own.info = e->out_info; own.sent = e->out_sent;
+    const GraphKey key = graph_key_of(e, rq, F_eff);
+    const CapturedGraph *enc = nullptr, *dec = nullptr;
     if (resident) {
-        // the decode graph alone, in its own slot.  No encoder runs: the call neither waits for enc_after's encoder nor
-        // records enc_done (watchers keep waiting for the most recent real encoder)
         if (!e->have_prefill) RCK(prefill_impl(e, x));          // after gitmi_encode_frames alone; outside the graph
-        if (!e->graph_r_valid || !(key == e->graph_r_key)) {
-            destroy_followup_graph(e);
-            HIPCK(hipStreamBeginCapture(x, hipStreamCaptureModeThreadLocal));
-            const int rc = generate_decode(e, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
-            hipGraph_t gr = nullptr;
-            const hipError_t ce = hipStreamEndCapture(x, &gr);
-            if (rc != 0) { if (gr) hipGraphDestroy(gr); return rc; }
-            HIPCK(ce);
-            e->graph_r = gr;
-            HIPCK(hipGraphInstantiate(&e->graph_exec_r, e->graph_r, nullptr, nullptr, 0));
-            e->graph_r_key = key;
-            e->graph_r_valid = true;
+        if (!e->follow_slot.valid || !(key == e->follow_slot.key)) {
+            e->follow_slot.valid = false;
+            RCK(e->graph_follow.capture(x, [&] { return generate_decode(e, own, x, false); }));
+            e->follow_slot = {key, true};
         }
-        if (e->profile_mode != 2) {
-            HIPCK(hipGraphLaunch(e->graph_exec_r, x));
-        } else {            // the decode graph timed as in a full call; nothing is added to the encode side
-            for (auto& ev : e->gev)
-                if (!ev) HIPCK(hipEventCreate(&ev));
-            HIPCK(hipEventRecord(e->gev[1], x));
-            HIPCK(hipGraphLaunch(e->graph_exec_r, x));
-            HIPCK(hipEventRecord(e->gev[2], x));
-            HIPCK(hipStreamSynchronize(x));
-            float b = 0;
-            HIPCK(hipEventElapsedTime(&b, e->gev[1], e->gev[2]));
-            e->split_decode_ms += b; e->split_calls += 1; e->split_steps += sp->max_steps - 1;
-        }
-    } else if (!e->graph_valid || !(key == e->graph_key) || split != e->graph_is_split) {
-        destroy_full_graph(e);
-        std::vector<const float*> fp(F_eff);
-        for (int f = 0; f < F_eff; ++f) fp[f] = e->frame_stage[f];
-        auto capture = [&](int part, hipGraph_t* gr_out) -> int {       // part 0: whole call, 1: encode + prefill, 2: decode
-            HIPCK(hipStreamBeginCapture(x, hipStreamCaptureModeThreadLocal));
-            int rc = 0;
-            if (part == 0) rc = generate_body(e, fp.data(), F_eff, B, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp,
-                                              e->out_info, e->out_sent, x, false);
-            else if (part == 1) rc = generate_encode(e, fp.data(), F_eff, B, x);
-            else rc = generate_decode(e, Q, minP, maxP, prefixed, sp, e->out_tokens, e->out_lp, e->out_info, e->out_sent, x, false);
-            hipGraph_t gr = nullptr;
-            hipError_t ce = hipStreamEndCapture(x, &gr);
-            // a failed capture ran the host side of the encode (cur_B, have_feats) but nothing on the device
-            if (rc != 0) { if (gr) hipGraphDestroy(gr); drop_resident(e); return rc; }
-            HIPCK(ce);
-            *gr_out = gr;
-            return 0;
-        };
-        if (!split) {
-            RCK(capture(0, &e->graph));
-            HIPCK(hipGraphInstantiate(&e->graph_exec, e->graph, nullptr, nullptr, 0));
+        dec = &e->graph_follow;
+    } else {
+        // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
+        // enc_done record other contexts wait for
+        const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
+        if (!e->full_slot.valid || !(key == e->full_slot.key) || split != e->graph_is_split) {
+            e->full_slot.valid = false;
+            e->graph_decode.reset();
+            if (!split) {
+                RCK(e->graph_full.capture(x, [&] { return generate_body(e, own, x, false); }));
+            } else {
+                RCK(e->graph_full.capture(x, [&] { return generate_encode(e, own, x); }));
+                RCK(e->graph_decode.capture(x, [&] { return generate_decode(e, own, x, false); }));
+            }
+            e->full_slot = {key, true}; e->graph_is_split = split;
         } else {
-            RCK(capture(1, &e->graph));
-            HIPCK(hipGraphInstantiate(&e->graph_exec, e->graph, nullptr, nullptr, 0));
-            RCK(capture(2, &e->graph_b));
-            HIPCK(hipGraphInstantiate(&e->graph_exec_b, e->graph_b, nullptr, nullptr, 0));
+            // a replay: the host-side state that enqueueing the encode and the prefill leaves behind
+            set_resident(e, rq.B, F_eff);
+            set_prefilled(e);
         }
-        e->graph_key = key;
-        e->graph_valid = true;
-        e->graph_is_split = split;
-    } else {
-        // host-side mirror of the state generate_body leaves behind
-        e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = F_eff * e->N;
-        e->have_feats = e->have_prefill = true;
+        enc = &e->graph_full;
+        if (split) dec = &e->graph_decode;
     }
-    if (resident) {
-        // launched above
-    } else if (!split) {
-        HIPCK(hipGraphLaunch(e->graph_exec, x));
-    } else if (e->profile_mode != 2) {
-        if (e->enc_after && e->enc_after->enc_done) HIPCK(hipStreamWaitEvent(x, e->enc_after->enc_done, 0));
-        HIPCK(hipGraphLaunch(e->graph_exec, x));
-        if (e->enc_done && !e->enc_watchers.empty()) HIPCK(hipEventRecord(e->enc_done, x));
-        HIPCK(hipGraphLaunch(e->graph_exec_b, x));
-    } else {
-        for (auto& ev : e->gev)
-            if (!ev) HIPCK(hipEventCreate(&ev));
-        HIPCK(hipEventRecord(e->gev[0], x));
-        HIPCK(hipGraphLaunch(e->graph_exec, x));
-        HIPCK(hipEventRecord(e->gev[1], x));
-        HIPCK(hipGraphLaunch(e->graph_exec_b, x));
-        HIPCK(hipEventRecord(e->gev[2], x));
-        HIPCK(hipStreamSynchronize(x));
-        float a = 0, b = 0;
-        HIPCK(hipEventElapsedTime(&a, e->gev[0], e->gev[1]));
-        HIPCK(hipEventElapsedTime(&b, e->gev[1], e->gev[2]));
-        e->split_encode_ms += a; e->split_decode_ms += b; e->split_calls += 1; e->split_steps += sp->max_steps - 1;
-    }
-    const size_t nout = (size_t)Q * (size_t)keep_best(*sp);      // sequences returned
-    // the caller's buffers: device memory or PAGE-LOCKED host memory (hipMemcpyDefault: the results then arrive on the host as part
-    // of the request itself -- a server reads them after the stream's event without enqueueing anything more, which matters when
-    // its other streams keep the device's queues full: a separate small read-back waits milliseconds for a queue slot)
-    HIPCK(hipMemcpyAsync(tokens_out, e->out_tokens, nout * sp->max_steps * sizeof(long long), hipMemcpyDefault, x));
-    HIPCK(hipMemcpyAsync(logprob_out, e->out_lp, nout * sizeof(float), hipMemcpyDefault, x));
-    HIPCK(hipMemcpyAsync(info_out, e->out_info, 4 * sizeof(int), hipMemcpyDefault, x));
-    if (sent_out) HIPCK(hipMemcpyAsync(sent_out, e->out_sent, (size_t)Q * 2 * sizeof(int), hipMemcpyDefault, x));
+    RCK(replay(e, rq, x, enc, dec));
+    // ---- results to the caller's buffers: device memory or PAGE-LOCKED host memory (hipMemcpyDefault: the results then arrive on
+    // the host as part of the request itself -- a server reads them after the stream's event without enqueueing anything more, which
+    // matters when its other streams keep the device's queues full: a separate small read-back waits milliseconds for a queue slot)
+    const size_t nout = (size_t)rq.Q * (size_t)keep_best(*rq.sp);      // sequences returned
+    HIPCK(hipMemcpyAsync(rq.tokens, e->out_tokens, nout * rq.sp->max_steps * sizeof(long long), hipMemcpyDefault, x));
+    HIPCK(hipMemcpyAsync(rq.logprob, e->out_lp, nout * sizeof(float), hipMemcpyDefault, x));
+    HIPCK(hipMemcpyAsync(rq.info, e->out_info, 4 * sizeof(int), hipMemcpyDefault, x));
+    if (rq.sent != e->out_sent) HIPCK(hipMemcpyAsync(rq.sent, e->out_sent, (size_t)rq.Q * 2 * sizeof(int), hipMemcpyDefault, x));
     if (x != s) {
         HIPCK(hipEventRecord(e->fence_out, x));
         HIPCK(hipStreamWaitEvent(s, e->fence_out, 0));
     }
     return 0;
+}
+
+// common tail of gitmi_generate / gitmi_generate_prefixed: start_dev / plen_dev / img_of_dev are already enqueued on `s`.
+// Eager launches for profiling spans and for long step budgets (which poll the finished count), else captured graphs.
+static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s) {
+    const bool long_budget = rq.sp->max_steps - rq.minP > 32;
+    const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
+    return settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
 }
 
 extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefix, int P,
@@ -1212,7 +1196,8 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     // start tokens [B, P] on device (shared prefix, or [CLS]) -- filled by a kernel, no host copy
     RCK(fill_uniform_sentences(e, B, (const long long*)prefix, P, s));
-    return generate_run(e, frames, F, B, B, P, P, false, sp, tokens_out, logprob_out, info_out, nullptr, s);
+    const Request rq{frames, F, B, B, P, P, false, sp, (long long*)tokens_out, logprob_out, info_out, e->out_sent};
+    return generate_run(e, rq, s);
 }
 
 // ---- caption scoring (GITMI_SEARCH_SCORE) -------------------------------------------------------------------------
@@ -1259,13 +1244,12 @@ static int score_alloc(gitmi_engine* e, size_t rows_needed) {
 // usual encode + prefill: embedding of every position, the decoder layers over all text rows at once (generic GEMM +
 // LayerNorm launches, the attention of kernels_score.hip against the prefill's image K/V), then the vocabulary head
 // reduced to (lp, mean_lp) per position.  tokens [Q][ld] device int64; lens / image_of already on the device.
-static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B, const long long* tokens, int ld, int Q, int maxlen,
-                      float* out, int32_t* info_out, hipStream_t s) {
+static int score_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
     const gitmi_config& c = e->cfg;
-    const int d = c.dec_hidden, ffn = c.dec_ffn, V = c.vocab;
-    if (frames) RCK(generate_encode(e, frames, F, B, s));
+    const int d = c.dec_hidden, ffn = c.dec_ffn, V = c.vocab, Q = rq.Q;
+    if (rq.frames) RCK(generate_encode(e, rq, s));
     else if (!e->have_prefill) RCK(prefill_impl(e, s));     // follow-up call: the resident images' K/V
-    const int Lp = round_up(maxlen, 16), M = Q * Lp;
+    const int Lp = round_up(rq.maxP, 16), M = Q * Lp;
     SpanGuard phase(e, s, TAG_DECODE, 0);
     HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
                                 e->pol.f32, d, V, c.max_pos, s));
@@ -1297,8 +1281,8 @@ static int score_impl(gitmi_engine* e, const float* const* frames, int F, int B,
     HIPCK(launch_score_combine(e->sc_part, ntiles, e->sc_zt, e->sc_tgt, M, Lp, ld, V, e->sc_out, e->sc_bad, s));
     if (e->ragged) HIPCK(launch_ragged_report(e->rg_meta, e->sc_img, Q, 0, nullptr, nullptr, e->sc_bad, s));
     HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s));
-    HIPCK(hipMemcpyAsync(out, e->sc_out, (size_t)Q * ld * sizeof(float2), hipMemcpyDefault, s));
-    HIPCK(hipMemcpyAsync(info_out, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
+    HIPCK(hipMemcpyAsync(rq.logprob, e->sc_out, (size_t)Q * ld * sizeof(float2), hipMemcpyDefault, s));
+    HIPCK(hipMemcpyAsync(rq.info, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
     return 0;
 }
 
@@ -1351,9 +1335,9 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         RCK(score_alloc(e, (size_t)Q * round_up(span.maxP, 16)));
         RCK(upload_sentences(e, e->sc_lens, e->sc_img, s));
         if (frames) RCK(ragged_prepare(e, frames, F, B, s));
-        const int rc = score_impl(e, frames, F, B, (const long long*)prefixes, ld_prefix, Q, span.maxP, logprob_out, info_out, s);
-        if (rc != 0 && frames) drop_resident(e);
-        return rc;
+        // the sentences are whole captions of lengths [minP, maxP]; logprob_out receives (lp, mean_lp) per position
+        const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, nullptr, logprob_out, info_out, e->out_sent};
+        return settle_residency(e, rq, score_impl(e, rq, (const long long*)prefixes, ld_prefix, s));
     }
     if (!frames) RCK(check_resident(e, "generate_prefixed", B));
     if (!sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
@@ -1367,7 +1351,9 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
                       (size_t)span.maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
     e->img_identity = span.ident;
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
-    return generate_run(e, frames, F, B, Q, span.minP, span.maxP, true, sp, tokens_out, logprob_out, info_out, sent_out, s);
+    const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, (long long*)tokens_out, logprob_out, info_out,
+                     sent_out ? sent_out : e->out_sent};
+    return generate_run(e, rq, s);
 }
 
 // ---- profiling --------------------------------------------------------------------------
@@ -1504,14 +1490,13 @@ GITMI_EXP_EXPORT int gitmi_debug_import_stage(gitmi_engine* dst, gitmi_engine* s
     hipStream_t s = (hipStream_t)stream;
     const size_t M = (size_t)src->cur_B * src->cur_Nimg;
     HIPCK(launch_convert(src->feats, src->pol.f32, dst->feats, dst->pol.f32, M * a.vit_width, s));
-    dst->cur_B = src->cur_B; dst->cur_F = src->cur_F; dst->cur_Nimg = src->cur_Nimg;
-    dst->have_feats = true; dst->have_prefill = false;
+    set_resident(dst, src->cur_B, src->cur_F);      // src->N == dst->N: the same cur_Nimg
     if (stage == 2) {
         for (int l = 0; l < a.dec_layers; ++l) {
             HIPCK(launch_convert(src->img_kv[l], src->pol.f32, dst->img_kv[l], dst->pol.f32, M * 3 * a.dec_hidden, s));
             RCK(kv_repack(dst, l, dst->cur_B, dst->cur_Nimg, s));
         }
-        dst->have_prefill = true;
+        set_prefilled(dst);
     }
     return 0;
 }

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -57,16 +58,36 @@ struct GraphKey {
     int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident; double lp;
     int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
     // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds
-    static GraphKey of(int B, int Q, int F, int P, int H, int W, bool prefixed, bool ident, bool temb, bool resident,
-                       const gitmi_search& sp) {
-        return {B, Q, F, P, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, H, W, prefixed ? 1 : 0, ident ? 1 : 0,
-                temb ? 1 : 0, resident ? 1 : 0, sp.length_penalty, sp.do_sample, sp.top_k, keep_best(sp), sp.top_p,
-                sp.temperature, sp.repetition_penalty, sp.seed};
-    }
     auto fields() const {
         return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, lp, smp, top_k, nh, top_p, temp, rp, seed);
     }
     bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
+};
+struct GraphSlot { GraphKey key{}; bool valid = false; };
+
+// one captured launch sequence: the hipGraph of a stream capture and its executable
+struct CapturedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    void reset() {
+        if (exec) hipGraphExecDestroy(exec);
+        if (graph) hipGraphDestroy(graph);
+        exec = nullptr, graph = nullptr;
+    }
+    // replaces the graph by what fn() enqueues on `s` (engine.hip); on a failure of fn or of the capture the slot is left empty
+    int capture(hipStream_t s, const std::function<int()>& fn);
+    hipError_t launch(hipStream_t s) const { return hipGraphLaunch(exec, s); }
+};
+
+// what one gitmi_generate / gitmi_generate_prefixed call is (built once by the entry point; the capture paths pass a copy
+// whose frames and outputs are the engine's own buffers).  start_dev / plen_dev / img_of_dev describe the Q sentences.
+struct Request {
+    const float* const* frames;         // F frames of B images, or nullptr: a follow-up call over the resident images
+    int F, B, Q, minP, maxP;            // Q sentences with prefix lengths in [minP, maxP]
+    bool prefixed;
+    const gitmi_search* sp;
+    long long* tokens; float* logprob; int32_t* info;
+    int32_t* sent;                      // the caller's buffer, or e->out_sent
 };
 
 // packed weights on the device: produced by gitmi_finalize_weights, borrowed (the same pointers) by every clone
@@ -185,9 +206,6 @@ struct gitmi_engine {
     //                (what the production path costs: no per-launch host work, no event records inside the chain)
     int profile_mode = 0;
     bool profiling = false;             // profile_mode == 1
-    hipGraph_t graph_b = nullptr;
-    hipGraphExec_t graph_exec_b = nullptr;
-    bool graph_is_split = false;
     // LayerNorm folding (pol.ln_fold): row partials (sum, sumsq) per 256-column tile: [rows][4], ping-pong for the
     // post-norm prefill (a producer tile reads the previous partials of a row while another tile writes the new ones)
     float2 *v_part = nullptr, *p_part[2] = {nullptr, nullptr};
@@ -204,17 +222,13 @@ struct gitmi_engine {
     size_t event_next = 0;
     double last_decode_step_bytes = 0;
 
-    // hipGraph cache for gitmi_generate
-    bool graph_valid = false;
-    GraphKey graph_key{};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    // ... and the slot beside it for follow-up calls: the decode part alone (GraphKey::resident), so that full and follow-up
-    // calls with unchanged arguments alternate without re-capturing either
-    bool graph_r_valid = false;
-    GraphKey graph_r_key{};
-    hipGraph_t graph_r = nullptr;
-    hipGraphExec_t graph_exec_r = nullptr;
+    // hipGraph cache for gitmi_generate: a full call replays graph_full (the whole call) or, when something has to happen
+    // between the two (graph_is_split), graph_full (encode + prefill) and graph_decode; both belong to full_slot.  A
+    // follow-up call replays graph_follow (the decode part alone, GraphKey::resident) of follow_slot, so that full and
+    // follow-up calls with unchanged arguments alternate without re-capturing either
+    CapturedGraph graph_full, graph_decode, graph_follow;
+    GraphSlot full_slot, follow_slot;
+    bool graph_is_split = false;
     std::vector<float*> frame_stage;   // engine-owned copies of the input frames (graph inputs)
     long long* out_tokens = nullptr;   // graph outputs, copied to the caller's buffers after the launch
     float* out_lp = nullptr;
