@@ -329,6 +329,29 @@ GITMI_EXP_EXPORT int gitmi_debug_score_attn(const void* qkv, const void* img_kv,
                             (hipStream_t)stream));
     return 0;
 }
+// attention map of one layer: the attention launch with its statistics, then the map kernel -> out fp32 [Q][Lp][N_img + Lp]
+// (ntok: int32 [B] on the device, the image keys of every image, or NULL).  Synchronises the stream.
+GITMI_EXP_EXPORT int gitmi_debug_score_attn_map(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, float* out,
+                                                int Q, int H, int N_img, int Lp, int dtype, void* stream) {
+    if (!qkv || !img_kv || !image_of || !out || Q < 1 || H < 1 || N_img < 1 || Lp < 1) return fail("debug_score_attn_map: bad argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_attn_map: dtype %d not served by this build", dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const bool f32 = dtype == GITMI_DTYPE_F32;
+    const int d = H * 64, Kc = N_img + Lp;
+    void* ctx = nullptr; float2* stats = nullptr;
+    auto body = [&]() -> int {
+        HIPCK(hipMalloc(&ctx, (size_t)Q * Lp * d * (f32 ? 4 : 2)));
+        HIPCK(hipMalloc(&stats, (size_t)Q * H * Lp * sizeof(float2)));
+        HIPCK(launch_score_attn(qkv, img_kv, image_of, ctx, Q, H, d, N_img, Lp, 0.125f, f32, s, ntok, stats));
+        HIPCK(launch_score_attn_map(qkv, img_kv, image_of, ntok, stats, nullptr, out, (size_t)Lp * Kc, (size_t)Kc, Lp, Q, H, N_img, Lp,
+                                    0.125f, f32, nullptr, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(ctx); hipFree(stats);
+    return rc;
+}
 // head + combine: logits z = A [M][K] W [V][K]^T + bias (never stored in the 16-bit form) -> out fp32 [M][2] =
 // (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) for rows with tgt[m] >= 0, 0 elsewhere.  Synchronises the stream.
 GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K,

@@ -290,6 +290,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->sc_allocs) hipFree(p);
+    hipFree(e->at_out); hipFree(e->at_stats);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -886,6 +887,7 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (B < 1 || B > e->cfg.max_batch || ld < 1 || ld > e->cfg.max_text_len) return fail("%s: bad B/P", who);
     if (vocab < 2) return fail("%s: bad vocab", who);
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("%s: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)", who);
+    if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("%s: GITMI_SEARCH_ATTEND is not a search (gitmi_generate_prefixed returns the attention maps of sentences)", who);
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1185,6 +1187,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     RCK(check_ready(e));
     const gitmi_config& c = e->cfg;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("generate: GITMI_SEARCH_ATTEND maps given sentences: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1286,7 +1289,71 @@ static int score_impl(gitmi_engine* e, const Request& rq, const long long* token
     return 0;
 }
 
-// Sentence tables of gitmi_generate_prefixed (both kinds): read_sentences checks Q <= Qmax (`cap` names it), lengths in
+// ---- attention maps (GITMI_SEARCH_ATTEND) --------------------------------------------------------------------------------
+// The output [Q, ld, layers, Kc] and one layer's statistics [Q, heads, Lp]: allocated by the first attend call, grown when a
+// later call needs more (engines that never attend keep their footprint).  The text pass itself runs in score_alloc's workspaces.
+static int attend_alloc(gitmi_engine* e, size_t floats, size_t stat_rows) {
+    if (e->at_floats < floats) {
+        hipFree(e->at_out);
+        e->at_out = nullptr; e->at_floats = 0;
+        if (hipMalloc(&e->at_out, floats * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("attend: out of device memory for the %zu floats of the maps", floats);
+        }
+        e->at_floats = floats;
+    }
+    if (e->at_stat_rows < stat_rows) {
+        hipFree(e->at_stats);
+        e->at_stats = nullptr; e->at_stat_rows = 0;
+        if (hipMalloc(&e->at_stats, stat_rows * sizeof(float2)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("attend: out of device memory for the softmax statistics of %zu rows", stat_rows);
+        }
+        e->at_stat_rows = stat_rows;
+    }
+    return 0;
+}
+// image key rows of one image in a call: what an encode of these frames makes resident, or what is
+static int call_Nimg(const gitmi_engine* e, const float* const* frames, int F) {
+    if (!frames) return e->cur_Nimg;
+    return (e->cfg.num_frames > 0 ? std::min(F, (int)e->cfg.num_frames) : F) * e->N;
+}
+
+// score_impl's text pass with the probabilities kept instead of the vocabulary head: every layer's attention launch also
+// writes its softmax statistics, and the map kernel turns them into the head-mean probabilities of that layer's slice of
+// at_out [Q, ld, layers, Kc] (zero-filled: rows past a sentence's length, text columns past a row, image columns past a
+// ragged image's own rows stay 0).  The last layer stops after its attention: nothing reads its output.
+static int attend_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    const int d = c.dec_hidden, V = c.vocab, Q = rq.Q, L = c.dec_layers;
+    if (rq.frames) RCK(generate_encode(e, rq, s));
+    else if (!e->have_prefill) RCK(prefill_impl(e, s));     // follow-up call: the resident images' K/V
+    const int Lp = round_up(rq.maxP, 16), M = Q * Lp;
+    const int Nk = e->cur_Nimg, Kc = Nk + ld;
+    const size_t total = (size_t)Q * ld * L * Kc;
+    SpanGuard phase(e, s, TAG_DECODE, 0);
+    HIPCK(hipMemsetAsync(e->at_out, 0, total * sizeof(float), s));
+    HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
+    HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
+                                e->pol.f32, d, V, c.max_pos, s));
+    const int* ntok = e->ragged ? e->rg_ntok : nullptr;
+    for (int l = 0; l < L; ++l) {
+        const DecLayerW& W = e->w.dec[l];
+        RCK(gemm(e, s, e->sc_ht, d, W.wqkv, W.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
+        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, Nk, Lp, 0.125f, e->pol.f32, s, ntok,
+                                e->at_stats));
+        HIPCK(launch_score_attn_map(e->sc_qkv, e->img_kv[l], e->sc_img, ntok, e->at_stats, e->sc_lens, e->at_out + (size_t)l * Kc,
+                                    (size_t)ld * L * Kc, (size_t)L * Kc, ld, Q, c.dec_heads, Nk, Lp, 0.125f, e->pol.f32, e->sc_bad, s));
+        if (l + 1 < L) RCK(dec_layer_tail(e, s, W, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
+    }
+    if (e->ragged) HIPCK(launch_ragged_report(e->rg_meta, e->sc_img, Q, 0, nullptr, nullptr, e->sc_bad, s));
+    HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s, Kc, L));
+    HIPCK(hipMemcpyAsync(rq.logprob, e->at_out, total * sizeof(float), hipMemcpyDefault, s));
+    HIPCK(hipMemcpyAsync(rq.info, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
+    return 0;
+}
+
+// Sentence tables of gitmi_generate_prefixed (every kind): read_sentences checks Q <= Qmax (`cap` names it), lengths in
 // [1, ld] and images in [0, B) into plen_host / img_of_host; upload_sentences copies them to the caller's device tables.
 struct SentenceSpan { int minP, maxP; bool ident; };
 static int read_sentences(gitmi_engine* e, const char* who, const int32_t* plen, const int32_t* image_of, int ld, int B, int Q,
@@ -1325,19 +1392,26 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     const gitmi_config& c = e->cfg;
     hipStream_t s = (hipStream_t)stream;
     SentenceSpan span;
-    if (sp && sp->kind == GITMI_SEARCH_SCORE) {
-        if (!frames) RCK(check_resident(e, "score", B));
-        if (!logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("score: null argument");
-        if (frames) RCK(check_frames(e, "score", frames, F, B));
-        if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("score: ld=%d outside [1,%d] (max_text_len)", ld_prefix, c.max_text_len);
-        RCK(read_sentences(e, "score", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch * c.max_beams,
+    if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND)) {
+        const bool attend = sp->kind == GITMI_SEARCH_ATTEND;
+        const char* who = attend ? "attend" : "score";
+        if (!frames) RCK(check_resident(e, who, B));
+        if (!logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("%s: null argument", who);
+        if (frames) RCK(check_frames(e, who, frames, F, B));
+        if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("%s: ld=%d outside [1,%d] (max_text_len)", who, ld_prefix, c.max_text_len);
+        RCK(read_sentences(e, who, prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch * c.max_beams,
                            "max_batch x max_beams", &span));
-        RCK(score_alloc(e, (size_t)Q * round_up(span.maxP, 16)));
+        const int Lp = round_up(span.maxP, 16);
+        RCK(score_alloc(e, (size_t)Q * Lp));
+        if (attend)
+            RCK(attend_alloc(e, (size_t)Q * ld_prefix * c.dec_layers * (call_Nimg(e, frames, F) + ld_prefix),
+                             (size_t)Q * c.dec_heads * Lp));
         RCK(upload_sentences(e, e->sc_lens, e->sc_img, s));
         if (frames) RCK(ragged_prepare(e, frames, F, B, s));
-        // the sentences are whole captions of lengths [minP, maxP]; logprob_out receives (lp, mean_lp) per position
+        // the sentences are whole captions of lengths [minP, maxP]; logprob_out receives (lp, mean_lp) per position, or the maps
         const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, nullptr, logprob_out, info_out, e->out_sent};
-        return settle_residency(e, rq, score_impl(e, rq, (const long long*)prefixes, ld_prefix, s));
+        const long long* tokens = (const long long*)prefixes;
+        return settle_residency(e, rq, attend ? attend_impl(e, rq, tokens, ld_prefix, s) : score_impl(e, rq, tokens, ld_prefix, s));
     }
     if (!frames) RCK(check_resident(e, "generate_prefixed", B));
     if (!sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)

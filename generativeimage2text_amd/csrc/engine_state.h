@@ -246,6 +246,11 @@ struct gitmi_engine {
     float4* sc_part = nullptr;
     int *sc_tgt = nullptr, *sc_lens = nullptr, *sc_img = nullptr, *sc_bad = nullptr, *sc_info = nullptr;
     float2* sc_out = nullptr;
+    // attention maps (GITMI_SEARCH_ATTEND): the softmax statistics of one layer's text rows and the [Q, ld, layers, Kc] output,
+    // allocated by the first attend call and grown on demand (attend_alloc)
+    size_t at_floats = 0, at_stat_rows = 0;
+    float* at_out = nullptr;
+    float2* at_stats = nullptr;
 };
 
 namespace gitmi {

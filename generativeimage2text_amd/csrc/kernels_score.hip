@@ -11,6 +11,9 @@
 //                          (row, 128-column tile) and z at the row's target column -- the logits never reach HBM
 //   score_rowstats_kernel  the same statistics from materialised fp32 logits (f32 parity mode)
 //   score_combine_kernel   tiles -> (lp, mean_lp) per position, non-finite flags per sentence
+// Attention maps (GITMI_SEARCH_ATTEND): the two attention kernels also write the softmax statistics (m, l) of every (sentence,
+// head, text row); score_attn_map_mfma_kernel / score_attn_map_kernel recompute S per key chunk and write the head mean of
+// exp(s - m) / l.  Score calls instantiate the attention kernels without the statistics store: their results are what they were.
 #include "gitmi_common.h"
 #include "launchers.h"
 
@@ -121,10 +124,12 @@ __device__ __forceinline__ void ld8(const bf16_t* p, float* o) {
     unpack2op(u.w, o[6], o[7]);
 }
 
-template <typename T>
+// STATS: also stats[(q * H + h) * Lp + j] = (m, l), the row's score maximum and sum of exp(s - m) over its visible keys
+template <typename T, bool STATS>
 __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ img_kv,
                                                         const int* __restrict__ image_of, T* __restrict__ out, int d,
-                                                        int N_img, int Lp, float scale, const int* __restrict__ ntok) {
+                                                        int N_img, int Lp, float scale, const int* __restrict__ ntok,
+                                                        float2* __restrict__ stats) {
     __shared__ float sK[SA_KC][64];
     __shared__ float sV[SA_KC][64];
     const int lane = threadIdx.x;
@@ -215,6 +220,7 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
         }
     }
     if (j >= Lp) return;
+    if constexpr (STATS) stats[((size_t)q * gridDim.y + h) * Lp + j] = make_float2(m, l);
     const float inv = 1.0f / l;
     T* op = out + (row_base + j) * d + h * 64;
     if constexpr (sizeof(T) == 4) {
@@ -242,10 +248,11 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
 constexpr int SM_KB = 32;                 // keys per block
 constexpr int SM_KP = 64 + 8;             // padded LDS row of sK (elements)
 constexpr int SM_VP = SM_KB + 8;          // padded LDS row of sVt / sP
+template <bool STATS>
 __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ img_kv,
                                                               const int* __restrict__ image_of, bf16_t* __restrict__ out,
                                                               int d, int N_img, int Lp, float scale,
-                                                              const int* __restrict__ ntok) {
+                                                              const int* __restrict__ ntok, float2* __restrict__ stats) {
     __shared__ __attribute__((aligned(16))) bf16_t sK[SM_KB][SM_KP];
     __shared__ __attribute__((aligned(16))) bf16_t sVt[64][SM_VP];
     __shared__ __attribute__((aligned(16))) bf16_t sP[4][16][SM_VP];
@@ -333,6 +340,8 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
     for (int i = 0; i < 4; ++i) {
         const int j = jw + 4 * g + i;
         if (j >= Lp) continue;
+        if constexpr (STATS)
+            if (c == 0) stats[((size_t)q * gridDim.y + h) * Lp + j] = make_float2(m[i], l[i]);
         const float inv = 1.0f / l[i];
         bf16_t* op = out + (row_base + j) * d + h * 64 + c;
 #pragma unroll
@@ -341,15 +350,195 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
 }
 
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
-                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok) {
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok, float2* stats) {
     if (d != H * 64 || Q < 1 || Lp < 1 || N_img < 1) return hipErrorInvalidValue;
     const dim3 grid(Q, H, (Lp + 63) / 64);
+    if (is_f32) {
+        const auto k = stats ? score_attn_kernel<float, true> : score_attn_kernel<float, false>;
+        hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const float*)qkv, (const float*)img_kv, image_of, (float*)out, d, N_img, Lp,
+                           scale, ntok, stats);
+    } else {
+        const auto k = stats ? score_attn_mfma_kernel<true> : score_attn_mfma_kernel<false>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv, image_of, (bf16_t*)out, d, N_img,
+                           Lp, scale, ntok, stats);
+    }
+    return hipGetLastError();
+}
+
+// ---- attention maps ------------------------------------------------------------------------------------------------
+// out[q][j][col] = (1 / H) sum_h exp(s_h(j, col) - m_h(j)) / l_h(j) for the text rows j < len_q of sentence q: columns
+// [0, N_img) are the image keys of image_of[q] (0 past the image's own ntok rows), columns N_img + t its text keys (0 for
+// t > j).  A workgroup owns (sentence, 16 text rows, AM_COLS columns) and loops over the heads with the head sum in
+// registers: every element is written once, by one thread, in a fixed order of additions -- no atomics, and the value does
+// not depend on the grid.  s is recomputed exactly as the attention kernel of the same mode computes it (the same MFMA
+// sequence / the same fused multiply-add chain), so that m is the maximum of the very values exponentiated here.
+// Rows j >= len_q and columns >= N_img + Tc are not written (the caller's buffer is zero-filled).
+constexpr int AM_ROWS = 16, AM_COLS = 128;
+
+// the key row behind an output column and whether it is a key of this sentence at all (clamped to a readable row if not)
+template <typename T>
+__device__ __forceinline__ const T* map_key_row(const T* qkv, const T* img_kv, size_t row_base, int img, int n_i, int N_img,
+                                                int Lp, int ld3, int col, bool* live) {
+    if (col < N_img) {
+        *live = col < n_i;
+        return img_kv + ((size_t)img * N_img + (*live ? col : 0)) * ld3;
+    }
+    const int t = col - N_img;
+    *live = t < Lp;
+    return qkv + (row_base + (*live ? t : 0)) * ld3;
+}
+
+// 16-bit modes.  4 waves; wave w owns columns col0 + 32 w .. + 32 as two 16-column MFMA blocks.  Q rows (A operand) and key
+// rows (B operand) are loaded straight from global memory in operand order, 16 bytes per lane and fragment.
+__global__ __launch_bounds__(256) void score_attn_map_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ img_kv,
+                                                                  const int* __restrict__ image_of, const int* __restrict__ ntok,
+                                                                  const float2* __restrict__ stats, const int* __restrict__ lens,
+                                                                  float* __restrict__ out, size_t out_sq, size_t out_sj, int Tc,
+                                                                  int H, int N_img, int Lp, float scale, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x, j0 = blockIdx.y * AM_ROWS, col0 = blockIdx.z * AM_COLS + wave * 32;
+    const int g = lane >> 4, c = lane & 15;
+    const int len = lens ? min(lens[q], Lp) : Lp;
+    const int Kc = N_img + Tc;
+    if (j0 >= len || col0 >= Kc) return;
+    const int d = H * 64, ld3 = 3 * d;
+    const size_t row_base = (size_t)q * Lp;
+    const int img = image_of[q];
+    const int n_i = ntok ? ntok[img] : N_img;
+    const bf16_t* kp[2];
+    bool live[2];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+        kp[blk] = map_key_row(qkv, img_kv, row_base, img, n_i, N_img, Lp, ld3, col0 + blk * 16 + c, &live[blk]) + d + 8 * g;
+    const bf16_t* qp = qkv + (row_base + min(j0 + c, Lp - 1)) * ld3 + 8 * g;          // A operand: row = query j0 + c
+    float acc[2][4];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[blk][i] = 0.f;
+    for (int h = 0; h < H; ++h) {
+        const bf16x8_t q0 = *reinterpret_cast<const bf16x8_t*>(qp + h * 64), q1 = *reinterpret_cast<const bf16x8_t*>(qp + h * 64 + 32);
+        f32x4_t sfr[2];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const bf16x8_t b0 = *reinterpret_cast<const bf16x8_t*>(kp[blk] + h * 64);
+            const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t*>(kp[blk] + h * 64 + 32);
+            sfr[blk] = mfma16(q0, b0, f32x4_t{0.f, 0.f, 0.f, 0.f});
+            sfr[blk] = mfma16(q1, b1, sfr[blk]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = j0 + 4 * g + i;                                              // query row of this lane's element i
+            const float2 ml = stats[((size_t)q * H + h) * Lp + min(j, Lp - 1)];
+            const float inv = 1.0f / ml.y;
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk) {
+                const int col = col0 + blk * 16 + c;
+                const bool ok = live[blk] && (col < N_img || col - N_img <= j);
+                if (ok) acc[blk][i] += __expf(sfr[blk][i] * scale - ml.x) * inv;
+            }
+        }
+    }
+    const float invH = 1.0f / (float)H;
+    bool nonfinite = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = j0 + 4 * g + i;
+        if (j >= len) continue;
+        float* op = out + (size_t)q * out_sq + (size_t)j * out_sj;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const int col = col0 + blk * 16 + c;
+            if (col >= Kc) continue;
+            const float v = acc[blk][i] * invH;
+            op[col] = v;
+            nonfinite = nonfinite || !isfinite(v);
+        }
+    }
+    if (nonfinite && bad) bad[q] = 1;
+}
+
+// f32 mode.  Thread = one column, its key row of the head in registers; the 16 query rows of the head (scaled, as the
+// attention kernel scales them) and their statistics in LDS, read by every thread at the same address (broadcast).
+__global__ __launch_bounds__(AM_COLS) void score_attn_map_kernel(const float* __restrict__ qkv, const float* __restrict__ img_kv,
+                                                                 const int* __restrict__ image_of, const int* __restrict__ ntok,
+                                                                 const float2* __restrict__ stats, const int* __restrict__ lens,
+                                                                 float* __restrict__ out, size_t out_sq, size_t out_sj, int Tc,
+                                                                 int H, int N_img, int Lp, float scale, int* __restrict__ bad) {
+    __shared__ __attribute__((aligned(16))) float sQ[AM_ROWS][64];
+    __shared__ float2 sMl[AM_ROWS];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x, j0 = blockIdx.y * AM_ROWS, col = blockIdx.z * AM_COLS + tid;
+    const int len = lens ? min(lens[q], Lp) : Lp;
+    const int Kc = N_img + Tc;
+    if (j0 >= len) return;                                                             // the whole workgroup
+    const int d = H * 64, ld3 = 3 * d;
+    const size_t row_base = (size_t)q * Lp;
+    const int img = image_of[q];
+    const int n_i = ntok ? ntok[img] : N_img;
+    bool live;
+    const float* kp = map_key_row(qkv, img_kv, row_base, img, n_i, N_img, Lp, ld3, min(col, Kc - 1), &live) + d;
+    live = live && col < Kc;
+    const int sr = tid >> 3, sc = (tid & 7) * 8;                                       // staging: row sr, dims sc .. sc + 8
+    float acc[AM_ROWS];
+#pragma unroll
+    for (int r = 0; r < AM_ROWS; ++r) acc[r] = 0.f;
+    for (int h = 0; h < H; ++h) {
+        __syncthreads();
+        {
+            float t8[8];
+            ld8(qkv + (row_base + min(j0 + sr, Lp - 1)) * ld3 + h * 64 + sc, t8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sQ[sr][sc + i] = t8[i] * scale;
+            if (tid < AM_ROWS) {
+                const float2 ml = stats[((size_t)q * H + h) * Lp + min(j0 + tid, Lp - 1)];
+                sMl[tid] = make_float2(ml.x, 1.0f / ml.y);
+            }
+        }
+        __syncthreads();
+        float kv[64];
+#pragma unroll
+        for (int c = 0; c < 64; c += 8) ld8(kp + h * 64 + c, &kv[c]);
+#pragma unroll 4
+        for (int r = 0; r < AM_ROWS; ++r) {
+            float sdot = 0.f;
+#pragma unroll
+            for (int c = 0; c < 64; c += 4) {
+                const f32x4_t q4 = *reinterpret_cast<const f32x4_t*>(&sQ[r][c]);
+                sdot = fmaf(q4[0], kv[c], sdot);
+                sdot = fmaf(q4[1], kv[c + 1], sdot);
+                sdot = fmaf(q4[2], kv[c + 2], sdot);
+                sdot = fmaf(q4[3], kv[c + 3], sdot);
+            }
+            const bool ok = live && (col < N_img || col - N_img <= j0 + r);
+            if (ok) acc[r] += __expf(sdot - sMl[r].x) * sMl[r].y;
+        }
+    }
+    if (col >= Kc) return;
+    const float invH = 1.0f / (float)H;
+    bool nonfinite = false;
+#pragma unroll
+    for (int r = 0; r < AM_ROWS; ++r) {
+        const int j = j0 + r;
+        if (j >= len) break;
+        const float v = acc[r] * invH;
+        out[(size_t)q * out_sq + (size_t)j * out_sj + col] = v;
+        nonfinite = nonfinite || !isfinite(v);
+    }
+    if (nonfinite && bad) bad[q] = 1;
+}
+
+hipError_t launch_score_attn_map(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, const float2* stats,
+                                 const int* lens, float* out, size_t out_sq, size_t out_sj, int Tc, int Q, int H, int N_img,
+                                 int Lp, float scale, bool is_f32, int* bad, hipStream_t s) {
+    if (Q < 1 || H < 1 || Lp < 1 || N_img < 1 || Tc < 1 || !stats || !out) return hipErrorInvalidValue;
+    const dim3 grid(Q, (Lp + AM_ROWS - 1) / AM_ROWS, (N_img + Tc + AM_COLS - 1) / AM_COLS);
     if (is_f32)
-        hipLaunchKernelGGL(score_attn_kernel<float>, grid, dim3(64), 0, s, (const float*)qkv, (const float*)img_kv, image_of,
-                           (float*)out, d, N_img, Lp, scale, ntok);
+        hipLaunchKernelGGL(score_attn_map_kernel, grid, dim3(AM_COLS), 0, s, (const float*)qkv, (const float*)img_kv, image_of, ntok,
+                           stats, lens, out, out_sq, out_sj, Tc, H, N_img, Lp, scale, bad);
     else
-        hipLaunchKernelGGL(score_attn_mfma_kernel, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv,
-                           image_of, (bf16_t*)out, d, N_img, Lp, scale, ntok);
+        hipLaunchKernelGGL(score_attn_map_mfma_kernel, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv, image_of,
+                           ntok, stats, lens, out, out_sq, out_sj, Tc, H, N_img, Lp, scale, bad);
     return hipGetLastError();
 }
 
@@ -533,8 +722,8 @@ hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt,
     return hipGetLastError();
 }
 
-// info = {ld, 0, 0, sentences with a non-finite value}
-__global__ void score_info_kernel(const int* __restrict__ bad, int Q, int ld, int* __restrict__ info) {
+// info = {ld, i1, i2, sentences with a non-finite value} (score: i1 = i2 = 0; attention maps: Kc, layers)
+__global__ void score_info_kernel(const int* __restrict__ bad, int Q, int ld, int i1, int i2, int* __restrict__ info) {
     __shared__ int s_n;
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
@@ -542,11 +731,11 @@ __global__ void score_info_kernel(const int* __restrict__ bad, int Q, int ld, in
     for (int q = threadIdx.x; q < Q; q += blockDim.x) n += bad[q] ? 1 : 0;
     atomicAdd(&s_n, n);
     __syncthreads();
-    if (threadIdx.x == 0) { info[0] = ld; info[1] = 0; info[2] = 0; info[3] = s_n; }
+    if (threadIdx.x == 0) { info[0] = ld; info[1] = i1; info[2] = i2; info[3] = s_n; }
 }
 
-hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s) {
-    hipLaunchKernelGGL(score_info_kernel, dim3(1), dim3(256), 0, s, bad, Q, ld, info);
+hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s, int i1, int i2) {
+    hipLaunchKernelGGL(score_info_kernel, dim3(1), dim3(256), 0, s, bad, Q, ld, i1, i2, info);
     return hipGetLastError();
 }
 

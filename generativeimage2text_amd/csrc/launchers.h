@@ -231,8 +231,16 @@ hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp,
                                  int D, int vocab, int max_pos, hipStream_t s);
 // qkv [Q * Lp][3d] text rows, img_kv [B * N_img][3d] prefill rows of the same layer, image_of [Q] -> out [Q * Lp][d]
 // ntok (ragged batches): image keys of every image (<= N_img, the row stride of an image's block); nullptr: N_img each
+// stats (attention maps; nullptr: none, the score call's kernels): fp32 [Q][H][Lp] = (m, l), the softmax statistics of every row
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
-                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok = nullptr);
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok = nullptr,
+                             float2* stats = nullptr);
+// attention map of one layer from launch_score_attn's operands and stats: out[q * out_sq + j * out_sj + col] = head mean of the
+// probability text row (q, j) gives column col -- [0, N_img) the image keys of image_of[q] (0 past ntok), N_img + t (t < Tc) its
+// text keys (0 for t > j).  Rows j >= lens[q] (nullptr: Lp rows each) are not written; bad[q] = 1 on a non-finite value (or nullptr).
+hipError_t launch_score_attn_map(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, const float2* stats,
+                                 const int* lens, float* out, size_t out_sq, size_t out_sj, int Tc, int Q, int H, int N_img,
+                                 int Lp, float scale, bool is_f32, int* bad, hipStream_t s);
 int score_head_tiles(int V);      // 128-column tiles of the fused head
 // part [M][score_head_tiles(V)] = (max, sum exp, sum z), zt [M] = z at tgt[row] (tgt < 0: none); 16-bit A [M][lda], W [V][K]
 hipError_t launch_score_head(const void* A, int lda, const void* W, const float* bias, const int* tgt, int M, int V, int K,
@@ -243,7 +251,7 @@ hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const i
                                 hipStream_t s);
 hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt, const int* tgt, int M, int Lp, int ld, int V,
                                 float2* out, int* bad, hipStream_t s);
-hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s);
+hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s, int i1 = 0, int i2 = 0);   // info = {ld, i1, i2, bad}
 
 // GPU image transform (Pillow-exact bicubic resize + centre crop + CLIP normalisation)
 hipError_t launch_preprocess(const unsigned char* rgb, int H, int W, int crop, unsigned char* tmp, float* out, hipStream_t s);

@@ -22,6 +22,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 DTYPE_F16_STREAM = 3      # gitmi_op_gemm's out_dtype only: fp16 residual-stream rows, fp16 residual rows in
 SEARCH_AUTOREGRESSIVE, SEARCH_GENERATOR, SEARCH_TRIE = 0, 1, 2
 SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given sentences (Engine.score)
+SEARCH_ATTEND = 4    # not a search: gitmi_generate_prefixed returns the attention maps of given sentences (Engine.attend)
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
 
 EXPORTED_SYMBOLS = [
@@ -41,7 +42,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
-    "gitmi_debug_layernorm_map",
+    "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map",
 ]
 
 
@@ -149,6 +150,7 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_set_dgemm.argtypes = [i32]
         lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        lib.gitmi_debug_score_attn_map.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attention_ragged.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_vocab_topm_rules.argtypes = [vp, vp, vp, vp, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32,
@@ -350,6 +352,8 @@ class Engine:
     def _init_resident(self) -> None:
         self._resident: Optional[int] = None
         self._generation = 0
+        # (Nk image key rows per image, F frames, [(grid h, grid w)] per image): of the resident set / of the frames of this call
+        self._geometry = self._call_geometry = None
 
     @property
     def resident(self) -> Optional[int]:
@@ -364,6 +368,13 @@ class Engine:
         images it was issued for are still the ones this context holds (model.Pending)."""
         return self._generation
 
+    @property
+    def resident_geometry(self):
+        """(Nk, F, [(grid rows, grid columns)] per image) of the resident images, or None: Nk image key rows per image (the
+        image columns of Engine.attend), F frames of grid_h * grid_w + 1 tokens each (ragged input: F = 1, every image its own
+        grid inside its max_tokens rows)."""
+        return self._geometry if self._resident is not None else None
+
     def _drop_resident(self) -> None:
         self._resident = None
         self._generation += 1
@@ -376,6 +387,7 @@ class Engine:
         self._generation += 1
         if rc == 0:
             self._resident = int(B)
+            self._geometry = self._call_geometry
             return
         msg = (self.lib.gitmi_last_error() or b"").decode("utf-8", "replace")
         if old is not None:
@@ -460,6 +472,8 @@ class Engine:
                 self._hw = (0, 0)
                 self.n_tok = self.max_tokens
                 self._drop_resident()
+            p = int(self.c.patch)
+            self._call_geometry = (self.max_tokens, 1, [(h // p, w // p) for h, w in frames.shapes])
             buf = frames.buffer
             if buf.device != torch.device(f"cuda:{self.device}") or buf.dtype != torch.float32:
                 raise ValueError("a ragged input buffer must be fp32 on the engine's device (Engine.pack_images)")
@@ -469,6 +483,8 @@ class Engine:
         for f in keep:
             assert f.shape == (B, 3, H, W), f"frame shape {tuple(f.shape)}: all frames of a call share one resolution"
         self.set_image_shape(H, W)
+        F_eff = min(len(keep), self.c.num_frames) if self.c.num_frames > 0 else len(keep)
+        self._call_geometry = (F_eff * self.n_tok, F_eff, [(H // self.c.patch, W // self.c.patch)] * B)
         arr = (C.c_void_p * len(keep))(*[f.data_ptr() for f in keep])
         return arr, keep, B
 
@@ -604,6 +620,32 @@ class Engine:
         -> fp32 [Q, L, 2] on the device: (lp, mean_lp) at position j = (log_softmax(z)[tokens[q, j]],
         mean_c log_softmax(z)[c]) with z the logits at position j - 1; position 0 and positions >= length are 0.
         frames None: a follow-up call -- the sentences are scored over the resident images, nothing is encoded."""
+        arr, keep, B, tok, lens = self._sentence_args(frames, tokens, lengths, image_of)
+        Q, L = tok.shape
+        out = self._empty((Q, L, 2), torch.float32, tok.device)
+        self._sentence_call(SEARCH_SCORE, frames, arr, keep, B, tok, lens, image_of, out)
+        return out
+
+    def attend(self, frames: Optional[Sequence[torch.Tensor]], tokens, lengths: Optional[Sequence[int]] = None,
+               image_of: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Where every token of given sentences looked (include/gitmi.h GITMI_SEARCH_ATTEND): the attention probabilities of
+        the text rows of every decoder layer over [image tokens | text], averaged over the heads.  Arguments and checks as
+        for score.
+        -> fp32 [Q, L, layers, Kc] on the device, Kc = Nk + L: columns [0, Nk) the image tokens of the sentence's image in
+        prefill order (frame-major, class token first; Nk = F * n_tok, or max_tokens in ragged mode), column Nk + t text
+        position t.  Rows j >= length, text columns t > j and (ragged) image columns past the image's own tokens are 0.
+        frames None: a follow-up call over the resident images, nothing is encoded."""
+        arr, keep, B, tok, lens = self._sentence_args(frames, tokens, lengths, image_of)
+        Q, L = tok.shape
+        geometry = self._geometry if frames is None else self._call_geometry
+        Nk = geometry[0] if geometry else 0              # no resident images: the library refuses the call by name
+        out = self._empty((Q, L, int(self.c.dec_layers), Nk + L), torch.float32, tok.device)
+        self._sentence_call(SEARCH_ATTEND, frames, arr, keep, B, tok, lens, image_of, out)
+        return out
+
+    def _sentence_args(self, frames, tokens, lengths, image_of):
+        """The argument checks score and attend share -> (frames argument, tensors to keep alive, B, tokens int64 [Q, L] on the
+        device with zeros past every length, lengths)."""
         arr, keep, B = self._frames_arg(frames)
         dev = torch.device(f"cuda:{self.device}")
         tok = torch.as_tensor(tokens).detach().to("cpu", torch.int64)
@@ -626,14 +668,17 @@ class Engine:
             raise ValueError(f"{Q} sentences over {B} images: image_of is required")
         if image_of is not None and len(image_of) != Q:
             raise ValueError(f"image_of has {len(image_of)} entries for {Q} sentences")
-        out = self._empty((Q, L, 2), torch.float32, dev)
-        info = self._empty(4, torch.int32, dev)
+        return arr, keep, B, tok, lens
+
+    def _sentence_call(self, kind: int, frames, arr, keep, B: int, tok: torch.Tensor, lens, image_of, out: torch.Tensor) -> None:
+        """gitmi_generate_prefixed with a kind that is not a search (score, attend): `out` is its logprob_out."""
+        Q, L = tok.shape
+        info = self._empty(4, torch.int32, tok.device)
         search = GitmiSearch()
-        search.kind = SEARCH_SCORE
+        search.kind = kind
         self._done(self._call(frames, self.lib.gitmi_generate_prefixed(
             self._h, arr, len(keep), B, tok.data_ptr(), L, *_sentence_tables(lens, image_of), Q, C.byref(search), None,
             out.data_ptr(), None, info.data_ptr(), _stream()), B), info, True)
-        return out
 
     # -- search seam ---------------------------------------------------------------------------
     def search_begin(self, search: GitmiSearch, start: torch.Tensor, vocab: int) -> None:
@@ -1031,6 +1076,19 @@ def op_score_attn(qkv: torch.Tensor, img_kv: torch.Tensor, image_of: torch.Tenso
     out = torch.empty(Q * Lp, H * 64, device=qkv.device, dtype=qkv.dtype)
     _ck(_experiment_only(lib, "gitmi_debug_score_attn")(qkv.data_ptr(), img_kv.data_ptr(), img.data_ptr(), out.data_ptr(), Q, H,
                                                         N_img, Lp, _torch_dtype_code(qkv), _stream()), lib)
+    return out
+
+
+def op_score_attn_map(qkv: torch.Tensor, img_kv: torch.Tensor, image_of: torch.Tensor, Q: int, H: int, N_img: int, Lp: int,
+                      ntok: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention map of one layer (measurement build): op_score_attn's operands, ntok int [B] (the image keys of every
+    image; None: N_img each) -> fp32 [Q, Lp, N_img + Lp], the head mean of the probabilities of every text row."""
+    lib = load_library()
+    img = image_of.to(device=qkv.device, dtype=torch.int32).contiguous()
+    nt = None if ntok is None else ntok.to(device=qkv.device, dtype=torch.int32).contiguous()
+    out = torch.empty(Q, Lp, N_img + Lp, device=qkv.device, dtype=torch.float32)
+    _ck(_experiment_only(lib, "gitmi_debug_score_attn_map")(qkv.data_ptr(), img_kv.data_ptr(), img.data_ptr(), _ptr(nt),
+                                                            out.data_ptr(), Q, H, N_img, Lp, _torch_dtype_code(qkv), _stream()), lib)
     return out
 
 

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Dict, Mapping, Optional, Sequence, Union
+from typing import Dict, Mapping, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -372,6 +372,29 @@ def _is_image_list(images) -> bool:
         all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in images)
 
 
+class AttentionMaps:
+    """What CaptioningModel.attend returns, fp32 on the CPU.
+      image [Q, L, layers, Nk]: the attention of text row (q, j) of every decoder layer to the Nk image key rows of its image,
+                                head mean; frame-major, the class token first within each frame (ragged input: the image's own
+                                tokens, then zeros up to the capacity);
+      text  [Q, L, layers, L] : the same row's attention to the text positions (0 past j).
+    image and text of a row j < lengths[q] sum to 1 together; rows past a caption's length are 0."""
+
+    def __init__(self, att: torch.Tensor, Nk: int, lengths: Sequence[int], image_of: Sequence[int], F: int,
+                 grids: Sequence[Tuple[int, int]]):
+        self.image, self.text = att[..., :Nk], att[..., Nk:]
+        self.lengths, self.image_of, self.frames, self.grids = list(lengths), list(image_of), int(F), list(grids)
+
+    def patch_grid(self, q: int) -> torch.Tensor:
+        """[L_q, layers, F, H/p, W/p]: the image columns of caption q's own rows laid out on the patch grid of its image,
+        class columns dropped (ragged input: that image's own grid)."""
+        gh, gw = self.grids[self.image_of[q]]
+        n = gh * gw + 1
+        rows = self.image[q, :self.lengths[q], :, :self.frames * n]
+        Lq, layers = rows.shape[:2]
+        return rows.reshape(Lq, layers, self.frames, n)[..., 1:].reshape(Lq, layers, self.frames, gh, gw)
+
+
 class CaptioningModel:
     """Callable like the reference model: ``model(batch) -> {'predictions', 'logprobs'}``.
 
@@ -621,30 +644,10 @@ class CaptioningModel:
         e.g. the captions that call just generated; nothing is encoded.
         -> {'logprobs' [Q, L] (lp of tokens[:, j], 0 at position 0), 'mean_logprobs' [Q, L] (mean log-prob over the
             vocabulary at that position), 'sum' [Q], 'mean' [Q] (over the counted positions)}, all fp32 on the CPU."""
-        if not self._loaded:
-            raise RuntimeError("weights not loaded (call load_state_dict first)")
         if not isinstance(captions, torch.Tensor):
             captions = id_table(captions)
         tokens = captions.detach().cpu().long()
-        is_list = isinstance(images, (list, tuple))
-        if images is None:
-            eng, stream = self._followup_context(on)
-            if stream is None:
-                out = eng.score(None, tokens, image_of=image_of).cpu()
-            else:
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):
-                    out = eng.score(None, tokens, image_of=image_of).cpu()
-        elif _is_image_list(images):
-            self._check_ragged()
-            self.engine.set_temporal_embedding(False)
-            out = self.engine.score(self.engine.ragged(images), tokens, image_of=image_of).cpu()
-            self._last = self.engine
-        else:
-            frames = list(images) if is_list else [images]
-            self.engine.set_temporal_embedding(is_list)                      # decoder.py:845-857: list branch only
-            out = self.engine.score(frames, tokens, image_of=image_of).cpu()
-            self._last = self.engine
+        out, _ = self._sentence_pass("score", images, tokens, image_of, on)
         lp, mean_lp = out[..., 0], out[..., 1]
         if need_predict is None:
             need_predict = (tokens != 0).long()
@@ -656,6 +659,51 @@ class CaptioningModel:
         n = sel.sum(1)
         return {"logprobs": lp, "mean_logprobs": mean_lp, "sum": total,
                 "mean": total / n.clamp(min=1).to(total.dtype)}
+
+    def _sentence_pass(self, method: str, images, tokens: torch.Tensor, image_of, on, **kw):
+        """One engine pass over given sentences (Engine.score / Engine.attend) routed like every request: images None -> the
+        follow-up context of `on` on its stream, a list of [3, h, w] images -> one ragged call, else frames; the calls that
+        encode run on context 0.  -> (the result on the CPU, the engine context that ran it)"""
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        is_list = isinstance(images, (list, tuple))
+        if images is None:
+            eng, stream = self._followup_context(on)
+            if stream is None:
+                return getattr(eng, method)(None, tokens, image_of=image_of, **kw).cpu(), eng
+            stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(stream):
+                return getattr(eng, method)(None, tokens, image_of=image_of, **kw).cpu(), eng
+        eng = self.engine
+        if _is_image_list(images):
+            self._check_ragged()
+            eng.set_temporal_embedding(False)
+            frames = eng.ragged(images)
+        else:
+            frames = list(images) if is_list else [images]
+            eng.set_temporal_embedding(is_list)                              # decoder.py:845-857: list branch only
+        out = getattr(eng, method)(frames, tokens, image_of=image_of, **kw).cpu()
+        self._last = eng
+        return out, eng
+
+    def attend(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], captions,
+               image_of: Optional[Sequence[int]] = None, on=None) -> "AttentionMaps":
+        """Where every token of given captions looked: the attention of the decoder's text rows to the image tokens and to
+        their own text, per layer, averaged over the heads (the reference's BertSelfAttention.output_attentions).  captions,
+        image_of, images and on as for score: images None runs over the RESIDENT images -- `generate`, then
+        `attend(None, captions)` locates what the caption just generated was read from, with no re-encode.
+        -> AttentionMaps: .image [Q, L, layers, Nk], .text [Q, L, layers, L], .patch_grid(q) [L_q, layers, F, H/p, W/p]."""
+        if isinstance(captions, torch.Tensor):
+            tokens = captions.detach().cpu().long()
+            pos = torch.arange(1, tokens.shape[1] + 1)
+            lengths = ((tokens != 0).long() * pos).amax(1).clamp(min=1).tolist()      # 0 pads: a caption ends at its last id
+        else:
+            lengths = [len(c) for c in captions]
+            tokens = id_table(captions)
+        out, eng = self._sentence_pass("attend", images, tokens, image_of, on, lengths=lengths)
+        Nk, F, grids = eng.resident_geometry
+        return AttentionMaps(out, Nk, lengths, list(range(len(lengths))) if image_of is None else [int(i) for i in image_of],
+                             F, grids)
 
     def _check_ragged(self) -> None:
         if not self._loaded:

@@ -48,6 +48,9 @@ extern "C" {
 #define GITMI_SEARCH_TRIE           2  /* TrieAutoRegressiveBeamSearch (beam 1, token trie: gitmi_set_trie)  trie_decoder.py:27-218 */
 #define GITMI_SEARCH_SCORE          3  /* not a search: score given sentences (CaptioningModel.forward_one_ce, decoder.py:916-972);
                                         * gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_ATTEND         4  /* not a search: the attention the text rows of given sentences pay to the image tokens and
+                                        * to their own text (BertSelfAttention.output_attentions, head mean); gitmi_generate_prefixed
+                                        * only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -294,6 +297,26 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * Like a generate call it replaces the engine's encoded images and prefill (with frames == NULL it scores over the resident
  * images instead: follow-up calls, above gitmi_generate); its workspaces are allocated by the first score call (engines that
  * never score keep their footprint). */
+/* ---- attention maps: search->kind == GITMI_SEARCH_ATTEND runs the same text pass over the same inputs with the same checks
+ * as GITMI_SEARCH_SCORE (prefixes [Q, ld] DEVICE, prefix_len_host, image_of_host, Q <= max_batch x max_beams, frames or NULL
+ * for a follow-up over the resident images) and returns where every token looked instead of how likely it was: the
+ * probabilities BertSelfAttention.output_attentions exposes (layers/bert/modeling_bert.py:99-158), text rows only, averaged
+ * over the heads.  With q_{l,h}, k_{l,h} the query / key rows of decoder layer l, head h (head_dim 64, scale 1/8 in fp32):
+ *     att[q, j, l, k] = (1/H) sum_h softmax_k'( q_{l,h}(q, j) . k_{l,h}(k') / 8 )[k]
+ * k' over the image keys of image image_of[q] and the text keys 0..j of sentence q (the joint mask of decoder.py:111-149).
+ *   logprob_out     : fp32 [Q, ld, dec_layers, Kc], device or page-locked host buffer; Kc = Nk + ld, Nk = the image key rows
+ *                     of one image in this call: F * N for uniform input (F after the num_frames truncation), the
+ *                     max_image_tokens capacity Nmax in ragged mode.
+ *                     Column order: columns [0, Nk) are the image tokens in the row order of the prefill -- frame-major, the
+ *                     class token first within each frame; column Nk + t is text position t.
+ *                     The zeros: rows j >= len_q, text columns t > j and, in ragged mode, image columns >= n_b (the image's
+ *                     own token count) are exactly 0.  Every other row sums to 1.
+ *   tokens_out, sent_out: ignored (may be NULL); info_out = { ld, Kc, dec_layers, sentences with a non-finite value }
+ *                     (ragged mode: sentences over a rejected image are counted there, as score counts them)
+ *   the other gitmi_search fields are ignored; the vocabulary head does not run.  gitmi_generate and gitmi_search_begin
+ *   refuse this kind.  Residency, the eager launch path (no hipGraph) and the serving schedule are those of a score call;
+ *   score calls return exactly what they return without this kind.  The output workspace (Q ld dec_layers Kc floats) is
+ *   allocated by the first attend call and grown on demand: engines that never attend keep their footprint. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

@@ -39,10 +39,16 @@ int  gitmi_debug_set_dgemm(int dbg);
  *   score_attn: text-row attention of one layer -- qkv [Q * Lp][3 H 64] packed q|k|v text rows (sentence q, position j at
  *               row q * Lp + j), img_kv [B * N_img][3 H 64] prefill rows, image_of int32 [Q] -> out [Q * Lp][H 64]; every
  *               text row attends to all N_img image keys of its image and causally to its sentence's text keys, scale 1/8.
+ *   score_attn_map: the same operands (ntok: int32 [B] DEVICE, the image keys of every image as in the ragged hooks below, or
+ *               NULL) -> out fp32 [Q][Lp][N_img + Lp], the attention map of GITMI_SEARCH_ATTEND for one layer: the head mean of
+ *               the probabilities row (q, j) gives the image keys (columns [0, N_img), 0 past ntok) and its text keys (columns
+ *               N_img + t, 0 for t > j).  Runs the attention launch for its softmax statistics first; synchronises the stream.
  *   score_head: out fp32 [M][2] = (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) of z = A [M][K] W [V][K]^T + bias for
  *               rows with tgt[m] >= 0 (0 elsewhere).  Synchronises the stream. */
 int  gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int N_img, int Lp,
                             int dtype, void* stream);
+int  gitmi_debug_score_attn_map(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, float* out, int Q, int H,
+                                int N_img, int Lp, int dtype, void* stream);
 int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K, int dtype,
                             float* out, void* stream);
 

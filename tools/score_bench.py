@@ -5,6 +5,8 @@
   (b) 16 images x 16 candidates x 16 tokens: the whole score call; with --trace the per-kernel times come from a
       `rocprofv3 --kernel-trace --stats` run of this script (score_head_kernel = the head, score_attn_kernel = attention)
   (c) the same scores from a gitmi_step_logits replay (t decode steps per position, logits to the host), for contrast
+  --attend: an attention-map call (GITMI_SEARCH_ATTEND) on the sentences of (a) and of (b) as well; under rocprofv3 the map
+      kernel is score_attn_map_mfma_kernel (score_attn_map_kernel in the f32 mode)
 
     python tools/score_bench.py [--precision f16] [--iters 20] [--out profiles/r07_score_bench.json]
 Prints one JSON object (and writes it to --out)."""
@@ -48,6 +50,7 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--skip-replay", action="store_true")
+    ap.add_argument("--attend", action="store_true")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = GitModelConfig()
@@ -65,6 +68,9 @@ def main() -> None:
     res["a_generate_ms"] = timed(lambda: eng.generate(frames, search), a.iters)
     res["a_score_ms"] = timed(lambda: eng.score(frames, tok), a.iters)
     res["a_score_lt_generate"] = res["a_score_ms"] < res["a_generate_ms"]
+    if a.attend:
+        res["a_attend_ms"] = timed(lambda: eng.attend(frames, tok), a.iters)
+        res["a_attend_out_mb"] = 64 * 20 * cfg.dec_layers * (eng.n_tok + 20) * 4 / 1e6
 
     # (b) 16 images x 16 candidates x 16 tokens
     fr16 = [f[:16].contiguous() for f in frames]
@@ -72,6 +78,9 @@ def main() -> None:
     tb[:, 0] = cfg.sos
     image_of = [q // 16 for q in range(256)]
     res["b_score_ms"] = timed(lambda: eng.score(fr16, tb, image_of=image_of), a.iters)
+    if a.attend:
+        res["b_attend_ms"] = timed(lambda: eng.attend(fr16, tb, image_of=image_of), a.iters)
+        res["b_attend_out_mb"] = 256 * 16 * cfg.dec_layers * (eng.n_tok + 16) * 4 / 1e6
     M = 256 * 16
     res["b_head_gflop"] = 2.0 * M * cfg.vocab * cfg.dec_hidden / 1e9
     res["b_head_peak_ms"] = 2.0 * M * cfg.vocab * cfg.dec_hidden / PEAK_16BIT * 1e3
