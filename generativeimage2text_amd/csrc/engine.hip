@@ -84,52 +84,71 @@ static int gemm(gitmi_engine* e, hipStream_t s, const void* A, int lda, const vo
                 const float* res, int ldr, void* C, int ldc, bool out_f32, int M, int N, int K, int act, int tag) {
     return gemm_run(e, s, gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, act), e->pol.f32, out_f32, tag);
 }
-// GEMM whose output (and residual, if any) are rows of a residual stream: fp32, or fp16 with stream_f16
-static int gemm_stream(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
-                       const void* res, int ldr, void* C, int ldc, int M, int N, int K, int tag) {
-    GemmArgs g = gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, 0);
-    g.out_f16 = e->pol.stream_f16 ? 1 : 0;
-    return gemm_run(e, s, g, e->pol.f32, !e->pol.stream_f16, tag);
-}
-// ---- folded LayerNorm (e->pol.ln_fold): what a GEMM needs to know about the LayerNorm in front of it / of its residual
-struct LnRef {
-    const float2* part = nullptr; int nparts = 0; int D = 0; float eps = 0.f;
-    const float* gamma = nullptr; const float* beta = nullptr;       // residual form only
-};
-// consumer: C = act(LayerNorm(x) W^T + b) with x the raw stream rows, f the folded set of W
-static int gemm_ln(gitmi_engine* e, hipStream_t s, const void* x, int ldx, const Folded& f, const LnRef& ln, void* C, int ldc,
-                   int M, int N, int K, int act, int tag) {
-    GemmArgs g = gemm_args(x, ldx, f.w, f.bias, nullptr, 0, C, ldc, M, N, K, act);
-    g.ln_part = ln.part; g.ln_nparts = ln.nparts; g.ln_colsum = f.colsum; g.ln_inv_d = 1.0f / (float)ln.D; g.ln_eps = ln.eps;
-    return gemm_run(e, s, g, false, false, tag);
-}
-// producer: stream rows C = A W^T + b (+ res, or + LayerNorm(res) when res_ln is given) and their row partials
-static int gemm_stream_part(gitmi_engine* e, hipStream_t s, const void* A, int lda, const void* W, const float* bias,
-                            const void* res, int ldr, const LnRef* res_ln, void* C, int ldc, float2* part_out, int M, int N, int K,
-                            int tag) {
-    GemmArgs g = gemm_args(A, lda, W, bias, res, ldr, C, ldc, M, N, K, 0);
-    g.out_f16 = 1;
-    g.part_out = part_out;
-    if (res_ln) {
-        g.res_part = res_ln->part; g.res_nparts = res_ln->nparts; g.res_gamma = res_ln->gamma; g.res_beta = res_ln->beta;
-        g.res_inv_d = 1.0f / (float)res_ln->D; g.res_eps = res_ln->eps;
-    }
-    return gemm_run(e, s, g, false, false, tag);
-}
 // does a 16-bit GEMM of this shape run on gemm_p8_kernel (the only kernel with the folded epilogues)?
 static bool on_p8(const void* A, int lda, const void* W, const void* C, int ldc, int M, int N, int K, bool stream_out) {
     GemmArgs g = gemm_args(A, lda, W, nullptr, nullptr, 0, const_cast<void*>(C), ldc, M, N, K, 0);
     g.out_f16 = stream_out ? 1 : 0;
     return gemm_uses_p8(g, false, false);
 }
-// LayerNorm of stream rows x -> operand copy y_t (compute dtype) [+ stream copy y_s]
-static int ln_stream(gitmi_engine* e, hipStream_t s, const void* x, int ldx, const float* gamma, const float* beta, float eps,
-                     void* y_t, int ld_t, void* y_s, int ld_s, int rows, int D) {
+// ---- the residual stream of a pass (ViT blocks: v_x, prefill layers: p_y; fp32 rows, or fp16 with stream_f16) and the
+// LayerNorm (gamma, beta, eps) that stands between its rows and their consumers right now.  A layer is written once, on
+// ln_gemm / gemm_to_stream; its LayerNorms have two realisations.  Folded (the pass's gate; implies stream_f16): x keeps the raw
+// sums, the consumer GEMMs read them as their A operand, and whoever writes the rows leaves their row partials `part`.
+// Unfolded: a launch materialises LayerNorm(x) as the operand copy `t` (and as the stream rows `xn`).
+struct Stream {
+    void* x = nullptr; int M = 0, D = 0, tag = 0;
+    bool fold = false;
+    void* t = nullptr;
+    // post-norm passes (BERT) keep the normalised rows: a producer's residual is LayerNorm(x) -- xn, or rebuilt from the
+    // partials when folded -- where a pre-norm pass (ViT, xn == nullptr) adds x itself
+    float* xn = nullptr;
+    // partials buffers, attached by the gate when the pass folds.  Post-norm passes need two: a producer's tile reads the
+    // previous partials of a row for the residual while another tile (another workgroup) writes the new ones
+    float2* parts[2] = {nullptr, nullptr};
+    const float2* part = nullptr; const float* gamma = nullptr; const float* beta = nullptr; float eps = 0.f;
+};
+// where the next writer of the rows leaves their partials: the buffer that is not being read (nullptr: the pass is not folded)
+static float2* stream_part_out(const Stream& st) { return st.part == st.parts[0] ? st.parts[1] : st.parts[0]; }
+// the rows were (re)written, with their partials in `part`: LayerNorm(gamma, beta, eps) stands in front of the consumers from here on
+static void stream_written(Stream& st, const float2* part, const float* gamma, const float* beta, float eps) {
+    st.part = part; st.gamma = gamma; st.beta = beta; st.eps = eps;
+}
+// consumer: columns [col0, col0 + N) of C = act(LayerNorm(stream) W^T + b); f: 16-bit(W . gamma), beta W^T + b, column sums
+static int ln_gemm(gitmi_engine* e, hipStream_t s, const Stream& st, const Folded& f, const void* W, const float* bias, void* C,
+                   int ldc, int col0, int N, int act) {
+    const int D = st.D;
+    const size_t woff = (size_t)col0 * D * e->pol.esz;
+    C = (char*)C + (size_t)col0 * e->pol.esz;
+    if (st.fold) {
+        GemmArgs g = gemm_args(st.x, D, (const char*)f.w + woff, f.bias + col0, nullptr, 0, C, ldc, st.M, N, D, act);
+        g.ln_part = st.part; g.ln_nparts = D / 256; g.ln_colsum = f.colsum + col0; g.ln_inv_d = 1.0f / (float)D; g.ln_eps = st.eps;
+        return gemm_run(e, s, g, false, false, st.tag);
+    }
     if (e->pol.stream_f16)
-        HIPCK(launch_layernorm_s16(x, ldx, gamma, beta, eps, nullptr, y_t, ld_t, false, y_s, ld_s, rows, D, 0, 0, 0, s));
+        HIPCK(launch_layernorm_s16(st.x, D, st.gamma, st.beta, st.eps, nullptr, st.t, D, false, st.xn, st.xn ? D : 0, st.M, D, 0, 0, 0, s));
     else
-        HIPCK(launch_layernorm((const float*)x, ldx, gamma, beta, eps, nullptr, y_t, ld_t, e->pol.f32, (float*)y_s, ld_s, rows, D,
-                               0, 0, 0, s));
+        HIPCK(launch_layernorm((const float*)st.x, D, st.gamma, st.beta, st.eps, nullptr, st.t, D, e->pol.f32, st.xn, st.xn ? D : 0, st.M,
+                               D, 0, 0, 0, s));
+    return gemm(e, s, st.t, D, (const char*)W + woff, bias + col0, nullptr, 0, C, ldc, e->pol.f32, st.M, N, D, act, st.tag);
+}
+// producer: stream rows = A W^T + b (+ the pass's residual), after which LayerNorm(gamma, beta, eps) stands on them
+// (gamma == nullptr: none of the pass's own follows, nobody reads partials of these rows)
+static int gemm_to_stream(gitmi_engine* e, hipStream_t s, Stream& st, const void* A, int lda, const void* W, const float* bias, int K,
+                          bool residual, const float* gamma, const float* beta, float eps) {
+    const int D = st.D;
+    float2* part = gamma ? stream_part_out(st) : nullptr;
+    const void* res = !residual ? nullptr : st.xn && !st.fold ? st.xn : st.x;
+    GemmArgs g = gemm_args(A, lda, W, bias, res, residual ? D : 0, st.x, D, st.M, D, K, 0);
+    g.out_f16 = e->pol.stream_f16 ? 1 : 0;
+    if (st.fold) {
+        g.part_out = part;
+        if (residual && st.xn) {        // the residual added is LayerNorm(res), rebuilt from the partials of the raw rows
+            g.res_part = st.part; g.res_nparts = D / 256; g.res_gamma = st.gamma; g.res_beta = st.beta;
+            g.res_inv_d = 1.0f / (float)D; g.res_eps = st.eps;
+        }
+    }
+    RCK(gemm_run(e, s, g, e->pol.f32, !e->pol.stream_f16, st.tag));
+    stream_written(st, part, gamma, beta, eps);
     return 0;
 }
 // full attention over packed q|k|v rows [batch * N][3 * width] -> out [batch * N][width]
@@ -331,6 +350,35 @@ extern "C" int gitmi_set_image_shape(gitmi_engine* e, int H, int W, void* stream
     return 0;
 }
 
+// ---- the fold gates, one per pass: a pass folds its LayerNorms (pol.ln_fold, fp16-operand build) when every GEMM either side
+// of them runs on gemm_p8_kernel, i.e. at more than 512 rows; otherwise every LayerNorm is a launch.  They return the pass's
+// stream record with the decision and, when it folds, the partials buffers.
+static Stream vit_stream(gitmi_engine* e, int M) {
+    const int D = e->cfg.vit_width;
+    const VitLayerW& L = e->w.vit[0];
+    Stream st;
+    st.x = e->v_x; st.M = M; st.D = D; st.tag = TAG_GEMM_VIT; st.t = e->v_h;
+    st.fold = e->pol.ln_fold && on_p8(e->v_x, D, L.qkv_f.w, e->v_qkv, 3 * D, M, 3 * D, D, false) &&
+              on_p8(e->v_x, D, L.ffn1_f.w, e->v_u, 4 * D, M, 4 * D, D, false) && on_p8(e->v_ctx, D, L.wo, e->v_x, D, M, D, D, true) &&
+              on_p8(e->v_u, 4 * D, L.w2, e->v_x, D, M, D, 4 * D, true);
+    if (st.fold) st.parts[0] = st.parts[1] = e->v_part;     // pre-norm: no producer reads partials, one buffer in place
+    return st;
+}
+// prefill: the visual projection, Q|K|V and the last layer's K|V slice; FFN1, out-proj and FFN2 only where a layer runs them
+static Stream prefill_stream(gitmi_engine* e, int M) {
+    const int d = e->cfg.dec_hidden, ffn = e->cfg.dec_ffn, D = e->cfg.vit_width;
+    const DecLayerW& L = e->w.dec[0];
+    Stream st;
+    st.x = e->p_y; st.M = M; st.D = d; st.tag = TAG_GEMM_OTHER; st.t = e->p_ht; st.xn = e->p_hf;
+    st.fold = e->pol.ln_fold && on_p8(e->feats, D, e->w.vp_w, e->p_y, d, M, d, D, true) &&
+              on_p8(e->p_y, d, L.qkv_pf.w, e->img_kv[0], 3 * d, M, 3 * d, d, false) &&
+              on_p8(e->p_y, d, L.qkv_pf.w, e->img_kv[0], 3 * d, M, 2 * d, d, false) &&
+              (e->cfg.dec_layers < 2 || (on_p8(e->p_y, d, L.ffn1_pf.w, e->p_u, ffn, M, ffn, d, false) &&
+                                         on_p8(e->p_ctx, d, L.wo, e->p_y, d, M, d, d, true) && on_p8(e->p_u, ffn, L.w2, e->p_y, d, M, d, ffn, true)));
+    if (st.fold) { st.parts[0] = e->p_part[0]; st.parts[1] = e->p_part[1]; }
+    return st;
+}
+
 // ---------------------------------------------------------------------------------------
 static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F, int B, float* feats_out,
                               hipStream_t s) {
@@ -354,39 +402,23 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
                             e->H, e->W, c.patch, e->Kp, e->Kp_pad, s));
     RCK(gemm(e, s, e->patches, e->Kp_pad, e->w.conv_w, nullptr, nullptr, 0, e->patch_out, D, true, BI * g2, D, e->Kp_pad, 0,
              TAG_GEMM_VIT));
-    // LayerNorm folding (fp16-operand build): ln_1 / ln_2 disappear into the GEMMs either side of them when every GEMM of the
-    // pass runs on gemm_p8_kernel (more than 512 rows); the stream rows v_x are then the QKV / c_fc GEMMs' A operand as they are
-    const bool fold = e->pol.ln_fold && on_p8(e->v_x, D, e->w.vit[0].qkv_f.w, e->v_qkv, 3 * D, M, 3 * D, D, false) &&
-                      on_p8(e->v_x, D, e->w.vit[0].ffn1_f.w, e->v_u, 4 * D, M, 4 * D, D, false) &&
-                      on_p8(e->v_ctx, D, e->w.vit[0].wo, e->v_x, D, M, D, D, true) && on_p8(e->v_u, 4 * D, e->w.vit[0].w2, e->v_x, D, M, D, 4 * D, true);
-    LnRef vln;
-    vln.part = e->v_part; vln.nparts = D / 256; vln.D = D; vln.eps = 1e-5f;
+    Stream x = vit_stream(e, M);
+    float2* part = stream_part_out(x);
     if (e->ragged)
         HIPCK(launch_vit_assemble_ragged(e->patch_out, e->w.cls, e->w.pos, e->g_nat, e->rg_meta, e->w.lnpre_g, e->w.lnpre_b, 1e-5f, e->v_x,
-                                         e->pol.stream_f16, BI, N, c.patch, D, fold ? e->v_part : nullptr, s));
+                                         e->pol.stream_f16, BI, N, c.patch, D, part, s));
     else
     HIPCK(launch_vit_assemble_ln(e->patch_out, e->w.cls, e->pos_cur, e->w.lnpre_g, e->w.lnpre_b, 1e-5f, e->v_x, e->pol.stream_f16, BI, N, D,
-                                 fold ? e->v_part : nullptr, D / 256, s));
-    for (int l = 0; l < c.vit_layers; ++l) {
+                                 part, D / 256, s));
+    stream_written(x, part, e->w.vit[0].ln1g, e->w.vit[0].ln1b, 1e-5f);
+    for (int l = 0; l < c.vit_layers; ++l) {        // pre-norm block: x += attn(ln_1(x)); x += mlp(ln_2(x))
         const VitLayerW& L = e->w.vit[l];
-        if (fold) {
-            RCK(gemm_ln(e, s, e->v_x, D, L.qkv_f, vln, e->v_qkv, 3 * D, M, 3 * D, D, 0, TAG_GEMM_VIT));
-        } else {
-            RCK(ln_stream(e, s, e->v_x, D, L.ln1g, L.ln1b, 1e-5f, e->v_h, D, nullptr, 0, M, D));
-            RCK(gemm(e, s, e->v_h, D, L.wqkv, L.bqkv, nullptr, 0, e->v_qkv, 3 * D, e->pol.f32, M, 3 * D, D, 0, TAG_GEMM_VIT));
-        }
+        const VitLayerW* Ln = l + 1 < c.vit_layers ? &e->w.vit[l + 1] : nullptr;   // ln_post after the last block is a launch of its own
+        RCK(ln_gemm(e, s, x, L.qkv_f, L.wqkv, L.bqkv, e->v_qkv, 3 * D, 0, 3 * D, 0));
         RCK(attn_full_packed(e, e->v_qkv, e->v_ctx, D, c.vit_heads, N, BI, s));
-        if (fold) {     // pre-norm blocks: the residual is the raw stream; every producer leaves the partials of its rows
-            RCK(gemm_stream_part(e, s, e->v_ctx, D, L.wo, L.bo, e->v_x, D, nullptr, e->v_x, D, e->v_part, M, D, D, TAG_GEMM_VIT));
-            RCK(gemm_ln(e, s, e->v_x, D, L.ffn1_f, vln, e->v_u, 4 * D, M, 4 * D, D, 1, TAG_GEMM_VIT));
-            RCK(gemm_stream_part(e, s, e->v_u, 4 * D, L.w2, L.b2, e->v_x, D, nullptr, e->v_x, D, l + 1 < c.vit_layers ? e->v_part : nullptr,
-                                 M, D, 4 * D, TAG_GEMM_VIT));
-            continue;
-        }
-        RCK(gemm_stream(e, s, e->v_ctx, D, L.wo, L.bo, e->v_x, D, e->v_x, D, M, D, D, TAG_GEMM_VIT));
-        RCK(ln_stream(e, s, e->v_x, D, L.ln2g, L.ln2b, 1e-5f, e->v_h, D, nullptr, 0, M, D));
-        RCK(gemm(e, s, e->v_h, D, L.w1, L.b1, nullptr, 0, e->v_u, 4 * D, e->pol.f32, M, 4 * D, D, 1, TAG_GEMM_VIT));
-        RCK(gemm_stream(e, s, e->v_u, 4 * D, L.w2, L.b2, e->v_x, D, e->v_x, D, M, D, 4 * D, TAG_GEMM_VIT));
+        RCK(gemm_to_stream(e, s, x, e->v_ctx, D, L.wo, L.bo, D, true, L.ln2g, L.ln2b, 1e-5f));
+        RCK(ln_gemm(e, s, x, L.ffn1_f, L.w1, L.b1, e->v_u, 4 * D, 0, 4 * D, 1));
+        RCK(gemm_to_stream(e, s, x, e->v_u, 4 * D, L.w2, L.b2, 4 * D, true, Ln ? Ln->ln1g : nullptr, Ln ? Ln->ln1b : nullptr, 1e-5f));
     }
     // ln_post (+ temporal embedding of the frame), scattered into the concatenated [B, F*N, D] feature tensor
     for (int fr = 0; fr < F_eff; ++fr) {
@@ -428,64 +460,21 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
     const int B = e->cur_B, Nimg = e->cur_Nimg, M = B * Nimg;
     e->have_prefill = false;
     SpanGuard phase(e, s, TAG_PREFILL, 0);
-    const bool fold = e->pol.ln_fold && on_p8(e->feats, D, e->w.vp_w, e->p_y, d, M, d, D, true) &&
-                      on_p8(e->p_y, d, e->w.dec[0].qkv_pf.w, e->img_kv[0], 3 * d, M, 3 * d, d, false) &&
-                      on_p8(e->p_y, d, e->w.dec[0].qkv_pf.w, e->img_kv[0], 3 * d, M, 2 * d, d, false) &&
-                      (c.dec_layers < 2 || (on_p8(e->p_y, d, e->w.dec[0].ffn1_pf.w, e->p_u, ffn, M, ffn, d, false) &&
-                                            on_p8(e->p_ctx, d, e->w.dec[0].wo, e->p_y, d, M, d, d, true) &&
-                                            on_p8(e->p_u, ffn, e->w.dec[0].w2, e->p_y, d, M, d, ffn, true)));
-    if (fold) {
-        // Post-norm layers with every LayerNorm folded: p_y holds the RAW sums (dense + residual) in place, the consumer GEMMs
-        // read it as their A operand, and the residual LayerNorm(previous raw row) is rebuilt inside the next producer's
-        // epilogue from the partials of the previous producer (ping-pong: tiles of one row run in different workgroups).
-        int cur = 0;
-        LnRef ln;                   // the LayerNorm that stands between p_y and its consumers right now
-        ln.nparts = d / 256; ln.D = d;
-        RCK(gemm_stream_part(e, s, e->feats, D, e->w.vp_w, e->w.vp_b, nullptr, 0, nullptr, e->p_y, d, e->p_part[cur], M, d, D, TAG_GEMM_OTHER));
-        ln.part = e->p_part[cur]; ln.eps = 1e-5f; ln.gamma = e->w.vp_lng; ln.beta = e->w.vp_lnb;
-        for (int l = 0; l < c.dec_layers; ++l) {
-            const DecLayerW& L = e->w.dec[l];
-            if (l + 1 == c.dec_layers) {      // only K and V of the last layer's image rows are ever read
-                const Folded kv{(char*)L.qkv_pf.w + (size_t)d * d * e->pol.esz, L.qkv_pf.bias + d, L.qkv_pf.colsum + d};
-                RCK(gemm_ln(e, s, e->p_y, d, kv, ln, (char*)e->img_kv[l] + (size_t)d * e->pol.esz, 3 * d, M, 2 * d, d, 0, TAG_GEMM_OTHER));
-                RCK(kv_repack(e, l, B, Nimg, s));
-                break;
-            }
-            RCK(gemm_ln(e, s, e->p_y, d, L.qkv_pf, ln, e->img_kv[l], 3 * d, M, 3 * d, d, 0, TAG_GEMM_OTHER));
-            RCK(kv_repack(e, l, B, Nimg, s));
-            RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, s));
-            RCK(gemm_stream_part(e, s, e->p_ctx, d, L.wo, L.bo, e->p_y, d, &ln, e->p_y, d, e->p_part[cur ^ 1], M, d, d, TAG_GEMM_OTHER));
-            cur ^= 1;
-            ln.part = e->p_part[cur]; ln.eps = 1e-12f; ln.gamma = L.lnag; ln.beta = L.lnab;
-            RCK(gemm_ln(e, s, e->p_y, d, L.ffn1_pf, ln, e->p_u, ffn, M, ffn, d, 2, TAG_GEMM_OTHER));
-            RCK(gemm_stream_part(e, s, e->p_u, ffn, L.w2, L.b2, e->p_y, d, &ln, e->p_y, d, e->p_part[cur ^ 1], M, d, ffn, TAG_GEMM_OTHER));
-            cur ^= 1;
-            ln.part = e->p_part[cur]; ln.eps = 1e-12f; ln.gamma = L.lnog; ln.beta = L.lnob;
-        }
-        set_prefilled(e);
-        return 0;
-    }
-    RCK(gemm_stream(e, s, e->feats, D, e->w.vp_w, e->w.vp_b, nullptr, 0, e->p_y, d, M, d, D, TAG_GEMM_OTHER));
-    RCK(ln_stream(e, s, e->p_y, d, e->w.vp_lng, e->w.vp_lnb, 1e-5f, e->p_ht, d, e->p_hf, d, M, d));
+    // post-norm layers: y = LayerNorm(dense(..) + LayerNorm(previous y)), the first LayerNorm the visual projection's own
+    Stream y = prefill_stream(e, M);
+    RCK(gemm_to_stream(e, s, y, e->feats, D, e->w.vp_w, e->w.vp_b, D, false, e->w.vp_lng, e->w.vp_lnb, 1e-5f));
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayerW& L = e->w.dec[l];
+        // the last layer's image-row outputs are never consumed: only the K|V columns of its projection, and nothing after them
         const bool last = l + 1 == c.dec_layers;
-        if (!last) {
-            RCK(gemm(e, s, e->p_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->img_kv[l], 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
-            RCK(kv_repack(e, l, B, Nimg, s));
-        } else {
-            // the last layer's image-row outputs are never consumed: only its K and V are needed
-            RCK(gemm(e, s, e->p_ht, d, (char*)L.wqkv + (size_t)d * d * e->pol.esz, L.bqkv + d, nullptr, 0,
-                     (char*)e->img_kv[l] + (size_t)d * e->pol.esz, 3 * d, e->pol.f32, M, 2 * d, d, 0, TAG_GEMM_OTHER));
-            RCK(kv_repack(e, l, B, Nimg, s));
-            break;
-        }
+        const int col0 = last ? d : 0;
+        RCK(ln_gemm(e, s, y, L.qkv_pf, L.wqkv, L.bqkv, e->img_kv[l], 3 * d, col0, 3 * d - col0, 0));
+        RCK(kv_repack(e, l, B, Nimg, s));
+        if (last) break;
         RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, s));
-        RCK(gemm_stream(e, s, e->p_ctx, d, L.wo, L.bo, e->p_hf, d, e->p_y, d, M, d, d, TAG_GEMM_OTHER));
-        RCK(ln_stream(e, s, e->p_y, d, L.lnag, L.lnab, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
-        RCK(gemm(e, s, e->p_ht, d, L.w1, L.b1, nullptr, 0, e->p_u, ffn, e->pol.f32, M, ffn, d, 2, TAG_GEMM_OTHER));
-        RCK(gemm_stream(e, s, e->p_u, ffn, L.w2, L.b2, e->p_hf, d, e->p_y, d, M, d, ffn, TAG_GEMM_OTHER));
-        RCK(ln_stream(e, s, e->p_y, d, L.lnog, L.lnob, 1e-12f, e->p_ht, d, e->p_hf, d, M, d));
+        RCK(gemm_to_stream(e, s, y, e->p_ctx, d, L.wo, L.bo, d, true, L.lnag, L.lnab, 1e-12f));
+        RCK(ln_gemm(e, s, y, L.ffn1_pf, L.w1, L.b1, e->p_u, ffn, 0, ffn, 2));
+        RCK(gemm_to_stream(e, s, y, e->p_u, ffn, L.w2, L.b2, ffn, true, L.lnog, L.lnob, 1e-12f));
     }
     set_prefilled(e);
     return 0;
@@ -530,24 +519,47 @@ static int dgemm(gitmi_engine* e, hipStream_t s, const DGemmArgs& g_in) {
     return 0;
 }
 
+// ---- argument builders of the chain: the consumer / producer pair of ln_gemm / gemm_to_stream on strip partials.  DLn: a
+// LayerNorm of the chain, i.e. the strip partials of the rows it normalises and its (gamma, beta, eps)
+struct DLn { const float2* stats; int strips; float inv_d, eps; const float* gamma; const float* beta; };
+// consumer: C = act(LayerNorm(A) W^T + b) with the LayerNorm folded into f (ln == nullptr: plain A, f.colsum is not read)
+static DGemmArgs dgemm_ln(const void* A, const Folded& f, const DLn* ln, void* C, int c_frag, int act, int M, int N, int K) {
+    DGemmArgs g{};
+    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)f.w; g.bias = f.bias;
+    if (ln) { g.colsum = f.colsum; g.stats_in = ln->stats; g.strips_in = ln->strips; g.inv_d = ln->inv_d; g.eps_in = ln->eps; }
+    g.C = C; g.ldc = N; g.c_frag = c_frag; g.act = act; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+// producer: x_out = A W^T + b + residual (res_x itself, or LayerNorm(res_x) rebuilt from res_ln), its bf16 copy and strip partials
+static DGemmArgs dgemm_to_stream(const void* A, const void* W, const float* bias, const float* res_x, const DLn* res_ln, float* x_out,
+                                 void* xb_out, float2* stats_out, int M, int N, int K) {
+    DGemmArgs g{};
+    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
+    g.res_x = res_x;
+    if (res_ln) {
+        g.res_stats = res_ln->stats; g.res_strips = res_ln->strips; g.res_gamma = res_ln->gamma; g.res_beta = res_ln->beta;
+        g.res_inv_d = res_ln->inv_d; g.res_eps = res_ln->eps;
+    }
+    g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = stats_out;
+    g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
 static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, int pos, int R, int beams, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, ffn = c.dec_ffn;
     const int B = R / beams;
     const bool chain = e->pol.skinny && !e->pol.f32;
-    const int strips = d / 16;
-    const float inv_d = 1.0f / (float)d;
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayerW& L = e->w.dec[l];
+        // chain: ln_o, the previous layer's output LayerNorm over xo (layer 0: none, the embedded rows are normalised already),
+        // and ln_a, this layer's attention-output LayerNorm over xa
         const DecLayerW* Lp = l > 0 ? &e->w.dec[l - 1] : nullptr;
+        const DLn ln_prev{e->stats_o, d / 16, 1.0f / (float)d, 1e-12f, Lp ? Lp->lnog : nullptr, Lp ? Lp->lnob : nullptr};
+        const DLn ln_a{e->stats_a, d / 16, 1.0f / (float)d, 1e-12f, L.lnag, L.lnab};
+        const DLn* ln_o = Lp ? &ln_prev : nullptr;
         if (chain) {
-            DGemmArgs q{};
-            q.A = (const unsigned short*)(l == 0 ? e->d_ht : e->xo_b); q.lda = d;
-            q.W = (const unsigned short*)L.qkv_f.w;
-            q.bias = L.qkv_f.bias;
-            if (l > 0) { q.colsum = L.qkv_f.colsum; q.stats_in = e->stats_o; q.strips_in = strips; q.inv_d = inv_d; q.eps_in = 1e-12f; }
-            q.C = e->d_qkv; q.ldc = 3 * d; q.act = 0; q.M = R; q.N = 3 * d; q.K = d;
-            if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, q));
+            if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, dgemm_ln(l == 0 ? e->d_ht : e->xo_b, L.qkv_f, ln_o, e->d_qkv, 0, 0, R, 3 * d, d)));
         } else {
             RCK(gemm(e, s, e->d_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->d_qkv, 3 * d, e->pol.f32, R, 3 * d, d, 0, TAG_GEMM_OTHER));
         }
@@ -574,25 +586,11 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, true, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
-            DGemmArgs o{};
-            o.A = (const unsigned short*)e->d_ctx; o.lda = d; o.W = (const unsigned short*)L.wo_p; o.bias = L.bo;
-            o.res_x = l == 0 ? e->d_hf : e->xo_f;
-            if (l > 0) { o.res_stats = e->stats_o; o.res_strips = strips; o.res_gamma = Lp->lnog; o.res_beta = Lp->lnob; o.res_inv_d = inv_d; o.res_eps = 1e-12f; }
-            o.x_out = e->xa_f; o.xb_out = (unsigned short*)e->xa_b; o.stats_out = e->stats_a;
-            o.M = R; o.N = d; o.K = d;
-            if (!GITMI_SKIPPED(e, 4)) RCK(dgemm(e, s, o));
-            DGemmArgs f1{};
-            f1.A = (const unsigned short*)e->xa_b; f1.lda = d; f1.W = (const unsigned short*)L.ffn1_f.w; f1.bias = L.ffn1_f.bias; f1.colsum = L.ffn1_f.colsum;
-            f1.stats_in = e->stats_a; f1.strips_in = strips; f1.inv_d = inv_d; f1.eps_in = 1e-12f;
-            f1.C = e->d_u; f1.ldc = ffn; f1.c_frag = 1; f1.act = 2; f1.M = R; f1.N = ffn; f1.K = d;
-            if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, f1));
-            DGemmArgs f2{};
-            f2.A = (const unsigned short*)e->d_u; f2.lda = ffn; f2.W = (const unsigned short*)L.w2_p; f2.bias = L.b2;
-            f2.res_x = e->xa_f; f2.res_stats = e->stats_a; f2.res_strips = strips; f2.res_gamma = L.lnag; f2.res_beta = L.lnab;
-            f2.res_inv_d = inv_d; f2.res_eps = 1e-12f;
-            f2.x_out = e->xo_f; f2.xb_out = (unsigned short*)e->xo_b; f2.stats_out = e->stats_o;
-            f2.M = R; f2.N = d; f2.K = ffn;
-            if (!GITMI_SKIPPED(e, 4)) RCK(dgemm(e, s, f2));
+            if (!GITMI_SKIPPED(e, 4))
+                RCK(dgemm(e, s, dgemm_to_stream(e->d_ctx, L.wo_p, L.bo, l == 0 ? e->d_hf : e->xo_f, ln_o, e->xa_f, e->xa_b, e->stats_a, R, d, d)));
+            if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, dgemm_ln(e->xa_b, L.ffn1_f, &ln_a, e->d_u, 1, 2, R, ffn, d)));
+            if (!GITMI_SKIPPED(e, 4))
+                RCK(dgemm(e, s, dgemm_to_stream(e->d_u, L.w2_p, L.b2, e->xa_f, &ln_a, e->xo_f, e->xo_b, e->stats_o, R, d, ffn)));
         } else {
             RCK(dec_layer_tail(e, s, L, e->d_ctx, e->d_hf, e->d_ht, e->d_y, e->d_u, R));
         }
@@ -701,6 +699,22 @@ extern "C" int gitmi_encode_frames(gitmi_engine* e, const float* const* frames, 
     return encode_frames_impl(e, frames, F, B, feats_out, (hipStream_t)stream);
 }
 
+static EmbedArgs embed_args(gitmi_engine* e, bool on) {
+    EmbedArgs em{};
+    if (!on) return em;
+    em.words = e->w.words_f; em.positions = e->w.positions_f; em.gamma = e->w.emb_lng; em.beta = e->w.emb_lnb; em.eps = 1e-8f;
+    em.h_f = e->d_hf; em.h_t = e->d_ht; em.D = e->cfg.dec_hidden; em.vocab = e->cfg.vocab;
+    em.frag = (e->pol.skinny && !e->pol.f32) ? 1 : 0;
+    return em;
+}
+// embeds position `pos` of the R token rows ids [R][ld_ids] into d_hf / d_ht (every later position: the search step's fused embedding)
+static int embed_position(gitmi_engine* e, const int* ids, int ld_ids, int pos, int R, hipStream_t s) {
+    const EmbedArgs em = embed_args(e, true);
+    HIPCK(launch_embed_ln(ids, ld_ids, pos, em.words, em.positions, em.gamma, em.beta, em.eps, em.h_f, em.h_t, e->pol.f32, R, em.D,
+                          em.vocab, em.frag != 0, s));
+    return 0;
+}
+
 extern "C" int gitmi_prefill(gitmi_engine* e, void* stream) {
     RCK(check_ready(e));
     if (!e->have_feats) return fail("prefill: no encoded frames");
@@ -725,8 +739,7 @@ extern "C" int gitmi_step_logits(gitmi_engine* e, const int64_t* tokens, int R, 
     StepCands cands{};
     for (int pos = 0; pos < t; ++pos) {
         SpanGuard step(e, s, TAG_STEP, 0);
-        HIPCK(launch_embed_ln(e->ss.ids[0], T, pos, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->d_hf,
-                              e->d_ht, e->pol.f32, R, c.dec_hidden, c.vocab, e->pol.skinny && !e->pol.f32, s));
+        RCK(embed_position(e, e->ss.ids[0], T, pos, R, s));
         RCK(decode_layers_impl(e, e->ss.kv_src[0], T, pos, R, beams, s));
         if (pos == t - 1) RCK(decode_head_impl(e, nullptr, T, t, R, beams, 0, 1, logits_out, c.vocab, s, &cands));
     }
@@ -812,15 +825,6 @@ static int trie_candidates(gitmi_engine* e, const float* logits, int ldl, int cu
     cands->part_val = e->part_val; cands->part_idx = e->part_idx; cands->part_lse = e->part_lse;
     cands->nparts = 1; cands->slots = 1;
     return 0;
-}
-
-static EmbedArgs embed_args(gitmi_engine* e, bool on) {
-    EmbedArgs em{};
-    if (!on) return em;
-    em.words = e->w.words_f; em.positions = e->w.positions_f; em.gamma = e->w.emb_lng; em.beta = e->w.emb_lnb; em.eps = 1e-8f;
-    em.h_f = e->d_hf; em.h_t = e->d_ht; em.D = e->cfg.dec_hidden; em.vocab = e->cfg.vocab;
-    em.frag = (e->pol.skinny && !e->pol.f32) ? 1 : 0;
-    return em;
 }
 
 // one search step on the candidate lists of the current step (+ the embedding of the appended tokens)
@@ -1009,6 +1013,11 @@ static int generate_encode(gitmi_engine* e, const Request& rq, hipStream_t s) {
     RCK(encode_frames_impl(e, rq.frames, rq.F, rq.B, nullptr, s));
     return prefill_impl(e, s);
 }
+// the image K/V a call runs over: encode + prefill of its frames; a follow-up call: the resident images' prefill if it is not current
+static int images_ready(gitmi_engine* e, const Request& rq, hipStream_t s) {
+    if (rq.frames) return generate_encode(e, rq, s);
+    return e->have_prefill ? 0 : prefill_impl(e, s);
+}
 
 // search over the text positions (teacher-forced prefix positions, then searched ones) + result formatting.
 // rq.Q sentences (start_dev / plen_dev / img_of_dev describe them), prefix lengths in [minP, maxP].
@@ -1023,8 +1032,7 @@ static int generate_decode(gitmi_engine* e, const Request& rq, hipStream_t s, bo
     {
         SpanGuard phase(e, s, TAG_DECODE, 0);
         // position 0 is embedded here; every later position by the search step that appends its token
-        HIPCK(launch_embed_ln(st.ids[0], T, 0, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->d_hf, e->d_ht,
-                              e->pol.f32, R, c.dec_hidden, c.vocab, e->pol.skinny && !e->pol.f32, s));
+        RCK(embed_position(e, st.ids[0], T, 0, R, s));
         e->ss_len = 1;
         StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, 1};
         while (e->ss_len < T) {
@@ -1057,11 +1065,10 @@ static int generate_decode(gitmi_engine* e, const Request& rq, hipStream_t s, bo
     return 0;
 }
 
-// the whole call: encode + prefill of the frames (a follow-up: the prefill, if it is not current), then the search
+// the whole call: the image K/V, then the search
 static int generate_body(gitmi_engine* e, const Request& rq, hipStream_t s, bool allow_poll) {
     SpanGuard total(e, s, 99, 0);
-    if (rq.frames) RCK(generate_encode(e, rq, s));
-    else if (!e->have_prefill) RCK(prefill_impl(e, s));
+    RCK(images_ready(e, rq, s));
     return generate_decode(e, rq, s, allow_poll);
 }
 
@@ -1128,7 +1135,7 @@ static int generate_graphed(gitmi_engine* e, const Request& rq, hipStream_t s) {
     const GraphKey key = graph_key_of(e, rq, F_eff);
     const CapturedGraph *enc = nullptr, *dec = nullptr;
     if (resident) {
-        if (!e->have_prefill) RCK(prefill_impl(e, x));          // after gitmi_encode_frames alone; outside the graph
+        RCK(images_ready(e, rq, x));        // the prefill, after gitmi_encode_frames alone: outside the graph
         if (!e->follow_slot.valid || !(key == e->follow_slot.key)) {
             e->follow_slot.valid = false;
             RCK(e->graph_follow.capture(x, [&] { return generate_decode(e, own, x, false); }));
@@ -1243,52 +1250,6 @@ static int score_alloc(gitmi_engine* e, size_t rows_needed) {
     return 0;
 }
 
-// One pass of the textual head over whole sentences (CaptioningModel.forward_one_ce, decoder.py:916-972) after the
-// usual encode + prefill: embedding of every position, the decoder layers over all text rows at once (generic GEMM +
-// LayerNorm launches, the attention of kernels_score.hip against the prefill's image K/V), then the vocabulary head
-// reduced to (lp, mean_lp) per position.  tokens [Q][ld] device int64; lens / image_of already on the device.
-static int score_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
-    const gitmi_config& c = e->cfg;
-    const int d = c.dec_hidden, ffn = c.dec_ffn, V = c.vocab, Q = rq.Q;
-    if (rq.frames) RCK(generate_encode(e, rq, s));
-    else if (!e->have_prefill) RCK(prefill_impl(e, s));     // follow-up call: the resident images' K/V
-    const int Lp = round_up(rq.maxP, 16), M = Q * Lp;
-    SpanGuard phase(e, s, TAG_DECODE, 0);
-    HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
-                                e->pol.f32, d, V, c.max_pos, s));
-    for (int l = 0; l < c.dec_layers; ++l) {
-        const DecLayerW& L = e->w.dec[l];
-        RCK(gemm(e, s, e->sc_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
-        HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, e->cur_Nimg, Lp, 0.125f, e->pol.f32, s,
-                                e->ragged ? e->rg_ntok : nullptr));
-        RCK(dec_layer_tail(e, s, L, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
-    }
-    HIPCK(launch_score_targets(tokens, ld, Lp, e->sc_lens, V, M, e->sc_tgt, s));
-    int ntiles = 1;
-    if (e->pol.f32) {
-        // parity mode: logits in chunks of the decode workspace's rows, then one statistics row each
-        const int chunk = round_up(c.max_batch * c.max_beams, 64);
-        for (int r0 = 0; r0 < M; r0 += chunk) {
-            const int rows = std::min(chunk, M - r0);
-            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, rows,
-                     V, d, 0, TAG_GEMM_OTHER));
-            HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
-        }
-    } else {
-        SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
-        ntiles = score_head_tiles(V);
-        HIPCK(launch_score_head(e->sc_ht, d, e->w.out_w, e->w.out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
-    }
-    HIPCK(hipMemsetAsync(e->sc_out, 0, (size_t)Q * ld * sizeof(float2), s));
-    HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
-    HIPCK(launch_score_combine(e->sc_part, ntiles, e->sc_zt, e->sc_tgt, M, Lp, ld, V, e->sc_out, e->sc_bad, s));
-    if (e->ragged) HIPCK(launch_ragged_report(e->rg_meta, e->sc_img, Q, 0, nullptr, nullptr, e->sc_bad, s));
-    HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s));
-    HIPCK(hipMemcpyAsync(rq.logprob, e->sc_out, (size_t)Q * ld * sizeof(float2), hipMemcpyDefault, s));
-    HIPCK(hipMemcpyAsync(rq.info, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
-    return 0;
-}
-
 // ---- attention maps (GITMI_SEARCH_ATTEND) --------------------------------------------------------------------------------
 // The output [Q, ld, layers, Kc] and one layer's statistics [Q, heads, Lp]: allocated by the first attend call, grown when a
 // later call needs more (engines that never attend keep their footprint).  The text pass itself runs in score_alloc's workspaces.
@@ -1319,21 +1280,51 @@ static int call_Nimg(const gitmi_engine* e, const float* const* frames, int F) {
     return (e->cfg.num_frames > 0 ? std::min(F, (int)e->cfg.num_frames) : F) * e->N;
 }
 
-// score_impl's text pass with the probabilities kept instead of the vocabulary head: every layer's attention launch also
-// writes its softmax statistics, and the map kernel turns them into the head-mean probabilities of that layer's slice of
-// at_out [Q, ld, layers, Kc] (zero-filled: rows past a sentence's length, text columns past a row, image columns past a
-// ragged image's own rows stay 0).  The last layer stops after its attention: nothing reads its output.
-static int attend_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
+// vocabulary head of the score pass over the M text rows in sc_ht, reduced to per-row statistics: sc_part [M][*ntiles], sc_zt
+static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles) {
+    const gitmi_config& c = e->cfg;
+    const int d = c.dec_hidden, V = c.vocab;
+    *ntiles = 1;
+    if (e->pol.f32) {
+        // parity mode: logits in chunks of the decode workspace's rows, then one statistics row each
+        const int chunk = round_up(c.max_batch * c.max_beams, 64);
+        for (int r0 = 0; r0 < M; r0 += chunk) {
+            const int rows = std::min(chunk, M - r0);
+            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, rows,
+                     V, d, 0, TAG_GEMM_OTHER));
+            HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
+        }
+    } else {
+        SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
+        *ntiles = score_head_tiles(V);
+        HIPCK(launch_score_head(e->sc_ht, d, e->w.out_w, e->w.out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
+    }
+    return 0;
+}
+// The text pass of GITMI_SEARCH_SCORE / _ATTEND: the textual head over whole sentences (CaptioningModel.forward_one_ce,
+// decoder.py:916-972) after the usual encode + prefill: embedding of every position, then the decoder layers over all text rows
+// at once (generic GEMM + LayerNorm launches, the attention of kernels_score.hip against the prefill's image K/V).  tokens [Q][ld]
+// device int64; lens / image_of already on the device.  score: then the vocabulary head, reduced to (lp, mean_lp) per position
+// in sc_out [Q][ld].  attend: every layer's attention launch also writes its softmax statistics and the map kernel turns them
+// into the head-mean probabilities of the layer's slice of at_out [Q, ld, layers, Kc] (zero-filled first: rows past a sentence's
+// length, text columns past a row, image columns past a ragged image's own rows stay 0); the last layer stops after its
+// attention (nothing reads its output) and there is no head.
+static int text_pass_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, V = c.vocab, Q = rq.Q, L = c.dec_layers;
-    if (rq.frames) RCK(generate_encode(e, rq, s));
-    else if (!e->have_prefill) RCK(prefill_impl(e, s));     // follow-up call: the resident images' K/V
+    const bool attend = rq.sp->kind == GITMI_SEARCH_ATTEND;
+    RCK(images_ready(e, rq, s));
     const int Lp = round_up(rq.maxP, 16), M = Q * Lp;
     const int Nk = e->cur_Nimg, Kc = Nk + ld;
-    const size_t total = (size_t)Q * ld * L * Kc;
+    void* const out = attend ? (void*)e->at_out : (void*)e->sc_out;
+    const size_t out_bytes = attend ? (size_t)Q * ld * L * Kc * sizeof(float) : (size_t)Q * ld * sizeof(float2);
+    auto zero_outputs = [&]() -> int {
+        HIPCK(hipMemsetAsync(out, 0, out_bytes, s));
+        HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
+        return 0;
+    };
     SpanGuard phase(e, s, TAG_DECODE, 0);
-    HIPCK(hipMemsetAsync(e->at_out, 0, total * sizeof(float), s));
-    HIPCK(hipMemsetAsync(e->sc_bad, 0, (size_t)Q * sizeof(int), s));
+    if (attend) RCK(zero_outputs());       // the map kernels of every layer write into it
     HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
                                 e->pol.f32, d, V, c.max_pos, s));
     const int* ntok = e->ragged ? e->rg_ntok : nullptr;
@@ -1341,14 +1332,21 @@ static int attend_impl(gitmi_engine* e, const Request& rq, const long long* toke
         const DecLayerW& W = e->w.dec[l];
         RCK(gemm(e, s, e->sc_ht, d, W.wqkv, W.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
         HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, Nk, Lp, 0.125f, e->pol.f32, s, ntok,
-                                e->at_stats));
-        HIPCK(launch_score_attn_map(e->sc_qkv, e->img_kv[l], e->sc_img, ntok, e->at_stats, e->sc_lens, e->at_out + (size_t)l * Kc,
-                                    (size_t)ld * L * Kc, (size_t)L * Kc, ld, Q, c.dec_heads, Nk, Lp, 0.125f, e->pol.f32, e->sc_bad, s));
-        if (l + 1 < L) RCK(dec_layer_tail(e, s, W, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
+                                attend ? e->at_stats : nullptr));
+        if (attend)
+            HIPCK(launch_score_attn_map(e->sc_qkv, e->img_kv[l], e->sc_img, ntok, e->at_stats, e->sc_lens, e->at_out + (size_t)l * Kc,
+                                        (size_t)ld * L * Kc, (size_t)L * Kc, ld, Q, c.dec_heads, Nk, Lp, 0.125f, e->pol.f32, e->sc_bad, s));
+        if (!attend || l + 1 < L) RCK(dec_layer_tail(e, s, W, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
+    }
+    if (int ntiles = 1; !attend) {
+        HIPCK(launch_score_targets(tokens, ld, Lp, e->sc_lens, V, M, e->sc_tgt, s));
+        RCK(score_head_impl(e, M, s, &ntiles));
+        RCK(zero_outputs());
+        HIPCK(launch_score_combine(e->sc_part, ntiles, e->sc_zt, e->sc_tgt, M, Lp, ld, V, e->sc_out, e->sc_bad, s));
     }
     if (e->ragged) HIPCK(launch_ragged_report(e->rg_meta, e->sc_img, Q, 0, nullptr, nullptr, e->sc_bad, s));
-    HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s, Kc, L));
-    HIPCK(hipMemcpyAsync(rq.logprob, e->at_out, total * sizeof(float), hipMemcpyDefault, s));
+    HIPCK(launch_score_info(e->sc_bad, Q, ld, e->sc_info, s, attend ? Kc : 0, attend ? L : 0));
+    HIPCK(hipMemcpyAsync(rq.logprob, out, out_bytes, hipMemcpyDefault, s));
     HIPCK(hipMemcpyAsync(rq.info, e->sc_info, 4 * sizeof(int), hipMemcpyDefault, s));
     return 0;
 }
@@ -1411,7 +1409,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         // the sentences are whole captions of lengths [minP, maxP]; logprob_out receives (lp, mean_lp) per position, or the maps
         const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, nullptr, logprob_out, info_out, e->out_sent};
         const long long* tokens = (const long long*)prefixes;
-        return settle_residency(e, rq, attend ? attend_impl(e, rq, tokens, ld_prefix, s) : score_impl(e, rq, tokens, ld_prefix, s));
+        return settle_residency(e, rq, text_pass_impl(e, rq, tokens, ld_prefix, s));
     }
     if (!frames) RCK(check_resident(e, "generate_prefixed", B));
     if (!sp || !tokens_out || !logprob_out || !info_out || !prefixes || !prefix_len_host)
