@@ -13,6 +13,12 @@ cannot (PIL hands the interpreter lock back only inside the entropy decoder: mea
     and runs the resize / crop / normalise for all of it in one launch pair per 24 images (gitmi_preprocess_batch).
 
 Nothing here touches the GPU; `tests/test_host.py` runs it on the CPU.
+
+jpeg="gpu" (opt-in; the default "host" is the protocol above, unchanged): a worker runs only the ENTROPY decode of a JPEG
+(jpeg.entropy_decode_into, libgitmi_jpeg_host.so -- plain C++, the worker still never opens the GPU) and leaves a coefficient
+record in the slot; the parent uploads it and the GPU reconstructs the pixels (gitmi_jpeg_reconstruct_batch).  Every slot then
+begins with a SLOT_HEADER that says which of the two it holds: the worker falls back to Pillow RGB in the same slot when the
+stream is not one the fast path takes, the row is not a JPEG, the record does not fit the slot, or the library is missing.
 """
 from __future__ import annotations
 
@@ -46,6 +52,10 @@ TASK = struct.Struct("<qq")                       # (slot, row); slot < 0: stop
 RESULT_BYTES = 256
 RESULT_HEAD = struct.Struct("<qqiii")             # slot, row, H, W, length of the key (or of an error text when H == W == 0)
 KEY_MAX = RESULT_BYTES - RESULT_HEAD.size
+# jpeg="gpu" only: the first SLOT_HEADER_BYTES of a slot = (kind, 0, payload bytes); the payload follows the header
+SLOT_HEADER = struct.Struct("<IIQ")
+SLOT_HEADER_BYTES = 128
+SLOT_RGB, SLOT_COEF = 0, 1
 
 
 def _read_exact(fd: int, n: int) -> bytes:
@@ -58,13 +68,18 @@ def _read_exact(fd: int, n: int) -> bytes:
     return buf
 
 
-def worker_main(tsv_path: str, shm_path: str, shm_size: int, slot_bytes: int, task_fd: int, result_fd: int) -> None:
+def worker_main(tsv_path: str, shm_path: str, shm_size: int, slot_bytes: int, task_fd: int, result_fd: int,
+                jpeg: str = "host") -> None:
     """One worker: fixed-size task records in (shared pipe, one record per read), pixels into the shared staging buffer, one
     fixed-size result record out (a write below PIPE_BUF is atomic: all workers share one result pipe)."""
     from PIL import Image
     mem = _map_shared(shm_path, shm_size)
     offsets = _offsets_of(tsv_path)
     fp = open(tsv_path, "rb")
+    if jpeg == "gpu":
+        _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes, task_fd, result_fd)
+        fp.close()
+        return
 
     def reply(slot, row, h, w, text: bytes):
         text = text[:KEY_MAX]
@@ -96,6 +111,55 @@ def worker_main(tsv_path: str, shm_path: str, shm_size: int, slot_bytes: int, ta
     fp.close()
 
 
+def _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes: int, task_fd: int, result_fd: int) -> None:
+    """worker_main's loop for jpeg="gpu": coefficient record or Pillow RGB behind a SLOT_HEADER."""
+    import ctypes
+    try:                                                        # once per worker; without the library: the Pillow path
+        from . import jpeg as J
+        J.load_host_library()
+    except Exception:
+        J = None
+    base = ctypes.addressof(ctypes.c_char.from_buffer(mem))
+    room = slot_bytes - SLOT_HEADER_BYTES
+
+    def reply(slot, row, h, w, text: bytes):
+        text = text[:KEY_MAX]
+        os.write(result_fd, (RESULT_HEAD.pack(slot, row, h, w, len(text)) + text).ljust(RESULT_BYTES, b"\0"))
+
+    while True:
+        rec = _read_exact(task_fd, TASK.size)
+        if not rec:
+            break
+        slot, row = TASK.unpack(rec)
+        if slot < 0:
+            break
+        try:
+            fp.seek(offsets[row])
+            line = fp.readline()
+            key, b64 = line.rstrip(b"\n").split(b"\t")[:2]
+            raw = base64.b64decode(b64)
+            if len(key) > KEY_MAX:
+                key = b""
+            at = slot * slot_bytes
+            if J is not None and raw[:2] == b"\xff\xd8":
+                rc, info = J.entropy_decode_into(raw, base + at + SLOT_HEADER_BYTES, room)
+                if rc == J.OK:
+                    SLOT_HEADER.pack_into(mem, at, SLOT_COEF, 0, info.record_bytes)
+                    reply(slot, row, info.height, info.width, key)
+                    continue
+            img = Image.open(io.BytesIO(raw)).convert("RGB")
+            w, h = img.size
+            n = h * w * 3
+            if n > room:
+                reply(slot, row, -h, -w, key)
+                continue
+            SLOT_HEADER.pack_into(mem, at, SLOT_RGB, 0, n)
+            mem[at + SLOT_HEADER_BYTES: at + SLOT_HEADER_BYTES + n] = img.tobytes()
+            reply(slot, row, h, w, key)
+        except Exception as exc:
+            reply(slot, row, 0, 0, ("%s: %s" % (type(exc).__name__, exc)).encode("utf-8", "replace"))
+
+
 class DecodePool:
     """slots: number of image slots of `slot_bytes` bytes each in the shared staging buffer.
 
@@ -105,9 +169,12 @@ class DecodePool:
     engine stalls for seconds (measured: 24 forked workers = 0.5k captions/s end to end, the parent blocked in kernel launches);
     multiprocessing's spawn re-imports the parent's __main__ -- torch and all -- in every worker."""
 
-    def __init__(self, tsv_path: str, workers: int, slots: int, slot_bytes: int = 1 << 20):
+    def __init__(self, tsv_path: str, workers: int, slots: int, slot_bytes: int = 1 << 20, jpeg: str = "host"):
         import subprocess
         import sys
+        if jpeg not in ("host", "gpu"):
+            raise ValueError("DecodePool: jpeg must be 'host' or 'gpu', got %r" % (jpeg,))
+        self.jpeg = jpeg
         if not os.path.isfile(os.path.splitext(tsv_path)[0] + ".lineidx.8b"):
             from .tsv_io import build_lineidx
             build_lineidx(tsv_path)
@@ -134,6 +201,8 @@ class DecodePool:
         task_r = [r for r, _ in task_pipes]
         cmd = [sys.executable, "-m", "generativeimage2text_amd.decode_pool", tsv_path, self.path, str(size), str(self.slot_bytes),
                str(result_w)] + [str(fd) for fd in task_r]
+        if jpeg == "gpu":
+            cmd.insert(3, "--jpeg-gpu")
         self.procs = [subprocess.Popen(cmd, env=env, pass_fds=tuple(task_r) + (result_w,), stdin=subprocess.DEVNULL)]
         for fd in task_r:
             os.close(fd)
@@ -159,6 +228,12 @@ class DecodePool:
         if h == 0 and w == 0:
             raise RuntimeError("row %d: %s" % (row, text))
         return slot, row, text, h, w
+
+    def slot_payload(self, slot: int) -> Tuple[int, np.ndarray]:
+        """jpeg="gpu": (SLOT_RGB or SLOT_COEF, the payload bytes of the slot -- a view of the staging buffer)"""
+        at = slot * self.slot_bytes
+        kind, _, n = SLOT_HEADER.unpack_from(self.buffer, at)
+        return kind, self.buffer[at + SLOT_HEADER_BYTES: at + SLOT_HEADER_BYTES + n]
 
     def close(self) -> None:
         """Stop the workers and remove the backing file (the mapping itself goes when its last view does)."""
@@ -197,6 +272,9 @@ if __name__ == "__main__":
     import sys
     from PIL import Image  # noqa: F401  (imported once here; the forked workers share it)
     _a = sys.argv[1:]
+    _jpeg = "host"
+    if _a[0] == "--jpeg-gpu":
+        _jpeg, _a = "gpu", _a[1:]
     _result_fd, _task_fds = int(_a[4]), [int(v) for v in _a[5:]]
     _kids = []
     for _i, _fd in enumerate(_task_fds):
@@ -206,7 +284,10 @@ if __name__ == "__main__":
                 if _other != _fd:
                     os.close(_other)
             try:
-                worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd)
+                if _jpeg == "gpu":
+                    worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd, jpeg="gpu")
+                else:
+                    worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd)
             finally:
                 os._exit(0)
         _kids.append(_pid)

@@ -17,7 +17,9 @@ Differences forced by the environment, not by design:
     headline measures.  "f32" = token ids bit-identical to the reference's fp32 run; "bf16" = BASELINE.json's named operand
     format (+2 % captions/s, 5e-3 of the span on trained-like weights).  Environment read by this module (and by nothing in the
     shared libraries): GIT_VOCAB (vocabulary file or "ids"), GIT_DECODE_THREADS / GIT_DECODE_PROCS / GIT_DECODE_SLOT_MB (host JPEG decoding of the TSV task: threads of the
-    per-image path, worker processes and slot size of the pooled captioning path), the
+    per-image path, worker processes and slot size of the pooled captioning path), GIT_DECODE_JPEG ("gpu": the pooled path's
+    workers run only the entropy decode of a JPEG and the GPU reconstructs the pixels, bit for bit Pillow's; same as
+    gpu_jpeg=True; anything else: Pillow decodes on the host, the default), the
     launcher's RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* (and OMPI_COMM_WORLD_*).
 """
 from __future__ import annotations
@@ -528,20 +530,25 @@ def run_tsv_inference(image_tsv: str, question_tsv: Optional[str], out_tsv: str,
 
 
 def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int, procs: int, crop: int, in_flight: int,
-                           slot_bytes: int = 2 << 20, stats: Optional[dict] = None):
+                           slot_bytes: int = 2 << 20, stats: Optional[dict] = None, gpu_jpeg: bool = False):
     """The host side of the captioning task at the engine's rate: rows [start, end) of `image_tsv` as (keys, fp32 batch
     [n, 3, crop, crop] on the device) in input order.  `procs` worker processes decode straight into a shared staging buffer
     (decode_pool.DecodePool), `in_flight + 2` batches of slots deep; a finished batch is uploaded image by image into ONE
     device buffer (only the bytes used) and transformed by ONE launch pair per 24 images (gitmi_preprocess_batch) --
-    bit-identical to load_image_by_pil + gpu_image_transform per image."""
+    bit-identical to load_image_by_pil + gpu_image_transform per image.
+    gpu_jpeg: the workers leave coefficient records of the JPEGs the fast path takes (DecodePool(jpeg="gpu")); those are
+    uploaded as they are and reconstructed on the device straight into the buffer the transform reads
+    (jpeg.decode_batch_to, one launch pair per 64 images); Pillow RGB slots are uploaded into the same buffer as before."""
     import time
-    from .decode_pool import DecodePool
+    from .decode_pool import DecodePool, SLOT_COEF, SLOT_HEADER_BYTES
     from .engine import preprocess_batch
+    if gpu_jpeg:
+        from . import jpeg as J
     ring = max(2, in_flight) + 2
     n_rows = end - start
     n_batches = (n_rows + batch_size - 1) // batch_size
     t_pool = time.perf_counter()
-    pool = DecodePool(image_tsv, procs, slots=ring * batch_size, slot_bytes=slot_bytes)
+    pool = DecodePool(image_tsv, procs, slots=ring * batch_size, slot_bytes=slot_bytes, **({"jpeg": "gpu"} if gpu_jpeg else {}))
     host = torch.from_numpy(pool.buffer)
     pinned = False
     try:                                            # page-lock the staging buffer: uploads become asynchronous DMA
@@ -551,6 +558,8 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
     if stats is not None:
         stats.update(decode_procs=procs, staging_pinned=pinned, staging_mb=host.numel() >> 20,
                      pool_start_s=time.perf_counter() - t_pool, t_pool_started=time.perf_counter())
+        if gpu_jpeg:
+            stats.update(jpeg_gpu=0, jpeg_fallback=0)
     tsv = None
     try:
         meta = {}                                   # batch -> {position: (key, H, W)}
@@ -591,7 +600,18 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
                 offs.append(offs[-1] + (n + 63) // 64 * 64)
             dev = torch.empty(offs[-1], dtype=torch.uint8, device="cuda")
             desc = []
+            coef_items = []                         # gpu_jpeg: (position, payload view) of the slots that hold coefficients
             for j, (key, h, w, slot) in enumerate(items):
+                if gpu_jpeg and h >= 0:
+                    kind, payload = pool.slot_payload(slot)
+                    at = slot * slot_bytes + SLOT_HEADER_BYTES
+                    payload = host[at: at + payload.size]           # the same bytes as a view of the (page-locked) staging tensor
+                    if kind == SLOT_COEF:
+                        coef_items.append((j, payload))
+                    else:
+                        dev[offs[j]: offs[j] + sizes[j]].copy_(payload, non_blocking=True)
+                    desc.append((offs[j], h, w))
+                    continue
                 if h < 0:                           # did not fit its slot: decoded here (rare; GIT_DECODE_SLOT_MB raises the size)
                     if tsv is None:
                         tsv = TSVFile(image_tsv)
@@ -601,10 +621,22 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
                 else:
                     dev[offs[j]: offs[j] + sizes[j]].copy_(host[slot * slot_bytes: slot * slot_bytes + sizes[j]], non_blocking=True)
                 desc.append((offs[j], h, w))
+            if coef_items:
+                coffs = [0]
+                for _, payload in coef_items:
+                    coffs.append(coffs[-1] + (payload.numel() + 127) // 128 * 128)
+                cbuf = torch.empty(coffs[-1], dtype=torch.uint8, device="cuda")
+                for (_, payload), o in zip(coef_items, coffs):
+                    cbuf[o: o + payload.numel()].copy_(payload, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             uploaded[b % ring] = ev
             t_c = time.perf_counter()
+            if coef_items:
+                J.decode_batch_to(dev, [desc[j] for j, _ in coef_items], cbuf, coffs[:-1])
+            if gpu_jpeg and stats is not None:
+                stats["jpeg_gpu"] += len(coef_items)
+                stats["jpeg_fallback"] += want - len(coef_items)
             out = preprocess_batch(dev, desc, crop)
             if stats is not None:           # where the parent's time goes: waiting for the workers / uploads / the transform launches
                 stats["wait_decode_s"] = stats.get("wait_decode_s", 0.0) + (t_b - t_a)
@@ -633,7 +665,7 @@ class _Mapped:
 
 
 def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, *, checkpoint=None,
-                                  batch_size=64, precision="f16", contexts=4, stats=None, mixed_shapes=False):
+                                  batch_size=64, precision="f16", contexts=4, stats=None, mixed_shapes=False, gpu_jpeg=False):
     """inference.py:134-225.  image_tsv rows: key \\t base64(jpeg).  question_tsv (optional) rows:
     key \\t json list of {'question', 'question_id'}.  Writes out_tsv rows
     key \\t [{"caption": ...}]   or the one-column   {"answer": ..., "question_id": ...}.
@@ -647,8 +679,18 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
     (gitmi_generate_prefixed takes ragged questions about several images) instead of one call per image.
     mixed_shapes: VQA question files are batched ACROSS shapes instead -- up to batch_size images or max_batch questions per
     call, every image at its own size in one ragged engine call (CaptioningModel.submit_ragged); answers are those of the
-    per-shape calls.  The default path is unchanged."""
+    per-shape calls.  The default path is unchanged.
+    gpu_jpeg (or GIT_DECODE_JPEG=gpu): on the pooled captioning path the worker processes run only the entropy decode of a
+    JPEG and the GPU reconstructs the pixels (include/gitmi_jpeg.h) -- the same bytes Pillow returns, hence the same token ids;
+    rows the fast path does not take (progressive, CMYK, PNG, ...) are decoded by Pillow as before.  stats["jpeg_gpu"] /
+    stats["jpeg_fallback"] count the two.  Raises when libgitmi_jpeg*.so have not been built.  The per-image paths (VQA, aspect-
+    preserving models, GIT_DECODE_PROCS=0) decode with Pillow either way."""
     import time
+    gpu_jpeg = bool(gpu_jpeg) or os.environ.get("GIT_DECODE_JPEG", "") == "gpu"
+    if gpu_jpeg:                                # fail here, not in a worker: a missing library is an error, never a quiet fallback
+        from . import jpeg as _jpeg
+        _jpeg.load_host_library()
+        _jpeg.load_gpu_library()
     t_build = time.perf_counter()
     param, from_file = _task_param(model_name, "output")                    # inference.py:135-137
     tokenizer = get_tokenizer()
@@ -727,7 +769,8 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
         crop = int(param.get("test_crop_size", 224))
         slot = int(os.environ.get("GIT_DECODE_SLOT_MB", "2")) << 20
         batch_source = lambda s_, e_: pooled_caption_batches(image_tsv, s_, e_, batch_size, procs, crop,
-                                                             contexts if pipelined else 1, slot_bytes=slot, stats=stats)
+                                                             contexts if pipelined else 1, slot_bytes=slot, stats=stats,
+                                                             **({"gpu_jpeg": True} if gpu_jpeg else {}))
     t_run = time.perf_counter()
     # decode on the pool all the way to the uint8 array the GPU transform uploads (stand-in models of the CPU tests keep PIL images)
     decode = decode_to_array if hasattr(model, "engine") else load_image_by_pil
