@@ -96,7 +96,6 @@ extern "C" int gitmi_op_attention(const void* qkv, void* out, int B, int N, int 
     a.ldq = a.ldk = a.ldv = 3 * D;
     a.ldo = D;
     a.N = N; a.H = H; a.scale = 0.125f;
-    if (attn_decode_configure() != hipSuccess) return fail("configure failed");
     HIPCK(launch_attn_full(a, B, dtype == GITMI_DTYPE_F32, impl, (hipStream_t)stream));
     return 0;
 }
@@ -226,7 +225,7 @@ extern "C" int gitmi_op_attn_decode(const void* qkv, const void* img_k, const vo
     // 1, 2), bits 18.. workgroups of the streaming kernel (0 = register kernels)
     a.scale = 0.125f; a.dbg = dbg & 0xffff; a.waves_per_pair = (dbg >> 16) & 3; a.stream_wgs = dbg >> 18;
     if (dtype == GITMI_DTYPE_F32) {
-        HIPCK(launch_attn_decode(a, B, H, true, (hipStream_t)stream));
+        HIPCK(launch_attn_decode(a, B, H, (hipStream_t)stream));
         return 0;
     }
     // 16-bit: img_k / img_v are the MFMA operand layouts written by gitmi_op_kv_repack (keys padded to 32)
@@ -269,7 +268,7 @@ GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void*
     a.kv_src = kv_src; a.ld_src = T_max; a.d = H * 64; a.N_img = N_img; a.T_max = T_max; a.pos = pos; a.beams = beams;
     a.scale = 0.125f; a.ntok = ntok;
     if (dtype == GITMI_DTYPE_F32) {
-        HIPCK(launch_attn_decode(a, B, H, true, (hipStream_t)stream));
+        HIPCK(launch_attn_decode(a, B, H, (hipStream_t)stream));
         return 0;
     }
     a.N_pad = round_up(N_img, 32);

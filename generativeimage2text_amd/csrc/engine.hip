@@ -234,7 +234,6 @@ extern "C" int gitmi_create(const gitmi_config* cfg, int device, gitmi_engine** 
     if (const char* env = getenv("GITMI_ATTN_DBG")) e->pol.attn_dbg = atoi(env);
     if (const char* env = getenv("GITMI_ATTN_PW")) e->pol.attn_pw = atoi(env);
     if (const char* env = getenv("GITMI_ATTN_NH")) e->pol.attn_nh = atoi(env);
-    if (const char* env = getenv("GITMI_ATTN_PPW")) e->pol.attn_ppw = atoi(env);
     if (const char* env = getenv("GITMI_ATTN_STREAM")) e->pol.attn_stream = atoi(env);
     if (const char* env = getenv("GITMI_DECODE_SKIP")) e->pol.decode_skip = atoi(env);
     if (const char* env = getenv("GITMI_GEMM_TALL")) e->pol.gemm_tall = atoi(env);
@@ -249,7 +248,6 @@ extern "C" int gitmi_create(const gitmi_config* cfg, int device, gitmi_engine** 
 #endif
     e->pol.ln_fold = e->pol.ln_fold && e->pol.stream_f16;
     e->pol.ln_fold_ready = e->pol.ln_fold;
-    if (attn_decode_configure() != hipSuccess) { delete e; return fail("hipFuncSetAttribute failed"); }
     *out = e;
     return 0;
 }
@@ -449,7 +447,7 @@ static int kv_repack(gitmi_engine* e, int l, int B, int Nimg, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     void* kh = e->img_kh[l];
     void* vh = e->img_vh[l];
-    if (e->pol.f32) HIPCK(launch_kv_repack(e->img_kv[l], kh, vh, B, Nimg, c.dec_heads, c.dec_hidden, true, s));
+    if (e->pol.f32) HIPCK(launch_kv_repack(e->img_kv[l], kh, vh, B, Nimg, c.dec_heads, c.dec_hidden, s));
     else HIPCK(launch_kv_repack_frag(e->img_kv[l], kh, vh, B, Nimg, round_up(Nimg, 32), c.dec_heads, c.dec_hidden, s));
     return 0;
 }
@@ -573,7 +571,6 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         a.dbg = e->pol.attn_dbg;
         a.waves_per_pair = e->pol.attn_nh;
         a.pairs_per_wg = e->pol.attn_pw > 0 ? e->pol.attn_pw : e->pol.shared_device ? 8 : 4;
-        a.pairs_per_wave = e->pol.attn_ppw > 0 ? e->pol.attn_ppw : 1;
         // a context that has the device to itself streams the image K/V through LDS rings (kernels_attn_decode.hip: all of a
         // pair's first 36 KiB requested at once, no second memory round trip): 11.7 instead of 15.6 us per launch on 192
         // workgroups.  Same arithmetic as the one-wave register kernel, every fused multiply-add written out in both, so the
@@ -583,7 +580,7 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         const bool stream_ok = !e->pol.shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->pol.attn_nh != 2;
         a.stream_wgs = e->pol.attn_stream >= 0 ? e->pol.attn_stream : stream_ok ? 192 : 0;
         if (e->ragged) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }      // per-image key counts: the register kernels
-        if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, true, s));
+        if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
             if (!GITMI_SKIPPED(e, 4))

@@ -789,38 +789,24 @@ hipError_t launch_attn_full(const AttnFullArgs& a, int B, bool is_f32, int impl,
     return hipGetLastError();
 }
 
-hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, bool is_f32, hipStream_t s) {
+// the f32 mode's head-major K/V cache and decode attention (the 16-bit modes: kernels_attn_decode.hip)
+hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, hipStream_t s) {
     if (B <= 0 || N <= 0) return hipSuccess;
-    const size_t total = 2 * (size_t)B * H * N * (is_f32 ? 16 : 8);
+    const size_t total = 2 * (size_t)B * H * N * 16;
     size_t grid = (total + 255) / 256;
     grid = grid > 8192 ? 8192 : grid;
-    if (is_f32) hipLaunchKernelGGL(kv_repack_kernel<float>, dim3((int)grid), dim3(256), 0, s, (const float*)qkv, (float*)kh,
-                                   (float*)vh, B, N, H, d);
-    else hipLaunchKernelGGL(kv_repack_kernel<bf16_t>, dim3((int)grid), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kh,
-                            (bf16_t*)vh, B, N, H, d);
+    hipLaunchKernelGGL(kv_repack_kernel<float>, dim3((int)grid), dim3(256), 0, s, (const float*)qkv, (float*)kh, (float*)vh, B, N,
+                       H, d);
     return hipGetLastError();
 }
 
-hipError_t attn_decode_configure() { return hipSuccess; }   // (no dynamic LDS any more)
-
-size_t attn_decode_lds_bytes(int beams, int N_img, int pos) {
-    (void)N_img; (void)pos;
-    return sizeof(float) * 4 * (size_t)beams * (HD + 2);
-}
-
-template <typename T>
-static void launch_attn_decode_t(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
-    if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_kernel<T, 1>), dim3(H, B), dim3(256), 0, s, a);
-    else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_kernel<T, 2>), dim3(H, B), dim3(256), 0, s, a);
-    else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_kernel<T, 4>), dim3(H, B), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_decode_kernel<T, 8>), dim3(H, B), dim3(256), 0, s, a);
-}
-
-hipError_t launch_attn_decode(const AttnDecodeArgs& a, int B, int H, bool is_f32, hipStream_t s) {
+hipError_t launch_attn_decode(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.beams > 8) return hipErrorInvalidValue;
-    if (is_f32) launch_attn_decode_t<float>(a, B, H, s);
-    else launch_attn_decode_t<bf16_t>(a, B, H, s);
+    if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_kernel<float, 1>), dim3(H, B), dim3(256), 0, s, a);
+    else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_kernel<float, 2>), dim3(H, B), dim3(256), 0, s, a);
+    else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_kernel<float, 4>), dim3(H, B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<float, 8>), dim3(H, B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

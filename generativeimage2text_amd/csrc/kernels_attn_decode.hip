@@ -21,6 +21,12 @@
 #include "gitmi_common.h"
 #include "launchers.h"
 #include <algorithm>
+#include <type_traits>
+
+// Every fused multiply-add of the softmax bookkeeping is written out (fmaf): with contraction left to the compiler the
+// a*b + c*d updates fuse differently per instantiation, and results must not depend on the packing or the kernel form.
+// File scope: the shared per-pair functions and both kernels are covered.
+#pragma clang fp contract(off)
 
 namespace gitmi {
 
@@ -59,11 +65,285 @@ __global__ __launch_bounds__(256) void kv_repack_frag_kernel(const bf16_t* __res
     *reinterpret_cast<u32x4_t*>(vdst + (((size_t)s * 4 + dt) * 64 + lane) * 8) = ov;
 }
 
-__device__ __forceinline__ void ld8bf(const bf16_t* p, float (&v)[8]) {
-    const u32x4_t r = *reinterpret_cast<const u32x4_t*>(p);
+__device__ __forceinline__ void unpack8(const u32x4_t& r, float (&v)[8]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         unpack2op(r[i], v[2 * i], v[2 * i + 1]);
+    }
+}
+__device__ __forceinline__ void ld8bf(const bf16_t* p, float (&v)[8]) { unpack8(*reinterpret_cast<const u32x4_t*>(p), v); }
+
+// ---- the arithmetic of one (sentence, head) pair, written ONCE for both kernels ---------------------------------------
+// The register kernel and the streaming kernel below differ in how pairs map to waves, where the K/V operands of the MFMAs
+// come from and which barriers their form needs; everything a wave COMPUTES for a pair is in these functions, so the two
+// cannot drift apart (gitmi_set_shared_device's promise of identical results rests on it).  A pair is shared by `ngrp`
+// eight-lane groups (8 per wave); t = thread of the pair, grp = t / 8, sub = t % 8.
+constexpr int ACS = 4;          // key steps per chunk and wave
+
+struct Pair {
+    int h, row0;       // head; first beam row of the sentence
+    bool on;           // false: a packed workgroup's pair past the last one (the wave runs along on zeros, writes nothing)
+};
+
+// K / V of text item (beam j, position s), this lane's 8 dims: the new position from the QKV rows, earlier ones from the
+// text cache through the beam indirection
+template <int KB>
+__device__ __forceinline__ void load_text_kv(const AttnDecodeArgs& a, const Pair& p, int j, int s, int sub, u32x4_t& kr, u32x4_t& vr) {
+    if (s == a.pos) {
+        const bf16_t* src = reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + a.d + p.h * HD + sub * 8;
+        kr = *reinterpret_cast<const u32x4_t*>(src);
+        vr = *reinterpret_cast<const u32x4_t*>(src + a.d);
+    } else {
+        // one beam: histories are never re-ordered, the cache row is the row itself (no dependent index load)
+        const int srow = KB == 1 ? p.row0 : a.kv_src[(size_t)(p.row0 + j) * a.ld_src + s];
+        const size_t off = ((size_t)srow * a.T_max + s) * a.d + p.h * HD + sub * 8;
+        kr = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(a.txt_k) + off);
+        vr = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const bf16_t*>(a.txt_v) + off);
+    }
+}
+
+// the first TI text items of every group, requested up front (item = beam * (pos + 1) + position)
+template <int KB, int TI>
+struct TextItems {
+    int j[TI];                  // beam of item u, -1: none
+    u32x4_t kr[TI], vr[TI];
+    __device__ __forceinline__ void load(const AttnDecodeArgs& a, const Pair& p, int grp, int ngrp, int sub) {
+        const int nt = a.pos + 1;
+#pragma unroll
+        for (int u = 0; u < TI; ++u) {
+            const int it = grp + ngrp * u;
+            j[u] = (p.on && it < a.beams * nt) ? it / nt : -1;
+            const int s = it < a.beams * nt ? it % nt : 0;
+            kr[u] = u32x4_t{0u, 0u, 0u, 0u};
+            vr[u] = kr[u];
+            if (j[u] >= 0) load_text_kv<KB>(a, p, j[u], s, sub, kr[u], vr[u]);
+        }
+    }
+};
+
+// append this position's K/V of every beam to the text cache (16-byte copies by the first beams*8 threads of the pair)
+__device__ __forceinline__ void append_text_cache(const AttnDecodeArgs& a, const Pair& p, int t, int sub) {
+    if (p.on && t < a.beams * 8) {
+        const int j = t >> 3;
+        const bf16_t* src = reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + a.d + p.h * HD + sub * 8;
+        const size_t dst = ((size_t)(p.row0 + j) * a.T_max + a.pos) * a.d + p.h * HD + sub * 8;
+        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_k) + dst) = *reinterpret_cast<const u32x4_t*>(src);
+        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_v) + dst) = *reinterpret_cast<const u32x4_t*>(src + a.d);
+    }
+}
+
+// Q operand of the S MFMAs: lane (row = l15, lg) holds dims ds*32 + lg*8 .. +8 of beam row l15, pre-scaled by 1/8 (exact in bf16)
+__device__ __forceinline__ void load_q_frag(const AttnDecodeArgs& a, const Pair& p, int l15, int lg, bf16x8_t (&qf)[2]) {
+#pragma unroll
+    for (int ds = 0; ds < 2; ++ds) {
+        float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (p.on && l15 < a.beams)
+            ld8bf(reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + l15) * (3 * a.d) + p.h * HD + ds * 32 + lg * 8, qv);
+        u32x4_t t;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = pack2bf(qv[2 * e] * a.scale, qv[2 * e + 1] * a.scale);
+        qf[ds] = __builtin_bit_cast(bf16x8_t, t);
+    }
+}
+
+// running softmax of beam row l15 over the wave's image keys: max, (per-lane partial) sum, O accumulators of the P V MFMAs
+struct ImagePartial {
+    float m, l;
+    f32x4_t o[4];
+    __device__ __forceinline__ void init() {
+        m = -INFINITY;
+        l = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
+    // the two score tiles of key step s (lane (row l15, lg) holds keys 32s + t*16 + lg*4 + r): masks padded keys / steps and
+    // folds the rest into the lane's maximum over the chunk
+    __device__ __forceinline__ static void mask_max(f32x4_t (&sc)[2], int s, int nimg_steps, int n_img, int lg, float& cm) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (s * 32 + t * 16 + lg * 4 + r >= n_img || s >= nimg_steps) sc[t][r] = -INFINITY;   // padded keys / steps
+                cm = fmaxf(cm, sc[t][r]);
+            }
+    }
+    // the row's new max after a chunk with per-lane max cm; every chunk but the first rescales what is accumulated.  Returns
+    // the max the chunk's exponentials are taken against.
+    __device__ __forceinline__ float new_max(float cm, bool rescale) {
+        cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
+        cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
+        const float mn = fmaxf(m, cm);                     // the chunk's first step holds >= 1 real key: mn is finite
+        if (rescale) {
+            const float al = fast_exp(m - mn);
+            l *= al;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) { o[dt][0] *= al; o[dt][1] *= al; o[dt][2] *= al; o[dt][3] *= al; }
+        }
+        m = mn;
+        return mn;
+    }
+    // one key step: its 8 exponentials into the sum, and as the P operand of the step's P V MFMAs
+    __device__ __forceinline__ bf16x8_t p_frag(const f32x4_t (&sc)[2], float mn) {
+        float p[8];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                p[t * 4 + r] = fast_exp(sc[t][r] - mn);    // exp(-inf) = 0 for padded keys
+                l += p[t * 4 + r];
+            }
+        u32x4_t pp;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pp[e] = pack2bf(p[2 * e], p[2 * e + 1]);
+        return __builtin_bit_cast(bf16x8_t, pp);
+    }
+    // after the last chunk: the row's sum over the four lane groups
+    __device__ __forceinline__ void finish() {
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+    }
+    // to the wave's LDS slot [beam]: o[64], m, l.  Lane (row l15 < beams, lg) holds dims dt*16 + lg*4 + r
+    template <int KB>
+    __device__ __forceinline__ void publish(float (&slot)[KB][HD + 2], int k, int l15, int lg) const {
+        if (l15 < k) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) slot[l15][dt * 16 + lg * 4 + r] = o[dt][r];
+            if (lg == 0) { slot[l15][HD] = m; slot[l15][HD + 1] = l; }
+        }
+    }
+};
+
+// text keys (beam-specific): 8 lanes per key, online update per beam row; this lane's 8 dims of q (pre-scaled) and o
+template <int KB>
+struct TextPartial {
+    float q[KB][8], m[KB], l[KB], o[KB][8];
+    __device__ __forceinline__ void init(const AttnDecodeArgs& a, const Pair& p, int sub) {
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+            m[j] = -INFINITY;
+            l[j] = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { q[j][e] = 0.f; o[j][e] = 0.f; }
+            if (p.on && j < a.beams) {
+                ld8bf(reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + p.h * HD + sub * 8, q[j]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) q[j][e] *= a.scale;
+            }
+        }
+    }
+    // one key of beam jj (uniform within the 8-lane group)
+    __device__ __forceinline__ void item(int jj, const u32x4_t& kr, const u32x4_t& vr) {
+        float kv[8], vv[8];
+        unpack8(kr, kv);
+        unpack8(vr, vv);
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+            if (j == jj) {
+                float sv = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sv = fmaf(q[j][e], kv[e], sv);
+                sv += __shfl_xor(sv, 1, 64);
+                sv += __shfl_xor(sv, 2, 64);
+                sv += __shfl_xor(sv, 4, 64);                // all 8 lanes of the group hold the 64-dim dot product
+                const float mn = fmaxf(m[j], sv);
+                const float al = fast_exp(m[j] - mn);
+                const float pe = fast_exp(sv - mn);
+                l[j] = fmaf(l[j], al, pe);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[j][e] = fmaf(o[j][e], al, pe * vv[e]);
+                m[j] = mn;
+            }
+        }
+    }
+    template <int TI>
+    __device__ __forceinline__ void items(const TextItems<KB, TI>& ti, bool enabled) {
+#pragma unroll
+        for (int u = 0; u < TI; ++u) {
+            if (ti.j[u] >= 0 && enabled) item(ti.j[u], ti.kr[u], ti.vr[u]);
+        }
+    }
+    // long texts: the items past the TI up-front ones, on a dependent-load path
+    template <int TI>
+    __device__ __forceinline__ void tail(const AttnDecodeArgs& a, const Pair& p, int grp, int ngrp, int sub) {
+        if (!p.on) return;
+        const int nt = a.pos + 1;
+        for (int it = grp + ngrp * TI; it < a.beams * nt; it += ngrp) {
+            u32x4_t kr, vr;
+            load_text_kv<KB>(a, p, it / nt, it % nt, sub, kr, vr);
+            item(it / nt, kr, vr);
+        }
+    }
+    // merge the 8 groups of the wave (lanes with equal `sub`): lanes 0..7 end up with the wave's text partial (m, l, o[8])
+    __device__ __forceinline__ void merge_groups() {
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+#pragma unroll
+            for (int off = 8; off < 64; off <<= 1) {
+                const float m2 = __shfl_xor(m[j], off, 64);
+                const float l2 = __shfl_xor(l[j], off, 64);
+                const float mn = fmaxf(m[j], m2);
+                const float a1 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
+                const float a2 = m2 == -INFINITY ? 0.f : fast_exp(m2 - mn);
+                l[j] = fmaf(l[j], a1, l2 * a2);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float o2 = __shfl_xor(o[j][e], off, 64);
+                    o[j][e] = fmaf(o[j][e], a1, o2 * a2);
+                }
+                m[j] = mn;
+            }
+        }
+    }
+    // fold the wave's text partial into its published image partial (lanes 0..7, one beam row at a time; text part: lanes
+    // 0..7 hold dims sub*8 + e of row j)
+    __device__ __forceinline__ void fold_into(float (&slot)[KB][HD + 2], int k, int lane, int sub) const {
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+            if (lane < 8 && j < k) {
+                const float mi = slot[j][HD], li = slot[j][HD + 1];
+                const float mn = fmaxf(mi, m[j]);
+                const float a1 = mi == -INFINITY ? 0.f : fast_exp(mi - mn);
+                const float a2 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) slot[j][sub * 8 + e] = fmaf(slot[j][sub * 8 + e], a1, o[j][e] * a2);
+                if (sub == 0) { slot[j][HD] = mn; slot[j][HD + 1] = fmaf(li, a1, l[j] * a2); }
+            }
+        }
+    }
+};
+
+__device__ __forceinline__ void store_out(const AttnDecodeArgs& a, int row, int col, float r) {
+    bf16_t* O = reinterpret_cast<bf16_t*>(a.out);
+    if (a.out_frag) O[frag_offset(row, col, a.d >> 5)] = f2bf(r);
+    else O[(size_t)row * a.d + col] = f2bf(r);
+}
+// the pair's output rows from ONE partial per row (one wave per pair); nthr threads of the pair, this is thread t
+template <int KB>
+__device__ __forceinline__ void write_rows(const AttnDecodeArgs& a, const Pair& p, const float (&s0)[KB][HD + 2], int t, int nthr) {
+    if (!p.on) return;
+    for (int i = t; i < a.beams * HD; i += nthr) {
+        const int j = i / HD, dd = i % HD;
+        const float r1 = s0[j][dd] / s0[j][HD + 1];
+        store_out(a, p.row0 + j, p.h * HD + dd, r1);
+    }
+}
+// ... from the partials of the two waves that split the pair's key steps
+template <int KB>
+__device__ __forceinline__ void write_rows(const AttnDecodeArgs& a, const Pair& p, const float (&s0)[KB][HD + 2],
+                                           const float (&s1)[KB][HD + 2], int t, int nthr) {
+    if (!p.on) return;
+    for (int i = t; i < a.beams * HD; i += nthr) {
+        const int j = i / HD, dd = i % HD;
+        const float m0 = s0[j][HD], m1 = s1[j][HD];
+        const float mm = fmaxf(m0, m1);
+        const float a0 = m0 == -INFINITY ? 0.f : fast_exp(m0 - mm);
+        const float a1 = m1 == -INFINITY ? 0.f : fast_exp(m1 - mm);
+        const float num = fmaf(a0, s0[j][dd], a1 * s1[j][dd]);
+        const float den = fmaf(a0, s0[j][HD + 1], a1 * s1[j][HD + 1]);
+        const float r = num / den;
+        store_out(a, p.row0 + j, p.h * HD + dd, r);
     }
 }
 
@@ -72,23 +352,16 @@ __device__ __forceinline__ void ld8bf(const bf16_t* p, float (&v)[8]) {
 // and its text items; each wave requests ALL of its image K/V fragments (up to 4 steps = 32 sixteen-byte loads per
 // lane) in its first instructions, computes every score tile, does ONE max / exp pass and then the P V products; the two
 // halves meet once in LDS.  KB >= beams (1, 2, 4 or 8); TI: text items per 8-lane group loaded up front.
-constexpr int ACS = 4;          // key steps per chunk and wave
-
+//
 // PW: (sentence, head) pairs per workgroup (a wave needs 214 registers, so 8 waves fill a CU).  1 spreads a launch over
 // every CU (fastest on an idle device); next to the image encoder of another context every CU that holds even one of
 // these waves is closed to a GEMM workgroup (8 waves x 232 registers, 128 KiB LDS) until the wave retires, so the launcher
 // packs the one-wave kernel (launch_attn_decode_mfma).
 // NH: waves per pair.  2 = the two waves of a head split its key steps (one memory round trip each); 1 = ONE wave walks
 // all key steps in chunks of ACS (two round trips at 197 image keys): half the resident waves for ~1.3x the time.
-// LOOP (packed one-wave form only): a wave serves a.pairs_per_wave pairs one after the other, the next pair's first K/V
-// chunk requested while the current pair's merge and output are worked off.  A separate instantiation: the loop-carried
-// K/V registers cost the 512-thread form a few spilled registers, which the single-pair form must not pay.
 // RAGGED: a.ntok gives every image's keys (a separate instantiation: the uniform ones are the kernels as they were)
-template <int KB, int TI = 3, int PW = 1, int NH = 2, bool LOOP = false, bool RAGGED = false>
+template <int KB, int TI = 3, int PW = 1, int NH = 2, bool RAGGED = false>
 __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDecodeArgs a) {
-    // every fused multiply-add of the softmax bookkeeping is written out (fmaf): with contraction left to the compiler the
-    // a*b + c*d updates fuse differently per instantiation, and results must not depend on the packing or the kernel form
-#pragma clang fp contract(off)
     __shared__ float part[PW][NH][KB][HD + 2];    // [pair][half][beam]: o[64], m, l
     constexpr int PT = 64 * NH;                   // threads of a pair
 
@@ -97,42 +370,30 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
     const int hp = wave / NH, half = wave % NH;    // pair of the workgroup, half of the head's keys
     const int H = a.d / HD;
     const int k = a.beams;                       // k <= KB <= 8 < 16 MFMA rows
-    const bf16_t* QKV = reinterpret_cast<const bf16_t*>(a.qkv);
-    bf16_t* TK = reinterpret_cast<bf16_t*>(a.txt_k);
-    bf16_t* TV = reinterpret_cast<bf16_t*>(a.txt_v);
-    bf16_t* O = reinterpret_cast<bf16_t*>(a.out);
-    const int ld3 = 3 * a.d;
     const int Np = a.N_pad, nsteps = Np >> 5;
-    // a wave serves `reps` pairs one after the other (launcher: 1 unless the one-wave kernel is packed further): pair index
-    // of repetition r.  PW == 1 keeps the (head, sentence) grid of the two-wave kernel.
-    const int reps = LOOP ? a.pairs_per_wave : 1;
-    auto pair_of = [&](int r) {
-        if constexpr (NH == 2) return (int)(blockIdx.y * H + blockIdx.x);      // grid = (H, sentences)
-        else return ((int)blockIdx.x * reps + r) * PW + hp;
-    };
-    struct PairKV { const bf16_t* Kf; const bf16_t* Vt; int nimg_steps, n_img; };
-    auto kv_of = [&](int pair) {
-        const bool on = PW == 1 || pair < a.n_pairs;
-        const int h = on ? pair % H : 0, b = on ? pair / H : 0;
-        const int bi = a.img_of ? a.img_of[b] : b;   // sentence -> image (several questions per image)
-        PairKV r;
-        r.Kf = reinterpret_cast<const bf16_t*>(a.img_k) + ((size_t)bi * H + h) * Np * HD;
-        r.Vt = reinterpret_cast<const bf16_t*>(a.img_v) + ((size_t)bi * H + h) * Np * HD;
-        // ragged batches: the image's own keys; its 32-key steps past them are skipped (N_pad stays the row stride)
-        r.n_img = RAGGED ? a.ntok[bi] : a.N_img;
-        r.nimg_steps = (!on || (a.dbg & 1)) ? 0 : RAGGED ? (r.n_img + 31) >> 5 : nsteps;
-        return r;
-    };
+    // PW == 1 keeps the (head, sentence) grid of the two-wave kernel; packed workgroups: the last one's pairs may not exist
+    const int pair = NH == 2 ? (int)(blockIdx.y * H + blockIdx.x) : (int)blockIdx.x * PW + hp;
+    Pair p;
+    p.on = PW == 1 || pair < a.n_pairs;
+    p.h = p.on ? pair % H : 0;
+    const int b = p.on ? pair / H : 0;
+    p.row0 = b * k;
+    const int bi = a.img_of ? a.img_of[b] : b;   // sentence -> image (several questions per image)
+    const bf16_t* Kf = reinterpret_cast<const bf16_t*>(a.img_k) + ((size_t)bi * H + p.h) * Np * HD;
+    const bf16_t* Vt = reinterpret_cast<const bf16_t*>(a.img_v) + ((size_t)bi * H + p.h) * Np * HD;
+    // ragged batches: the image's own keys; its 32-key steps past them are skipped (N_pad stays the row stride)
+    const int n_img = RAGGED ? a.ntok[bi] : a.N_img;
+    const int nimg_steps = (!p.on || (a.dbg & 1)) ? 0 : RAGGED ? (n_img + 31) >> 5 : nsteps;
 
     // ---- image K/V of a chunk of key steps: requested before anything else (the longest latency) ---------------
     bf16x8_t kq[ACS][2][2], vq[ACS][4];
-    auto load_chunk = [&](const PairKV& p, int s0) {              // steps s0, s0 + NH, ... (this half's parity)
+    auto load_chunk = [&](int s0) {                               // steps s0, s0 + NH, ... (this half's parity)
 #pragma unroll
         for (int c = 0; c < ACS; ++c) {
             const int s = s0 + NH * c;
-            const bool on = s < p.nimg_steps && !(a.dbg & 8);
-            const bf16_t* kp = p.Kf + frag_tile(2 * s, 0, 2, lane);            // the step's 4 KiB of K, then of V^T: contiguous
-            const bf16_t* vp = p.Vt + ((size_t)s * 4 * 64 + lane) * 8;
+            const bool on = s < nimg_steps && !(a.dbg & 8);
+            const bf16_t* kp = Kf + frag_tile(2 * s, 0, 2, lane);              // the step's 4 KiB of K, then of V^T: contiguous
+            const bf16_t* vp = Vt + ((size_t)s * 4 * 64 + lane) * 8;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -147,116 +408,36 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
             }
         }
     };
-    PairKV cur = kv_of(pair_of(0));
-    load_chunk(cur, half);
+    load_chunk(half);
 
-  for (int rep = 0; rep < reps; ++rep) {
-    const int pair = pair_of(rep);
-    const bool head_on = PW == 1 || pair < a.n_pairs;
-    const int h = head_on ? pair % H : 0, b = head_on ? pair / H : 0;
-    const int row0 = b * k;
-    const int nimg_steps = cur.nimg_steps, n_img = cur.n_img;
-    if constexpr (LOOP) {
-        if (rep > 0 && (a.dbg & 32)) load_chunk(cur, half);
-    }
-
-    // ---- text items: the 16 eight-lane groups of the head's two waves share them ----------------------------------
-    const int grp = (tid % PT) >> 3, sub = tid & 7;      // 8 * NH eight-lane groups per pair
-    const int nt = a.pos + 1;
-    int t_j[TI], t_s[TI];
-    u32x4_t tkr[TI], tvr[TI];
-#pragma unroll
-    for (int u = 0; u < TI; ++u) {
-        const int it = grp + 8 * NH * u;
-        t_j[u] = (head_on && it < k * nt) ? it / nt : -1;
-        t_s[u] = it < k * nt ? it % nt : 0;
-        tkr[u] = u32x4_t{0u, 0u, 0u, 0u};
-        tvr[u] = tkr[u];
-        if (t_j[u] >= 0) {
-            if (t_s[u] == a.pos) {
-                const bf16_t* src = QKV + (size_t)(row0 + t_j[u]) * ld3 + a.d + h * HD + sub * 8;
-                tkr[u] = *reinterpret_cast<const u32x4_t*>(src);
-                tvr[u] = *reinterpret_cast<const u32x4_t*>(src + a.d);
-            } else {
-                // one beam: histories are never re-ordered, the cache row is the row itself (no dependent index load)
-                const int srow = KB == 1 ? row0 : a.kv_src[(size_t)(row0 + t_j[u]) * a.ld_src + t_s[u]];
-                const size_t off = ((size_t)srow * a.T_max + t_s[u]) * a.d + h * HD + sub * 8;
-                tkr[u] = *reinterpret_cast<const u32x4_t*>(TK + off);
-                tvr[u] = *reinterpret_cast<const u32x4_t*>(TV + off);
-            }
-        }
-    }
-    // append this position's K/V of every beam to the text cache (16-byte copies by the first k*8 threads of the head)
-    if (head_on && (tid % PT) < k * 8) {
-        const int j = (tid % PT) >> 3;
-        const bf16_t* src = QKV + (size_t)(row0 + j) * ld3 + a.d + h * HD + sub * 8;
-        const size_t dst = ((size_t)(row0 + j) * a.T_max + a.pos) * a.d + h * HD + sub * 8;
-        *reinterpret_cast<u32x4_t*>(TK + dst) = *reinterpret_cast<const u32x4_t*>(src);
-        *reinterpret_cast<u32x4_t*>(TV + dst) = *reinterpret_cast<const u32x4_t*>(src + a.d);
-    }
+    // ---- text items (the 8 * NH eight-lane groups of the pair share them), text-cache append, Q operand -------------
+    const int t = tid % PT, grp = t >> 3, sub = tid & 7;
+    TextItems<KB, TI> ti;
+    ti.load(a, p, grp, 8 * NH, sub);
+    append_text_cache(a, p, t, sub);
+    bf16x8_t qf[2];
+    load_q_frag(a, p, l15, lg, qf);
 
     // ---- image part on the matrix cores -------------------------------------------------------------------------
-    // Q operand: lane (row = l15, lg) holds dims ds*32 + lg*8 .. +8 of beam row l15, pre-scaled by 1/8 (exact in bf16)
-    bf16x8_t qf[2];
-#pragma unroll
-    for (int ds = 0; ds < 2; ++ds) {
-        float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (head_on && l15 < k) ld8bf(QKV + (size_t)(row0 + l15) * ld3 + h * HD + ds * 32 + lg * 8, qv);
-        u32x4_t t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[e] = pack2bf(qv[2 * e] * a.scale, qv[2 * e + 1] * a.scale);
-        qf[ds] = __builtin_bit_cast(bf16x8_t, t);
-    }
-    float m_i = -INFINITY, l_i = 0.f;            // running max / (per-lane partial) sum of beam row l15
-    f32x4_t oacc[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
+    ImagePartial ip;
+    ip.init();
     for (int s0 = half; s0 < nimg_steps; s0 += NH * ACS) {
-        if (s0 != half) load_chunk(cur, s0);               // later chunks (long image sequences: video, VQA resolutions)
-        // every score tile of the chunk: lane (row l15, lg) holds keys 32s + t*16 + lg*4 + r
-        f32x4_t sc[ACS][2];
+        if (s0 != half) load_chunk(s0);                    // later chunks (long image sequences: video, VQA resolutions)
+        f32x4_t sc[ACS][2];                                // every score tile of the chunk
         float cm = -INFINITY;
 #pragma unroll
         for (int c = 0; c < ACS; ++c) {
-            const int s = s0 + NH * c;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                sc[c][t] = mfma16(kq[c][t][0], qf[0], f32x4_t{0.f, 0.f, 0.f, 0.f});
-                sc[c][t] = mfma16(kq[c][t][1], qf[1], sc[c][t]);
+            for (int u = 0; u < 2; ++u) {
+                sc[c][u] = mfma16(kq[c][u][0], qf[0], f32x4_t{0.f, 0.f, 0.f, 0.f});
+                sc[c][u] = mfma16(kq[c][u][1], qf[1], sc[c][u]);
             }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (s * 32 + t * 16 + lg * 4 + r >= (RAGGED ? n_img : a.N_img) || s >= nimg_steps) sc[c][t][r] = -INFINITY;   // padded keys / steps
-                    cm = fmaxf(cm, sc[c][t][r]);
-                }
+            ip.mask_max(sc[c], s0 + NH * c, nimg_steps, RAGGED ? n_img : a.N_img, lg, cm);
         }
-        cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
-        cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-        const float mn = fmaxf(m_i, cm);                   // the chunk's first step holds >= 1 real key: mn is finite
-        if (s0 != half) {
-            const float al = fast_exp(m_i - mn);
-            l_i *= al;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) { oacc[dt][0] *= al; oacc[dt][1] *= al; oacc[dt][2] *= al; oacc[dt][3] *= al; }
-        }
-        m_i = mn;
+        const float mn = ip.new_max(cm, s0 != half);
 #pragma unroll
         for (int c = 0; c < ACS; ++c) {
-            float p[8];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    p[t * 4 + r] = fast_exp(sc[c][t][r] - mn);    // exp(-inf) = 0 for padded keys
-                    l_i += p[t * 4 + r];
-                }
-            u32x4_t pp;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pp[e] = pack2bf(p[2 * e], p[2 * e + 1]);
-            const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pp);
+            const bf16x8_t pf = ip.p_frag(sc[c], mn);
             if (a.dbg & 4) {      // timing experiment: no P V product
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) asm volatile("" ::"v"(vq[c][dt]));
@@ -264,154 +445,24 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
                 continue;
             }
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma16(vq[c][dt], pf, oacc[dt]);
+            for (int dt = 0; dt < 4; ++dt) ip.o[dt] = mfma16(vq[c][dt], pf, ip.o[dt]);
         }
     }
-    l_i += __shfl_xor(l_i, 16, 64);
-    l_i += __shfl_xor(l_i, 32, 64);
-    // ---- text keys (beam-specific): 8 lanes per key, online update -------------------------------------------------
-    float q[KB][8], m[KB], l[KB], o[KB][8];
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-        m[j] = -INFINITY;
-        l[j] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { q[j][e] = 0.f; o[j][e] = 0.f; }
-        if (head_on && j < k) {
-            ld8bf(QKV + (size_t)(row0 + j) * ld3 + h * HD + sub * 8, q[j]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q[j][e] *= a.scale;
-        }
-    }
-    auto dot8 = [&](const float (&x)[8], const float (&y)[8]) {
-        float p = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p = fmaf(x[e], y[e], p);
-        p += __shfl_xor(p, 1, 64);
-        p += __shfl_xor(p, 2, 64);
-        p += __shfl_xor(p, 4, 64);
-        return p;                                   // all 8 lanes of the group hold the 64-dim dot product
-    };
-    auto text_item = [&](int jj, const float (&kv)[8], const float (&vv)[8]) {
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            if (j == jj) {                              // uniform within the 8-lane group
-                const float sv = dot8(q[j], kv);
-                const float mn = fmaxf(m[j], sv);
-                const float al = fast_exp(m[j] - mn);
-                const float p = fast_exp(sv - mn);
-                l[j] = fmaf(l[j], al, p);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[j][e] = fmaf(o[j][e], al, p * vv[e]);
-                m[j] = mn;
-            }
-        }
-    };
-    auto unpack = [&](const u32x4_t& r, float (&v)[8]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            unpack2op(r[i], v[2 * i], v[2 * i + 1]);
-        }
-    };
-#pragma unroll
-    for (int u = 0; u < TI; ++u) {
-        if (t_j[u] >= 0 && !(a.dbg & 2)) {
-            float kv[8], vv[8];
-            unpack(tkr[u], kv);
-            unpack(tvr[u], vv);
-            text_item(t_j[u], kv, vv);
-        }
-    }
-    if (head_on) {
-        for (int it = grp + 8 * NH * TI; it < k * nt; it += 8 * NH) {   // long texts: dependent-load path
-            const int j = it / nt, sidx = it % nt;
-            float kv[8], vv[8];
-            if (sidx == a.pos) {
-                ld8bf(QKV + (size_t)(row0 + j) * ld3 + a.d + h * HD + sub * 8, kv);
-                ld8bf(QKV + (size_t)(row0 + j) * ld3 + 2 * a.d + h * HD + sub * 8, vv);
-            } else {
-                const int srow = KB == 1 ? row0 : a.kv_src[(size_t)(row0 + j) * a.ld_src + sidx];
-                ld8bf(TK + ((size_t)srow * a.T_max + sidx) * a.d + h * HD + sub * 8, kv);
-                ld8bf(TV + ((size_t)srow * a.T_max + sidx) * a.d + h * HD + sub * 8, vv);
-            }
-            text_item(j, kv, vv);
-        }
-    }
-    // the K/V registers (and the text items) are free: the first chunk of the wave's NEXT pair travels while this pair's
-    // merge and output are worked off (requested any earlier -- behind the image part -- the 512-thread form spills)
-    if constexpr (LOOP) {
-        if (rep + 1 < reps) {
-            cur = kv_of(pair_of(rep + 1));
-            if (!(a.dbg & 32)) load_chunk(cur, half);      // dbg 32 (A/B): no look-ahead, the chunk is requested at the top of the pair
-        }
-    }
-    // merge the 8 groups of the wave (lanes with equal `sub`): lanes 0..7 end up with the wave's text partial (m, l, o[8])
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-#pragma unroll
-        for (int off = 8; off < 64; off <<= 1) {
-            const float m2 = __shfl_xor(m[j], off, 64);
-            const float l2 = __shfl_xor(l[j], off, 64);
-            const float mn = fmaxf(m[j], m2);
-            const float a1 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
-            const float a2 = m2 == -INFINITY ? 0.f : fast_exp(m2 - mn);
-            l[j] = fmaf(l[j], a1, l2 * a2);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float o2 = __shfl_xor(o[j][e], off, 64);
-                o[j][e] = fmaf(o[j][e], a1, o2 * a2);
-            }
-            m[j] = mn;
-        }
-    }
-    // ---- this wave's partial per beam row = its image keys + its text items, published to LDS ----------------------
-    // image part: lane (row l15 < k, lg) holds dims dt*16 + lg*4 + r; text part: lanes 0..7 hold dims sub*8 + e of row j
-    if (l15 < k) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) part[hp][half][l15][dt * 16 + lg * 4 + r] = oacc[dt][r];
-        if (lg == 0) { part[hp][half][l15][HD] = m_i; part[hp][half][l15][HD + 1] = l_i; }
-    }
+    ip.finish();
+    // ---- text keys ------------------------------------------------------------------------------------------------
+    TextPartial<KB> tp;
+    tp.init(a, p, sub);
+    tp.items(ti, !(a.dbg & 2));
+    tp.template tail<TI>(a, p, grp, 8 * NH, sub);
+    tp.merge_groups();
+    // ---- this wave's partial per beam row = its image keys + its text items, through LDS ----------------------------
+    ip.publish(part[hp][half], k, l15, lg);
     // NH == 1: a wave reads back only what it wrote itself (LDS operations of a wave complete in order): no workgroup barrier
-    // -- a __syncthreads() here would also wait for the next pair's K/V loads
     if constexpr (NH > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
-    // fold the text partial of this wave into its slot (lanes 0..7, one beam row at a time), then combine the halves
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-        if (lane < 8 && j < k) {
-            const float mi = part[hp][half][j][HD], li = part[hp][half][j][HD + 1];
-            const float mn = fmaxf(mi, m[j]);
-            const float a1 = mi == -INFINITY ? 0.f : fast_exp(mi - mn);
-            const float a2 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) part[hp][half][j][sub * 8 + e] = fmaf(part[hp][half][j][sub * 8 + e], a1, o[j][e] * a2);
-            if (sub == 0) { part[hp][half][j][HD] = mn; part[hp][half][j][HD + 1] = fmaf(li, a1, l[j] * a2); }
-        }
-    }
+    tp.fold_into(part[hp][half], k, lane, sub);
     if constexpr (NH > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
-    if (head_on)
-    for (int i = tid % PT; i < k * HD; i += PT) {
-        const int j = i / HD, dd = i % HD;
-        if constexpr (NH == 1) {
-            const float r1 = part[hp][0][j][dd] / part[hp][0][j][HD + 1];
-            if (a.out_frag) O[frag_offset(row0 + j, h * HD + dd, a.d >> 5)] = f2bf(r1);
-            else O[(size_t)(row0 + j) * a.d + h * HD + dd] = f2bf(r1);
-            continue;
-        }
-        constexpr int H1 = NH - 1;
-        const float m0 = part[hp][0][j][HD], m1 = part[hp][H1][j][HD];
-        const float mm = fmaxf(m0, m1);
-        const float a0 = m0 == -INFINITY ? 0.f : fast_exp(m0 - mm);
-        const float a1 = m1 == -INFINITY ? 0.f : fast_exp(m1 - mm);
-        const float num = fmaf(a0, part[hp][0][j][dd], a1 * part[hp][H1][j][dd]);
-        const float den = fmaf(a0, part[hp][0][j][HD + 1], a1 * part[hp][H1][j][HD + 1]);
-        const float r = num / den;
-        if (a.out_frag) O[frag_offset(row0 + j, h * HD + dd, a.d >> 5)] = f2bf(r);
-        else O[(size_t)(row0 + j) * a.d + h * HD + dd] = f2bf(r);
-    }
-    if constexpr (NH == 1) __builtin_amdgcn_wave_barrier();      // the next pair reuses this wave's LDS slot
-  }
+    if constexpr (NH == 1) write_rows(a, p, part[hp][0], t, PT);
+    else write_rows(a, p, part[hp][0], part[hp][NH - 1], t, PT);
 }
 
 // ---- streaming form of the one-wave kernel -----------------------------------------------------------------------
@@ -426,9 +477,9 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
 // RING slots ahead of the consumer, across chunk AND pair boundaries: the stream never drains between pairs, text keys,
 // merge and output of one pair are worked off while the next pair's slots land.  A wave holds ~100 registers instead of
 // 215, a workgroup is 4 waves x RING x 4 KiB of LDS = one per CU.
-// The arithmetic is the one-wave kernel's, operation for operation (same chunks of ACS key steps, same max / rescale
-// order, every fused multiply-add of the bookkeeping written out with `fp contract(off)` + explicit fmaf in BOTH kernels), so
-// the two agree BIT FOR BIT over whole decodes: the engine selects between them by policy (engine.hip: streaming for a
+// The arithmetic is the one-wave kernel's because it is the same code: both kernels call the per-pair functions above
+// (TextItems, ImagePartial, TextPartial, write_rows; same chunks of ACS key steps, same max / rescale order), so the
+// two agree BIT FOR BIT over whole decodes: the engine selects between them by policy (engine.hip: streaming for a
 // context alone with >= 384 (sentence, head) pairs and <= 256 padded keys, the register form otherwise), and
 // gitmi_set_shared_device's promise of identical results rests on it.  Guards: tests/test_gpu_ops.py (streaming == register
 // kernel on the unit entry) and tests/test_gpu_policy.py::test_shared_device_policy_is_bitwise_neutral (features, ids and
@@ -463,7 +514,6 @@ constexpr int AS_SLOT = 4096;                  // bytes: K or V^T of one 32-key 
 
 template <int KB, int TI, int RING>
 __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnDecodeArgs a) {
-#pragma clang fp contract(off)
     static_assert(RING >= 2 && RING <= 12, "ring depth");
     __shared__ __attribute__((aligned(16))) unsigned char ring_mem[AS_WAVES][RING * AS_SLOT];
     __shared__ float part[AS_WAVES][KB][HD + 2];   // [wave][beam]: o[64], m, l
@@ -473,11 +523,6 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
     const int l15 = lane & 15, lg = lane >> 4;
     const int H = a.d / HD;
     const int k = a.beams;
-    const bf16_t* QKV = reinterpret_cast<const bf16_t*>(a.qkv);
-    bf16_t* TK = reinterpret_cast<bf16_t*>(a.txt_k);
-    bf16_t* TV = reinterpret_cast<bf16_t*>(a.txt_v);
-    bf16_t* O = reinterpret_cast<bf16_t*>(a.out);
-    const int ld3 = 3 * a.d;
     const int Np = a.N_pad, nsteps = Np >> 5;
     unsigned char* ring = ring_mem[wave];
 
@@ -534,68 +579,28 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
         issue_slot();
     };
 
+
     for (int ord = 0; ord < npw; ++ord) {
         const int pair = w0 + ord * W;
-        const int h = pair % H, b = pair / H;
-        const int row0 = b * k;
+        const Pair p{pair % H, (pair / H) * k, true};
 
-        // ---- text items: the 8 eight-lane groups of the wave share them -------------------------------------------
+        // ---- text items (the 8 eight-lane groups of the wave share them), text-cache append, Q operand -------------
         const int grp = lane >> 3, sub = lane & 7;
-        const int nt = a.pos + 1;
-        int t_j[TI], t_s[TI];
-        u32x4_t tkr[TI], tvr[TI];
-#pragma unroll
-        for (int u = 0; u < TI; ++u) {
-            const int it = grp + 8 * u;
-            t_j[u] = it < k * nt ? it / nt : -1;
-            t_s[u] = it < k * nt ? it % nt : 0;
-            tkr[u] = u32x4_t{0u, 0u, 0u, 0u};
-            tvr[u] = tkr[u];
-            if (t_j[u] >= 0) {
-                if (t_s[u] == a.pos) {
-                    const bf16_t* src = QKV + (size_t)(row0 + t_j[u]) * ld3 + a.d + h * HD + sub * 8;
-                    tkr[u] = *reinterpret_cast<const u32x4_t*>(src);
-                    tvr[u] = *reinterpret_cast<const u32x4_t*>(src + a.d);
-                } else {
-                    const int srow = KB == 1 ? row0 : a.kv_src[(size_t)(row0 + t_j[u]) * a.ld_src + t_s[u]];
-                    const size_t off = ((size_t)srow * a.T_max + t_s[u]) * a.d + h * HD + sub * 8;
-                    tkr[u] = *reinterpret_cast<const u32x4_t*>(TK + off);
-                    tvr[u] = *reinterpret_cast<const u32x4_t*>(TV + off);
-                }
-            }
-        }
-        // append this position's K/V of every beam to the text cache
-        if (lane < k * 8) {
-            const int j = lane >> 3;
-            const bf16_t* src = QKV + (size_t)(row0 + j) * ld3 + a.d + h * HD + sub * 8;
-            const size_t dst = ((size_t)(row0 + j) * a.T_max + a.pos) * a.d + h * HD + sub * 8;
-            *reinterpret_cast<u32x4_t*>(TK + dst) = *reinterpret_cast<const u32x4_t*>(src);
-            *reinterpret_cast<u32x4_t*>(TV + dst) = *reinterpret_cast<const u32x4_t*>(src + a.d);
-        }
+        TextItems<KB, TI> ti;
+        ti.load(a, p, grp, 8, sub);
+        append_text_cache(a, p, lane, sub);
+        bf16x8_t qf[2];
+        load_q_frag(a, p, l15, lg, qf);
 
         // ---- image part on the matrix cores: operands from the ring ------------------------------------------------
-        bf16x8_t qf[2];
-#pragma unroll
-        for (int ds = 0; ds < 2; ++ds) {
-            float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (l15 < k) ld8bf(QKV + (size_t)(row0 + l15) * ld3 + h * HD + ds * 32 + lg * 8, qv);
-            u32x4_t t;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = pack2bf(qv[2 * e] * a.scale, qv[2 * e + 1] * a.scale);
-            qf[ds] = __builtin_bit_cast(bf16x8_t, t);
-        }
-        float m_i = -INFINITY, l_i = 0.f;
-        f32x4_t oacc[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
+        ImagePartial ip;
+        ip.init();
         for (int s0 = 0; s0 < nsteps; s0 += ACS) {
             f32x4_t sc[ACS][2];
             float cm = -INFINITY;
 #pragma unroll
             for (int c = 0; c < ACS; ++c) {
-                const int s = s0 + c;
-                if (s < nsteps) {                                              // wave-uniform
+                if (s0 + c < nsteps) {                                         // wave-uniform
                     const unsigned char* sl = slot_ready();
                     bf16x8_t kq[2][2];
 #pragma unroll
@@ -614,38 +619,12 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
                     sc[c][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
                     sc[c][1] = sc[c][0];
                 }
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (s * 32 + t * 16 + lg * 4 + r >= a.N_img || s >= nsteps) sc[c][t][r] = -INFINITY;   // padded keys / steps
-                        cm = fmaxf(cm, sc[c][t][r]);
-                    }
+                ip.mask_max(sc[c], s0 + c, nsteps, a.N_img, lg, cm);
             }
-            cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
-            cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-            const float mn = fmaxf(m_i, cm);
-            if (s0 != 0) {
-                const float al = fast_exp(m_i - mn);
-                l_i *= al;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) { oacc[dt][0] *= al; oacc[dt][1] *= al; oacc[dt][2] *= al; oacc[dt][3] *= al; }
-            }
-            m_i = mn;
+            const float mn = ip.new_max(cm, s0 != 0);
 #pragma unroll
             for (int c = 0; c < ACS; ++c) {
-                float p[8];
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        p[t * 4 + r] = fast_exp(sc[c][t][r] - mn);    // exp(-inf) = 0 for padded keys
-                        l_i += p[t * 4 + r];
-                    }
-                u32x4_t pp;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pp[e] = pack2bf(p[2 * e], p[2 * e + 1]);
-                const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pp);
+                const bf16x8_t pf = ip.p_frag(sc[c], mn);
                 if (s0 + c < nsteps) {
                     const unsigned char* sl = slot_ready();
                     bf16x8_t vq[4];
@@ -653,128 +632,27 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
                     for (int dt = 0; dt < 4; ++dt) vq[dt] = *reinterpret_cast<const bf16x8_t*>(sl + dt * 1024 + lane * 16);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma16(vq[dt], pf, oacc[dt]);
+                    for (int dt = 0; dt < 4; ++dt) ip.o[dt] = mfma16(vq[dt], pf, ip.o[dt]);
                     slot_done();
                 } else {
-                    // the register kernels multiply an all-zero V^T step by P = 0 here: adds +0 to every accumulator
+                    // the register kernel multiplies an all-zero V^T step by P = 0 here: adds +0 to every accumulator
 #pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) oacc[dt] = mfma16(bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}, pf, oacc[dt]);
+                    for (int dt = 0; dt < 4; ++dt) ip.o[dt] = mfma16(bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}, pf, ip.o[dt]);
                 }
             }
         }
-        l_i += __shfl_xor(l_i, 16, 64);
-        l_i += __shfl_xor(l_i, 32, 64);
-        // ---- text keys (beam-specific): 8 lanes per key, online update ---------------------------------------------
-        float q[KB][8], m[KB], l[KB], o[KB][8];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            m[j] = -INFINITY;
-            l[j] = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { q[j][e] = 0.f; o[j][e] = 0.f; }
-            if (j < k) {
-                ld8bf(QKV + (size_t)(row0 + j) * ld3 + h * HD + sub * 8, q[j]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) q[j][e] *= a.scale;
-            }
-        }
-        auto dot8 = [&](const float (&x)[8], const float (&y)[8]) {
-            float p = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) p = fmaf(x[e], y[e], p);
-            p += __shfl_xor(p, 1, 64);
-            p += __shfl_xor(p, 2, 64);
-            p += __shfl_xor(p, 4, 64);
-            return p;
-        };
-        auto text_item = [&](int jj, const float (&kv)[8], const float (&vv)[8]) {
-#pragma unroll
-            for (int j = 0; j < KB; ++j) {
-                if (j == jj) {
-                    const float sv = dot8(q[j], kv);
-                    const float mn = fmaxf(m[j], sv);
-                    const float al = fast_exp(m[j] - mn);
-                    const float p = fast_exp(sv - mn);
-                    l[j] = fmaf(l[j], al, p);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[j][e] = fmaf(o[j][e], al, p * vv[e]);
-                    m[j] = mn;
-                }
-            }
-        };
-        auto unpack = [&](const u32x4_t& r, float (&v)[8]) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) unpack2op(r[i], v[2 * i], v[2 * i + 1]);
-        };
-#pragma unroll
-        for (int u = 0; u < TI; ++u) {
-            if (t_j[u] >= 0) {
-                float kv[8], vv[8];
-                unpack(tkr[u], kv);
-                unpack(tvr[u], vv);
-                text_item(t_j[u], kv, vv);
-            }
-        }
-        for (int it = grp + 8 * TI; it < k * nt; it += 8) {                  // long texts: dependent-load path
-            const int j = it / nt, sidx = it % nt;
-            float kv[8], vv[8];
-            if (sidx == a.pos) {
-                ld8bf(QKV + (size_t)(row0 + j) * ld3 + a.d + h * HD + sub * 8, kv);
-                ld8bf(QKV + (size_t)(row0 + j) * ld3 + 2 * a.d + h * HD + sub * 8, vv);
-            } else {
-                const int srow = KB == 1 ? row0 : a.kv_src[(size_t)(row0 + j) * a.ld_src + sidx];
-                ld8bf(TK + ((size_t)srow * a.T_max + sidx) * a.d + h * HD + sub * 8, kv);
-                ld8bf(TV + ((size_t)srow * a.T_max + sidx) * a.d + h * HD + sub * 8, vv);
-            }
-            text_item(j, kv, vv);
-        }
-        // merge the 8 groups of the wave (lanes with equal `sub`): lanes 0..7 end up with the wave's text partial
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-#pragma unroll
-            for (int off = 8; off < 64; off <<= 1) {
-                const float m2 = __shfl_xor(m[j], off, 64);
-                const float l2 = __shfl_xor(l[j], off, 64);
-                const float mn = fmaxf(m[j], m2);
-                const float a1 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
-                const float a2 = m2 == -INFINITY ? 0.f : fast_exp(m2 - mn);
-                l[j] = fmaf(l[j], a1, l2 * a2);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float o2 = __shfl_xor(o[j][e], off, 64);
-                    o[j][e] = fmaf(o[j][e], a1, o2 * a2);
-                }
-                m[j] = mn;
-            }
-        }
-        // ---- the wave's partial per beam row = image keys + text items, through its own LDS slot -------------------
-        if (l15 < k) {
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) part[wave][l15][dt * 16 + lg * 4 + r] = oacc[dt][r];
-            if (lg == 0) { part[wave][l15][HD] = m_i; part[wave][l15][HD + 1] = l_i; }
-        }
+        ip.finish();
+        // ---- text keys, then the wave's partial per beam row = image keys + text items, through its own LDS slot -------
+        TextPartial<KB> tp;
+        tp.init(a, p, sub);
+        tp.items(ti, true);
+        tp.template tail<TI>(a, p, grp, 8, sub);
+        tp.merge_groups();
+        ip.publish(part[wave], k, l15, lg);
         __builtin_amdgcn_wave_barrier();       // a wave reads back only what it wrote itself (its LDS operations complete in order)
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            if (lane < 8 && j < k) {
-                const float mi = part[wave][j][HD], li = part[wave][j][HD + 1];
-                const float mn = fmaxf(mi, m[j]);
-                const float a1 = mi == -INFINITY ? 0.f : fast_exp(mi - mn);
-                const float a2 = m[j] == -INFINITY ? 0.f : fast_exp(m[j] - mn);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) part[wave][j][sub * 8 + e] = fmaf(part[wave][j][sub * 8 + e], a1, o[j][e] * a2);
-                if (sub == 0) { part[wave][j][HD] = mn; part[wave][j][HD + 1] = fmaf(li, a1, l[j] * a2); }
-            }
-        }
+        tp.fold_into(part[wave], k, lane, sub);
         __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < k * HD; i += 64) {
-            const int j = i / HD, dd = i % HD;
-            const float r1 = part[wave][j][dd] / part[wave][j][HD + 1];
-            if (a.out_frag) O[frag_offset(row0 + j, h * HD + dd, a.d >> 5)] = f2bf(r1);
-            else O[(size_t)(row0 + j) * a.d + h * HD + dd] = f2bf(r1);
-        }
+        write_rows(a, p, part[wave], lane, 64);
         __builtin_amdgcn_wave_barrier();       // the next pair reuses this wave's LDS slot
     }
 }
@@ -786,6 +664,15 @@ hipError_t launch_kv_repack_frag(const void* qkv, void* kf, void* vt, int B, int
     hipLaunchKernelGGL(kv_repack_frag_kernel, dim3(N_pad / 32, H, B), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kf,
                        (bf16_t*)vt, N, N_pad, H, d);
     return hipGetLastError();
+}
+
+// beams -> KB, the kernels' compile-time beam rows (1, 2, 4 or 8): f gets it as a std::integral_constant
+template <typename F>
+static void with_beam_rows(int beams, F&& f) {
+    if (beams <= 1) f(std::integral_constant<int, 1>{});
+    else if (beams <= 2) f(std::integral_constant<int, 2>{});
+    else if (beams <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
 }
 
 hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
@@ -806,27 +693,19 @@ hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStr
     if (a.stream_wgs > 0) {
         // streaming kernel (the solo policy's choice, engine.hip; also the unit entry): workgroups = min(stream_wgs, pairs / 4)
         const int nwg = std::max(1, std::min(a.stream_wgs, (p.n_pairs + AS_WAVES - 1) / AS_WAVES));
-        if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_stream_kernel<1, 3, 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
-        else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_stream_kernel<2, 3, 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
-        else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_stream_kernel<4, 3, 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
-        else hipLaunchKernelGGL((attn_decode_stream_kernel<8, 3, 8>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
-        return hipGetLastError();
-    }
-    if (a.ntok) {       // ragged batches: the two-wave kernel whatever the geometry (the VQA capacity grids choose it anyway)
-        const dim3 grid(H, B);
-        if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_mfma_kernel<1, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
-        else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_mfma_kernel<2, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
-        else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_mfma_kernel<4, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
-        else hipLaunchKernelGGL((attn_decode_mfma_kernel<8, 3, 1, 2, false, true>), grid, dim3(128), 0, s, p);
+        with_beam_rows(a.beams, [&](auto kb) {
+            constexpr int KB = decltype(kb)::value;
+            hipLaunchKernelGGL((attn_decode_stream_kernel<KB, 3, KB == 8 ? 8 : 9>), dim3(nwg), dim3(64 * AS_WAVES), 0, s, p);
+        });
         return hipGetLastError();
     }
     const bool one_wave = a.waves_per_pair == 1 || (a.waves_per_pair != 2 && a.N_pad <= 8 * 32);
-    if (!one_wave) {
-        const dim3 grid(H, B);
-        if (a.beams <= 1) hipLaunchKernelGGL((attn_decode_mfma_kernel<1>), grid, dim3(128), 0, s, p);
-        else if (a.beams <= 2) hipLaunchKernelGGL((attn_decode_mfma_kernel<2>), grid, dim3(128), 0, s, p);
-        else if (a.beams <= 4) hipLaunchKernelGGL((attn_decode_mfma_kernel<4>), grid, dim3(128), 0, s, p);
-        else hipLaunchKernelGGL((attn_decode_mfma_kernel<8>), grid, dim3(128), 0, s, p);
+    if (a.ntok || !one_wave) {     // ragged batches: the two-wave kernel whatever the geometry (the VQA capacity grids choose it anyway)
+        with_beam_rows(a.beams, [&](auto kb) {
+            constexpr int KB = decltype(kb)::value;
+            if (a.ntok) hipLaunchKernelGGL((attn_decode_mfma_kernel<KB, 3, 1, 2, true>), dim3(H, B), dim3(128), 0, s, p);
+            else hipLaunchKernelGGL((attn_decode_mfma_kernel<KB>), dim3(H, B), dim3(128), 0, s, p);
+        });
         return hipGetLastError();
     }
     // pairs per workgroup (same per-wave arithmetic whatever the packing): 4 by default, 8 = a full CU under the serving
@@ -834,25 +713,18 @@ hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStr
     // never fewer than 96 workgroups: a small batch packed onto a handful of CUs streams its K/V through too few of them
     int pw = a.pairs_per_wg >= 8 ? 8 : a.pairs_per_wg >= 4 || a.pairs_per_wg <= 0 ? 4 : a.pairs_per_wg >= 2 ? 2 : 1;
     while (pw > 1 && p.n_pairs / pw < 96) pw >>= 1;
-    // pairs per WAVE (one after the other, the same per-pair arithmetic): only on top of full workgroups, and never fewer
-    // than 24 workgroups
-    int ppw = pw == 8 && a.pairs_per_wave > 1 ? a.pairs_per_wave : 1;
-    while (ppw > 1 && p.n_pairs / (pw * ppw) < 24) --ppw;
-    p.pairs_per_wave = ppw;
-    const int per_wg = pw * ppw;
-#define GITMI_ATTN1(KBV)                                                                                                   \
-    do {                                                                                                                   \
-        if (pw == 8 && ppw > 1) hipLaunchKernelGGL((attn_decode_mfma_kernel<KBV, 3, 8, 1, true>), dim3((p.n_pairs + per_wg - 1) / per_wg), dim3(512), 0, s, p); \
-        else if (pw == 8) hipLaunchKernelGGL((attn_decode_mfma_kernel<KBV, 3, 8, 1>), dim3((p.n_pairs + 7) / 8), dim3(512), 0, s, p); \
-        else if (pw == 4) hipLaunchKernelGGL((attn_decode_mfma_kernel<KBV, 3, 4, 1>), dim3((p.n_pairs + 3) / 4), dim3(256), 0, s, p); \
-        else if (pw == 2) hipLaunchKernelGGL((attn_decode_mfma_kernel<KBV, 3, 2, 1>), dim3((p.n_pairs + 1) / 2), dim3(128), 0, s, p); \
-        else hipLaunchKernelGGL((attn_decode_mfma_kernel<KBV, 3, 1, 1>), dim3(p.n_pairs), dim3(64), 0, s, p);                         \
-    } while (0)
-    if (a.beams <= 1) GITMI_ATTN1(1);
-    else if (a.beams <= 2) GITMI_ATTN1(2);
-    else if (a.beams <= 4) GITMI_ATTN1(4);
-    else { if (pw == 8) { pw = 4; ppw = 1; p.pairs_per_wave = 1; } GITMI_ATTN1(8); }       // 8 beams: 269 registers, one wave per SIMD: 4 pairs fill a CU
-#undef GITMI_ATTN1
+    if (a.beams > 4 && pw == 8) pw = 4;         // 8 beams: 269 registers, one wave per SIMD: 4 pairs fill a CU
+    with_beam_rows(a.beams, [&](auto kb) {
+        constexpr int KB = decltype(kb)::value;
+        auto packed = [&](auto pwc) {
+            constexpr int PW = decltype(pwc)::value;
+            hipLaunchKernelGGL((attn_decode_mfma_kernel<KB, 3, PW, 1>), dim3((p.n_pairs + PW - 1) / PW), dim3(64 * PW), 0, s, p);
+        };
+        if (pw == 8) { if constexpr (KB < 8) packed(std::integral_constant<int, 8>{}); }
+        else if (pw == 4) packed(std::integral_constant<int, 4>{});
+        else if (pw == 2) packed(std::integral_constant<int, 2>{});
+        else packed(std::integral_constant<int, 1>{});
+    });
     return hipGetLastError();
 }
 

@@ -136,24 +136,23 @@ struct AttnDecodeArgs {
     int N_pad;           // MFMA kernel (bf16): image keys padded to a multiple of 32; img_k / img_v in the layouts of kv_repack_frag
     int out_frag;        // write `out` in the fragment-major operand layout of the decode chain (bf16)
     float scale;
-    int dbg;             // timing experiments: 1 skip image K/V loads, 2 skip scores, 4 skip PV
+    int dbg;             // timing experiments.  MFMA register kernel: 1 no image key steps, 2 no up-front text items, 4 no P V
+                         // products, 8 zeros instead of the image K/V loads, 16 plain instead of non-temporal K/V loads; the
+                         // fp32 kernel: 1 no image K/V loads; the streaming kernel reads none
     int pairs_per_wg;    // MFMA kernel: (sentence, head) pairs per workgroup (1, 2, 4, 8); > 1 packs the launch onto fewer CUs
-    int pairs_per_wave;  // one-wave MFMA kernel: pairs a wave serves one after the other (the next pair's first K/V chunk is
-                         // requested while the current pair's text keys / output are worked off); 0 / 1 = one
     int stream_wgs;      // > 0: the streaming kernel (K/V through an LDS ring, 4 independent waves per workgroup) on at most this
                          // many workgroups -- each wave walks its share of the pairs; 0: the register kernels above
-    int n_pairs;         // set by the launcher
     int waves_per_pair;  // MFMA kernel: 0 / 1 = one wave walks all key steps of a pair (default); 2 = two waves split them (A/B)
+    int n_pairs;         // set by the launcher
     const int* ntok;     // ragged batches: image keys of every image ([B images] <= N_img; N_img stays the row stride); nullptr:
                          // all N_img.  The streaming kernel does not serve ragged batches (stream_wgs must be 0).
 };
-hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, bool is_f32, hipStream_t s);
-size_t attn_decode_lds_bytes(int beams, int N_img, int pos);
-hipError_t launch_attn_decode(const AttnDecodeArgs& a, int B, int H, bool is_f32, hipStream_t s);
+// the f32 mode's decode attention (VALU, kernels_attn.hip) and its head-major fp32 K/V cache
+hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, hipStream_t s);
+hipError_t launch_attn_decode(const AttnDecodeArgs& a, int B, int H, hipStream_t s);
 // bf16 decode attention on the matrix cores (kernels_attn_decode.hip) and its cache layouts
 hipError_t launch_kv_repack_frag(const void* qkv, void* kf, void* vt, int B, int N, int N_pad, int H, int d, hipStream_t s);
 hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStream_t s);
-hipError_t attn_decode_configure();
 
 constexpr int SS_NHMAX = 8;            // num_keep_best supported by the device search
 struct SearchState {

@@ -367,7 +367,10 @@ def _check_tie_order(M, mtop, dtype):
 
 
 @pytest.mark.parametrize("B,H,N_img,pos,beams", [(2, 2, 17, 0, 1), (3, 12, 197, 5, 1), (2, 12, 197, 7, 4), (1, 2, 300, 3, 3),
-                                                  (1, 1, 1182, 11, 2), (2, 2, 40, 60, 4)])
+                                                  (1, 1, 1182, 11, 2), (2, 2, 40, 60, 4),
+                                                  # packed one-wave forms with an absent pair in the last workgroup:
+                                                  # 193 pairs -> 2 per workgroup, 387 pairs -> 4 per workgroup
+                                                  (193, 1, 40, 2, 1), (129, 3, 40, 2, 2)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_attention_decode(B, H, N_img, pos, beams, dtype):
     """one new text position per row against [shared image K/V | per-beam text K/V through kv_src]"""

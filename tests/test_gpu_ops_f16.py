@@ -267,7 +267,10 @@ def _decode_ref(qkv, ik, iv, tk, tv, src, B, H, pos, beams):
 
 
 @pytest.mark.parametrize("B,H,N_img,pos,beams", [(2, 2, 17, 0, 1), (3, 12, 197, 5, 1), (2, 12, 197, 7, 4), (1, 2, 300, 3, 3),
-                                                  (1, 1, 1182, 11, 2), (2, 2, 40, 60, 4)])
+                                                  (1, 1, 1182, 11, 2), (2, 2, 40, 60, 4),
+                                                  # packed one-wave forms with an absent pair in the last workgroup:
+                                                  # 193 pairs -> 2 per workgroup, 387 pairs -> 4 per workgroup
+                                                  (193, 1, 40, 2, 1), (129, 3, 40, 2, 2)])
 def test_attention_decode_f16(B, H, N_img, pos, beams):
     """test_attention_decode's cases on fp16: the default, one-wave-per-pair and streaming (1, 2, 96 workgroups) forms against
     fp64 (_attn_bound; the text keys run in fp32, which the bound covers), and the streaming forms bitwise equal to the
