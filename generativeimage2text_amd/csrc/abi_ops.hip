@@ -259,14 +259,26 @@ GITMI_EXP_EXPORT int gitmi_debug_attention_ragged(const void* qkv, void* out, co
     HIPCK(launch_attn_full(a, B, dtype == GITMI_DTYPE_F32, impl, (hipStream_t)stream));
     return 0;
 }
-GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
-                                                    const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max,
-                                                    int pos, int beams, int dtype, void* stream) {
-    if (!ntok) return fail("debug_attn_decode_ragged: ntok is required");
+// every launch form of the decode attention (tests/test_gpu_attn_decode_forms.py): an argument check + the launcher the engine's
+// decode step calls, with the AttnDecodeArgs fields that gitmi_op_attn_decode leaves at their defaults -- so the launcher's choice
+// of kernel (packing, beam rows, one / two waves, streaming) is part of what runs.  dbg stays 0.
+GITMI_EXP_EXPORT int gitmi_debug_attn_decode_form(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                                  const int* kv_src, void* out, const int* ntok, const int* img_of, int n_images,
+                                                  int B, int H, int N_img, int T_max, int pos, int beams, int dtype, int out_frag,
+                                                  int pairs_per_wg, int waves_per_pair, int stream_wgs, void* stream) {
+    RCK(check_dtype("debug_attn_decode_form", "dtype", dtype));
+    if (!qkv || !img_k || !img_v || !txt_k || !txt_v || !kv_src || !out) return fail("debug_attn_decode_form: null argument");
+    if (beams < 1 || beams > 8) return fail("debug_attn_decode_form: beams=%d outside [1, 8]", beams);
+    if (n_images < 1) return fail("debug_attn_decode_form: n_images=%d", n_images);
+    if (B < 1 || H < 1 || N_img < 1 || pos < 0 || pos >= T_max)
+        return fail("debug_attn_decode_form: B=%d H=%d N_img=%d pos=%d T_max=%d", B, H, N_img, pos, T_max);
+    if (out_frag && dtype == GITMI_DTYPE_F32) return fail("debug_attn_decode_form: out_frag needs 16-bit rows");
+    if (ntok && stream_wgs > 0) return fail("debug_attn_decode_form: the streaming kernel does not serve ragged batches (ntok)");
     AttnDecodeArgs a{};
     a.qkv = qkv; a.img_k = img_k; a.img_v = img_v; a.txt_k = txt_k; a.txt_v = txt_v; a.out = out;
     a.kv_src = kv_src; a.ld_src = T_max; a.d = H * 64; a.N_img = N_img; a.T_max = T_max; a.pos = pos; a.beams = beams;
-    a.scale = 0.125f; a.ntok = ntok;
+    a.scale = 0.125f; a.ntok = ntok; a.img_of = img_of; a.out_frag = out_frag;
+    a.pairs_per_wg = pairs_per_wg; a.waves_per_pair = waves_per_pair; a.stream_wgs = stream_wgs;
     if (dtype == GITMI_DTYPE_F32) {
         HIPCK(launch_attn_decode(a, B, H, (hipStream_t)stream));
         return 0;
@@ -274,6 +286,13 @@ GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void*
     a.N_pad = round_up(N_img, 32);
     HIPCK(launch_attn_decode_mfma(a, B, H, (hipStream_t)stream));
     return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                                    const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max,
+                                                    int pos, int beams, int dtype, void* stream) {
+    if (!ntok) return fail("debug_attn_decode_ragged: ntok is required");
+    return gitmi_debug_attn_decode_form(qkv, img_k, img_v, txt_k, txt_v, kv_src, out, ntok, nullptr, B, B, H, N_img, T_max, pos, beams,
+                                        dtype, 0, 0, 0, 0, stream);
 }
 
 // ---- GPU image transform -------------------------------------------------------

@@ -42,7 +42,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
-    "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map",
+    "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form",
 ]
 
 
@@ -153,6 +153,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_score_attn_map.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attention_ragged.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_attn_decode_form.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                                     i32, i32, i32, vp]
         lib.gitmi_debug_vocab_topm_rules.argtypes = [vp, vp, vp, vp, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32,
                                                      i32, C.c_float, vp, vp, vp, vp, i32, vp]
         lib.gitmi_debug_search_begin_prefixed.argtypes = [vp, C.POINTER(GitmiSearch), i32, vp, i32, vp, i32, vp]
@@ -1064,6 +1066,39 @@ def op_attn_decode_ragged(qkv, img_k, img_v, txt_k, txt_v, kv_src, ntok, B, H, N
     _ck(_experiment_only(lib, "gitmi_debug_attn_decode_ragged")(qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(),
                                                                 txt_v.data_ptr(), kv_src.data_ptr(), out.data_ptr(), nt.data_ptr(), B,
                                                                 H, N_img, T_max, pos, beams, _torch_dtype_code(qkv), _stream()), lib)
+    return out
+
+
+def op_attn_decode_form(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, pos, beams, *, out=None, img_of=None,
+                        ntok=None, out_frag=False, pairs_per_wg=0, waves_per_pair=0, stream_wgs=0):
+    """op_attn_decode through the launcher with everything the engine's decode step sets (measurement build): img_of [B]
+    sentence -> image (img_k / img_v / ntok are per image), ntok per-image key counts, out_frag (the fragment-major rows of the
+    decode chain: the raw round_up(R, 16)-row buffer comes back, from_frag decodes it), pairs_per_wg / waves_per_pair /
+    stream_wgs as in AttnDecodeArgs.  txt_k / txt_v are appended to in place; `out` may be supplied (pre-filled) by the caller."""
+    lib = load_library()
+    R, d = B * beams, H * 64
+    n_images = img_k.shape[0] if img_k.dim() == 4 else img_k.numel() // (H * ((N_img + 31) // 32 * 32) * 64)
+    if qkv.dtype != torch.float32 and img_k.dim() == 4:
+        img_k, img_v = kv_repack(img_k, img_v)
+    if img_of is None:
+        if n_images < B:
+            raise ValueError(f"{n_images} images for {B} sentences and no img_of")
+    else:
+        host = torch.as_tensor(img_of, dtype=torch.int64).cpu()
+        if host.numel() != B or int(host.min()) < 0 or int(host.max()) >= n_images:
+            raise ValueError(f"img_of {host.tolist()} does not map {B} sentences onto {n_images} images")
+        img_of = host.to(device=qkv.device, dtype=torch.int32)
+    if ntok is not None:
+        ntok = torch.as_tensor(ntok, dtype=torch.int32).to(qkv.device)
+        if ntok.numel() != n_images:
+            raise ValueError(f"ntok holds {ntok.numel()} counts for {n_images} images")
+    if out is None:
+        rows = (R + 15) // 16 * 16 if out_frag else R
+        out = torch.empty(rows, d, device=qkv.device, dtype=qkv.dtype)
+    _ck(_experiment_only(lib, "gitmi_debug_attn_decode_form")(
+        qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(), kv_src.data_ptr(), out.data_ptr(),
+        _ptr(ntok), _ptr(img_of), n_images, B, H, N_img, T_max, pos, beams, _torch_dtype_code(qkv), int(bool(out_frag)),
+        int(pairs_per_wg), int(waves_per_pair), int(stream_wgs), _stream()), lib)
     return out
 
 

@@ -56,11 +56,23 @@ int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, con
  * device, the rows of image b (<= N / N_img, which stay the row stride of an image's block); keys past ntok[b] are never used.
  *   attention_ragged: gitmi_op_attention's layout and impl; query rows past ntok[b] are written as zeros.
  *   attn_decode_ragged: gitmi_op_attn_decode's layouts (bf16: the kv_repack operand layouts, N_pad = round_up(N_img, 32));
- *                       the ragged decode kernel is the two-wave MFMA form (16-bit) / the VALU form (f32). */
+ *                       the ragged decode kernel is the two-wave MFMA form (16-bit) / the VALU form (f32).
+ *   attn_decode_form:   the same operands (ntok may be NULL) and the rest of what the engine's decode step sets
+ *                       (tests/test_gpu_attn_decode_forms.py): img_of int32 [B sentences] DEVICE, the image (< n_images) whose K/V
+ *                       sentence b attends to, or NULL (sentence b <-> image b); img_k / img_v and ntok are indexed by image;
+ *                       out_frag != 0: `out` is the fragment-major operand layout of the decode chain (16-bit only;
+ *                       round_up(B * beams, 16) rows, rows past B * beams are not written); pairs_per_wg, waves_per_pair and
+ *                       stream_wgs as in AttnDecodeArgs (0: the launcher's defaults).  An argument check + the launcher the
+ *                       engine calls.  Refused: null pointers, beams outside 1..8, n_images < 1, out_frag with fp32, ntok with
+ *                       stream_wgs > 0. */
 int  gitmi_debug_attention_ragged(const void* qkv, void* out, const int* ntok, int B, int N, int H, int dtype, int impl, void* stream);
 int  gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
                                     const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max, int pos,
                                     int beams, int dtype, void* stream);
+int  gitmi_debug_attn_decode_form(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                  const int* kv_src, void* out, const int* ntok, const int* img_of, int n_images, int B, int H,
+                                  int N_img, int T_max, int pos, int beams, int dtype, int out_frag, int pairs_per_wg,
+                                  int waves_per_pair, int stream_wgs, void* stream);
 
 /* op hooks of the fused decode step (kernels_dgemm.hip vocab_topm_kernel, kernels_search.hip search_step_kernel;
  * tests/test_gpu_search_ops.py).  All list / id / plen pointers are DEVICE memory unless named _host.

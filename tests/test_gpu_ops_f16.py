@@ -251,18 +251,26 @@ def test_attention_full_f16(B, N, H):
         _check16(out.cpu(), ref, bound, f"impl {impl}")
 
 
-def _decode_ref(qkv, ik, iv, tk, tv, src, B, H, pos, beams):
-    """fp64 decode attention, vectorised: row r = (image b, beam) attends to image b's keys, its text history through
-    kv_src (positions < pos) and its own new key.  -> (q, K, V, out) as [R, H, keys, 64] / [R, H, 1, 64]."""
+def _decode_ref(qkv, ik, iv, tk, tv, src, B, H, pos, beams, img_of=None, ntok=None):
+    """fp64 decode attention, vectorised: row r = (sentence b, beam) attends to the keys of image img_of[b] (None: image b),
+    its text history through kv_src (positions < pos) and its own new key; ntok (per IMAGE): image keys past the count are masked.
+    -> (q, K, V, out) as [R, H, keys, 64] / [R, H, 1, 64]; K / V come back whole, the mask is applied to the scores only."""
     R, d = B * beams, H * 64
     q = qkv[:, :d].double().reshape(R, H, 1, 64)
     img = torch.arange(R) // beams
+    if img_of is not None:
+        img = torch.as_tensor(img_of).long()[img]
     rows = src[:, :pos].long()
     hk = tk.double()[rows, torch.arange(pos)].reshape(R, pos, H, 64).permute(0, 2, 1, 3)
     hv = tv.double()[rows, torch.arange(pos)].reshape(R, pos, H, 64).permute(0, 2, 1, 3)
     K = torch.cat([ik.double()[img], hk, qkv[:, d:2 * d].double().reshape(R, H, 1, 64)], 2)
     V = torch.cat([iv.double()[img], hv, qkv[:, 2 * d:].double().reshape(R, H, 1, 64)], 2)
-    o = torch.softmax(q @ K.transpose(-1, -2) / 8.0, -1) @ V
+    s = q @ K.transpose(-1, -2) / 8.0
+    if ntok is not None:
+        N_img = ik.shape[2]
+        pad = torch.arange(N_img)[None, :] >= torch.as_tensor(ntok).long()[img][:, None]                  # [R, N_img]
+        s[..., :N_img] = s[..., :N_img].masked_fill(pad[:, None, None, :], float("-inf"))
+    o = torch.softmax(s, -1) @ V
     return q, K, V, o
 
 
