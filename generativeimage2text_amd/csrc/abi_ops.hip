@@ -136,6 +136,52 @@ extern "C" int gitmi_op_dgemm_res(const void* A, const void* W, const float* bia
     HIPCK(launch_dgemm(g, (hipStream_t)stream));
     return 0;
 }
+// every launch form of the decode-chain GEMMs (tests/test_gpu_dgemm_forms.py): an argument check + the launcher the engine's
+// dgemm() calls, with the three DGemmArgs fields the engine sets by policy and gitmi_op_dgemm / gitmi_op_dgemm_res leave at 0
+// (rows_per_wg, strips_per_wg, no_row_walk) -- so launch_dgemm_t's choice of kernel is part of what runs.  One epilogue per
+// call: C (the arguments of gitmi_op_dgemm) or x_out (those of gitmi_op_dgemm_res); the other's pointers are null.  a_rows:
+// the rows allocated behind A; every form loads whole 16-row tiles up to the next multiple of 64 rows at most.  dbg stays 0.
+GITMI_EXP_EXPORT int gitmi_debug_dgemm_form(const void* A, int a_rows, const void* W, const float* bias, const float* colsum,
+                                            const float* stats, int strips, float eps, void* C, int c_frag, int act,
+                                            const float* res_x, const float* res_stats, int res_strips, const float* res_gamma,
+                                            const float* res_beta, float res_eps, float* x_out, void* xb_out, float* stats_out,
+                                            int M, int N, int K, int rows_per_wg, int strips_per_wg, int no_row_walk,
+                                            void* stream) {
+    if (!A || !W || !bias) return fail("debug_dgemm_form: null argument (A, W, bias)");
+    if (M < 0 || N < 0 || K < 0) return fail("debug_dgemm_form: M=%d N=%d K=%d", M, N, K);
+    if ((C != nullptr) == (x_out != nullptr)) return fail("debug_dgemm_form: exactly one of C and x_out selects the epilogue");
+    if (K % 32) return fail("debug_dgemm_form: K must be a multiple of 32 (K=%d)", K);
+    if (a_rows < round_up(M, 64)) return fail("debug_dgemm_form: a_rows=%d, but M=%d rows are loaded as %d", a_rows, M, round_up(M, 64));
+    if (rows_per_wg < 0 || strips_per_wg < 0) return fail("debug_dgemm_form: rows_per_wg=%d strips_per_wg=%d", rows_per_wg, strips_per_wg);
+    DGemmArgs g{};
+    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
+    g.M = M; g.N = N; g.K = K;
+    g.rows_per_wg = rows_per_wg; g.strips_per_wg = strips_per_wg; g.no_row_walk = no_row_walk;
+    if (C) {
+        if (res_x || res_stats || xb_out || stats_out) return fail("debug_dgemm_form: residual arguments with the C epilogue");
+        if (c_frag && N % 32) return fail("debug_dgemm_form: c_frag needs N %% 32 == 0 (N=%d)", N);
+        if (stats) {
+            if (!colsum) return fail("debug_dgemm_form: stats without colsum");
+            if (strips < 1 || strips > 64) return fail("debug_dgemm_form: strips=%d outside [1, 64]", strips);
+            g.colsum = colsum; g.stats_in = (const float2*)stats; g.strips_in = strips; g.inv_d = 1.0f / (float)K; g.eps_in = eps;
+        }
+        g.C = C; g.ldc = N; g.c_frag = c_frag; g.act = act;
+    } else {
+        if (stats || colsum || c_frag || act) return fail("debug_dgemm_form: consumer arguments with the x_out epilogue");
+        if (N % 16) return fail("debug_dgemm_form: the x_out epilogue needs N %% 16 == 0 (N=%d)", N);
+        if (!xb_out || !stats_out || !res_x) return fail("debug_dgemm_form: the x_out epilogue needs xb_out, stats_out and res_x");
+        g.res_x = res_x;
+        if (res_stats) {
+            if (!res_gamma || !res_beta) return fail("debug_dgemm_form: res_stats without res_gamma / res_beta");
+            if (res_strips < 1 || res_strips > 64) return fail("debug_dgemm_form: res_strips=%d outside [1, 64]", res_strips);
+            g.res_stats = (const float2*)res_stats; g.res_strips = res_strips; g.res_gamma = res_gamma; g.res_beta = res_beta;
+            g.res_inv_d = 1.0f / (float)N; g.res_eps = res_eps;
+        }
+        g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = (float2*)stats_out;
+    }
+    HIPCK(launch_dgemm(g, (hipStream_t)stream));
+    return 0;
+}
 // the VocabArgs fields gitmi_op_vocab_topm and gitmi_debug_vocab_topm_rules share (everything but the rule inputs)
 static VocabArgs vocab_op_args(const void* A, const void* W, const float* bias, const float* colsum, const float* stats, int strips,
                                float eps, int M, int V, int K, int cols_per_wg, float* part_val, int* part_idx, float* part_lse,

@@ -249,7 +249,9 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs g) {
         uint2 t;
         t.x = pack2bf(v[0], v[1]);
         t.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(g.xb_out + frag_offset(fm, fn, g.N >> 5)) = t;      // fragment-major operand copy
+        // fragment-major operand copy, round_up(N, 32) columns wide: with N % 32 == 16 the last k-step is half used (N >> 5
+        // k-steps would put its columns into the next row tile, and those of the last row tile behind the buffer)
+        *reinterpret_cast<uint2*>(g.xb_out + frag_offset(fm, fn, (g.N + 31) >> 5)) = t;
         if (lg == 0) g.stats_out[(size_t)blockIdx.x * g.M + fm] = float2{s, q};
     }
 }

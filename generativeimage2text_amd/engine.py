@@ -42,7 +42,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
-    "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form",
+    "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
 ]
 
 
@@ -148,6 +148,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_head_from.argtypes = [vp, vp, i32, vp, vp]
         lib.gitmi_debug_set_gemm_impl.argtypes = [i32]
         lib.gitmi_debug_set_dgemm.argtypes = [i32]
+        lib.gitmi_debug_dgemm_form.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.c_float, vp, i32, i32, vp, vp, i32, vp, vp, C.c_float,
+                                               vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         lib.gitmi_debug_score_attn_map.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -957,13 +959,50 @@ def op_dgemm_res(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, res_x: to
     K = A.shape[1]
     Af, Wf = (A, W) if packed else (to_frag(A, 64), to_frag(W))
     x = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    xb = torch.empty((M + 15) // 16 * 16, N, device=A.device, dtype=A.dtype)
+    xb = torch.empty((M + 15) // 16 * 16, (N + 31) // 32 * 32, device=A.device, dtype=A.dtype)
     st = torch.empty(N // 16, M, 2, device=A.device, dtype=torch.float32)
     strips = 0 if res_stats is None else int(res_stats.shape[0])
     _ck(lib.gitmi_op_dgemm_res(Af.data_ptr(), Wf.data_ptr(), bias.data_ptr(), res_x.data_ptr(), _ptr(res_stats), strips,
                                _ptr(res_gamma), _ptr(res_beta), res_eps, x.data_ptr(), xb.data_ptr(), st.data_ptr(),
                                M, N, K, _stream()), lib)
-    return x, (xb if packed else from_frag(xb, M)), st
+    return x, (xb if packed else from_frag(xb, M)[:, :N].contiguous()), st
+
+
+def op_dgemm_form(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, M: Optional[int] = None, *, colsum=None, stats=None,
+                  eps: float = 1e-12, act: int = ACT_NONE, frag_out: bool = False, out: Optional[torch.Tensor] = None,
+                  res_x=None, res_stats=None, res_gamma=None, res_beta=None, res_eps: float = 1e-12, x=None, xb=None,
+                  stats_out=None, packed: bool = False, rows_per_wg: int = 0, strips_per_wg: int = 0, no_row_walk: int = 0):
+    """op_dgemm / op_dgemm_res through the launcher with the three fields the engine's dgemm() sets by policy (measurement
+    build): rows_per_wg, strips_per_wg, no_row_walk.  res_x given: the N = hidden form -> (x, xb, stats_out), else the QKV /
+    FFN1 form -> out.  The outputs may be supplied (pre-filled, with guard rows behind them) by the caller; xb and a frag_out
+    `out` come back as the raw fragment-major buffers (from_frag decodes them; xb is round_up(N, 32) columns wide).  packed=True: A (rows a multiple of 64) and W are
+    fragment-major already and M is required; otherwise they are packed here and M is A's row count."""
+    lib = load_library()
+    own = {DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16}[lib.gitmi_operand_dtype()]
+    if A.dtype != own or W.dtype != own:
+        raise GitmiError(f"operands must be {own} in this library, got {A.dtype} / {W.dtype}")
+    if packed:
+        if M is None:
+            raise ValueError("packed operands: M is required")
+        Af, Wf = A, W
+    else:
+        M = int(A.shape[0]) if M is None else int(M)
+        Af, Wf = to_frag(A, 64), to_frag(W)
+    M, N, K = int(M), int(bias.numel()), int(A.shape[1])
+    Mp = (M + 15) // 16 * 16
+    producer = res_x is not None
+    if producer:
+        x = torch.empty(M, N, device=A.device, dtype=torch.float32) if x is None else x
+        xb = torch.empty(Mp, (N + 31) // 32 * 32, device=A.device, dtype=own) if xb is None else xb
+        stats_out = torch.empty(N // 16, M, 2, device=A.device, dtype=torch.float32) if stats_out is None else stats_out
+    elif out is None:
+        out = torch.empty(Mp if frag_out else M, N, device=A.device, dtype=own)
+    _ck(_experiment_only(lib, "gitmi_debug_dgemm_form")(
+        Af.data_ptr(), int(Af.shape[0]), Wf.data_ptr(), _ptr(bias), _ptr(colsum), _ptr(stats),
+        0 if stats is None else int(stats.shape[0]), eps, _ptr(out), int(bool(frag_out)), int(act), _ptr(res_x), _ptr(res_stats),
+        0 if res_stats is None else int(res_stats.shape[0]), _ptr(res_gamma), _ptr(res_beta), res_eps, _ptr(x), _ptr(xb),
+        _ptr(stats_out), M, N, K, int(rows_per_wg), int(strips_per_wg), int(no_row_walk), _stream()), lib)
+    return (x, xb, stats_out) if producer else out
 
 
 def _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V):

@@ -402,7 +402,9 @@ int  gitmi_op_attention(const void* qkv, void* out, int B, int N, int H, int dty
  *                        With stats: W must be W . gamma rounded to the operand type, bias = beta W^T + b,
  *                        colsum[n] = sum_k W'[n][k].
  *   gitmi_op_dgemm_res : x = A W^T + bias + r,  r = res_x (res_stats == NULL) or LayerNorm(res_x; res_gamma, res_beta)
- *                        rebuilt from res_stats; writes x fp32, its 16-bit copy and stats_out [N/16][M][2].  N % 16 == 0.
+ *                        rebuilt from res_stats; writes x fp32, its 16-bit copy and stats_out [N/16][M][2].  N % 16 == 0;
+ *                        xb_out is fragment-major over round_up(N, 32) columns (round_up(M, 16) rows of that width; rows
+ *                        past M and columns past N are not written).
  *                        strips_per_wg (QKV / FFN1 form, 33..64 rows): 16-column strips a workgroup computes one after
  *                        the other -- 0 / 1 (one workgroup per strip), 2, 4 or 6; results do not depend on it. */
 int  gitmi_op_dgemm(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,

@@ -34,6 +34,23 @@ int  gitmi_debug_set_gemm_impl(int impl);
 /* timing bits of the decode-chain GEMMs (kernels_dgemm.hip; tools/dgemm_bench.py) for gitmi_op_dgemm / gitmi_op_dgemm_res */
 int  gitmi_debug_set_dgemm(int dbg);
 
+/* every launch form of the decode-chain GEMMs (tests/test_gpu_dgemm_forms.py): an argument check + launch_dgemm, the launcher
+ * the engine's decode step calls, with the three DGemmArgs fields the engine sets by policy and the gitmi_op_dgemm* hooks leave
+ * at 0: rows_per_wg (N = hidden form and N < 1536: 0 / 16, 32, 64), strips_per_wg (wide form at 33..64 rows: 0 / 1, 2, 4, 6)
+ * and no_row_walk (wide form above 64 rows: one workgroup per (strip, row block)).  One epilogue per call, the other's pointers
+ * NULL: C (gitmi_op_dgemm's arguments: colsum / stats / strips / eps, c_frag, act) or x_out (gitmi_op_dgemm_res's: res_x,
+ * res_stats / res_strips / res_gamma / res_beta / res_eps, xb_out, stats_out).  A, W fragment-major 16-bit operands of the
+ * build's type; a_rows: the rows allocated behind A, at least round_up(M, 64) (every form loads whole 16-row tiles, up to the
+ * next multiple of 64 rows).  Refused by name, nothing launched: null A / W / bias, both or neither of C and x_out, K % 32,
+ * a_rows too small, c_frag with N % 32, stats without colsum, strips / res_strips outside 1..64, the x_out epilogue with
+ * N % 16 or without xb_out / stats_out / res_x, res_stats without res_gamma / res_beta, arguments of the other epilogue.
+ * M == 0 succeeds and launches nothing.  The timing bits of gitmi_debug_set_dgemm do not apply (dbg = 0). */
+int  gitmi_debug_dgemm_form(const void* A, int a_rows, const void* W, const float* bias, const float* colsum, const float* stats,
+                            int strips, float eps, void* C, int c_frag, int act, const float* res_x, const float* res_stats,
+                            int res_strips, const float* res_gamma, const float* res_beta, float res_eps, float* x_out,
+                            void* xb_out, float* stats_out, int M, int N, int K, int rows_per_wg, int strips_per_wg,
+                            int no_row_walk, void* stream);
+
 /* op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py).  dtype: GITMI_DTYPE_F32 (the
  * kernels of the f32 parity mode) or the build's 16-bit operand dtype (gitmi_operand_dtype).
  *   score_attn: text-row attention of one layer -- qkv [Q * Lp][3 H 64] packed q|k|v text rows (sentence q, position j at

@@ -27,6 +27,14 @@ def _hulp16(x):
     return torch.exp2(e - 11)
 
 
+def _hulp(x, dt=torch.float16):
+    """Half an ulp of the 16-bit type dt at |x|: fp16 as _hulp16; bf16 (8 significant bits, fp32's exponent range) 2^(e - 8)."""
+    if dt == torch.float16:
+        return _hulp16(x)
+    e = torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126)))
+    return torch.exp2(e - 8)
+
+
 def _check16(out, ref, bound, what=""):
     """|out - ref| <= bound element by element, and the bound is tight enough to tell fp16 from bf16: its largest value is
     below half the error rounding ref through bf16 causes at ref's largest magnitude (half a bf16 ulp there, 2^(e - 8))."""
@@ -344,8 +352,9 @@ def _fold16(W, bias, gamma, beta):
     return Wf, (bias.double() + W.double() @ beta.double()).float(), Wf.double().sum(1).float()
 
 
-def _fold_bound(x, Wf, cs, exact, eps, act, exact_partials=False, rstd_term=True):
-    """Bound of the folded-LayerNorm epilogue act(rstd (A W'^T - mean colsum) + b') against fp64 on the same fp16 A = fp16(x),
+def _fold_bound(x, Wf, cs, exact, eps, act, exact_partials=False, rstd_term=True, dt=torch.float16):
+    """Bound of the folded-LayerNorm epilogue act(rstd (A W'^T - mean colsum) + b') against fp64 on the same fp16 A = fp16(x)
+    (dt: the 16-bit operand and output type, fp16 unless given),
     W' and fp32 colsum, mean / var of the raw fp32 rows:
       - A W'^T in fp32: _acc_err; mean colsum and the subtraction: 2 u |mean colsum| + u |A W'^T - mean colsum|;
       - the statistics: fp32 16-column strip sums (16 roundings) added over K/16 strips, so sum and sum of squares carry
@@ -357,13 +366,13 @@ def _fold_bound(x, Wf, cs, exact, eps, act, exact_partials=False, rstd_term=True
     x64 = x.double()
     mean, var = x64.mean(1, keepdim=True), x64.var(1, unbiased=False, keepdim=True)
     rstd = 1.0 / torch.sqrt(var + eps)
-    A = x.half()
+    A = x.to(dt)
     raw = A.double() @ Wf.double().t()
     mc = mean * cs.double()[None, :]
     e_acc = _acc_err(A, Wf, exact_partials) + 2 * U * mc.abs() + U * (raw - mc).abs()
     drstd = 0.5 * (2 * (16 + K / 16) + 4) * U * (x64 * x64).mean(1, keepdim=True) / (var + eps) + 4 * U
     pre = (raw - mc) * rstd
-    b = ACT_SLOPE * (rstd * e_acc + (pre.abs() * drstd if rstd_term else 0.0)) + 8 * U * exact.abs() + _hulp16(exact)
+    b = ACT_SLOPE * (rstd * e_acc + (pre.abs() * drstd if rstd_term else 0.0)) + 8 * U * exact.abs() + _hulp(exact, dt)
     return b if rstd_term else (b, drstd)
 
 
