@@ -110,14 +110,11 @@ static const int g_dgemm_dbg = 0;
 extern "C" int gitmi_op_dgemm(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
                               int strips, float eps, void* C, int c_frag, int M, int N, int K, int act, int strips_per_wg,
                               void* stream) {
-    DGemmArgs g{};
+    if (c_frag && N % 32) return fail("op_dgemm: a fragment-major output needs N %% 32 == 0");
+    const DLn ln{(const float2*)stats, strips, 1.0f / (float)K, eps, nullptr, nullptr};
+    DGemmArgs g = dgemm_ln(A, W, bias, colsum, stats ? &ln : nullptr, C, c_frag, act, M, N, K);
     g.dbg = g_dgemm_dbg;
     g.strips_per_wg = strips_per_wg;
-    g.c_frag = c_frag;
-    if (c_frag && N % 32) return fail("op_dgemm: a fragment-major output needs N %% 32 == 0");
-    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
-    if (stats) { g.colsum = colsum; g.stats_in = (const float2*)stats; g.strips_in = strips; g.inv_d = 1.0f / (float)K; g.eps_in = eps; }
-    g.C = C; g.ldc = N; g.act = act; g.M = M; g.N = N; g.K = K;
     if (K % 32) return fail("op_dgemm: K must be a multiple of 32");
     HIPCK(launch_dgemm(g, (hipStream_t)stream));
     return 0;
@@ -125,13 +122,9 @@ extern "C" int gitmi_op_dgemm(const void* A, const void* W, const float* bias, c
 extern "C" int gitmi_op_dgemm_res(const void* A, const void* W, const float* bias, const float* res_x, const float* res_stats,
                                   int res_strips, const float* res_gamma, const float* res_beta, float res_eps,
                                   float* x_out, void* xb_out, float* stats_out, int M, int N, int K, void* stream) {
-    DGemmArgs g{};
+    const DLn res_ln{(const float2*)res_stats, res_strips, 1.0f / (float)N, res_eps, res_gamma, res_beta};
+    DGemmArgs g = dgemm_to_stream(A, W, bias, res_x, res_stats ? &res_ln : nullptr, x_out, xb_out, (float2*)stats_out, M, N, K);
     g.dbg = g_dgemm_dbg;
-    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
-    g.res_x = res_x;
-    if (res_stats) { g.res_stats = (const float2*)res_stats; g.res_strips = res_strips; g.res_gamma = res_gamma; g.res_beta = res_beta; g.res_inv_d = 1.0f / (float)N; g.res_eps = res_eps; }
-    g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = (float2*)stats_out;
-    g.M = M; g.N = N; g.K = K;
     if (K % 32 || N % 16) return fail("op_dgemm_res: need K %% 32 == 0 and N %% 16 == 0");
     HIPCK(launch_dgemm(g, (hipStream_t)stream));
     return 0;
@@ -153,32 +146,28 @@ GITMI_EXP_EXPORT int gitmi_debug_dgemm_form(const void* A, int a_rows, const voi
     if (K % 32) return fail("debug_dgemm_form: K must be a multiple of 32 (K=%d)", K);
     if (a_rows < round_up(M, 64)) return fail("debug_dgemm_form: a_rows=%d, but M=%d rows are loaded as %d", a_rows, M, round_up(M, 64));
     if (rows_per_wg < 0 || strips_per_wg < 0) return fail("debug_dgemm_form: rows_per_wg=%d strips_per_wg=%d", rows_per_wg, strips_per_wg);
-    DGemmArgs g{};
-    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
-    g.M = M; g.N = N; g.K = K;
-    g.rows_per_wg = rows_per_wg; g.strips_per_wg = strips_per_wg; g.no_row_walk = no_row_walk;
+    DGemmArgs g;
     if (C) {
         if (res_x || res_stats || xb_out || stats_out) return fail("debug_dgemm_form: residual arguments with the C epilogue");
         if (c_frag && N % 32) return fail("debug_dgemm_form: c_frag needs N %% 32 == 0 (N=%d)", N);
         if (stats) {
             if (!colsum) return fail("debug_dgemm_form: stats without colsum");
             if (strips < 1 || strips > 64) return fail("debug_dgemm_form: strips=%d outside [1, 64]", strips);
-            g.colsum = colsum; g.stats_in = (const float2*)stats; g.strips_in = strips; g.inv_d = 1.0f / (float)K; g.eps_in = eps;
         }
-        g.C = C; g.ldc = N; g.c_frag = c_frag; g.act = act;
+        const DLn ln{(const float2*)stats, strips, 1.0f / (float)K, eps, nullptr, nullptr};
+        g = dgemm_ln(A, W, bias, colsum, stats ? &ln : nullptr, C, c_frag, act, M, N, K);
     } else {
         if (stats || colsum || c_frag || act) return fail("debug_dgemm_form: consumer arguments with the x_out epilogue");
         if (N % 16) return fail("debug_dgemm_form: the x_out epilogue needs N %% 16 == 0 (N=%d)", N);
         if (!xb_out || !stats_out || !res_x) return fail("debug_dgemm_form: the x_out epilogue needs xb_out, stats_out and res_x");
-        g.res_x = res_x;
         if (res_stats) {
             if (!res_gamma || !res_beta) return fail("debug_dgemm_form: res_stats without res_gamma / res_beta");
             if (res_strips < 1 || res_strips > 64) return fail("debug_dgemm_form: res_strips=%d outside [1, 64]", res_strips);
-            g.res_stats = (const float2*)res_stats; g.res_strips = res_strips; g.res_gamma = res_gamma; g.res_beta = res_beta;
-            g.res_inv_d = 1.0f / (float)N; g.res_eps = res_eps;
         }
-        g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = (float2*)stats_out;
+        const DLn res_ln{(const float2*)res_stats, res_strips, 1.0f / (float)N, res_eps, res_gamma, res_beta};
+        g = dgemm_to_stream(A, W, bias, res_x, res_stats ? &res_ln : nullptr, x_out, xb_out, (float2*)stats_out, M, N, K);
     }
+    g.rows_per_wg = rows_per_wg; g.strips_per_wg = strips_per_wg; g.no_row_walk = no_row_walk;
     HIPCK(launch_dgemm(g, (hipStream_t)stream));
     return 0;
 }

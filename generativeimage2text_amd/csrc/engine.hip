@@ -517,30 +517,9 @@ static int dgemm(gitmi_engine* e, hipStream_t s, const DGemmArgs& g_in) {
     return 0;
 }
 
-// ---- argument builders of the chain: the consumer / producer pair of ln_gemm / gemm_to_stream on strip partials.  DLn: a
-// LayerNorm of the chain, i.e. the strip partials of the rows it normalises and its (gamma, beta, eps)
-struct DLn { const float2* stats; int strips; float inv_d, eps; const float* gamma; const float* beta; };
-// consumer: C = act(LayerNorm(A) W^T + b) with the LayerNorm folded into f (ln == nullptr: plain A, f.colsum is not read)
+// the chain's consumer (launchers.h: dgemm_ln / dgemm_to_stream, the pair of ln_gemm / gemm_to_stream on strip partials) of a folded set
 static DGemmArgs dgemm_ln(const void* A, const Folded& f, const DLn* ln, void* C, int c_frag, int act, int M, int N, int K) {
-    DGemmArgs g{};
-    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)f.w; g.bias = f.bias;
-    if (ln) { g.colsum = f.colsum; g.stats_in = ln->stats; g.strips_in = ln->strips; g.inv_d = ln->inv_d; g.eps_in = ln->eps; }
-    g.C = C; g.ldc = N; g.c_frag = c_frag; g.act = act; g.M = M; g.N = N; g.K = K;
-    return g;
-}
-// producer: x_out = A W^T + b + residual (res_x itself, or LayerNorm(res_x) rebuilt from res_ln), its bf16 copy and strip partials
-static DGemmArgs dgemm_to_stream(const void* A, const void* W, const float* bias, const float* res_x, const DLn* res_ln, float* x_out,
-                                 void* xb_out, float2* stats_out, int M, int N, int K) {
-    DGemmArgs g{};
-    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
-    g.res_x = res_x;
-    if (res_ln) {
-        g.res_stats = res_ln->stats; g.res_strips = res_ln->strips; g.res_gamma = res_ln->gamma; g.res_beta = res_ln->beta;
-        g.res_inv_d = res_ln->inv_d; g.res_eps = res_ln->eps;
-    }
-    g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = stats_out;
-    g.M = M; g.N = N; g.K = K;
-    return g;
+    return dgemm_ln(A, f.w, f.bias, f.colsum, ln, C, c_frag, act, M, N, K);
 }
 
 static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, int pos, int R, int beams, hipStream_t s) {

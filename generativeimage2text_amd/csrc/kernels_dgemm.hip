@@ -21,6 +21,13 @@
 // all loads of a chunk in flight before the first MFMA), partial accumulators are exchanged through LDS and summed
 // in a FIXED order -- deterministic, batch-invariant (a row's result does not depend on which rows share its tile).
 //
+// File layout: row statistics (stats_issue / stats_finish, shared with the vocabulary head); then ONE set of helpers for the GEMM
+// kernels -- k_slice, load_cols4, the register-held slice (load_w_slice / load_x_slice / mfma_slice), sum_waves,
+// DGEMM_CONSUMER_FINISH, consumer_store; then dgemm_kernel<MT, NW, EPI> (default consumer form, and the only producer form) and
+// the two wide consumer forms dgemm_wide_rows_kernel / dgemm_wide_strips_kernel<NST>, which are bit-identical to
+// dgemm_kernel<4, 4, DEPI_BF16> because they call the same helpers; then the vocabulary head; then the launchers
+// (launch_narrow / launch_wide say the kernel policy once).
+//
 // Operand layout: BOTH operands are fragment-major (gitmi_common.h frag_offset): every fragment load of a wave is one
 // contiguous 1-KiB read.  Weights are repacked once at finalisation; activations are WRITTEN in that order by their
 // producers (the N = 768 epilogue, the FFN1 epilogue, decode attention, the embedding), so the chain never transposes.
@@ -74,6 +81,125 @@ __device__ __forceinline__ void stats_finish(const RowStatLoads& L, float inv_d,
     rstd = rsqrtf(var + eps);
 }
 
+// ---- what the GEMM kernels of the chain share ----------------------------------------------------------------------
+// The two wide forms promise the bits of dgemm_kernel<4, 4, DEPI_BF16>, and the serving policy switches between the three.
+// They keep the promise by CALLING the same code: the K slice of a wave, the MFMA sequence over a register-held slice, the
+// wave-order sum and the consumer epilogue are written here and nowhere else.  A kernel body keeps what is its own: its row /
+// strip mapping, which loads it issues and when, its LDS exchange buffers and barriers, its dbg switches.
+
+// k-steps [kb, ke) of wave `wave` when `ksteps` k-steps of 32 are split over nw waves (kb >= ke: the wave has none)
+struct KSlice { int kb, ke; };
+__device__ __forceinline__ KSlice k_slice(int ksteps, int nw, int wave) {
+    const int per = (ksteps + nw - 1) / nw;
+    const int kb = wave * per;
+    return KSlice{kb, min(kb + per, ksteps)};
+}
+
+// entries n .. n+3 of a per-column constant (bias, colsum) of N entries; indices past the end are clamped, their columns never stored
+__device__ __forceinline__ float4 load_cols4(const float* p, int n, int N) {
+    float4 r;
+    r.x = p[n < N ? n : N - 1];
+    r.y = p[n + 1 < N ? n + 1 : N - 1];
+    r.z = p[n + 2 < N ? n + 2 : N - 1];
+    r.w = p[n + 3 < N ? n + 3 : N - 1];
+    return r;
+}
+
+// Register-held K slice of the wide forms: at most DW_KS k-steps per wave, zero past ke.
+constexpr int DW_KS = 6;        // k-steps per wave held in registers: K <= 4 * 6 * 32 = 768
+// the wave's slice of weight strip `strip` (read once: non-temporal).  Returned by value, and mfma_slice adds to accumulators the
+// kernel has zeroed: with the fragments filled through a reference, or the zeroing inside mfma_slice, dgemm_wide_strips_kernel<6>
+// loses the fused multiply-adds of its epilogue (same note as at DGEMM_CONSUMER_FINISH below)
+struct WSlice { bf16x8_t f[DW_KS]; };
+__device__ __forceinline__ WSlice load_w_slice(const bf16_t* W, int strip, KSlice ks, int ksteps, int lane) {
+    WSlice w;
+    const bf16_t* wp = W + frag_tile(strip, 0, ksteps, lane);
+#pragma unroll
+    for (int u = 0; u < DW_KS; ++u)
+        w.f[u] = ks.kb + u < ks.ke ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wp + (size_t)(ks.kb + u) * 512))
+                                   : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    return w;
+}
+// the wave's slice of the four row tiles rt0 .. rt0+3 of the activations
+__device__ __forceinline__ void load_x_slice(bf16x8_t (&xf)[DW_KS][4], const bf16_t* X, int rt0, KSlice ks, int ksteps, int lane) {
+#pragma unroll
+    for (int u = 0; u < DW_KS; ++u)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            xf[u][i] = ks.kb + u < ks.ke ? *reinterpret_cast<const bf16x8_t*>(X + frag_tile(rt0 + i, ks.kb + u, ksteps, lane))
+                                         : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+}
+// acc[i] += partial of row tile i over the slice.  The guard is uniform per wave and stays: it is what keeps the MFMA sequence
+// of a wave equal to dgemm_kernel's (no MFMA on the zero fragments past ke)
+__device__ __forceinline__ void mfma_slice(f32x4_t (&acc)[4], const WSlice& w, const bf16x8_t (&xf)[DW_KS][4], KSlice ks) {
+#pragma unroll
+    for (int u = 0; u < DW_KS; ++u) {
+        if (ks.kb + u < ks.ke) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = mfma16(w.f[u], xf[u][i], acc[i]);
+        }
+    }
+}
+
+// red[writer][row tile][lane]: the total of row tile `tile`, writers summed in the FIXED order 0 .. NW-1, component by component
+template <int NW, int MT>
+__device__ __forceinline__ f32x4_t sum_waves(f32x4_t (*red)[MT][64], int tile, int lane) {
+    f32x4_t tot = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const f32x4_t t = red[w][tile][lane];
+        tot[0] += t[0]; tot[1] += t[1]; tot[2] += t[2]; tot[3] += t[3];
+    }
+    return tot;
+}
+
+// consumer (QKV / FFN1) epilogue, arithmetic: declares  float v[4] = act(rstd * (tot - mean * colsum) + bias)  with the LayerNorm
+// folded (have_stats), else act(tot + bias).  A MACRO, not a function, and the one place where that matters: this file compiles
+// with the default contraction, so which products fuse into FMAs is decided after inlining, from the shape the optimiser has
+// given the code by then.  Written as a __forceinline__ function (tried: v by reference, returned by value, one function per
+// arm, statistics inside or outside) the `+ biasv[r]` the two arms share ends up below their join in some or all kernels, the
+// fold's outer multiply-add is then a multiply and an add, and the last bit differs from every earlier build.  Expanded in
+// place, the statements compile to the instruction stream they had when each kernel carried its own copy (docs/LAB_NOTEBOOK.md,
+// profiles/r12_dgemm_static_resources.txt).  Check the FMA counts per kernel after any change near it.
+#define DGEMM_CONSUMER_FINISH(v, tot, bias4, cs4, have_stats, mean, rstd, act)              \
+    float v[4] = {(tot)[0], (tot)[1], (tot)[2], (tot)[3]};                                  \
+    {                                                                                       \
+        const float biasv[4] = {(bias4).x, (bias4).y, (bias4).z, (bias4).w};                \
+        if (have_stats) {                                                                   \
+            const float cs[4] = {(cs4).x, (cs4).y, (cs4).z, (cs4).w};                       \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = (rstd) * (v[r] - (mean) * cs[r]) + biasv[r]; \
+        } else {                                                                            \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] += biasv[r];                 \
+        }                                                                                   \
+        if ((act) != GITMI_ACT_NONE) {                                                      \
+            _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = apply_act(v[r], (act));    \
+        }                                                                                   \
+    }
+// consumer epilogue, store: columns fn .. fn+3 of row fm_raw (fm: the same row clamped to M - 1); absent rows and columns are skipped
+__device__ __forceinline__ void consumer_store(const DGemmArgs& g, const float (&v)[4], int fm_raw, int fm, int fn) {
+    if (fm_raw >= g.M || fn >= g.N) return;
+    if (g.c_frag) {
+        // operand of the next chain GEMM: 4 consecutive columns = 8 contiguous bytes.  PRECONDITION N % 32 == 0 (checked by the
+        // callers that set c_frag): N >> 5 k-steps per row tile; with N % 32 == 16 the last half k-step would land in the next
+        // row tile (the producer's copy below rounds up instead: its buffer is round_up(N, 32) columns wide)
+        uint2 t;
+        t.x = pack2bf(v[0], v[1]);
+        t.y = pack2bf(v[2], v[3]);
+        *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(g.C) + frag_offset(fm, fn, g.N >> 5)) = t;
+        return;
+    }
+    bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + (size_t)fm * g.ldc + fn;
+    if (fn + 3 < g.N && (g.ldc & 3) == 0) {
+        uint2 t;
+        t.x = pack2bf(v[0], v[1]);
+        t.y = pack2bf(v[2], v[3]);
+        *reinterpret_cast<uint2*>(cp) = t;
+    } else {
+        for (int r = 0; r < 4; ++r)
+            if (fn + r < g.N) cp[r] = f2bf(v[r]);
+    }
+}
+
 enum { DEPI_BF16 = 0, DEPI_RES = 1 };
 
 // grid = (ceil(N/16), ceil(M/(16*MT))); block = 64*NW
@@ -100,21 +226,13 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs g) {
     RowStatLoads sl;
     bool have_stats = false;
     float4 ep_a = {0.f, 0.f, 0.f, 0.f}, ep_b = ep_a, ep_c = ep_a, ep_d = ep_a;
-    auto ld4 = [&](const float* p, int n) {
-        float4 r;
-        r.x = p[n < g.N ? n : g.N - 1];
-        r.y = p[n + 1 < g.N ? n + 1 : g.N - 1];
-        r.z = p[n + 2 < g.N ? n + 2 : g.N - 1];
-        r.w = p[n + 3 < g.N ? n + 3 : g.N - 1];
-        return r;
-    };
     if (finisher && !(g.dbg & 8)) {
-        ep_a = ld4(g.bias, fn);
+        ep_a = load_cols4(g.bias, fn, g.N);
         if constexpr (EPI == DEPI_BF16) {
             if (g.stats_in) {
                 stats_issue(sl, g.stats_in, g.strips_in, g.M, fm, lg);
                 have_stats = true;
-                ep_b = ld4(g.colsum, fn);
+                ep_b = load_cols4(g.colsum, fn, g.N);
             }
         } else {
             // residual source (always 16-byte aligned: N % 16 == 0 for this epilogue)
@@ -130,9 +248,7 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs g) {
 
     // ---- K range of this wave, operand pointers ----------------------------------------------------------
     const int ksteps = g.K >> 5;
-    const int per = (ksteps + NW - 1) / NW;
-    const int kb = wave * per;
-    const int ke = min(kb + per, ksteps);
+    const KSlice ks = k_slice(ksteps, NW, wave);
 
     // fragment-major operands: tile (row tile, k-step) is 512 elements, this lane's 8 at lane*8
     const bf16_t* wp = W + frag_tile(blockIdx.x, 0, ksteps, lane);
@@ -173,60 +289,27 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs g) {
                 acc[i] = mfma16(wf[u], xf[u][i], acc[i]);
     };
     constexpr int UBIG = MT >= 4 ? 6 : 12;       // <= 30 sixteen-byte loads in flight per lane
-    int k = kb;
-    for (; k + UBIG <= ke; k += UBIG) chunk(std::integral_constant<int, UBIG>{}, k);
-    for (; k + 2 <= ke; k += 2) chunk(std::integral_constant<int, 2>{}, k);
-    for (; k < ke; ++k) chunk(std::integral_constant<int, 1>{}, k);
+    int k = ks.kb;
+    for (; k + UBIG <= ks.ke; k += UBIG) chunk(std::integral_constant<int, UBIG>{}, k);
+    for (; k + 2 <= ks.ke; k += 2) chunk(std::integral_constant<int, 2>{}, k);
+    for (; k < ks.ke; ++k) chunk(std::integral_constant<int, 1>{}, k);
 
     // ---- cross-wave reduction: every wave publishes all its tiles; wave i sums tile i over the writers 0..NW-1 --
 #pragma unroll
     for (int i = 0; i < MT; ++i) red[wave][i][lane] = acc[i];
     __syncthreads();
     if (!finisher) return;
-    f32x4_t tot = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const f32x4_t t = red[w][fi][lane];
-        tot[0] += t[0]; tot[1] += t[1]; tot[2] += t[2]; tot[3] += t[3];
-    }
-    float v[4] = {tot[0], tot[1], tot[2], tot[3]};
-    const float biasv[4] = {ep_a.x, ep_a.y, ep_a.z, ep_a.w};
+    const f32x4_t tot = sum_waves<NW>(red, fi, lane);
 
     if constexpr (EPI == DEPI_BF16) {
-        if (have_stats) {
-            float mean, rstd;
-            stats_finish(sl, g.inv_d, g.eps_in, mean, rstd);
-            const float cs[4] = {ep_b.x, ep_b.y, ep_b.z, ep_b.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = rstd * (v[r] - mean * cs[r]) + biasv[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += biasv[r];
-        }
-        if (g.act != GITMI_ACT_NONE) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = apply_act(v[r], g.act);
-        }
-        if (fm_raw >= g.M || fn >= g.N) return;
-        if (g.c_frag) {      // operand of the next chain GEMM (N % 32 == 0): 4 consecutive columns = 8 contiguous bytes
-            uint2 t;
-            t.x = pack2bf(v[0], v[1]);
-            t.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(g.C) + frag_offset(fm, fn, g.N >> 5)) = t;
-            return;
-        }
-        bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + (size_t)fm * g.ldc + fn;
-        if (fn + 3 < g.N && (g.ldc & 3) == 0) {
-            uint2 t;
-            t.x = pack2bf(v[0], v[1]);
-            t.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(cp) = t;
-        } else {
-            for (int r = 0; r < 4; ++r)
-                if (fn + r < g.N) cp[r] = f2bf(v[r]);
-        }
+        float mean = 0.f, rstd = 1.f;
+        if (have_stats) stats_finish(sl, g.inv_d, g.eps_in, mean, rstd);
+        DGEMM_CONSUMER_FINISH(v, tot, ep_a, ep_b, have_stats, mean, rstd, g.act);
+        consumer_store(g, v, fm_raw, fm, fn);
     } else {
         // x = A W^T + bias + residual, residual = LayerNorm_prev(x_prev) rebuilt from its strip partials
+        float v[4] = {tot[0], tot[1], tot[2], tot[3]};
+        const float biasv[4] = {ep_a.x, ep_a.y, ep_a.z, ep_a.w};
         float res[4] = {ep_b.x, ep_b.y, ep_b.z, ep_b.w};
         if (have_stats) {
             float mean, rstd;
@@ -257,12 +340,10 @@ __global__ __launch_bounds__(64 * NW) void dgemm_kernel(DGemmArgs g) {
 }
 
 // ---- wide form over MORE than 64 rows (beam batches, decode groups): the workgroup walks the row blocks ------------
-// grid = (ceil(N/16), 1); block = 256.  Same arithmetic per row as dgemm_kernel<4, 4, DEPI_BF16> (K split over 4 waves,
-// partials summed in wave order), so results are bit-identical; the wave's slice of the weight strip (K/4 <= 6 k-steps)
-// is loaded ONCE and stays in registers while the workgroup walks the 64-row blocks -- with one workgroup per (strip,
-// row block) a 256-row beam batch streamed every weight four times (9.1 us against 5.7 us for 64 rows).
-constexpr int DW_KS = 6;        // k-steps per wave held in registers: K <= 4 * 6 * 32 = 768
-
+// grid = (ceil(N/16), 1); block = 256.  Per row the arithmetic of dgemm_kernel<4, 4, DEPI_BF16> through the helpers above (K
+// split over 4 waves, partials summed in wave order), so results are bit-identical; the wave's slice of the weight strip
+// (K/4 <= 6 k-steps) is loaded ONCE and stays in registers while the workgroup walks the 64-row blocks -- with one workgroup
+// per (strip, row block) a 256-row beam batch streamed every weight four times (9.1 us against 5.7 us for 64 rows).
 __global__ __launch_bounds__(256) void dgemm_wide_rows_kernel(DGemmArgs g) {
     __shared__ __attribute__((aligned(16))) f32x4_t red[2][4][4][64];      // double-buffered: one barrier per row block
 
@@ -271,26 +352,12 @@ __global__ __launch_bounds__(256) void dgemm_wide_rows_kernel(DGemmArgs g) {
     const int n0 = blockIdx.x * 16, fn = n0 + lg * 4;
     const bf16_t* __restrict__ X = g.A;
     const int ksteps = g.K >> 5;
-    const int per = (ksteps + 3) / 4;
-    const int kb = wave * per, ke = min(kb + per, ksteps);
+    const KSlice ks = k_slice(ksteps, 4, wave);
 
-    auto ld4 = [&](const float* p, int n) {
-        float4 r;
-        r.x = p[n < g.N ? n : g.N - 1];
-        r.y = p[n + 1 < g.N ? n + 1 : g.N - 1];
-        r.z = p[n + 2 < g.N ? n + 2 : g.N - 1];
-        r.w = p[n + 3 < g.N ? n + 3 : g.N - 1];
-        return r;
-    };
     // per-column constants and this wave's weight fragments: once per workgroup
-    const float4 bias4 = ld4(g.bias, fn);
-    const float4 cs4 = g.stats_in ? ld4(g.colsum, fn) : float4{0.f, 0.f, 0.f, 0.f};
-    const bf16_t* wp = g.W + frag_tile(blockIdx.x, 0, ksteps, lane);
-    bf16x8_t wf[DW_KS];
-#pragma unroll
-    for (int u = 0; u < DW_KS; ++u)
-        wf[u] = kb + u < ke ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wp + (size_t)(kb + u) * 512))
-                            : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    const float4 bias4 = load_cols4(g.bias, fn, g.N);
+    const float4 cs4 = g.stats_in ? load_cols4(g.colsum, fn, g.N) : float4{0.f, 0.f, 0.f, 0.f};
+    const WSlice wf = load_w_slice(g.W, blockIdx.x, ks, ksteps, lane);
 
     const int nrb = (g.M + 63) >> 6;
     for (int rb = 0; rb < nrb; ++rb) {
@@ -300,75 +367,29 @@ __global__ __launch_bounds__(256) void dgemm_wide_rows_kernel(DGemmArgs g) {
         RowStatLoads sl;
         if (g.stats_in) stats_issue(sl, g.stats_in, g.strips_in, g.M, fm, lg);
         bf16x8_t xf[DW_KS][4];
-#pragma unroll
-        for (int u = 0; u < DW_KS; ++u)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                xf[u][i] = kb + u < ke ? *reinterpret_cast<const bf16x8_t*>(X + frag_tile(rb * 4 + i, kb + u, ksteps, lane))
-                                       : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        load_x_slice(xf, X, rb * 4, ks, ksteps, lane);
         f32x4_t acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < DW_KS; ++u) {
-            if (kb + u < ke) {                                   // uniform per wave; keeps the MFMA sequence of dgemm_kernel
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma16(wf[u], xf[u][i], acc[i]);
-            }
-        }
+        mfma_slice(acc, wf, xf, ks);
         f32x4_t(*rd)[4][64] = red[rb & 1];
 #pragma unroll
         for (int i = 0; i < 4; ++i) rd[wave][i][lane] = acc[i];
         __syncthreads();
-        f32x4_t tot = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const f32x4_t t = rd[w][wave][lane];
-            tot[0] += t[0]; tot[1] += t[1]; tot[2] += t[2]; tot[3] += t[3];
-        }
-        float v[4] = {tot[0], tot[1], tot[2], tot[3]};
-        const float biasv[4] = {bias4.x, bias4.y, bias4.z, bias4.w};
-        if (g.stats_in) {
-            float mean, rstd;
-            stats_finish(sl, g.inv_d, g.eps_in, mean, rstd);
-            const float cs[4] = {cs4.x, cs4.y, cs4.z, cs4.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = rstd * (v[r] - mean * cs[r]) + biasv[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += biasv[r];
-        }
-        if (g.act != GITMI_ACT_NONE) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = apply_act(v[r], g.act);
-        }
-        if (fm_raw >= g.M || fn >= g.N) continue;
-        if (g.c_frag) {
-            uint2 t;
-            t.x = pack2bf(v[0], v[1]);
-            t.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(g.C) + frag_offset(fm, fn, g.N >> 5)) = t;
-            continue;
-        }
-        bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + (size_t)fm * g.ldc + fn;
-        if (fn + 3 < g.N && (g.ldc & 3) == 0) {
-            uint2 t;
-            t.x = pack2bf(v[0], v[1]);
-            t.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(cp) = t;
-        } else {
-            for (int r = 0; r < 4; ++r)
-                if (fn + r < g.N) cp[r] = f2bf(v[r]);
-        }
+        const f32x4_t tot = sum_waves<4>(rd, wave, lane);
+        float mean = 0.f, rstd = 1.f;
+        if (g.stats_in) stats_finish(sl, g.inv_d, g.eps_in, mean, rstd);
+        DGEMM_CONSUMER_FINISH(v, tot, bias4, cs4, g.stats_in, mean, rstd, g.act);
+        consumer_store(g, v, fm_raw, fm, fn);
     }
 }
 
 // ---- wide form, <= 64 rows, NST adjacent 16-column strips per workgroup ----------------------------------------------
-// grid = (ceil(strips / NST), 1); block = 256.  Per element the arithmetic of dgemm_kernel<4, 4, DEPI_BF16> (K split over 4
-// waves, partials summed in wave order): bit-identical results.  The four waves load the activation fragments of their K
-// slice ONCE and the weight fragments of all NST strips up front (one memory round trip, as before), then run the strips
-// back to back: 1/NST of the workgroups / resident waves and of the activation traffic for ~1 us more per extra strip --
-// what a decode launch costs the image encoders running beside it is its resident waves x time.
+// grid = (ceil(strips / NST), 1); block = 256.  Per element the arithmetic of dgemm_kernel<4, 4, DEPI_BF16> through the helpers
+// above: bit-identical results.  The four waves load the activation fragments of their K slice ONCE and the weight fragments of
+// all NST strips up front (one memory round trip, as before), then run the strips back to back: 1/NST of the workgroups /
+// resident waves and of the activation traffic for ~1 us more per extra strip -- what a decode launch costs the image
+// encoders running beside it is its resident waves x time.
 template <int NST>
 __global__ __launch_bounds__(256) void dgemm_wide_strips_kernel(DGemmArgs g) {
     __shared__ __attribute__((aligned(16))) f32x4_t red[NST][4][4][64];      // [strip][wave][row tile][lane]
@@ -378,54 +399,30 @@ __global__ __launch_bounds__(256) void dgemm_wide_strips_kernel(DGemmArgs g) {
     const int nstrips = (g.N + 15) >> 4;
     const bf16_t* __restrict__ X = g.A;
     const int ksteps = g.K >> 5;
-    const int per = (ksteps + 3) / 4;
-    const int kb = wave * per, ke = min(kb + per, ksteps);
+    const KSlice ks = k_slice(ksteps, 4, wave);
     const int fm_raw = wave * 16 + l15;                       // wave i finishes row tile i
     const int fm = fm_raw < g.M ? fm_raw : g.M - 1;
 
-    auto ld4 = [&](const float* p, int n) {
-        float4 r;
-        r.x = p[n < g.N ? n : g.N - 1];
-        r.y = p[n + 1 < g.N ? n + 1 : g.N - 1];
-        r.z = p[n + 2 < g.N ? n + 2 : g.N - 1];
-        r.w = p[n + 3 < g.N ? n + 3 : g.N - 1];
-        return r;
-    };
     RowStatLoads sl;
     if (g.stats_in) stats_issue(sl, g.stats_in, g.strips_in, g.M, fm, lg);
     float4 bias4[NST], cs4[NST];
-    bf16x8_t wf[NST][DW_KS];
+    WSlice wf[NST];
 #pragma unroll
     for (int t = 0; t < NST; ++t) {
-        const int strip = min((int)blockIdx.x * NST + t, nstrips - 1);
+        const int strip = min((int)blockIdx.x * NST + t, nstrips - 1);      // an absent strip re-reads the last one; it is not stored
         const int fn = strip * 16 + lg * 4;
-        bias4[t] = ld4(g.bias, fn);
-        cs4[t] = g.stats_in ? ld4(g.colsum, fn) : float4{0.f, 0.f, 0.f, 0.f};
-        const bf16_t* wp = g.W + frag_tile(strip, 0, ksteps, lane);
-#pragma unroll
-        for (int u = 0; u < DW_KS; ++u)
-            wf[t][u] = kb + u < ke ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wp + (size_t)(kb + u) * 512))
-                                   : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        bias4[t] = load_cols4(g.bias, fn, g.N);
+        cs4[t] = g.stats_in ? load_cols4(g.colsum, fn, g.N) : float4{0.f, 0.f, 0.f, 0.f};
+        wf[t] = load_w_slice(g.W, strip, ks, ksteps, lane);
     }
     bf16x8_t xf[DW_KS][4];
-#pragma unroll
-    for (int u = 0; u < DW_KS; ++u)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            xf[u][i] = kb + u < ke ? *reinterpret_cast<const bf16x8_t*>(X + frag_tile(i, kb + u, ksteps, lane))
-                                   : bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    load_x_slice(xf, X, 0, ks, ksteps, lane);
 #pragma unroll
     for (int t = 0; t < NST; ++t) {
         f32x4_t acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < DW_KS; ++u) {
-            if (kb + u < ke) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = mfma16(wf[t][u], xf[u][i], acc[i]);
-            }
-        }
+        mfma_slice(acc, wf[t], xf, ks);
 #pragma unroll
         for (int i = 0; i < 4; ++i) red[t][wave][i][lane] = acc[i];
     }
@@ -437,44 +434,9 @@ __global__ __launch_bounds__(256) void dgemm_wide_strips_kernel(DGemmArgs g) {
         const int strip = (int)blockIdx.x * NST + t;
         if (strip >= nstrips) break;
         const int fn = strip * 16 + lg * 4;
-        f32x4_t tot = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const f32x4_t p = red[t][w][wave][lane];
-            tot[0] += p[0]; tot[1] += p[1]; tot[2] += p[2]; tot[3] += p[3];
-        }
-        float v[4] = {tot[0], tot[1], tot[2], tot[3]};
-        const float biasv[4] = {bias4[t].x, bias4[t].y, bias4[t].z, bias4[t].w};
-        if (g.stats_in) {
-            const float cs[4] = {cs4[t].x, cs4[t].y, cs4[t].z, cs4[t].w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = rstd * (v[r] - mean * cs[r]) + biasv[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += biasv[r];
-        }
-        if (g.act != GITMI_ACT_NONE) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = apply_act(v[r], g.act);
-        }
-        if (fm_raw >= g.M || fn >= g.N) continue;
-        if (g.c_frag) {
-            uint2 o;
-            o.x = pack2bf(v[0], v[1]);
-            o.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(g.C) + frag_offset(fm, fn, g.N >> 5)) = o;
-            continue;
-        }
-        bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + (size_t)fm * g.ldc + fn;
-        if (fn + 3 < g.N && (g.ldc & 3) == 0) {
-            uint2 o;
-            o.x = pack2bf(v[0], v[1]);
-            o.y = pack2bf(v[2], v[3]);
-            *reinterpret_cast<uint2*>(cp) = o;
-        } else {
-            for (int r = 0; r < 4; ++r)
-                if (fn + r < g.N) cp[r] = f2bf(v[r]);
-        }
+        const f32x4_t tot = sum_waves<4>(red[t], wave, lane);
+        DGEMM_CONSUMER_FINISH(v, tot, bias4[t], cs4[t], g.stats_in, mean, rstd, g.act);
+        consumer_store(g, v, fm_raw, fm, fn);
     }
 }
 
@@ -803,40 +765,59 @@ __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
 }
 
 // ---- host launchers ------------------------------------------------------------------
+// f(MT, NW) as std::integral_constants: the instantiation of dgemm_kernel for mt row tiles per workgroup, 8 waves at a long K
+template <class F>
+static void with_tile_waves(int mt, bool big_k, F&& f) {
+    auto with_nw = [&](auto mtc) {
+        if (big_k) f(mtc, std::integral_constant<int, 8>{});
+        else f(mtc, std::integral_constant<int, 4>{});
+    };
+    if (mt == 4) with_nw(std::integral_constant<int, 4>{});
+    else if (mt == 2) with_nw(std::integral_constant<int, 2>{});
+    else with_nw(std::integral_constant<int, 1>{});
+}
+// dgemm_kernel on 16 * mt rows per workgroup
 template <int EPI>
-static hipError_t launch_dgemm_t(const DGemmArgs& g, hipStream_t s) {
-    // rows per workgroup: all of a <=64-row batch share one pass over the weight strip when the strip count alone
-    // fills the chip (N >= 2304); the N = 768 GEMMs use 16-row blocks so that 48 strips x R/16 workgroups do
-    const bool wide = g.N >= 1536;
-    const int big_k = g.K >= 2048;
-    if (EPI == DEPI_RES || !wide) {
-        // g.rows_per_wg: 16 (default: 48 strips x R/16 workgroups, each re-reading its weight strip from the L2) / 32 / 64
-        // (one pass over the strip for 64 rows: a quarter of the workgroups and 40 % less L2 traffic, a longer launch)
-        const int mt = g.rows_per_wg >= 64 && g.M > 32 ? 4 : g.rows_per_wg >= 32 && g.M > 16 ? 2 : 1;
-        dim3 grid((g.N + 15) / 16, (g.M + 16 * mt - 1) / (16 * mt));
-        if (mt == 4) {
-            if (big_k) hipLaunchKernelGGL((dgemm_kernel<4, 8, EPI>), grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((dgemm_kernel<4, 4, EPI>), grid, dim3(256), 0, s, g);
-        } else if (mt == 2) {
-            if (big_k) hipLaunchKernelGGL((dgemm_kernel<2, 8, EPI>), grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((dgemm_kernel<2, 4, EPI>), grid, dim3(256), 0, s, g);
-        } else if (big_k) hipLaunchKernelGGL((dgemm_kernel<1, 8, EPI>), grid, dim3(512), 0, s, g);
-        else hipLaunchKernelGGL((dgemm_kernel<1, 4, EPI>), grid, dim3(256), 0, s, g);
-    } else if (g.M <= 16) {
-        hipLaunchKernelGGL((dgemm_kernel<1, 4, EPI>), dim3((g.N + 15) / 16, 1), dim3(256), 0, s, g);
-    } else if (g.M <= 32) {
-        hipLaunchKernelGGL((dgemm_kernel<2, 4, EPI>), dim3((g.N + 15) / 16, 1), dim3(256), 0, s, g);
-    } else if (EPI == DEPI_BF16 && g.M <= 64 && (g.K >> 5) <= 4 * DW_KS && g.strips_per_wg >= 2) {
+static void launch_tiles(const DGemmArgs& g, int mt, bool big_k, hipStream_t s) {
+    with_tile_waves(mt, big_k, [&](auto mtc, auto nwc) {
+        constexpr int MT = decltype(mtc)::value, NW = decltype(nwc)::value;
+        hipLaunchKernelGGL((dgemm_kernel<MT, NW, EPI>), dim3((g.N + 15) / 16, (g.M + 16 * MT - 1) / (16 * MT)), dim3(64 * NW), 0, s, g);
+    });
+}
+
+// producer (N = hidden) and narrow consumer (N < 1536): the strip count alone does not fill the chip, so the rows are split too.
+// g.rows_per_wg: 16 (default: 48 strips x R/16 workgroups, each re-reading its weight strip from the L2) / 32 / 64 (one pass
+// over the strip for 64 rows: a quarter of the workgroups and 40 % less L2 traffic, a longer launch)
+template <int EPI>
+static void launch_narrow(const DGemmArgs& g, hipStream_t s) {
+    const int mt = g.rows_per_wg >= 64 && g.M > 32 ? 4 : g.rows_per_wg >= 32 && g.M > 16 ? 2 : 1;
+    launch_tiles<EPI>(g, mt, g.K >= 2048, s);
+}
+// wide consumer (N >= 1536): all of a <= 64-row batch shares one pass over the weight strip, four waves whatever K
+static void launch_wide(const DGemmArgs& g, hipStream_t s) {
+    const bool k_in_regs = (g.K >> 5) <= 4 * DW_KS;
+    if (g.M <= 16) launch_tiles<DEPI_BF16>(g, 1, false, s);
+    else if (g.M <= 32) launch_tiles<DEPI_BF16>(g, 2, false, s);
+    else if (g.M <= 64 && k_in_regs && g.strips_per_wg >= 2) {
         const int nst = g.strips_per_wg >= 6 ? 6 : g.strips_per_wg >= 4 ? 4 : 2;                        // strips per workgroup
-        const dim3 grid(((g.N + 15) / 16 + nst - 1) / nst, 1);
-        if (nst == 6) hipLaunchKernelGGL(dgemm_wide_strips_kernel<6>, grid, dim3(256), 0, s, g);
-        else if (nst == 4) hipLaunchKernelGGL(dgemm_wide_strips_kernel<4>, grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(dgemm_wide_strips_kernel<2>, grid, dim3(256), 0, s, g);
-    } else if (EPI == DEPI_BF16 && g.M > 64 && (g.K >> 5) <= 4 * DW_KS && !g.dbg && !g.no_row_walk) {
+        auto strips = [&](auto nc) {
+            constexpr int NST = decltype(nc)::value;
+            hipLaunchKernelGGL(dgemm_wide_strips_kernel<NST>, dim3(((g.N + 15) / 16 + NST - 1) / NST, 1), dim3(256), 0, s, g);
+        };
+        if (nst == 6) strips(std::integral_constant<int, 6>{});
+        else if (nst == 4) strips(std::integral_constant<int, 4>{});
+        else strips(std::integral_constant<int, 2>{});
+    } else if (g.M > 64 && k_in_regs && !g.dbg && !g.no_row_walk) {
         hipLaunchKernelGGL(dgemm_wide_rows_kernel, dim3((g.N + 15) / 16, 1), dim3(256), 0, s, g);       // weights once for all row blocks
     } else {
-        hipLaunchKernelGGL((dgemm_kernel<4, 4, EPI>), dim3((g.N + 15) / 16, (g.M + 63) / 64), dim3(256), 0, s, g);
+        launch_tiles<DEPI_BF16>(g, 4, false, s);      // one workgroup per (strip, 64-row block)
     }
+}
+template <int EPI>
+static hipError_t launch_dgemm_t(const DGemmArgs& g, hipStream_t s) {
+    if constexpr (EPI == DEPI_RES) launch_narrow<EPI>(g, s);
+    else if (g.N >= 1536) launch_wide(g, s);
+    else launch_narrow<EPI>(g, s);
     return hipGetLastError();
 }
 

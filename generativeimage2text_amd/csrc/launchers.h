@@ -53,6 +53,30 @@ struct DGemmArgs {
     int no_row_walk;            // A/B: wide form over > 64 rows as one workgroup per (strip, row block) instead of the row-walking kernel
 };
 hipError_t launch_dgemm(const DGemmArgs& g, hipStream_t s);
+// The two argument records of the chain (the policy fields rows_per_wg / strips_per_wg / no_row_walk / dbg stay 0: the caller's).
+// DLn: a LayerNorm of the chain, i.e. the strip partials of the rows it normalises and its (gamma, beta, eps)
+struct DLn { const float2* stats; int strips; float inv_d, eps; const float* gamma; const float* beta; };
+// consumer: C = act(LayerNorm(A) W^T + b) with the LayerNorm folded into (W, bias, colsum); ln == nullptr: plain A, colsum is not read
+inline DGemmArgs dgemm_ln(const void* A, const void* W, const float* bias, const float* colsum, const DLn* ln, void* C, int c_frag,
+                          int act, int M, int N, int K) {
+    DGemmArgs g{};
+    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias;
+    if (ln) { g.colsum = colsum; g.stats_in = ln->stats; g.strips_in = ln->strips; g.inv_d = ln->inv_d; g.eps_in = ln->eps; }
+    g.C = C; g.ldc = N; g.c_frag = c_frag; g.act = act; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+// producer: x_out = A W^T + b + residual (res_x itself, or LayerNorm(res_x) rebuilt from res_ln), its bf16 copy and strip partials
+inline DGemmArgs dgemm_to_stream(const void* A, const void* W, const float* bias, const float* res_x, const DLn* res_ln, float* x_out,
+                                 void* xb_out, float2* stats_out, int M, int N, int K) {
+    DGemmArgs g{};
+    g.A = (const unsigned short*)A; g.lda = K; g.W = (const unsigned short*)W; g.bias = bias; g.res_x = res_x;
+    if (res_ln) {
+        g.res_stats = res_ln->stats; g.res_strips = res_ln->strips; g.res_gamma = res_ln->gamma; g.res_beta = res_ln->beta;
+        g.res_inv_d = res_ln->inv_d; g.res_eps = res_ln->eps;
+    }
+    g.x_out = x_out; g.xb_out = (unsigned short*)xb_out; g.stats_out = stats_out; g.M = M; g.N = N; g.K = K;
+    return g;
+}
 
 // vocabulary head with the running top-M / log-sum-exp fused: one sorted candidate list per (row, workgroup)
 struct VocabArgs {

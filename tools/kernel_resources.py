@@ -59,4 +59,11 @@ def main(out_path=None):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else None)
+    args = sys.argv[1:]
+    if "--help" in args or "-h" in args:
+        print(__doc__)
+        sys.exit(0)
+    paths = [a for a in args if a != "--f16"]
+    if len(paths) > 1 or any(a.startswith("-") for a in paths):       # an option taken for the output path would become a file name
+        sys.exit("kernel_resources.py: unexpected argument(s) %s\n\n%s" % (" ".join(paths), __doc__))
+    main(paths[0] if paths else None)
