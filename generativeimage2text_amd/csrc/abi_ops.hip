@@ -249,6 +249,68 @@ GITMI_EXP_EXPORT int gitmi_debug_set_gemm_impl(int impl) {
     return 0;
 }
 
+// every launch form of the large-M / tile GEMM (tests/test_gpu_gemm_forms.py): an argument check + launch_gemm with everything
+// the engine's gemm_args / gemm_run / ln_gemm / gemm_to_stream set -- leading dimensions of their own (a column slice of a wider
+// buffer: ldc > N with C, W, bias and colsum offset by the caller), the serving policy's `shared`, and the folded-LayerNorm
+// fields of the consumer (ln_part, colsum, ln_eps; K <= 1024) and of the producer (part_out; res_part / res_gamma / res_beta /
+// res_eps: the post-norm residual; N <= 1024).  out_dtype: fp32, the operand type, or GITMI_DTYPE_F16_STREAM (fp16 rows, and
+// `res` fp16 rows; the producer's only kind).  Row partials are [M][4] (sum, sumsq).  Tile heights and XCD partitions are forced
+// through gitmi_debug_set_gemm_impl, so the launcher's own choice is what runs without it.
+GITMI_EXP_EXPORT int gitmi_debug_gemm_form(const void* A, int lda, const void* W, const float* bias, const void* res, int ldr, void* C,
+                                           int ldc, int M, int N, int K, int act, int in_dtype, int out_dtype, int shared,
+                                           const float* ln_part, const float* colsum, float ln_eps, float* part_out,
+                                           const float* res_part, const float* res_gamma, const float* res_beta, float res_eps,
+                                           void* stream) {
+    if (!A || !W || !C) return fail("debug_gemm_form: null argument (A, W, C)");
+    if (M < 0 || N < 1 || K < 1) return fail("debug_gemm_form: M=%d N=%d K=%d", M, N, K);
+    if (lda < K) return fail("debug_gemm_form: lda=%d < K=%d", lda, K);
+    if (ldc < N) return fail("debug_gemm_form: ldc=%d < N=%d", ldc, N);
+    if (res && ldr < N) return fail("debug_gemm_form: ldr=%d < N=%d", ldr, N);
+    if (act < GITMI_ACT_NONE || act > GITMI_ACT_GELU_ERF) return fail("debug_gemm_form: act=%d", act);
+    RCK(check_dtype("debug_gemm_form", "in_dtype", in_dtype));
+    const bool in_f32 = in_dtype == GITMI_DTYPE_F32;
+    if ((in_f32 && K % 16) || (!in_f32 && K % 64)) return fail("debug_gemm_form: K must be a multiple of %d (K=%d)", in_f32 ? 16 : 64, K);
+    GemmArgs g{};
+    g.A = A; g.W = W; g.bias = bias; g.res = (const float*)res; g.C = C;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.ldr = res ? ldr : 0; g.act = act;
+    g.shared = shared ? 1 : 0;
+    if (out_dtype == GITMI_DTYPE_F16_STREAM) {
+        if (in_f32) return fail("debug_gemm_form: fp16 stream rows need 16-bit operands");
+        g.out_f16 = 1;
+    } else {
+        RCK(check_dtype("debug_gemm_form", "out_dtype", out_dtype));
+    }
+    const bool out_f32 = out_dtype == GITMI_DTYPE_F32;
+    const bool consumer = ln_part != nullptr, producer = part_out != nullptr || res_part != nullptr;
+    if (colsum && !consumer) return fail("debug_gemm_form: colsum without ln_part");
+    if ((res_gamma || res_beta) && !res_part) return fail("debug_gemm_form: res_gamma / res_beta without res_part");
+    if (consumer || producer) {
+#ifndef GITMI_OPS_F16
+        return fail("debug_gemm_form: the folded-LayerNorm forms are built into the fp16-operand library only");
+#endif
+        if (consumer && producer) return fail("debug_gemm_form: consumer (ln_part) and producer (part_out / res_part) arguments in one launch");
+        if (consumer) {
+            if (!colsum) return fail("debug_gemm_form: ln_part without colsum");
+            if (res || in_f32 || out_f32 || g.out_f16) return fail("debug_gemm_form: the consumer writes operand-type rows and takes no residual");
+            if (K > 1024) return fail("debug_gemm_form: row partials cover K <= 1024 (K=%d)", K);
+            g.ln_part = (const float2*)ln_part; g.ln_nparts = (K + 255) / 256; g.ln_colsum = colsum; g.ln_inv_d = 1.0f / (float)K; g.ln_eps = ln_eps;
+        } else {
+            if (!g.out_f16 || act != GITMI_ACT_NONE) return fail("debug_gemm_form: the producer writes fp16 stream rows and has no activation");
+            if (N > 1024) return fail("debug_gemm_form: row partials cover N <= 1024 (N=%d)", N);
+            g.part_out = (float2*)part_out;
+            if (res_part) {
+                if (!res || !res_gamma || !res_beta) return fail("debug_gemm_form: res_part without res / res_gamma / res_beta");
+                g.res_part = (const float2*)res_part; g.res_nparts = (N + 255) / 256; g.res_gamma = res_gamma; g.res_beta = res_beta;
+                g.res_inv_d = 1.0f / (float)N; g.res_eps = res_eps;
+            }
+        }
+        if (!gemm_uses_p8(g, false, false))
+            return fail("debug_gemm_form: the folded forms exist in gemm_p8_kernel only (more than 512 rows, N %% 256 == 0, K >= 128, 16-byte aligned rows)");
+    }
+    HIPCK(launch_gemm(g, in_f32, out_f32, (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" int gitmi_op_attn_decode(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
                                     const int* kv_src, void* out, int B, int H, int N_img, int T_max, int pos, int beams,
                                     int dtype, int dbg, void* stream) {

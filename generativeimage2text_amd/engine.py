@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgitmi.so")                 # bf16 operands (BASELINE's named precision; bench.py: alt_precision)
 LIB_PATH_F16 = os.path.join(_HERE, "libgitmi_f16.so")         # the same sources built for fp16 operands (-DGITMI_OPS_F16)
 LIB_PATH_EXP = os.path.join(_HERE, "libgitmi_exp.so")         # measurement build of libgitmi.so (-DGITMI_EXPERIMENT): see use_experiment_build
+LIB_PATH_F16_EXP = os.path.join(_HERE, "libgitmi_f16_exp.so") # measurement build of libgitmi_f16.so: the hooks of gitmi_experiment.h on fp16 operands
 
 PREC_BF16, PREC_F32 = 0, 1
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
@@ -36,13 +37,14 @@ EXPORTED_SYMBOLS = [
     "gitmi_search_done_count", "gitmi_set_trie", "gitmi_operand_dtype", "gitmi_set_shared_device", "gitmi_preprocess_batch",
     "gitmi_set_ln_fold", "gitmi_op_gemm_ln",
 ]
-# libgitmi_exp.so only (include/gitmi_experiment.h): schedules that measured slower than the default, debug hooks
+# libgitmi_exp.so and libgitmi_f16_exp.so only (include/gitmi_experiment.h): schedules that measured slower than the default, debug hooks
 EXPERIMENT_SYMBOLS = [
     "gitmi_debug_import_stage", "gitmi_debug_head_from", "gitmi_debug_set_gemm_impl", "gitmi_debug_set_dgemm",
     "gitmi_debug_score_attn", "gitmi_debug_score_head", "gitmi_debug_attention_ragged", "gitmi_debug_attn_decode_ragged",
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
+    "gitmi_debug_gemm_form",
 ]
 
 
@@ -78,24 +80,28 @@ class GitmiError(RuntimeError):
 
 _libs: Dict[str, C.CDLL] = {}
 _experiment = False
+_MEASUREMENT_LIBS = ("exp", "f16_exp")
+_gemm_impl = -1           # the last set_gemm_impl selector: a measurement library loaded later starts from it
 
 
 def use_experiment_build(on: bool = True) -> None:
     """Measurement harnesses only (bench.py --experiment, tools/): serve "bf16" from libgitmi_exp.so, the same kernels built
     with -DGITMI_EXPERIMENT -- kernel-shape overrides and work-skipping switches read from GITMI_* environment variables
-    at gitmi_create.  The product libraries read no environment; nothing in the package turns this on."""
+    at gitmi_create.  The product libraries read no environment; nothing in the package turns this on.  "f16" stays
+    libgitmi_f16.so (Engine(precision="f16") is the product library either way); the wrappers of the measurement-only entry points
+    (_exp_library) reach the fp16 measurement build, libgitmi_f16_exp.so, by the type of their tensors."""
     global _experiment
     _experiment = bool(on)
 
 
 def load_library(operands: str = "bf16") -> C.CDLL:
     """dlopen libgitmi.so (operands="bf16") or libgitmi_f16.so (operands="f16"); raises (never falls back) when it has
-    not been built."""
+    not been built.  "exp" / "f16_exp": their measurement builds."""
     if operands == "bf16" and _experiment:
         operands = "exp"
     if operands in _libs:
         return _libs[operands]
-    path = {"bf16": LIB_PATH, "f16": LIB_PATH_F16, "exp": LIB_PATH_EXP}[operands]
+    path = {"bf16": LIB_PATH, "f16": LIB_PATH_F16, "exp": LIB_PATH_EXP, "f16_exp": LIB_PATH_F16_EXP}[operands]
     if not os.path.exists(path):
         raise GitmiError(
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -143,13 +149,15 @@ def load_library(operands: str = "bf16") -> C.CDLL:
     lib.gitmi_op_attn_decode.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.gitmi_op_kv_repack.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     lib.gitmi_op_sample_rows.argtypes = [vp, i32, i32, C.c_float, i32, C.c_float, i32, C.c_uint64, i32, vp, vp, vp, vp]
-    if operands == "exp":
+    if operands in _MEASUREMENT_LIBS:
         lib.gitmi_debug_import_stage.argtypes = [vp, vp, i32, vp]
         lib.gitmi_debug_head_from.argtypes = [vp, vp, i32, vp, vp]
         lib.gitmi_debug_set_gemm_impl.argtypes = [i32]
         lib.gitmi_debug_set_dgemm.argtypes = [i32]
         lib.gitmi_debug_dgemm_form.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.c_float, vp, i32, i32, vp, vp, i32, vp, vp, C.c_float,
                                                vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_gemm_form.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, C.c_float,
+                                              vp, vp, vp, vp, C.c_float, vp]
         lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         lib.gitmi_debug_score_attn_map.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
@@ -169,24 +177,26 @@ def load_library(operands: str = "bf16") -> C.CDLL:
                                                  C.c_longlong, i32, i32, i32, i32, vp]
         lib.gitmi_debug_zero_pad_rows.argtypes = [vp, i32, i32, vp, i32, i32, vp]
         lib.gitmi_debug_layernorm_map.argtypes = [vp, i32, vp, vp, C.c_float, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
-    for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands == "exp" else []):
+    for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands in _MEASUREMENT_LIBS else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
     if lib.gitmi_abi_version() != 10:
         raise GitmiError("libgitmi.so ABI version mismatch")
     lib.gitmi_operand_dtype.restype = C.c_int
-    if lib.gitmi_operand_dtype() != {"bf16": DTYPE_BF16, "f16": DTYPE_F16, "exp": DTYPE_BF16}[operands]:
+    if lib.gitmi_operand_dtype() != {"bf16": DTYPE_BF16, "f16": DTYPE_F16, "exp": DTYPE_BF16, "f16_exp": DTYPE_F16}[operands]:
         raise GitmiError(f"{path} was not built for {operands} operands")
+    if operands in _MEASUREMENT_LIBS and _gemm_impl != -1:
+        _ck(lib.gitmi_debug_set_gemm_impl(_gemm_impl), lib)
     _libs[operands] = lib
     return lib
 
 
 def _experiment_only(lib, name: str):
-    """An entry point of include/gitmi_experiment.h: present in libgitmi_exp.so only."""
+    """An entry point of include/gitmi_experiment.h: present in libgitmi_exp.so / libgitmi_f16_exp.so only."""
     try:
         return getattr(lib, name)
     except AttributeError:
-        raise GitmiError(f"{name} is exported by the measurement build only (libgitmi_exp.so): call "
+        raise GitmiError(f"{name} is exported by the measurement build only (libgitmi_exp.so, libgitmi_f16_exp.so): call "
                          f"generativeimage2text_amd.engine.use_experiment_build() before creating the engine") from None
 
 
@@ -225,6 +235,21 @@ def _op_library(*dtypes: torch.dtype, fp32_ok: bool = False) -> C.CDLL:
     if len(dts) != 1 or next(iter(dts)) not in _OPERAND_LIBS:
         raise GitmiError(f"operands must all be bf16 or all fp16, got {sorted(str(d) for d in dts) or ['float32']}")
     return load_library(_OPERAND_LIBS[dts.pop()])
+
+
+def _exp_library(*dtypes: torch.dtype, operands: Optional[str] = None) -> C.CDLL:
+    """The library of a gitmi_debug_* call (include/gitmi_experiment.h), picked as _op_library picks the product one: by the
+    dtype of the call's tensors in the 16-bit OPERAND type -- fp16 -> libgitmi_f16_exp.so, bf16 or none -> libgitmi_exp.so.
+    operands ("bf16" | "f16") names it where no tensor can: fp16 residual-stream rows exist in both builds.  Without
+    use_experiment_build() the product library of that type comes back, and _experiment_only says what is missing."""
+    if operands is None:
+        dts = set(dtypes) - {torch.float32}
+        if len(dts) > 1 or not dts <= set(_OPERAND_LIBS):
+            raise GitmiError(f"operands must all be bf16 or all fp16, got {sorted(str(d) for d in dts)}")
+        operands = _OPERAND_LIBS[dts.pop()] if dts else "bf16"
+    if operands not in ("bf16", "f16"):
+        raise GitmiError(f"operands={operands!r}: bf16 or f16")
+    return load_library("f16_exp" if operands == "f16" and _experiment else operands)
 
 
 RAGGED_DESC_BYTES = 256    # the descriptor block of a ragged input is padded to this size (include/gitmi.h)
@@ -873,6 +898,26 @@ def op_gemm_ln(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], *
     return (out, part) if want_part else out
 
 
+def op_gemm_form(A: torch.Tensor, W: torch.Tensor, C: torch.Tensor, M: int, N: int, K: int, *, lda: Optional[int] = None,
+                 ldc: Optional[int] = None, bias=None, res=None, ldr: int = 0, act: int = ACT_NONE, stream_rows: bool = False,
+                 shared: bool = False, ln_part=None, colsum=None, ln_eps: float = 1e-5, part_out=None, res_part=None,
+                 res_gamma=None, res_beta=None, res_eps: float = 1e-5, operands: Optional[str] = None) -> None:
+    """One launch_gemm with everything the engine's gemm_args / gemm_run / ln_gemm / gemm_to_stream set (measurement build;
+    gitmi_debug_gemm_form): A / W / C / bias / res / colsum may be VIEWS that start inside larger buffers (a column slice: ldc > N),
+    C and part_out are caller-supplied and pre-filled.  A, W fp32 or one 16-bit type (that type's measurement build; fp32: the
+    one `operands` names, bf16 by default); C fp32, the operand type, or -- stream_rows -- fp16 residual-stream rows with an fp16
+    residual.  Tile heights and XCD partitions are forced through set_gemm_impl."""
+    if A.dtype != W.dtype:
+        raise GitmiError(f"operands must share one type, got {A.dtype} / {W.dtype}")
+    lib = _exp_library(A.dtype, *(() if stream_rows else (C.dtype,)), operands=operands)
+    out_code = DTYPE_F16_STREAM if stream_rows else _torch_dtype_code(C)
+    _ck(_experiment_only(lib, "gitmi_debug_gemm_form")(
+        A.data_ptr(), int(K if lda is None else lda), W.data_ptr(), _ptr(bias), _ptr(res), int(ldr), C.data_ptr(),
+        int(N if ldc is None else ldc), int(M), int(N), int(K), int(act), _torch_dtype_code(A), out_code, int(bool(shared)),
+        _ptr(ln_part), _ptr(colsum), float(ln_eps), _ptr(part_out), _ptr(res_part), _ptr(res_gamma), _ptr(res_beta), float(res_eps),
+        _stream()), lib)
+
+
 def op_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
                  out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """y = LayerNorm(x) of fp32 rows, written in out_dtype: fp32, or a 16-bit type (run in that type's library)."""
@@ -977,10 +1022,10 @@ def op_dgemm_form(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, M: Optio
     FFN1 form -> out.  The outputs may be supplied (pre-filled, with guard rows behind them) by the caller; xb and a frag_out
     `out` come back as the raw fragment-major buffers (from_frag decodes them; xb is round_up(N, 32) columns wide).  packed=True: A (rows a multiple of 64) and W are
     fragment-major already and M is required; otherwise they are packed here and M is A's row count."""
-    lib = load_library()
-    own = {DTYPE_BF16: torch.bfloat16, DTYPE_F16: torch.float16}[lib.gitmi_operand_dtype()]
-    if A.dtype != own or W.dtype != own:
-        raise GitmiError(f"operands must be {own} in this library, got {A.dtype} / {W.dtype}")
+    lib = _exp_library(A.dtype, W.dtype)
+    own = A.dtype
+    if own == torch.float32:
+        raise GitmiError(f"operands must be bf16 or fp16, got {A.dtype} / {W.dtype}")
     if packed:
         if M is None:
             raise ValueError("packed operands: M is required")
@@ -1005,10 +1050,11 @@ def op_dgemm_form(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, M: Optio
     return (x, xb, stats_out) if producer else out
 
 
-def _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V):
-    """What op_vocab_topm and op_vocab_topm_rules share: the library of the operands' type, the packed operands and the
-    output buffers -> (lib, leading arguments (A .. mtop) of the C entry point, trailing arguments, outputs)."""
-    lib = _op_library(A.dtype, W.dtype)
+def _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V, measurement=False):
+    """What op_vocab_topm and op_vocab_topm_rules share: the library of the operands' type (measurement: its measurement
+    build), the packed operands and the output buffers -> (lib, leading arguments (A .. mtop) of the C entry point, trailing
+    arguments, outputs)."""
+    lib = _exp_library(A.dtype, W.dtype) if measurement else _op_library(A.dtype, W.dtype)
     K = A.shape[1]
     V = int(bias.numel()) if V is None else int(V)
     if packed:
@@ -1050,7 +1096,8 @@ def op_vocab_topm_rules(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mt
     """op_vocab_topm with the rule inputs of a real search step (measurement build): ids int32 [M, ld_ids] row histories of
     cur_len tokens, plen int32 [M / beams] prefix lengths, suppress_kind (no immediate repeat on rows with cur_len > plen),
     rep_penalty.  Same outputs; the materialised logits are taken before the rules."""
-    lib, M, ops, shape, outs, result, keep = _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V)
+    lib, M, ops, shape, outs, result, keep = _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V,
+                                                              measurement=True)
     if ids is not None:
         ids = ids.to(device=A.device, dtype=torch.int32).contiguous()
         plen = plen.to(device=A.device, dtype=torch.int32).contiguous()
@@ -1064,9 +1111,16 @@ def op_vocab_topm_rules(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mt
 
 def set_gemm_impl(impl: int) -> None:
     """Measurement build only (use_experiment_build()): -1 auto, 0 register-staged tile kernel only, 9 the LDS-DMA kernel
-    wherever it can run; 9 | (bits << 8): 64 / 128 force its 192- / 256-row tile (tools/gemm_bench.py lists the others)."""
+    wherever it can run; 9 | (bits << 8): 64 / 128 force its 192- / 256-row tile (tools/gemm_bench.py lists the others).
+    The selector is a static of each library: it is set in the bf16 measurement build (loaded here, as before) and in the fp16
+    one if that is loaded already; loaded later, it starts from the selector in force (load_library)."""
+    global _gemm_impl
     lib = load_library()
     _ck(_experiment_only(lib, "gitmi_debug_set_gemm_impl")(int(impl)), lib)
+    _gemm_impl = int(impl)
+    other = _libs.get("f16_exp")
+    if other is not None and other is not lib:
+        _ck(other.gitmi_debug_set_gemm_impl(int(impl)), other)
 
 
 def op_attn_decode(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, pos, beams, dbg=0):
@@ -1109,12 +1163,14 @@ def op_attn_decode_ragged(qkv, img_k, img_v, txt_k, txt_v, kv_src, ntok, B, H, N
 
 
 def op_attn_decode_form(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, pos, beams, *, out=None, img_of=None,
-                        ntok=None, out_frag=False, pairs_per_wg=0, waves_per_pair=0, stream_wgs=0):
+                        ntok=None, out_frag=False, pairs_per_wg=0, waves_per_pair=0, stream_wgs=0, operands=None):
     """op_attn_decode through the launcher with everything the engine's decode step sets (measurement build): img_of [B]
     sentence -> image (img_k / img_v / ntok are per image), ntok per-image key counts, out_frag (the fragment-major rows of the
     decode chain: the raw round_up(R, 16)-row buffer comes back, from_frag decodes it), pairs_per_wg / waves_per_pair /
-    stream_wgs as in AttnDecodeArgs.  txt_k / txt_v are appended to in place; `out` may be supplied (pre-filled) by the caller."""
-    lib = load_library()
+    stream_wgs as in AttnDecodeArgs.  txt_k / txt_v are appended to in place; `out` may be supplied (pre-filled) by the caller.
+    All in one 16-bit type (that type's measurement build), or all fp32 (the build `operands` names, bf16 by default)."""
+    lib = _exp_library(qkv.dtype, img_k.dtype, img_v.dtype, txt_k.dtype, txt_v.dtype,
+                       operands=operands if qkv.dtype == torch.float32 else None)
     R, d = B * beams, H * 64
     n_images = img_k.shape[0] if img_k.dim() == 4 else img_k.numel() // (H * ((N_img + 31) // 32 * 32) * 64)
     if qkv.dtype != torch.float32 and img_k.dim() == 4:
@@ -1182,57 +1238,60 @@ def op_score_head(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tgt: tor
 
 # ---- op hooks of the encoder's image front end (measurement build; tests/test_gpu_frontend_ops.py).  Every output is a
 # caller-supplied device tensor (the tests put a sentinel-filled margin behind it); the launcher of encode_frames runs on it.
-def _front(name: str):
-    lib = load_library()
+# operands ("bf16" | "f16"): the measurement build to run in, where no tensor of the call is in the 16-bit operand type (fp32
+# and fp16-stream tensors exist in both builds); None: by the call's operand-type tensors, else bf16.
+def _front(name: str, *dtypes: torch.dtype, operands: Optional[str] = None):
+    lib = _exp_library(*dtypes, operands=operands)
     return lib, _experiment_only(lib, name)
 
 
-def op_im2col(img: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, p: int, Kpad: int) -> None:
+def op_im2col(img: torch.Tensor, out: torch.Tensor, B: int, H: int, W: int, p: int, Kpad: int, operands: Optional[str] = None) -> None:
     """img fp32 [B, 3, H, W] (any 4-byte aligned view) -> out [B * (H // p) * (W // p), Kpad] patch rows, fp32 or the build's
     16-bit operand type, zeros past K = 3 p p."""
-    lib, fn = _front("gitmi_debug_im2col")
+    lib, fn = _front("gitmi_debug_im2col", out.dtype, operands=operands)
     _ck(fn(img.data_ptr(), out.data_ptr(), _torch_dtype_code(out), B, H, W, p, 3 * p * p, Kpad, _stream()), lib)
 
 
-def op_pos_resize(pos: torch.Tensor, out: torch.Tensor, g: int, gh: int, gw: int) -> None:
+def op_pos_resize(pos: torch.Tensor, out: torch.Tensor, g: int, gh: int, gw: int, operands: Optional[str] = None) -> None:
     """pos fp32 [g * g + 1, D] -> out fp32 [gh * gw + 1, D]: bicubic resize of the grid rows, class row copied."""
-    lib, fn = _front("gitmi_debug_pos_resize")
+    lib, fn = _front("gitmi_debug_pos_resize", operands=operands)
     _ck(fn(pos.data_ptr(), out.data_ptr(), g, gh, gw, int(pos.shape[1]), _stream()), lib)
 
 
 def op_vit_assemble(patch_out: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                    eps: float, X: torch.Tensor, B: int, N: int, part: Optional[torch.Tensor] = None) -> None:
+                    eps: float, X: torch.Tensor, B: int, N: int, part: Optional[torch.Tensor] = None,
+                    operands: Optional[str] = None) -> None:
     """Class / patch rows + positional rows, ln_pre -> X [B * N, D] (fp32, or the fp16 stream when X is float16); part fp32
     [B * N, 4, 2]: the folded-LayerNorm partials (fp16 stream only)."""
-    lib, fn = _front("gitmi_debug_vit_assemble")
+    lib, fn = _front("gitmi_debug_vit_assemble", operands=operands)
     _ck(fn(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, X.data_ptr(),
            1 if X.dtype == torch.float16 else 0, B, N, int(cls.numel()), _ptr(part), _stream()), lib)
 
 
 def op_ragged_front(stage: int, B: int, p: int, max_pixels: int, Nmax: int, *, src=None, slots=None, meta=None, ntok=None,
                     patches=None, Kpad: int = 0, patch_out=None, cls=None, pos=None, g: int = 0, gamma=None, beta=None,
-                    eps: float = 1e-5, X=None, part=None) -> None:
+                    eps: float = 1e-5, X=None, part=None, operands: Optional[str] = None) -> None:
     """One stage of a ragged batch's front end on caller-supplied buffers: 0 staging (src -> slots, meta, ntok), 1 patch gather
     (slots, meta -> patches [B, Nmax - 1, Kpad]), 2 token assembly + ln_pre (patch_out, cls, pos, meta -> X [B * Nmax, D], part)."""
-    lib, fn = _front("gitmi_debug_ragged_front")
+    lib, fn = _front("gitmi_debug_ragged_front", *(() if patches is None else (patches.dtype,)), operands=operands)
     _ck(fn(int(stage), _ptr(src), _ptr(slots), _ptr(meta), _ptr(ntok), _ptr(patches),
            DTYPE_F32 if patches is None else _torch_dtype_code(patches), _ptr(patch_out), _ptr(cls), _ptr(pos), int(g), _ptr(gamma),
            _ptr(beta), eps, _ptr(X), 1 if X is not None and X.dtype == torch.float16 else 0, _ptr(part), B, p, int(max_pixels), Nmax,
            3 * p * p, int(Kpad), 0 if cls is None else int(cls.numel()), _stream()), lib)
 
 
-def op_zero_pad_rows(x: torch.Tensor, ntok: torch.Tensor, B: int, Nmax: int, ld: int) -> None:
+def op_zero_pad_rows(x: torch.Tensor, ntok: torch.Tensor, B: int, Nmax: int, ld: int, operands: Optional[str] = None) -> None:
     """Rows t >= ntok[b] of x [B, Nmax, ld] (fp32 or 16-bit elements) set to zero, in place."""
-    lib, fn = _front("gitmi_debug_zero_pad_rows")
+    lib, fn = _front("gitmi_debug_zero_pad_rows", operands=operands)
     _ck(fn(x.data_ptr(), 1 if x.dtype == torch.float32 else 0, ld, ntok.data_ptr(), B, Nmax, _stream()), lib)
 
 
 def op_layernorm_map(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, add_after: Optional[torch.Tensor],
                      y_t: Optional[torch.Tensor], y_s: Optional[torch.Tensor], rows: int, D: int, map_n_in: int = 0,
-                     map_n_out: int = 0, map_off: int = 0) -> None:
+                     map_n_out: int = 0, map_off: int = 0, operands: Optional[str] = None) -> None:
     """LayerNorm of `rows` rows of x (fp32, or fp16 stream rows) + add_after, scattered by the row map of ln_post: y_t fp32 or
     the build's 16-bit operand type, y_s the source's type (either may be None)."""
-    lib, fn = _front("gitmi_debug_layernorm_map")
+    lib, fn = _front("gitmi_debug_layernorm_map", *(() if y_t is None else (y_t.dtype,)), operands=operands)
     _ck(fn(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, gamma.data_ptr(), beta.data_ptr(), eps, _ptr(add_after), _ptr(y_t),
            DTYPE_F32 if y_t is None else _torch_dtype_code(y_t), _ptr(y_s), rows, D, map_n_in, map_n_out, map_off, _stream()), lib)
 

@@ -1,5 +1,7 @@
-/* gitmi_experiment.h -- entry points of the MEASUREMENT build only (libgitmi_exp.so: the product sources compiled with
- * -DGITMI_EXPERIMENT, `make exp`).  libgitmi.so / libgitmi_f16.so do not export them.
+/* gitmi_experiment.h -- entry points of the MEASUREMENT builds only (`make exp`: libgitmi_exp.so = the product sources compiled
+ * with -DGITMI_EXPERIMENT, bf16 operands; libgitmi_f16_exp.so = the same with -DGITMI_OPS_F16, fp16 operands -- the kernels of
+ * the benchmarked configuration, the folded-LayerNorm GEMM forms among them).  libgitmi.so / libgitmi_f16.so do not export them.
+ * Both measurement builds export the same 62 gitmi_ symbols (the 40 of gitmi.h + the 22 below); gitmi_operand_dtype tells them apart.
  *
  * What lives here: debug hooks that exchange stage products between contexts (tools/error_attribution.py), force a GEMM
  * variant (tools/gemm_bench.py, tests of the forced tile heights) or set the timing bits of the decode-chain GEMMs
@@ -50,6 +52,23 @@ int  gitmi_debug_dgemm_form(const void* A, int a_rows, const void* W, const floa
                             int res_strips, const float* res_gamma, const float* res_beta, float res_eps, float* x_out,
                             void* xb_out, float* stats_out, int M, int N, int K, int rows_per_wg, int strips_per_wg,
                             int no_row_walk, void* stream);
+
+/* every launch form of the large-M GEMM and of the tile kernel (tests/test_gpu_gemm_forms.py): an argument check + launch_gemm
+ * with everything the engine's gemm_args / gemm_run / ln_gemm / gemm_to_stream set.  A [M][lda], W [N][K] in in_dtype (fp32 or
+ * the build's operand type); C [M][ldc] in out_dtype: fp32, the operand type, or GITMI_DTYPE_F16_STREAM (fp16 residual-stream
+ * rows; `res` is then fp16 [M][ldr], fp32 otherwise).  A column slice of a wider buffer is ldc > N with C, W, bias and colsum
+ * offset by the caller.  shared: the serving policy's tile choice (the 256-row tile).  Folded LayerNorm (fp16-operand build,
+ * gemm_p8_kernel: more than 512 rows): consumer = ln_part fp32 [M][4][2] (sum, sumsq) row partials + colsum + ln_eps (K <= 1024,
+ * operand-type output, no residual); producer = part_out [M][4][2] (stream rows out, no activation, N <= 1024; slot t = column
+ * tile t, slots past N / 256 are not written) and, post-norm, res_part / res_gamma / res_beta / res_eps (the residual added is
+ * LayerNorm(res) rebuilt from the partials).  Tile heights and XCD partitions: gitmi_debug_set_gemm_impl.  Refused by name,
+ * nothing launched: null A / W / C, lda < K, ldc < N, ldr < N, K % 64 (fp32: % 16), a dtype of the other build, folded
+ * arguments in the bf16 build or on a shape the tile kernel would run, colsum without ln_part and the reverse, consumer and
+ * producer arguments together, res_part without res / res_gamma / res_beta. */
+int  gitmi_debug_gemm_form(const void* A, int lda, const void* W, const float* bias, const void* res, int ldr, void* C, int ldc,
+                           int M, int N, int K, int act, int in_dtype, int out_dtype, int shared, const float* ln_part,
+                           const float* colsum, float ln_eps, float* part_out, const float* res_part, const float* res_gamma,
+                           const float* res_beta, float res_eps, void* stream);
 
 /* op hooks of the caption-scoring kernels (kernels_score.hip; tests/test_gpu_score_ops.py).  dtype: GITMI_DTYPE_F32 (the
  * kernels of the f32 parity mode) or the build's 16-bit operand dtype (gitmi_operand_dtype).

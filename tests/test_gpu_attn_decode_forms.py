@@ -18,6 +18,7 @@ import functools
 import pytest
 import torch
 
+from test_gpu_dgemm_forms import on_both_operand_builds
 from test_gpu_ops_f16 import _attn_bound, _check16, _decode_ref
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,13 @@ GUARD = 3                # sentinel rows behind `out` and the caches
 Q_SCALE = 2.5
 
 
+# Every test of the file runs on the bf16 measurement build under its own name and, as <name>_f16, on the fp16 one
+# (on_both_operand_builds, last line): 16-bit tensors pick their library by type, the fp32 cases run in BUILD's (operands=).
+BUILD = {"ops": "bf16"}
+
+
 def _op_dtype():
-    from generativeimage2text_amd import engine
-    lib = engine.load_library()
-    return {engine.DTYPE_BF16: torch.bfloat16, engine.DTYPE_F16: torch.float16}[lib.gitmi_operand_dtype()]
+    return {"bf16": torch.bfloat16, "f16": torch.float16}[BUILD["ops"]]
 
 
 TWO = ("two waves", dict(waves_per_pair=2))
@@ -168,7 +172,8 @@ def _run(c, form=None, out_frag=False, txt=None, ntok=None):
         caches.append(buf.cuda())
     before = [b.cpu() for b in caches]
     E.op_attn_decode_form(c.qkv.cuda(), c.ik.cuda(), c.iv.cuda(), caches[0], caches[1], c.src.cuda(), c.B, c.H, c.N_img, T, c.pos,
-                          c.beams, out=out, img_of=c.img_of, ntok=ntok if ntok is not None else c.ntok, out_frag=out_frag, **(form or {}))
+                          c.beams, out=out, img_of=c.img_of, ntok=ntok if ntok is not None else c.ntok, out_frag=out_frag,
+                          operands=BUILD["ops"], **(form or {}))
     torch.cuda.synchronize()
     out = out.cpu()
     sent = _raw(_sentinel(1, d, dt))
@@ -275,7 +280,7 @@ def test_refusals(experiment_build):
     with pytest.raises(ValueError, match="img_of"):
         E.op_attn_decode_form(c.qkv.cuda(), c.ik.cuda(), c.iv.cuda(), c.tk.cuda(), c.tv.cuda(), c.src.cuda(), 2, 2, 40, c.T, 2, 2,
                               img_of=[0, 2])
-    lib = E.load_library()
+    lib = E._exp_library(_op_dtype())
     buf = torch.zeros(1 << 16, device="cuda")
     p, s, f32 = buf.data_ptr(), E._stream(), E.DTYPE_F32
 
@@ -464,3 +469,6 @@ def test_softmax_edges(experiment_build, two_wave, where):
         _check(c, _run_forms(c, ONE_WAVE), "packed / stream")
     c = _spiked_case(torch.float32, two_wave, where)
     _check(c, _run(c)[0], "fp32")
+
+
+on_both_operand_builds(globals(), BUILD)

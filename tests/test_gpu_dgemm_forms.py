@@ -39,10 +39,32 @@ STAT_GUARD = 64          # sentinel floats behind the strip partials
 EPS = 1e-12
 
 
+# ---- both operand builds -------------------------------------------------------------------------------------------------------
+# Every test of the file runs on the bf16 measurement build under its own name and, as <name>_f16, on the fp16 one
+# (libgitmi_f16_exp.so): engine.op_dgemm_form picks the library by its tensors' type, BUILD says which type the test makes.
+BUILD = {"ops": "bf16"}
+
+
 def _op_dtype():
-    from generativeimage2text_amd import engine
-    lib = engine.load_library()
-    return {engine.DTYPE_BF16: torch.bfloat16, engine.DTYPE_F16: torch.float16}[lib.gitmi_operand_dtype()]
+    return {"bf16": torch.bfloat16, "f16": torch.float16}[BUILD["ops"]]
+
+
+def on_both_operand_builds(tests, build):
+    """adds to the module namespace `tests` an fp16 twin <name>_f16 of every test_* function in it: the same marks, parameters
+    and fixtures, run with build["ops"] = "f16" (test_gpu_attn_decode_forms.py and test_gpu_frontend_ops.py use it too)"""
+    def twin_of(fn):
+        @functools.wraps(fn)
+        def twin(*args, **kw):
+            build["ops"] = "f16"
+            try:
+                return fn(*args, **kw)
+            finally:
+                build["ops"] = "bf16"
+        twin.__name__ = twin.__qualname__ = fn.__name__ + "_f16"
+        return twin
+    for name, fn in list(tests.items()):
+        if name.startswith("test_") and callable(fn) and not name.endswith("_f16"):
+            tests[name + "_f16"] = twin_of(fn)
 
 
 def _dev(t):
@@ -352,7 +374,7 @@ def test_refusals(experiment_build):
     """(e) every refusal of the hook: the error names it, nothing is launched (the outputs keep their sentinel).  M = 0 succeeds
     and writes nothing."""
     from generativeimage2text_amd import engine as E
-    lib = E.load_library()
+    lib = E._exp_library(_op_dtype())
     hook = E._experiment_only(lib, "gitmi_debug_dgemm_form")
     zeros = torch.zeros(1 << 20, device="cuda")
     outs = _dev(_sentinel((3, 1 << 18), torch.float32))
@@ -391,10 +413,12 @@ def test_refusals(experiment_build):
     assert consumer(M=0) == 0 and producer(M=0) == 0
     torch.cuda.synchronize()
     assert _is_sentinel(outs.cpu()) and zeros.abs().sum().item() == 0
-    own = torch.zeros(64, 64, dtype=_op_dtype(), device="cuda")
+    own = torch.zeros(64, 64, dtype=_op_dtype(), device="cuda")            # each 16-bit type has its library: a mixed pair has none
     other = own.to(torch.float16 if own.dtype == torch.bfloat16 else torch.bfloat16)
-    with pytest.raises(E.GitmiError, match="operands must be"):
-        E.op_dgemm_form(other, other, zeros[:64])
+    with pytest.raises(E.GitmiError, match="operands must"):
+        E.op_dgemm_form(own, other, zeros[:64])
+    with pytest.raises(E.GitmiError, match="operands must"):
+        E.op_dgemm_form(own.float(), own.float(), zeros[:64])
 
 
 # ---- one decoder layer's hand-over ------------------------------------------------------------------------------------------
@@ -464,3 +488,6 @@ def test_layer_hand_over(experiment_build, R):
     _check_res(s4, ref, bound, dt, "layer", f"R={R} FFN2")
     ref, bound, rnd = _fold_ref(s4[0], L.Wq, L.cq, L.csq, 0, dt)
     _hold(s5, ref, bound, rnd, dt, "layer", f"R={R} QKV")
+
+
+on_both_operand_builds(globals(), BUILD)

@@ -6,11 +6,14 @@ vit_assemble_ragged_kernel, zero_pad_rows_kernel) and the ln_post scatter (layer
 add_after and the row map).  References are torch fp64 on the CPU from the same inputs after their input rounding; gathers,
 staging and the ragged forms are compared bit for bit.  Every output sits in a sentinel-filled buffer whose margins must come
 back untouched.  The bounds are derived where they are used; docs/LAB_NOTEBOOK.md repeats them."""
+import functools
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from test_gpu_dgemm_forms import on_both_operand_builds
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +22,26 @@ SENT = 0x5A              # sentinel byte: 0x5A5A5A5A = 1.5e16 as fp32, 0x5A5A = 
 MARGIN = 4096            # sentinel bytes either side of every output
 
 
+# Every test of the file runs on the bf16 measurement build under its own name and, as <name>_f16, on the fp16 one
+# (on_both_operand_builds, last line).  Most front-end calls have no tensor in the operand type (fp32 and fp16-stream tensors
+# exist in both builds), so the engine module the tests see passes operands=BUILD["ops"] to every front-end hook.
+BUILD = {"ops": "bf16"}
+FRONT_HOOKS = ("op_im2col", "op_pos_resize", "op_vit_assemble", "op_ragged_front", "op_zero_pad_rows", "op_layernorm_map")
+
+
+class _Front:
+    def __getattr__(self, name):
+        from generativeimage2text_amd import engine
+        attr = getattr(engine, name)
+        return functools.partial(attr, operands=BUILD["ops"]) if name in FRONT_HOOKS else attr
+
+
 def _E():
-    from generativeimage2text_amd import engine
-    return engine
+    return _Front()
 
 
 def _op_dtype():
-    E = _E()
-    return {E.DTYPE_BF16: torch.bfloat16, E.DTYPE_F16: torch.float16}[E.load_library().gitmi_operand_dtype()]
+    return {"bf16": torch.bfloat16, "f16": torch.float16}[BUILD["ops"]]
 
 
 def _bits(t):
@@ -611,3 +626,6 @@ def test_ln_post_with_an_unaligned_embedding_falls_back_and_stays_correct(experi
     for mode in ("op", "both"):
         got, ref, bound = _run_ln_post(D, src, mode, True, temb_shift=1)
         _check_ln_post(got, ref, bound, f"unaligned D={D} src={src} {mode}")
+
+
+on_both_operand_builds(globals(), BUILD)

@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol():
 def test_product_libraries_export_the_c_abi_and_nothing_else():
     """nm -D: exactly the entry points of include/gitmi.h (no C++ launcher symbols, no experiment entry points), no getenv
     in the product (it reads no environment); the measurement build adds exactly include/gitmi_experiment.h (+ one timing
-    switch of the decode-chain unit entry point)."""
+    switch of the decode-chain unit entry point), in both operand types."""
     import shutil
     import subprocess
     if shutil.which("nm") is None:
@@ -56,10 +56,44 @@ def test_product_libraries_export_the_c_abi_and_nothing_else():
         lib = engine.load_library("bf16" if path == engine.LIB_PATH else "f16")
         for name in extra:
             assert not hasattr(lib, name), name
-    if os.path.exists(engine.LIB_PATH_EXP):
-        defined, undefined = dyn(engine.LIB_PATH_EXP)
-        assert defined == declared | extra
-        assert "getenv" in undefined
+    for path in (engine.LIB_PATH_EXP, engine.LIB_PATH_F16_EXP):
+        if os.path.exists(path):
+            defined, undefined = dyn(path)
+            assert defined == declared | extra, (path, sorted(defined ^ (declared | extra)))
+            assert "getenv" in undefined
+
+
+def test_measurement_hooks_pick_the_library_of_their_operand_type():
+    """_exp_library: fp16 tensors -> libgitmi_f16_exp.so, bf16 or none -> libgitmi_exp.so, `operands` where no tensor can say;
+    without use_experiment_build the product library of that type (whose missing hook _experiment_only reports); "f16" itself
+    stays the product library either way, and a selector set before the fp16 measurement build is loaded reaches it."""
+    import torch
+    for path in (engine.LIB_PATH, engine.LIB_PATH_F16, engine.LIB_PATH_EXP, engine.LIB_PATH_F16_EXP):
+        if not os.path.exists(path):
+            pytest.skip("library not built")
+    f16, bf16, f32 = torch.float16, torch.bfloat16, torch.float32
+    assert engine._exp_library(f16) is engine.load_library("f16") and engine._exp_library(bf16, f32) is engine.load_library("bf16")
+    with pytest.raises(engine.GitmiError, match="measurement build only"):
+        engine._experiment_only(engine._exp_library(f16), "gitmi_debug_gemm_form")
+    engine.use_experiment_build(True)
+    try:
+        engine.set_gemm_impl(9 | (128 << 8))
+        x = engine._exp_library(f16, f32)
+        assert x is engine.load_library("f16_exp") and x.gitmi_operand_dtype() == engine.DTYPE_F16
+        assert engine._exp_library(bf16) is engine.load_library("exp") and engine._exp_library(f32) is engine.load_library("exp")
+        assert engine._exp_library(f32, operands="f16") is x and engine._exp_library(operands="bf16") is engine.load_library("exp")
+        assert engine.load_library("f16") is not x and not hasattr(engine.load_library("f16"), "gitmi_debug_gemm_form")
+        for lib in (x, engine.load_library("exp")):
+            for name in engine.EXPERIMENT_SYMBOLS:
+                assert hasattr(lib, name), name
+        with pytest.raises(engine.GitmiError, match="operands must all be"):
+            engine._exp_library(f16, bf16)
+        with pytest.raises(engine.GitmiError, match="unknown selector"):
+            engine.set_gemm_impl(7)
+    finally:
+        engine.set_gemm_impl(-1)
+        engine.use_experiment_build(False)
+    assert engine._gemm_impl == -1
 
 
 def test_struct_layouts_match_header():
