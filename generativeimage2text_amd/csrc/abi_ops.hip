@@ -572,4 +572,31 @@ GITMI_EXP_EXPORT int gitmi_debug_layernorm_map(const void* x, int src_f16, const
                                map_n_out, map_off, (hipStream_t)stream));
     return 0;
 }
+// the context kernel of GITMI_SEARCH_CONTEXT (tests/test_gpu_context_ops.py): the host table context_call builds + the launcher it calls
+GITMI_EXP_EXPORT int gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len_host, const int32_t* image_of_host,
+                                               int Q, const float* words, int vocab, const float* positions, int max_pos,
+                                               const float* gamma, const float* beta, float eps, void* feats, int dtype, float* feats_f32,
+                                               int* ntok, int B, int n_img, int stride, int D, void* stream) {
+    if (!tokens || !words || !positions || !gamma || !beta || !feats || !ntok) return fail("debug_context_embed: null argument");
+    RCK(check_dtype("debug_context_embed", "dtype", dtype));
+    if (ld < 1 || vocab < 1 || max_pos < 1 || n_img < 0 || stride < 1 || D < 8 || D > 1024 || D % 8)
+        return fail("debug_context_embed: bad shape (D a multiple of 8 up to 1024)");
+    if (((uintptr_t)words | (uintptr_t)positions | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)feats | (uintptr_t)feats_f32) & 15)
+        return fail("debug_context_embed: tables and rows must be 16-byte aligned");
+    ContextTable t;
+    RCK(context_table("debug_context_embed", len_host, image_of_host, Q, B, std::min(ld, max_pos), n_img, stride, &t));
+    hipStream_t s = (hipStream_t)stream;
+    int* tab = nullptr;
+    HIPCK(hipMalloc((void**)&tab, t.tab.size() * sizeof(int)));
+    auto body = [&]() -> int {
+        HIPCK(hipMemcpy(tab, t.tab.data(), t.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCK(launch_context_embed((const long long*)tokens, ld, (const int4*)tab, Q, tab + 4 * (size_t)Q, words, positions, gamma, beta, eps,
+                                   feats, dtype == GITMI_DTYPE_F32, feats_f32, ntok, B, n_img, stride, D, vocab, max_pos, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(tab);
+    return rc;
+}
 #endif

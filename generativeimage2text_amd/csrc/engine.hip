@@ -152,7 +152,9 @@ static int gemm_to_stream(gitmi_engine* e, hipStream_t s, Stream& st, const void
     return 0;
 }
 // full attention over packed q|k|v rows [batch * N][3 * width] -> out [batch * N][width]
-static int attn_full_packed(gitmi_engine* e, const void* qkv, void* out, int width, int heads, int N, int batch, hipStream_t s) {
+// ntok: keys (and query rows) per block, or nullptr: N each
+static int attn_full_packed(gitmi_engine* e, const void* qkv, void* out, int width, int heads, int N, int batch, const int* ntok,
+                            hipStream_t s) {
     AttnFullArgs a{};
     a.q = qkv;
     a.k = (const char*)qkv + (size_t)width * e->pol.esz;
@@ -161,7 +163,7 @@ static int attn_full_packed(gitmi_engine* e, const void* qkv, void* out, int wid
     a.ldq = a.ldk = a.ldv = 3 * width;
     a.ldo = width;
     a.N = N; a.H = heads; a.scale = 0.125f;
-    a.ntok = e->ragged ? e->rg_ntok : nullptr;
+    a.ntok = ntok;
     HIPCK(launch_attn_full(a, batch, e->pol.f32, e->pol.attn_impl, s));
     return 0;
 }
@@ -272,10 +274,17 @@ static void destroy_graph(gitmi_engine* e) {
 // the engine's images stop being resident: an encode starts (or failed), or a setter changed what an encode would produce
 static void drop_resident(gitmi_engine* e) { e->have_feats = e->have_prefill = false; }
 // an encode of B images with F_eff frames each is enqueued (or replayed, or imported): they are resident, their K/V is not
-static void set_resident(gitmi_engine* e, int B, int F_eff) {
-    e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = F_eff * e->N;
+// stride: the rows of an image's block when they are more than its F_eff * N image rows (a context call), else 0.  Key counts
+// are in use from here on exactly when the front end is ragged; a context call turns them on itself (set_context)
+static void set_resident(gitmi_engine* e, int B, int F_eff, int stride = 0) {
+    e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = stride > 0 ? stride : F_eff * e->N;
     e->have_feats = true; e->have_prefill = false;
+    e->keyed = e->ragged; e->has_context = false;
 }
+// the resident images carry context rows behind their image rows, rg_ntok holds every image's key count
+static void set_context(gitmi_engine* e) { e->keyed = e->has_context = true; }
+// per-image key counts of the resident batch (ragged images, context rows), or nullptr: cur_Nimg keys each
+static const int* key_counts(const gitmi_engine* e) { return e->keyed ? e->rg_ntok : nullptr; }
 static void set_prefilled(gitmi_engine* e) { e->have_prefill = true; }
 // The failure rule, for every call that runs over images (rc: what its launches returned):
 //   a call that was given frames and fails after its first launch or capture leaves NOTHING resident (the workspaces are
@@ -307,7 +316,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->sc_allocs) hipFree(p);
-    hipFree(e->at_out); hipFree(e->at_stats);
+    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -378,12 +387,14 @@ static Stream prefill_stream(gitmi_engine* e, int M) {
 }
 
 // ---------------------------------------------------------------------------------------
+// stride > 0 (a context call, never ragged): the rows of an image's block in the feature tensor, more than its F_eff * N image
+// rows; the rows behind them are the caller's to write
 static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F, int B, float* feats_out,
-                              hipStream_t s) {
+                              hipStream_t s, int stride = 0) {
     const gitmi_config& c = e->cfg;
     const int D = c.vit_width, N = e->N;
     const int F_eff = c.num_frames > 0 ? std::min(F, c.num_frames) : F;   // zip() truncation, decoder.py:849
-    const int Nimg = F_eff * N;
+    const int Nimg = stride > 0 ? stride : F_eff * N;
     drop_resident(e);           // the workspaces are overwritten from here on: resident again once the whole pass is enqueued
     SpanGuard phase(e, s, TAG_VIT, 0);
     // all frames of the call go through the encoder as ONE batch of F*B images (the reference encodes frame by
@@ -413,7 +424,7 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
         const VitLayerW& L = e->w.vit[l];
         const VitLayerW* Ln = l + 1 < c.vit_layers ? &e->w.vit[l + 1] : nullptr;   // ln_post after the last block is a launch of its own
         RCK(ln_gemm(e, s, x, L.qkv_f, L.wqkv, L.bqkv, e->v_qkv, 3 * D, 0, 3 * D, 0));
-        RCK(attn_full_packed(e, e->v_qkv, e->v_ctx, D, c.vit_heads, N, BI, s));
+        RCK(attn_full_packed(e, e->v_qkv, e->v_ctx, D, c.vit_heads, N, BI, e->ragged ? e->rg_ntok : nullptr, s));
         RCK(gemm_to_stream(e, s, x, e->v_ctx, D, L.wo, L.bo, D, true, L.ln2g, L.ln2b, 1e-5f));
         RCK(ln_gemm(e, s, x, L.ffn1_f, L.w1, L.b1, e->v_u, 4 * D, 0, 4 * D, 1));
         RCK(gemm_to_stream(e, s, x, e->v_u, 4 * D, L.w2, L.b2, 4 * D, true, Ln ? Ln->ln1g : nullptr, Ln ? Ln->ln1b : nullptr, 1e-5f));
@@ -438,7 +449,7 @@ static int encode_frames_impl(gitmi_engine* e, const float* const* frames, int F
         if (feats_out) HIPCK(launch_zero_pad_rows(feats_out, true, D, e->rg_ntok, B, N, s));
     }
 
-    set_resident(e, B, F_eff);      // cur_Nimg == Nimg: N is e->N, ragged (Nmax) or not
+    set_resident(e, B, F_eff, stride);      // cur_Nimg == Nimg: N is e->N, ragged (Nmax) or not
     return 0;
 }
 
@@ -469,7 +480,7 @@ static int prefill_impl(gitmi_engine* e, hipStream_t s) {
         RCK(ln_gemm(e, s, y, L.qkv_pf, L.wqkv, L.bqkv, e->img_kv[l], 3 * d, col0, 3 * d - col0, 0));
         RCK(kv_repack(e, l, B, Nimg, s));
         if (last) break;
-        RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, s));
+        RCK(attn_full_packed(e, e->img_kv[l], e->p_ctx, d, c.dec_heads, Nimg, B, key_counts(e), s));
         RCK(gemm_to_stream(e, s, y, e->p_ctx, d, L.wo, L.bo, d, true, L.lnag, L.lnab, 1e-12f));
         RCK(ln_gemm(e, s, y, L.ffn1_pf, L.w1, L.b1, e->p_u, ffn, 0, ffn, 2));
         RCK(gemm_to_stream(e, s, y, e->p_u, ffn, L.w2, L.b2, ffn, true, L.lnog, L.lnob, 1e-12f));
@@ -558,7 +569,7 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         // of the streaming kernel only stretch the launch (profiles/r04_f_*)
         const bool stream_ok = !e->pol.shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->pol.attn_nh != 2;
         a.stream_wgs = e->pol.attn_stream >= 0 ? e->pol.attn_stream : stream_ok ? 192 : 0;
-        if (e->ragged) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }      // per-image key counts: the register kernels
+        if (e->keyed) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }       // per-image key counts: the register kernels
         if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
@@ -868,6 +879,7 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (vocab < 2) return fail("%s: bad vocab", who);
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("%s: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)", who);
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("%s: GITMI_SEARCH_ATTEND is not a search (gitmi_generate_prefixed returns the attention maps of sentences)", who);
+    if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("%s: GITMI_SEARCH_CONTEXT is not a search (gitmi_generate_prefixed puts context tokens into the decoder memory)", who);
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1051,8 +1063,12 @@ static int generate_body(gitmi_engine* e, const Request& rq, hipStream_t s, bool
 // hipGraph cache key of a call: everything the captured launch sequence depends on
 static GraphKey graph_key_of(const gitmi_engine* e, const Request& rq, int F_eff) {
     const gitmi_search& sp = *rq.sp;
+    // a follow-up call runs over the memory as it stands: the row stride of an image's block is an argument of every attention
+    // launch, and so is whether key counts are read (their values live in rg_ntok, whose pointer never changes)
+    const bool resident = rq.frames == nullptr;
     return {rq.B, rq.Q, F_eff, rq.minP, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, e->H, e->W,
-            rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, rq.frames ? 0 : 1, sp.length_penalty,
+            rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, resident ? 1 : 0,
+            resident ? e->cur_Nimg : 0, resident && e->keyed ? 1 : 0, sp.length_penalty,
             sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed};
 }
 
@@ -1171,6 +1187,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     const gitmi_config& c = e->cfg;
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("generate: GITMI_SEARCH_ATTEND maps given sentences: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("generate: GITMI_SEARCH_CONTEXT takes context segments: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1303,7 +1320,7 @@ static int text_pass_impl(gitmi_engine* e, const Request& rq, const long long* t
     if (attend) RCK(zero_outputs());       // the map kernels of every layer write into it
     HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
                                 e->pol.f32, d, V, c.max_pos, s));
-    const int* ntok = e->ragged ? e->rg_ntok : nullptr;
+    const int* ntok = key_counts(e);
     for (int l = 0; l < L; ++l) {
         const DecLayerW& W = e->w.dec[l];
         RCK(gemm(e, s, e->sc_ht, d, W.wqkv, W.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
@@ -1357,6 +1374,58 @@ static int upload_sentences(gitmi_engine* e, int* plen_dst, int* img_dst, hipStr
     return 0;
 }
 
+// ---- context tokens in the decoder memory (GITMI_SEARCH_CONTEXT, include/gitmi.h; decoder.py:861-871) ----------------------------
+// The segment table of a call lives in ctx_tab, allocated by the first context call and grown on demand.
+static int context_alloc(gitmi_engine* e, size_t ints) {
+    if (e->ctx_tab_ints >= ints) return 0;
+    hipFree(e->ctx_tab);
+    e->ctx_tab = nullptr; e->ctx_tab_ints = 0;
+    if (hipMalloc((void**)&e->ctx_tab, ints * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("context: out of device memory for the table of the segments");
+    }
+    e->ctx_tab_ints = ints;
+    return 0;
+}
+// Encode + context rows + prefill, eagerly: the images and their context are resident afterwards, in key-count mode.
+// Every check comes before the first launch (an argument error leaves the resident set as it was).
+static int context_call(gitmi_engine* e, const float* const* frames, int F, int B, const long long* tokens, int ld,
+                        const int32_t* len_host, const int32_t* image_of_host, int Q, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    if (!frames)
+        return fail("context: frames == NULL: context segments come with the call that encodes their images (appending context "
+                    "to resident images is not implemented)");
+    if (!tokens || !len_host || !info_out) return fail("context: null argument");
+    RCK(check_frames(e, "context", frames, F, B));
+    if (e->ragged)
+        return fail("context: ragged image mode (gitmi_set_image_shape(e, 0, 0)): context on images of mixed shapes is not implemented");
+    if (c.vit_width != c.dec_hidden)
+        return fail("context: visual_feature_size %d != hidden_size %d: the reference cannot concatenate the embedded tokens to "
+                    "the visual features of this model (decoder.py:866)", c.vit_width, c.dec_hidden);
+    if (ld < 1) return fail("context: ld=%d", ld);
+    const int n_img = call_Nimg(e, frames, F), cap = c.max_frames * e->Nmax;
+    ContextTable t;
+    RCK(context_table("context", len_host, image_of_host, Q, B, std::min(ld, (int)c.max_pos), n_img, cap, &t));
+    RCK(context_alloc(e, t.tab.size()));
+    // staged synchronously, as upload_sentences does: the previous call's work on `s` may still read the table
+    HIPCK(hipStreamSynchronize(s));
+    HIPCK(hipMemcpy(e->ctx_tab, t.tab.data(), t.tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int* tab = e->ctx_tab;
+    auto body = [&]() -> int {
+        RCK(encode_frames_impl(e, frames, F, B, nullptr, s, t.stride));
+        HIPCK(launch_context_embed(tokens, ld, (const int4*)tab, Q, tab + 4 * (size_t)Q, e->w.words_f, e->w.positions_f, e->w.emb_lng,
+                                   e->w.emb_lnb, 1e-8f, e->feats, e->pol.f32, nullptr, e->rg_ntok, B, n_img, t.stride, c.vit_width,
+                                   c.vocab, c.max_pos, s));
+        set_context(e);
+        RCK(prefill_impl(e, s));
+        HIPCK(hipMemcpyAsync(info_out, tab + 4 * (size_t)Q + B, 4 * sizeof(int), hipMemcpyDefault, s));
+        return 0;
+    };
+    const int rc = body();
+    if (rc != 0) drop_resident(e);
+    return rc;
+}
+
 // Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V)
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
@@ -1366,10 +1435,15 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     const gitmi_config& c = e->cfg;
     hipStream_t s = (hipStream_t)stream;
     SentenceSpan span;
+    if (sp && sp->kind == GITMI_SEARCH_CONTEXT)
+        return context_call(e, frames, F, B, (const long long*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND)) {
         const bool attend = sp->kind == GITMI_SEARCH_ATTEND;
         const char* who = attend ? "attend" : "score";
         if (!frames) RCK(check_resident(e, who, B));
+        if (attend && !frames && e->has_context)
+            return fail("attend: the resident images carry context rows; the attention map over [image | context | text] columns "
+                        "is not implemented (run the attend call with frames, or encode without context)");
         if (!logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("%s: null argument", who);
         if (frames) RCK(check_frames(e, who, frames, F, B));
         if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("%s: ld=%d outside [1,%d] (max_text_len)", who, ld_prefix, c.max_text_len);
@@ -1534,6 +1608,7 @@ GITMI_EXP_EXPORT int gitmi_debug_import_stage(gitmi_engine* dst, gitmi_engine* s
     if (a.vit_width != b.vit_width || a.dec_hidden != b.dec_hidden || a.dec_layers != b.dec_layers || a.dec_heads != b.dec_heads)
         return fail("debug_import_stage: the two contexts are different models");
     if (!src->have_feats || (stage == 2 && !src->have_prefill)) return fail("debug_import_stage: the source has not run that stage");
+    if (src->has_context) return fail("debug_import_stage: the source's resident images carry context rows");
     if (src->cur_B > a.max_batch || src->cur_F > a.max_frames || src->N != dst->N) return fail("debug_import_stage: capacity / resolution mismatch");
     hipStream_t s = (hipStream_t)stream;
     const size_t M = (size_t)src->cur_B * src->cur_Nimg;

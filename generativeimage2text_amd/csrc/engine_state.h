@@ -55,11 +55,13 @@ enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM
 
 // hipGraph cache key of gitmi_generate / gitmi_generate_prefixed: everything the captured launch sequence depends on
 struct GraphKey {
-    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident; double lp;
+    int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed; double lp;
     int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
-    // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds
+    // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds: Nimg rows per
+    // image block, with (keyed) or without per-image key counts; both 0 in a call with frames, which decides them itself
     auto fields() const {
-        return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, lp, smp, top_k, nh, top_p, temp, rp, seed);
+        return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed, lp, smp, top_k, nh, top_p, temp,
+                        rp, seed);
     }
     bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
@@ -158,7 +160,14 @@ struct gitmi_engine {
     // descriptor on the device; image b owns rows [b * Nmax, b * Nmax + ntok[b]) of the encoder / prefill blocks (N = Nmax)
     bool ragged = false;
     int4* rg_meta = nullptr;           // [max_batch] {h, w, ntok, rejected} of the staged call
-    int* rg_ntok = nullptr;            // [max_batch] token rows of every image (class token included)
+    int* rg_ntok = nullptr;            // [max_batch] key rows of every image: its token rows (class token included) in a ragged
+                                       // batch, image rows + context rows after a context call
+    // key counts in use: prefill attention, decode attention and the text pass read rg_ntok for the resident batch.  True for
+    // every ragged batch and for a batch that carries context rows (GITMI_SEARCH_CONTEXT); the ragged FRONT END is `ragged` alone
+    bool keyed = false;
+    bool has_context = false;          // the resident images' blocks are [image rows | context rows | zeros], cur_Nimg rows each
+    int* ctx_tab = nullptr;            // segment table of the last context call (engine.hip context_call), grown on demand
+    size_t ctx_tab_ints = 0;
 
     // ViT workspaces (one frame of max_batch images at a time)
     void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;

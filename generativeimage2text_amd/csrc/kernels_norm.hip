@@ -555,6 +555,94 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ i
     }
 }
 
+// Context tokens of the decoder memory (GITMI_SEARCH_CONTEXT; decoder.py:861-871): every valid token of every segment is
+// embedded -- words[tok] + positions[p], p restarting at 0 in every segment, LayerNorm(eps) -- into the row behind its image's
+// n_img feature rows: image b's block of `stride` rows becomes [n_img image rows | cnt[b] context rows | zero rows].
+// One wave per work item, four per workgroup.  Items [0, Q * ld): position p of segment q (seg[q] = {image, first context row
+// of the segment within its image, length, 0}; nothing to do past the length: ids there are never read).  Items past them: row
+// t of block b -- rows t >= n_img + cnt[b] are set to zero, the wave of row 0 writes ntok[b] = n_img + cnt[b]; image rows are
+// left as the ln_post launches wrote them.  A lane owns chunks of 8 consecutive elements (chunk lane + 64 i; D % 8 == 0,
+// D <= 1024): 16-byte table loads, 16-byte stores of the 16-bit rows, the row in registers, statistics in fp32 from centred
+// values across the wave.  Ids are device data: clamped into the table like embed_ln_kernel's, positions into [0, max_pos).
+template <typename TOut>
+__global__ __launch_bounds__(256) void context_embed_kernel(const long long* __restrict__ tokens, int ld,
+                                                            const int4* __restrict__ seg, int Q, const int* __restrict__ cnt,
+                                                            const float* __restrict__ words, const float* __restrict__ positions,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float eps, TOut* __restrict__ feats, float* __restrict__ feats_f,
+                                                            int* __restrict__ ntok, int B, int n_img, int stride, int D, int vocab,
+                                                            int max_pos) {
+    const int lane = threadIdx.x & 63;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n_ctx = Q * ld;
+    if (item >= n_ctx + B * stride) return;
+    constexpr int NCH = 2;
+    if (item >= n_ctx) {
+        const int r = item - n_ctx, b = r / stride, t = r - b * stride;
+        const int nt = n_img + cnt[b];
+        if (t == 0 && lane == 0) ntok[b] = nt;
+        if (t < nt) return;
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c = (lane + 64 * i) * 8;
+            if (c < D) {
+                st8(feats + (size_t)r * D + c, z);
+                if (feats_f) st8(feats_f + (size_t)r * D + c, z);
+            }
+        }
+        return;
+    }
+    const int q = item / ld, p = item - q * ld;
+    const int4 sg = seg[q];
+    if (p >= sg.z || sg.x < 0 || sg.x >= B || sg.y < 0 || n_img + sg.y + sg.z > stride) return;      // the host built the table; never past a block
+    const long long t = tokens[(size_t)q * ld + p];
+    const int tok = t < 0 ? 0 : (t >= vocab ? vocab - 1 : (int)t);
+    const int pos = p < max_pos ? p : max_pos - 1;
+    const float* wr = words + (size_t)tok * D;
+    const float* pr = positions + (size_t)pos * D;
+    float v[NCH][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = (lane + 64 * i) * 8;
+        if (c < D) {
+            float w8[8], p8[8];
+            ld8(wr + c, w8);
+            ld8(pr + c, p8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { v[i][j] = w8[j] + p8[j]; s += v[i][j]; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+        }
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        if ((lane + 64 * i) * 8 < D) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; sq += d * d; }
+        }
+    }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
+    const size_t orow = (size_t)sg.x * stride + n_img + sg.y + p;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = (lane + 64 * i) * 8;
+        if (c < D) {
+            float g8[8], b8[8], o[8];
+            ld8(gamma + c, g8);
+            ld8(beta + c, b8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * g8[j] + b8[j];
+            st8(feats + orow * D + c, o);
+            if (feats_f) st8(feats_f + orow * D + c, o);
+        }
+    }
+}
+
 // dst[r, 0..Kpad) = convert(src[r, 0..K)), zero padded
 template <typename TOut>
 __global__ void convert_pad_kernel(const float* __restrict__ src, TOut* __restrict__ dst, size_t rows, int K,
@@ -761,6 +849,24 @@ hipError_t launch_embed_ln(const int* ids, int ld_ids, int pos, const float* wor
     else
         hipLaunchKernelGGL(embed_ln_kernel<bf16_t>, grid, block, 0, s, ids, ld_ids, pos, words, positions, gamma,
                            beta, eps, h_f, (bf16_t*)h_t, R, D, vocab, frag ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_context_embed(const long long* tokens, int ld, const int4* seg, int Q, const int* cnt, const float* words,
+                                const float* positions, const float* gamma, const float* beta, float eps, void* feats, bool t_is_f32,
+                                float* feats_f, int* ntok, int B, int n_img, int stride, int D, int vocab, int max_pos, hipStream_t s) {
+    if (D > 1024 || (D & 7) || Q < 1 || ld < 1 || B < 1 || n_img < 0 || stride < n_img || vocab < 1 || max_pos < 1 ||
+        ((uintptr_t)feats & 15) || ((uintptr_t)feats_f & 15))
+        return hipErrorInvalidValue;
+    const size_t items = (size_t)Q * ld + (size_t)B * stride;
+    if (items > (size_t)1 << 30) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+    if (t_is_f32)
+        hipLaunchKernelGGL(context_embed_kernel<float>, grid, block, 0, s, tokens, ld, seg, Q, cnt, words, positions, gamma, beta, eps,
+                           (float*)feats, feats_f, ntok, B, n_img, stride, D, vocab, max_pos);
+    else
+        hipLaunchKernelGGL(context_embed_kernel<bf16_t>, grid, block, 0, s, tokens, ld, seg, Q, cnt, words, positions, gamma, beta, eps,
+                           (bf16_t*)feats, feats_f, ntok, B, n_img, stride, D, vocab, max_pos);
     return hipGetLastError();
 }
 

@@ -131,6 +131,14 @@ hipError_t launch_layernorm_s16(const void* x, int ldx, const float* gamma, cons
 hipError_t launch_embed_ln(const int* ids, int ld_ids, int pos, const float* words, const float* positions,
                            const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
                            int R, int D, int vocab, bool frag, hipStream_t s);
+// context tokens of the decoder memory (GITMI_SEARCH_CONTEXT): tokens int64 [Q][ld] DEVICE, seg [Q] = {image, first context row of
+// the segment within its image, length, 0} and cnt [B] context rows per image (DEVICE copies of context_table's output) ->
+// rows [n_img, n_img + cnt[b]) of image b's block of `stride` rows in feats [B][stride][D] (fp32 or the operand type; feats_f:
+// an optional fp32 copy) = LayerNorm(words[tok] + positions[p]), p from 0 in every segment; rows past them zero;
+// ntok[b] = n_img + cnt[b].  Image rows are not touched.  D % 8 == 0, D <= 1024.
+hipError_t launch_context_embed(const long long* tokens, int ld, const int4* seg, int Q, const int* cnt, const float* words,
+                                const float* positions, const float* gamma, const float* beta, float eps, void* feats, bool t_is_f32,
+                                float* feats_f, int* ntok, int B, int n_img, int stride, int D, int vocab, int max_pos, hipStream_t s);
 hipError_t launch_frag_pack(const void* src_bf16, void* dst_bf16, int rows, int rows_out, int K, hipStream_t s);
 hipError_t launch_convert_pad(const float* src, void* dst, bool dst_f32, size_t rows, int K, int Kpad,
                               hipStream_t s);

@@ -24,6 +24,7 @@ DTYPE_F16_STREAM = 3      # gitmi_op_gemm's out_dtype only: fp16 residual-stream
 SEARCH_AUTOREGRESSIVE, SEARCH_GENERATOR, SEARCH_TRIE = 0, 1, 2
 SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given sentences (Engine.score)
 SEARCH_ATTEND = 4    # not a search: gitmi_generate_prefixed returns the attention maps of given sentences (Engine.attend)
+SEARCH_CONTEXT = 5   # not a search: gitmi_generate_prefixed puts context tokens into the decoder memory (Engine.encode_context)
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
 
 EXPORTED_SYMBOLS = [
@@ -44,7 +45,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
-    "gitmi_debug_gemm_form",
+    "gitmi_debug_gemm_form", "gitmi_debug_context_embed",
 ]
 
 
@@ -177,6 +178,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
                                                  C.c_longlong, i32, i32, i32, i32, vp]
         lib.gitmi_debug_zero_pad_rows.argtypes = [vp, i32, i32, vp, i32, i32, vp]
         lib.gitmi_debug_layernorm_map.argtypes = [vp, i32, vp, vp, C.c_float, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_context_embed.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_float, vp, i32, vp, vp, i32, i32,
+                                                  i32, i32, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands in _MEASUREMENT_LIBS else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -269,6 +272,64 @@ def _sentence_tables(lens: Sequence[int], image_of: Optional[Sequence[int]]):
     return (C.c_int32 * Q)(*lens), None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
 
 
+class Geometry(tuple):
+    """Engine.resident_geometry: the tuple (Nk, F, grids) -- Nk key rows of an image's block (its row stride), F frames, the token
+    grid of every image -- plus, for a batch that carries context tokens (Engine.encode_context): image_rows, the F * n_tok image
+    rows at the head of every block, and context, the valid context rows of every image behind them (all 0 without context)."""
+
+    def __new__(cls, Nk: int, F: int, grids, image_rows: Optional[int] = None, context: Optional[Sequence[int]] = None):
+        self = super().__new__(cls, (int(Nk), int(F), list(grids)))
+        self.image_rows = int(Nk if image_rows is None else image_rows)
+        self.context = [0] * len(self[2]) if context is None else [int(v) for v in context]
+        return self
+
+    @property
+    def stride(self) -> int:
+        return self[0]
+
+
+def context_segments(context, B: int, vocab: int, max_pos: int):
+    """The reference's batch['context'] -- a list of {'tokens': int [B, Lc], 'length': int [B]} (decoder.py:861-871) -- as the
+    segments of Engine.encode_context: (segments [id lists], image_of [image of every segment]).  Segment i of the list gives
+    image b the first length[b] ids of its row (ids past the length are padding: the reference masks them as keys); zero-length
+    segments are dropped; the segments of one image keep the order of the list.  Every segment is embedded with positions
+    0 .. length - 1 (they restart in every segment).  Raises ValueError for ids outside [0, vocab) and lengths outside
+    [0, min(Lc, max_pos)]."""
+    segments, image_of = [], []
+    for i, seg in enumerate(context or []):
+        tokens = torch.as_tensor(seg["tokens"]).detach().to("cpu", torch.int64)
+        length = torch.as_tensor(seg["length"]).detach().to("cpu", torch.int64).reshape(-1)
+        if tokens.dim() != 2 or int(tokens.shape[0]) != B or int(length.numel()) != B:
+            raise ValueError(f"context[{i}]: 'tokens' must be [B, Lc] and 'length' [B] for the {B} images of the batch, got "
+                             f"{tuple(tokens.shape)} and {tuple(length.shape)}")
+        Lc = int(tokens.shape[1])
+        for b in range(B):
+            n = int(length[b])
+            if n < 0 or n > Lc:
+                raise ValueError(f"context[{i}]: length {n} of image {b} outside [0, {Lc}]")
+            if n > max_pos:
+                raise ValueError(f"context[{i}]: a segment of {n} tokens exceeds the {max_pos} positions of the textual embedding")
+            if n == 0:
+                continue
+            ids = tokens[b, :n].tolist()
+            if min(ids) < 0 or max(ids) >= vocab:
+                raise ValueError(f"context[{i}]: token ids of image {b} outside [0, {vocab})")
+            segments.append(ids)
+            image_of.append(b)
+    return segments, image_of
+
+
+def context_capacity(image_size: int, patch: int, max_image_tokens: int, max_frames: int, max_context: int) -> int:
+    """gitmi_config.max_image_tokens of an engine that must hold max_context context rows behind the image rows of every image
+    (Engine(max_context=...)): the workspaces hold max_frames x max(N, max_image_tokens) rows per image, N = (image_size //
+    patch)^2 + 1, and a context call needs max_frames * N + max_context of them at the native resolution.  max_context = 0
+    returns max_image_tokens unchanged: today's footprint."""
+    if max_context <= 0:
+        return int(max_image_tokens)
+    n_nat = (int(image_size) // int(patch)) ** 2 + 1
+    return max(n_nat, int(max_image_tokens)) + -(-int(max_context) // max(1, int(max_frames)))
+
+
 class RaggedImages:
     """B images of their own sizes in ONE device buffer: the input of a ragged engine call (gitmi_set_image_shape(e, 0, 0),
     include/gitmi.h).  buffer: fp32 [n] = int32 descriptor [B][4] = {h, w, offset, 0} padded to 256 bytes, then the [3, h, w]
@@ -323,9 +384,11 @@ class Engine:
 
     def __init__(self, model_cfg, precision: str = "bf16", max_batch: int = 64, max_beams: int = 4,
                  max_frames: int = 1, max_text_len: int = 40, device: Optional[int] = None,
-                 max_image_hw: Optional[Tuple[int, int]] = None):
+                 max_image_hw: Optional[Tuple[int, int]] = None, max_context: int = 0):
         """max_image_hw: largest (H, W) input the engine must accept when images are not all image_size x image_size
-        (MinMaxResizeForTest models); default: the model config's max_image_hw, else the native square."""
+        (MinMaxResizeForTest models); default: the model config's max_image_hw, else the native square.
+        max_context: context rows (encode_context) every image's block must hold behind max_frames frames of image rows at the
+        largest resolution; 0 (default): none are reserved, the footprint is what it was."""
         if not torch.cuda.is_available():
             raise GitmiError("no GPU visible: the GIT engine runs on MI355X (gfx950) only, there is no CPU fallback")
         # precision: "f16" (the benchmarked build: fp16 operands) / "bf16" (the same kernels on bf16 operands) / "f32" (exact parity mode)
@@ -346,6 +409,8 @@ class Engine:
             mh, mw = int(max_image_hw[0]), int(max_image_hw[1])
             c.max_image_pixels = mh * mw
             c.max_image_tokens = (mh // c.patch) * (mw // c.patch) + 1
+        c.max_image_tokens = context_capacity(c.image_size, c.patch, c.max_image_tokens, c.max_frames, max_context)
+        self.max_context = int(max_context)
         self.c = c
         self.n_tok = (c.image_size // c.patch) ** 2 + 1          # tokens per frame at the CURRENT input resolution
         self._hw = (int(c.image_size), int(c.image_size))
@@ -367,6 +432,7 @@ class Engine:
         other = object.__new__(Engine)
         other.lib, other.device, other.cfg, other.precision = self.lib, self.device, self.cfg, self.precision
         other.c = GitmiConfig.from_buffer_copy(self.c)
+        other.max_context = self.max_context
         other.n_tok = (self.c.image_size // self.c.patch) ** 2 + 1
         other._hw = (int(self.c.image_size), int(self.c.image_size))
         other._h = C.c_void_p()
@@ -401,7 +467,8 @@ class Engine:
     def resident_geometry(self):
         """(Nk, F, [(grid rows, grid columns)] per image) of the resident images, or None: Nk image key rows per image (the
         image columns of Engine.attend), F frames of grid_h * grid_w + 1 tokens each (ragged input: F = 1, every image its own
-        grid inside its max_tokens rows)."""
+        grid inside its max_tokens rows).  After encode_context a Geometry: Nk is the row stride of an image's block,
+        .image_rows its F * n_tok image rows and .context the context rows of every image behind them."""
         return self._geometry if self._resident is not None else None
 
     def _drop_resident(self) -> None:
@@ -526,6 +593,43 @@ class Engine:
             out = torch.empty(B, F_eff * self.n_tok, self.c.vit_width, device=keep[0].device, dtype=torch.float32)
         self._encoded(self.lib.gitmi_encode_frames(self._h, arr, F, B, _ptr(out), _stream()), B)
         return out
+
+    def encode_context(self, frames: Sequence[torch.Tensor], segments: Sequence[Sequence[int]],
+                       lengths: Optional[Sequence[int]] = None, image_of: Optional[Sequence[int]] = None) -> Dict[str, int]:
+        """Encode `frames` with context tokens in the decoder memory (include/gitmi.h GITMI_SEARCH_CONTEXT; the reference's
+        batch['context'], decoder.py:861-871): segments = id lists (or an int [Q, L] table with `lengths`), segment q belongs to
+        image image_of[q] (default: segment q <-> image q); the segments of one image are appended behind its image rows in
+        the order given, each embedded with positions from 0.  Runs the image encoder, the context kernel and the prefill; the
+        images and their context are resident afterwards and every follow-up call (frames=None: generate, generate_prefixed,
+        score) runs over [image | context].  -> {'stride', 'max_context', 'context_rows'}; resident_geometry has the rest.
+        Refused by the library, by message and with the resident set untouched: frames None, a ragged batch, a model whose
+        visual features and hidden states differ in width, rows beyond the engine's capacity (Engine(max_context=...))."""
+        table = torch.as_tensor(segments).to(torch.int64) if lengths is not None else id_table(segments)
+        lens = [int(v) for v in lengths] if lengths is not None else [len(r) for r in segments]
+        Q = int(table.shape[0])
+        if table.dim() != 2 or len(lens) != Q or (image_of is not None and len(image_of) != Q):
+            raise ValueError(f"segments must be [Q, L] with Q lengths (and Q image indices), got {tuple(table.shape)}")
+        arr, keep, B = self._frames_arg(frames)
+        dev = torch.device(f"cuda:{self.device}")
+        table = table.to(dev).contiguous()
+        info = self._empty(4, torch.int32, dev)
+        search = GitmiSearch()
+        search.kind = SEARCH_CONTEXT
+        rc = self.lib.gitmi_generate_prefixed(self._h, arr, len(keep), B, table.data_ptr(), int(table.shape[1]),
+                                              *_sentence_tables(lens, image_of), Q, C.byref(search), None, None, None,
+                                              info.data_ptr(), _stream())
+        if frames is None:          # the library refuses a follow-up by name (appending context to resident images)
+            self._ck(rc)
+        if rc == 0:
+            counts = [0] * B
+            for q, n in enumerate(lens):
+                counts[q if image_of is None else int(image_of[q])] += n
+            Nk, F_eff, grids = self._call_geometry
+            stride, max_c, total, _ = (int(v) for v in info.tolist())          # synchronises: the table upload did already
+            self._call_geometry = Geometry(stride, F_eff, grids, image_rows=Nk, context=counts)
+            assert max_c == max(counts) and total == sum(counts) and stride >= Nk + max_c
+        self._encoded(rc, B)
+        return {"stride": stride, "max_context": max_c, "context_rows": total}
 
     def prefill(self) -> None:
         self._ck(self.lib.gitmi_prefill(self._h, _stream()))
@@ -853,6 +957,29 @@ class Engine:
 
 
 # ---- single-kernel entry points (unit parity tests) -----------------------------------------------
+def op_context_embed(tokens: torch.Tensor, lengths: Sequence[int], image_of: Optional[Sequence[int]], words: torch.Tensor,
+                     positions: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, feats: torch.Tensor,
+                     n_img: int, want_f32: bool = False, operands: Optional[str] = None):
+    """The context kernel of GITMI_SEARCH_CONTEXT on its own (measurement build, include/gitmi_experiment.h): tokens int64
+    [Q, ld] on the device, lengths / image_of as Engine.encode_context takes them; feats [B, stride, D] (fp32 or the 16-bit operand
+    type) is updated IN PLACE: context rows behind the n_img image rows of every block, zeros behind them.
+    -> (ntok int32 [B], the fp32 copy [B, stride, D] of the rows written (zeros elsewhere) or None)"""
+    assert tokens.is_cuda and tokens.dtype == torch.int64 and tokens.is_contiguous() and feats.is_cuda and feats.is_contiguous()
+    B, stride, D = feats.shape
+    Q, ld = tokens.shape
+    lib = _exp_library(feats.dtype, operands=operands)
+    fn = _experiment_only(lib, "gitmi_debug_context_embed")
+    f32 = lambda t: t.to(device=feats.device, dtype=torch.float32).contiguous()
+    words, positions, gamma, beta = f32(words), f32(positions), f32(gamma), f32(beta)
+    ntok = torch.full((B,), -1, dtype=torch.int32, device=feats.device)
+    copy = torch.zeros(B, stride, D, dtype=torch.float32, device=feats.device) if want_f32 else None
+    lens, img = _sentence_tables([int(v) for v in lengths], image_of)
+    _ck(fn(tokens.data_ptr(), ld, lens, img, Q, words.data_ptr(), int(words.shape[0]), positions.data_ptr(), int(positions.shape[0]),
+           gamma.data_ptr(), beta.data_ptr(), float(eps), feats.data_ptr(), _torch_dtype_code(feats), _ptr(copy), ntok.data_ptr(),
+           B, int(n_img), stride, D, _stream()), lib)
+    return ntok, copy
+
+
 def op_gemm(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
             residual: Optional[torch.Tensor] = None, act: int = ACT_NONE,
             out_dtype: torch.dtype = torch.float32, stream_rows: bool = False) -> torch.Tensor:

@@ -256,14 +256,15 @@ def load_checkpoint(model_name: str, checkpoint: Optional[str] = None):
 
 
 def build_model(model_name: str, tokenizer, checkpoint=None, max_batch: int = 64, precision: str = "f16",
-                decoder=None, param: Optional[dict] = None) -> CaptioningModel:
+                decoder=None, param: Optional[dict] = None, max_context: int = 0) -> CaptioningModel:
     """param: the model's parameter dict when the caller already read it (a parameter.yaml); default: the built-in
-    table entry of `model_name`."""
+    table entry of `model_name`.  max_context: the most context tokens per image a batch['context'] may carry (0: none)."""
     cfg = config_for_model(model_name) if param is None else config_from_param(param, name=model_name)
     if decoder is None:
         decoder = GeneratorWithBeamSearch(eos_index=tokenizer.sep_token_id, max_steps=1024, beam_size=4,
                                           length_penalty=0.6)               # model.py:34-40
-    model = CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch)
+    model = CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch, max_context=max_context,
+                            context_not_share_embedding=bool((param or {}).get("context_not_share_embedding", False)))
     state = checkpoint if isinstance(checkpoint, dict) else load_checkpoint(model_name, checkpoint)
     model.load_state_dict(state)
     return model

@@ -18,7 +18,7 @@ from typing import Dict, Mapping, Optional, Sequence, Tuple, Union
 import torch
 
 from .configs import GitModelConfig, config_from_param
-from .engine import Engine, id_table
+from .engine import Engine, context_segments, id_table
 
 
 # ---- decoder.search(start_predictions, step): the reference's search seam as a method ----------------------------
@@ -410,7 +410,13 @@ class CaptioningModel:
     # 8 x smaller logit error: the build that meets the specification and the benchmarked one since round 6) or "bf16" (BASELINE.json's named precision)
     def __init__(self, cfg: GitModelConfig, decoder, precision: str = "f16", max_batch: int = 64,
                  max_frames: Optional[int] = None, max_text_len: Optional[int] = None,
-                 device: Optional[int] = None):
+                 device: Optional[int] = None, max_context: int = 0, context_not_share_embedding: bool = False):
+        """max_context: the most context tokens (batch['context'], all segments of one image together) a request may carry;
+        the engine's per-image rows are sized for max_frames frames plus that many.  0 (default): today's footprint, and any
+        non-empty context raises ValueError naming this argument."""
+        if context_not_share_embedding:
+            raise NotImplementedError("context_not_share_embedding=True: the reference cannot construct this model either "
+                                      "(decoder.py:825 calls .clone() on an nn.Module); only the shared textual embedding exists")
         self.cfg = cfg
         self.decoder = decoder
         self.sos_index = cfg.sos
@@ -421,7 +427,7 @@ class CaptioningModel:
             max_text_len = min(cfg.max_pos, max(int(decoder.max_steps), 2))
         self.engine = Engine(cfg, precision=precision, max_batch=max_batch,
                              max_beams=max(1, int(decoder.beam_size)), max_frames=max_frames,
-                             max_text_len=max_text_len, device=device)
+                             max_text_len=max_text_len, device=device, max_context=max_context)
         self._loaded = False
         # loss of the training-mode forward (model.py:55 builds the reference with loss_type='smooth'; None = cross entropy)
         self.loss_type: Optional[str] = "smooth"
@@ -541,6 +547,30 @@ class CaptioningModel:
             eng.set_trie(*self.decoder.trie.csr())
             eng._trie_loaded = self.decoder.trie
 
+    def _context_segments(self, eng, frames, context):
+        """batch['context'] of a call over `frames` -> (segments, image_of) for Engine.encode_context, or None when no image has
+        a non-empty segment (a plain call).  Checks the ids, the lengths and the engine's per-image row capacity on the host."""
+        if not context:
+            return None
+        B, _, H, W = frames[0].shape
+        segments, image_of = context_segments(context, int(B), int(self.cfg.vocab), int(self.cfg.max_pos))
+        if not segments:
+            return None
+        if self.cfg.vit_width != self.cfg.dec_hidden:
+            raise ValueError(f"'context' needs visual_feature_size == hidden_size (the reference concatenates the embedded tokens "
+                             f"to the visual features, decoder.py:866); this model has {self.cfg.vit_width} and {self.cfg.dec_hidden}")
+        counts = [0] * int(B)
+        for ids, b in zip(segments, image_of):
+            counts[b] += len(ids)
+        F_eff = min(len(frames), self.cfg.num_frames) if self.cfg.num_frames > 0 else len(frames)
+        rows = F_eff * ((int(H) // eng.c.patch) * (int(W) // eng.c.patch) + 1)
+        cap = int(eng.c.max_frames) * eng.max_tokens
+        if rows + max(counts) > cap:
+            raise ValueError(f"{max(counts)} context tokens behind {rows} image rows exceed the {cap} rows per image of this model: "
+                             f"construct CaptioningModel(..., max_context={max(counts)}) (workspaces are sized at construction; "
+                             f"now max_context={eng.max_context})")
+        return segments, image_of
+
     def submit(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
                search_param: Optional[dict] = None, on=None) -> "Pending":
         """Asynchronous model(batch): enqueue the request on the next context's stream and return at once; `.result()` waits
@@ -553,6 +583,8 @@ class CaptioningModel:
             return self.submit_followup(batch, search_param, on=on)
         if on is not None:
             raise ValueError("on= belongs to follow-up requests (a batch without 'image')")
+        if batch.get("bi_valid_mask_caption") is not None:
+            raise NotImplementedError("'bi_valid_mask_caption' (image rows attending to the text, decoder.py:139-146) is not implemented")
         image = batch["image"]
         is_list = isinstance(image, (list, tuple))
         frames = list(image) if is_list else [image]
@@ -565,12 +597,18 @@ class CaptioningModel:
         prefix = batch.get("prefix")
         if prefix is not None:
             assert len(prefix) == 1, "not supported"                       # decoder.py:988
+        # batch['context'] (decoder.py:861-871): the context call encodes images + context, the search is a follow-up over them
+        ctx = self._context_segments(eng, frames, batch.get("context"))
         search = self._search_struct(search_param)
         P = None if prefix is None else int(prefix.numel())
         nret = int((search_param or {}).get("num_return_sequences", 1))
         kind = self.decoder.kind
 
         def launch():
+            frames_arg = frames
+            if ctx is not None:
+                eng.encode_context(frames, ctx[0], image_of=ctx[1])
+                frames_arg = None
             if nret != 1:
                 # decoder.py:1093-1097: every image's start tokens num_return_sequences times -- r sentences per image, each
                 # with its own beams (they differ only when sampling); rows b * r + j, as the reference returns them
@@ -579,11 +617,11 @@ class CaptioningModel:
                 if B * nret > eng.c.max_batch:
                     raise ValueError(f"{B} images x num_return_sequences={nret} exceed max_batch={eng.c.max_batch}")
                 tokens, logprobs, _, info = eng.generate_prefixed(
-                    frames, search, [start] * (B * nret), image_of=[b for b in range(B) for _ in range(nret)], sync=False,
+                    frames_arg, search, [start] * (B * nret), image_of=[b for b in range(B) for _ in range(nret)], sync=False,
                     host_out=stream is not None)
             else:
                 # requests in flight on other streams: results straight into page-locked host memory (no read-back to enqueue)
-                tokens, logprobs, info = eng.generate(frames, search, prefix=prefix, sync=False, host_out=stream is not None)
+                tokens, logprobs, info = eng.generate(frames_arg, search, prefix=prefix, sync=False, host_out=stream is not None)
             return tokens, logprobs, info
 
         return Pending(stream, launch, lambda out: _finish_batch(eng, out, P, kind), keep=(frames, prefix), engine=eng)
@@ -621,33 +659,37 @@ class CaptioningModel:
     __call__ = forward
 
     def _loss_forward(self, batch) -> Dict[str, torch.Tensor]:
-        """forward_one_ce with self.training (decoder.py:938-966): {'vl_l_loss': loss} over batch['caption_tokens'] /
-        batch['need_predict'] of the images in batch['image'] (a tensor or a list of frames)."""
+        """forward_one_ce with self.training (decoder.py:938-966): {'vl_<hint>_loss': loss} over batch['caption_tokens'] /
+        batch['need_predict'] of the images in batch['image'] (a tensor or a list of frames) and, when given, the context tokens
+        of batch['context']; hint = batch['context_target_type'][0], default 'l'."""
         if "image" not in batch:
             raise NotImplementedError("the text-only branch ('l_*_loss') is not implemented")
-        if "context" in batch or batch.get("bi_valid_mask_caption") is not None:
-            raise NotImplementedError("'context' / 'bi_valid_mask_caption' inputs are not implemented")
+        if batch.get("bi_valid_mask_caption") is not None:
+            raise NotImplementedError("'bi_valid_mask_caption' (image rows attending to the text, decoder.py:139-146) is not implemented")
         tokens = torch.as_tensor(batch["caption_tokens"]).cpu()
         need_predict = torch.as_tensor(batch["need_predict"]).cpu()
-        out = self.score(batch["image"], tokens, need_predict=need_predict)
+        out = self.score(batch["image"], tokens, need_predict=need_predict, context=batch.get("context"))
         loss = caption_loss(out["logprobs"], out["mean_logprobs"], tokens, need_predict, self.loss_type,
                             self.label_smoothing, self.cfg.vocab)
-        return {"vl_l_loss": torch.tensor(loss, dtype=torch.float32)}
+        hint = batch["context_target_type"][0] if "context_target_type" in batch else "l"        # decoder.py:963
+        return {f"vl_{hint}_loss": torch.tensor(loss, dtype=torch.float32)}
 
     def score(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], captions,
-              image_of: Optional[Sequence[int]] = None, need_predict=None, on=None) -> Dict[str, torch.Tensor]:
+              image_of: Optional[Sequence[int]] = None, need_predict=None, on=None, context=None) -> Dict[str, torch.Tensor]:
         """Log-likelihood of given captions (validation loss / perplexity, reranking, retrieval, closed-set VQA).
         captions: int [Q, L] padded with 0 (or a list of id lists), each starting with [CLS]; caption q belongs to image
         image_of[q] of `images` (default: caption q <-> image q).  need_predict [Q, L] (default: the non-padding positions
         after [CLS]) selects the positions that count, e.g. 0 on a VQA question prefix.
         images None: the captions are scored over the RESIDENT images of `on`'s context (default: of the most recent call),
-        e.g. the captions that call just generated; nothing is encoded.
+        e.g. the captions that call just generated; nothing is encoded (their context, if that call had one, is part of them).
+        context: the reference's batch['context'] for `images` (a list of {'tokens' [B, Lc], 'length' [B]}): the captions are
+        scored over [image | context].
         -> {'logprobs' [Q, L] (lp of tokens[:, j], 0 at position 0), 'mean_logprobs' [Q, L] (mean log-prob over the
             vocabulary at that position), 'sum' [Q], 'mean' [Q] (over the counted positions)}, all fp32 on the CPU."""
         if not isinstance(captions, torch.Tensor):
             captions = id_table(captions)
         tokens = captions.detach().cpu().long()
-        out, _ = self._sentence_pass("score", images, tokens, image_of, on)
+        out, _ = self._sentence_pass("score", images, tokens, image_of, on, context=context)
         lp, mean_lp = out[..., 0], out[..., 1]
         if need_predict is None:
             need_predict = (tokens != 0).long()
@@ -660,13 +702,15 @@ class CaptioningModel:
         return {"logprobs": lp, "mean_logprobs": mean_lp, "sum": total,
                 "mean": total / n.clamp(min=1).to(total.dtype)}
 
-    def _sentence_pass(self, method: str, images, tokens: torch.Tensor, image_of, on, **kw):
+    def _sentence_pass(self, method: str, images, tokens: torch.Tensor, image_of, on, context=None, **kw):
         """One engine pass over given sentences (Engine.score / Engine.attend) routed like every request: images None -> the
         follow-up context of `on` on its stream, a list of [3, h, w] images -> one ragged call, else frames; the calls that
         encode run on context 0.  -> (the result on the CPU, the engine context that ran it)"""
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
         is_list = isinstance(images, (list, tuple))
+        if context and (images is None or _is_image_list(images)):
+            raise NotImplementedError("context comes with the call that encodes its images, all of one shape")
         if images is None:
             eng, stream = self._followup_context(on)
             if stream is None:
@@ -682,6 +726,10 @@ class CaptioningModel:
         else:
             frames = list(images) if is_list else [images]
             eng.set_temporal_embedding(is_list)                              # decoder.py:845-857: list branch only
+            ctx = self._context_segments(eng, frames, context)
+            if ctx is not None:          # the context call encodes images + context; the sentences run as a follow-up over them
+                eng.encode_context(frames, ctx[0], image_of=ctx[1])
+                frames = None
         out = getattr(eng, method)(frames, tokens, image_of=image_of, **kw).cpu()
         self._last = eng
         return out, eng
@@ -879,7 +927,7 @@ class Pending:
 
 
 def get_git_model(tokenizer, param: Optional[dict], precision: str = "f16", max_batch: int = 64,
-                  decoder=None, device: Optional[int] = None) -> CaptioningModel:
+                  decoder=None, device: Optional[int] = None, max_context: int = 0) -> CaptioningModel:
     """Same role as the reference's get_git_model (model.py:9-61): GIT decoder hyper-parameters are
     fixed, the encoder follows param['image_encoder_type'].  The default search is the shipped one:
     GeneratorWithBeamSearch(beam_size=4, length_penalty=0.6, max_steps=1024) (model.py:34-40)."""
@@ -892,4 +940,5 @@ def get_git_model(tokenizer, param: Optional[dict], precision: str = "f16", max_
     if decoder is None:
         decoder = GeneratorWithBeamSearch(eos_index=cfg.eos, max_steps=1024, beam_size=4, length_penalty=0.6)
     logging.info("building GIT engine: %s, search %s", cfg, type(decoder).__name__)
-    return CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch, device=device)
+    return CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch, device=device, max_context=max_context,
+                           context_not_share_embedding=bool((param or {}).get("context_not_share_embedding", False)))

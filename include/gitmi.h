@@ -51,6 +51,8 @@ extern "C" {
 #define GITMI_SEARCH_ATTEND         4  /* not a search: the attention the text rows of given sentences pay to the image tokens and
                                         * to their own text (BertSelfAttention.output_attentions, head mean); gitmi_generate_prefixed
                                         * only, see there */
+#define GITMI_SEARCH_CONTEXT        5  /* not a search: context tokens (the reference's batch['context'], decoder.py:861-871) put into
+                                        * the decoder memory behind the image tokens; gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -317,6 +319,42 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  *   refuse this kind.  Residency, the eager launch path (no hipGraph) and the serving schedule are those of a score call;
  *   score calls return exactly what they return without this kind.  The output workspace (Q ld dec_layers Kc floats) is
  *   allocated by the first attend call and grown on demand: engines that never attend keep their footprint. */
+/* ---- context tokens: search->kind == GITMI_SEARCH_CONTEXT turns gitmi_generate_prefixed into the reference's 'context' input
+ * (CaptioningModel.forward_one, decoder.py:861-871: OCR strings, tags, retrieved captions, dialogue history).  The reference
+ * embeds every segment with the textual embedding -- LayerNorm(words[tok] + positions[p], eps 1e-8), positions restarting at 0
+ * in every segment --, concatenates the rows to the visual features, runs the whole concatenation through the visual
+ * projection into the decoder memory and masks the positions past every segment's length as keys (decoder.py:97-149, 569).
+ * Embedded keys carry no position of their own, so the engine compacts an image's valid context rows directly behind its image
+ * rows: image b's block of the memory is [F N image rows | C_b context rows | zero rows] with the key count
+ * ntok[b] = F N + C_b -- the padded layout's mathematics, fp32 summation order aside.
+ *   frames          : must be non-NULL: the context comes with the call that encodes its images (a NULL follow-up is refused;
+ *                     appending context to resident images is not implemented)
+ *   prefixes        : int64 [Q, ld] on the DEVICE, row q = one context segment, its tokens at positions 0 .. len_q - 1; ids past
+ *                     the length are never read; ids outside the vocabulary are clamped into it (validate on the host)
+ *   prefix_len_host : int32 [Q], 1 <= len_q <= min(ld, max_pos)
+ *   image_of_host   : int32 [Q], the image of segment q (NULL: Q == B, segment q <-> image q).  The segments of one image are
+ *                     appended to its memory in increasing q, any interleaving between images is allowed; an image without a
+ *                     segment has no context
+ *   info_out        : { row stride of an image's block, max_b C_b, sum_b C_b, 0 }; tokens_out, logprob_out, sent_out: ignored
+ *                     (may be NULL); the other gitmi_search fields are ignored
+ * It runs the image encoder, one launch that writes every context row, the zero rows and the key counts, and the prefill; no
+ * decode step, no vocabulary head; eagerly (no hipGraph), as score does.  Afterwards the images AND their context are
+ * resident and the batch is in key-count mode: prefill attention, decode attention and the text pass read ntok[b] keys of
+ * image b.  Every follow-up form (frames == NULL) then runs over [image | context] with nothing changed at the interface:
+ * gitmi_generate with any search and a shared prefix, gitmi_generate_prefixed with ragged prefixes, GITMI_SEARCH_SCORE;
+ * gitmi_prefill / gitmi_step_logits see the same memory.  Every sentence gets what a batch-1 reference call with its image, its
+ * context and its prefix returns (the reference itself fails for B > 1 with beams > 1, decoder.py:1018-1025).  The captured
+ * decode graph of a follow-up is keyed on the row stride, the counts live in one device array: batches of equal stride and
+ * different counts replay one graph.  GITMI_SEARCH_ATTEND over a context-carrying resident batch is refused (the map with
+ * context columns is not implemented).  Any later call with frames replaces the resident set and leaves key-count mode: a
+ * plain call after a context call returns exactly what it returns on a fresh engine.  A clone starts with nothing resident.
+ * Capacity: F N + C_b, and the stride (F N + max_b C_b, rounded up to a multiple of 16 where that fits), must fit the
+ * max_frames x max(N, max_image_tokens) rows per image the workspaces are sized for; beyond that the call fails before any
+ * launch, the message names the rows asked for and the capacity, and the resident set stays as it was -- as for every
+ * argument error.  Also refused before any launch: ragged image mode (gitmi_set_image_shape(e, 0, 0)), vit_width != dec_hidden
+ * (the reference's torch.cat fails there too), a length outside its range.  gitmi_generate and gitmi_search_begin refuse this
+ * kind.  The segment table's device copy is allocated by the first context call: engines that never take context keep their
+ * footprint. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

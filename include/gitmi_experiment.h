@@ -1,7 +1,7 @@
 /* gitmi_experiment.h -- entry points of the MEASUREMENT builds only (`make exp`: libgitmi_exp.so = the product sources compiled
  * with -DGITMI_EXPERIMENT, bf16 operands; libgitmi_f16_exp.so = the same with -DGITMI_OPS_F16, fp16 operands -- the kernels of
  * the benchmarked configuration, the folded-LayerNorm GEMM forms among them).  libgitmi.so / libgitmi_f16.so do not export them.
- * Both measurement builds export the same 62 gitmi_ symbols (the 40 of gitmi.h + the 22 below); gitmi_operand_dtype tells them apart.
+ * Both measurement builds export the same 63 gitmi_ symbols (the 40 of gitmi.h + the 23 below); gitmi_operand_dtype tells them apart.
  *
  * What lives here: debug hooks that exchange stage products between contexts (tools/error_attribution.py), force a GEMM
  * variant (tools/gemm_bench.py, tests of the forced tile heights) or set the timing bits of the decode-chain GEMMs
@@ -161,6 +161,19 @@ int  gitmi_debug_zero_pad_rows(void* x, int is_f32, int ld, const int* ntok, int
 int  gitmi_debug_layernorm_map(const void* x, int src_f16, const float* gamma, const float* beta, float eps, const float* add_after,
                                void* y_t, int out_dtype, void* y_s, int rows, int D, int map_n_in, int map_n_out, int map_off,
                                void* stream);
+
+/* op hook of the context kernel of GITMI_SEARCH_CONTEXT (kernels_norm.hip; tests/test_gpu_context_ops.py): the host table the
+ * engine's context call builds + the launcher it calls.  tokens int64 [Q][ld] DEVICE; len_host / image_of_host int32 [Q] HOST
+ * as in gitmi_generate_prefixed (image_of_host NULL: Q == B); words fp32 [vocab][D], positions fp32 [max_pos][D], gamma / beta
+ * fp32 [D] DEVICE.  feats [B][stride][D] (dtype: fp32 or the build's operand type): rows [n_img, n_img + C_b) of block b =
+ * LayerNorm(words[tok] + positions[p], eps), p from 0 in every segment, the segments of an image in increasing q; rows
+ * [n_img + C_b, stride) zero; rows [0, n_img) not touched; feats_f32 (or NULL): an fp32 copy of the rows written; ntok int32
+ * [B] DEVICE = n_img + C_b.  Refused by name, nothing launched: null or misaligned pointers, D not a multiple of 8 up to 1024,
+ * a length outside [1, min(ld, max_pos)], an image outside [0, B), n_img + C_b > stride.  Synchronises the stream. */
+int  gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len_host, const int32_t* image_of_host, int Q,
+                               const float* words, int vocab, const float* positions, int max_pos, const float* gamma,
+                               const float* beta, float eps, void* feats, int dtype, float* feats_f32, int* ntok, int B, int n_img,
+                               int stride, int D, void* stream);
 
 #ifdef __cplusplus
 }
