@@ -384,6 +384,47 @@ GITMI_EXP_EXPORT int gitmi_debug_attn_decode_form(const void* qkv, const void* i
     HIPCK(launch_attn_decode_mfma(a, B, H, (hipStream_t)stream));
     return 0;
 }
+// the attention launch that computes its own q | k | v (tests/test_gpu_attn_decode_qkv.py): an argument check + the launcher the
+// engine's decode step calls where its policy packs 8 one-wave pairs per workgroup.  The attention operands of
+// gitmi_debug_attn_decode_form without qkv, and the QKV GEMM's operands as gitmi_debug_dgemm_form takes them (x fragment-major
+// [x_rows][K = H * 64], w fragment-major [3 K][K], bias / colsum [3 K], stats [strips][B] strip partials or NULL).  The launch
+// is of this one form whatever B is; a call outside it is refused by name, nothing launched.
+GITMI_EXP_EXPORT int gitmi_debug_attn_decode_qkv(const void* x, int x_rows, const void* w, const float* bias, const float* colsum,
+                                                 const float* stats, int strips, float eps, const void* img_k, const void* img_v,
+                                                 void* txt_k, void* txt_v, const int* kv_src, void* out, const int* ntok,
+                                                 const int* img_of, int n_images, int B, int H, int N_img, int T_max, int pos,
+                                                 int beams, int dtype, int out_frag, int pairs_per_wg, int waves_per_pair,
+                                                 int stream_wgs, void* stream) {
+    RCK(check_dtype("debug_attn_decode_qkv", "dtype", dtype));
+    if (dtype == GITMI_DTYPE_F32) return fail("debug_attn_decode_qkv: 16-bit operands only (the f32 mode keeps its QKV launch)");
+    if (!x || !w || !bias || !img_k || !img_v || !txt_k || !txt_v || !kv_src || !out) return fail("debug_attn_decode_qkv: null argument");
+    if (n_images < 1) return fail("debug_attn_decode_qkv: n_images=%d", n_images);
+    if (B < 1 || H < 1 || N_img < 1 || pos < 0 || pos >= T_max)
+        return fail("debug_attn_decode_qkv: B=%d H=%d N_img=%d pos=%d T_max=%d", B, H, N_img, pos, T_max);
+    if (beams != 1) return fail("debug_attn_decode_qkv: beams=%d (beam batches keep the QKV launch)", beams);
+    if (ntok) return fail("debug_attn_decode_qkv: ntok (ragged batches keep the QKV launch)");
+    if (waves_per_pair == 2) return fail("debug_attn_decode_qkv: waves_per_pair=2 (two-wave pairs keep the QKV launch)");
+    if (stream_wgs != 0) return fail("debug_attn_decode_qkv: stream_wgs=%d (the streaming form keeps the QKV launch)", stream_wgs);
+    if (pairs_per_wg != 8) return fail("debug_attn_decode_qkv: pairs_per_wg=%d (the form packs 8 pairs)", pairs_per_wg);
+    if (round_up(N_img, 32) > 256) return fail("debug_attn_decode_qkv: N_img=%d (more than 256 padded keys: the two-wave form)", N_img);
+    if (H * 64 > 768) return fail("debug_attn_decode_qkv: hidden=%d > 768", H * 64);
+    if (x_rows < round_up(B, 16)) return fail("debug_attn_decode_qkv: x_rows=%d, but B=%d rows are loaded as %d", x_rows, B, round_up(B, 16));
+    if (stats) {
+        if (!colsum) return fail("debug_attn_decode_qkv: stats without colsum");
+        if (strips < 1 || strips > 64) return fail("debug_attn_decode_qkv: strips=%d outside [1, 64]", strips);
+    }
+    AttnDecodeArgs a{};
+    a.img_k = img_k; a.img_v = img_v; a.txt_k = txt_k; a.txt_v = txt_v; a.out = out;
+    a.kv_src = kv_src; a.ld_src = T_max; a.d = H * 64; a.N_img = N_img; a.T_max = T_max; a.pos = pos; a.beams = beams;
+    a.scale = 0.125f; a.img_of = img_of; a.out_frag = out_frag; a.pairs_per_wg = pairs_per_wg; a.waves_per_pair = waves_per_pair;
+    a.N_pad = round_up(N_img, 32);
+    const DLn ln{(const float2*)stats, strips, 1.0f / (float)a.d, eps, nullptr, nullptr};
+    const DGemmArgs g = dgemm_ln(x, w, bias, colsum, stats ? &ln : nullptr, nullptr, 0, 0, B, 3 * a.d, a.d);
+    attn_decode_set_qkv(a, g);
+    if (!attn_decode_qkv_form(a, B, H)) return fail("debug_attn_decode_qkv: not a launch of the form");
+    HIPCK(launch_attn_decode_qkv(a, B, H, (hipStream_t)stream));
+    return 0;
+}
 GITMI_EXP_EXPORT int gitmi_debug_attn_decode_ragged(const void* qkv, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
                                                     const int* kv_src, void* out, const int* ntok, int B, int H, int N_img, int T_max,
                                                     int pos, int beams, int dtype, void* stream) {

@@ -546,11 +546,6 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         const DLn ln_prev{e->stats_o, d / 16, 1.0f / (float)d, 1e-12f, Lp ? Lp->lnog : nullptr, Lp ? Lp->lnob : nullptr};
         const DLn ln_a{e->stats_a, d / 16, 1.0f / (float)d, 1e-12f, L.lnag, L.lnab};
         const DLn* ln_o = Lp ? &ln_prev : nullptr;
-        if (chain) {
-            if (!GITMI_SKIPPED(e, 2)) RCK(dgemm(e, s, dgemm_ln(l == 0 ? e->d_ht : e->xo_b, L.qkv_f, ln_o, e->d_qkv, 0, 0, R, 3 * d, d)));
-        } else {
-            RCK(gemm(e, s, e->d_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->d_qkv, 3 * d, e->pol.f32, R, 3 * d, d, 0, TAG_GEMM_OTHER));
-        }
         AttnDecodeArgs a{};
         a.qkv = e->d_qkv; a.img_k = e->img_kh[l]; a.img_v = e->img_vh[l]; a.txt_k = e->txt_k[l]; a.txt_v = e->txt_v[l]; a.out = e->d_ctx;
         a.kv_src = kv_src; a.ld_src = ld_ids; a.d = d; a.N_img = e->cur_Nimg; a.T_max = c.max_text_len;
@@ -570,7 +565,22 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
         const bool stream_ok = !e->pol.shared_device && a.N_pad <= 8 * 32 && B * c.dec_heads >= 384 && e->pol.attn_nh != 2;
         a.stream_wgs = e->pol.attn_stream >= 0 ? e->pol.attn_stream : stream_ok ? 192 : 0;
         if (e->keyed) { a.ntok = e->rg_ntok; a.stream_wgs = 0; }       // per-image key counts: the register kernels
+        // QKV projection.  Where the policy packs the one-wave register kernel 8 pairs to a workgroup (greedy batches next to other
+        // contexts), the attention launch computes its pairs' q | k | v itself (launch_attn_decode_qkv: the same values bit for
+        // bit, kernels_attn_decode.hip): 26 launches per step instead of 32.  Everything else -- beam batches, keyed batches,
+        // two-wave pairs, the streaming form of a context alone, f32 -- keeps the QKV launch.  Measurement builds: with any
+        // GITMI_DECODE_SKIP bit set the step runs unfused, so bit 16 (the QKV launch alone left out) prices the path it bounds.
+        bool qkv_inside = false;
+        if (chain) {
+            const DGemmArgs g = dgemm_ln(l == 0 ? e->d_ht : e->xo_b, L.qkv_f, ln_o, e->d_qkv, 0, 0, R, 3 * d, d);
+            attn_decode_set_qkv(a, g);
+            qkv_inside = !GITMI_SKIPPED(e, ~0) && !e->pol.dgemm_dbg && attn_decode_qkv_form(a, B, c.dec_heads) && attn_decode_pairs_per_wg(a, B, c.dec_heads) == 8;
+            if (!qkv_inside && !GITMI_SKIPPED(e, 2) && !GITMI_SKIPPED(e, 16)) RCK(dgemm(e, s, g));
+        } else {
+            RCK(gemm(e, s, e->d_ht, d, L.wqkv, L.bqkv, nullptr, 0, e->d_qkv, 3 * d, e->pol.f32, R, 3 * d, d, 0, TAG_GEMM_OTHER));
+        }
         if (e->pol.f32) HIPCK(launch_attn_decode(a, B, c.dec_heads, s));
+        else if (qkv_inside) HIPCK(launch_attn_decode_qkv(a, B, c.dec_heads, s));
         else if (!GITMI_SKIPPED(e, 1)) HIPCK(launch_attn_decode_mfma(a, B, c.dec_heads, s));
         if (chain) {
             if (!GITMI_SKIPPED(e, 4))

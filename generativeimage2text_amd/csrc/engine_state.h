@@ -136,7 +136,8 @@ struct Policy {
     int gemm_tall = 1;                  // serving policy: encoder GEMMs always on 256-row tiles (1) or on the modelled height (0; GITMI_GEMM_TALL)
     int dgemm_rows = 0;                 // rows per workgroup of the N = 768 chain GEMMs (GITMI_DGEMM_ROWS: 16 / 32 / 64; 0 = by policy)
     int decode_skip = 0;                // MEASUREMENT BUILDS ONLY (GITMI_EXPERIMENT, GITMI_DECODE_SKIP): launches of the decode chain left
-                                        // out -- 1 attention, 2 QKV / FFN1 GEMMs, 4 out-proj / FFN2 GEMMs, 8 vocabulary head (ids are garbage)
+                                        // out -- 1 attention, 2 QKV / FFN1 GEMMs, 4 out-proj / FFN2 GEMMs, 8 vocabulary head, 16 the QKV GEMM alone
+                                        // (ids are garbage)
 };
 
 struct gitmi_engine {

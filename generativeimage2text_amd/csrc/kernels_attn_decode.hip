@@ -20,6 +20,7 @@
 // 8-lanes-per-key scalar path and are folded into the wave's partial before the two halves are combined.
 #include "gitmi_common.h"
 #include "launchers.h"
+#include "dgemm_shared.h"      // before the pragma below: its functions keep the default contraction (the chain GEMMs' arithmetic)
 #include <algorithm>
 #include <type_traits>
 
@@ -85,14 +86,26 @@ struct Pair {
     bool on;           // false: a packed workgroup's pair past the last one (the wave runs along on zeros, writes nothing)
 };
 
+// Where the new position's q | k | v of the pair's beam rows are, this head's 64 columns of each: the rows the QKV GEMM wrote
+// (qkv_rows), or the workgroup's LDS rows in the form that projects them itself (attn_decode_qkv_kernel)
+struct QkvSrc {
+    const bf16_t* q0;          // q of beam row 0
+    int row_stride, part;      // elements between beam rows, and from q to k and from k to v
+    __device__ __forceinline__ const bf16_t* q(int j) const { return q0 + (size_t)j * row_stride; }
+    __device__ __forceinline__ const bf16_t* k(int j) const { return q(j) + part; }
+    __device__ __forceinline__ const bf16_t* v(int j) const { return q(j) + 2 * part; }
+};
+__device__ __forceinline__ QkvSrc qkv_rows(const AttnDecodeArgs& a, const Pair& p) {
+    return QkvSrc{reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)p.row0 * (3 * a.d) + p.h * HD, 3 * a.d, a.d};
+}
+
 // K / V of text item (beam j, position s), this lane's 8 dims: the new position from the QKV rows, earlier ones from the
 // text cache through the beam indirection
 template <int KB>
-__device__ __forceinline__ void load_text_kv(const AttnDecodeArgs& a, const Pair& p, int j, int s, int sub, u32x4_t& kr, u32x4_t& vr) {
+__device__ __forceinline__ void load_text_kv(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int j, int s, int sub, u32x4_t& kr, u32x4_t& vr) {
     if (s == a.pos) {
-        const bf16_t* src = reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + a.d + p.h * HD + sub * 8;
-        kr = *reinterpret_cast<const u32x4_t*>(src);
-        vr = *reinterpret_cast<const u32x4_t*>(src + a.d);
+        kr = *reinterpret_cast<const u32x4_t*>(qs.k(j) + sub * 8);
+        vr = *reinterpret_cast<const u32x4_t*>(qs.v(j) + sub * 8);
     } else {
         // one beam: histories are never re-ordered, the cache row is the row itself (no dependent index load)
         const int srow = KB == 1 ? p.row0 : a.kv_src[(size_t)(p.row0 + j) * a.ld_src + s];
@@ -107,7 +120,7 @@ template <int KB, int TI>
 struct TextItems {
     int j[TI];                  // beam of item u, -1: none
     u32x4_t kr[TI], vr[TI];
-    __device__ __forceinline__ void load(const AttnDecodeArgs& a, const Pair& p, int grp, int ngrp, int sub) {
+    __device__ __forceinline__ void load(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int grp, int ngrp, int sub) {
         const int nt = a.pos + 1;
 #pragma unroll
         for (int u = 0; u < TI; ++u) {
@@ -116,29 +129,28 @@ struct TextItems {
             const int s = it < a.beams * nt ? it % nt : 0;
             kr[u] = u32x4_t{0u, 0u, 0u, 0u};
             vr[u] = kr[u];
-            if (j[u] >= 0) load_text_kv<KB>(a, p, j[u], s, sub, kr[u], vr[u]);
+            if (j[u] >= 0) load_text_kv<KB>(a, p, qs, j[u], s, sub, kr[u], vr[u]);
         }
     }
 };
 
 // append this position's K/V of every beam to the text cache (16-byte copies by the first beams*8 threads of the pair)
-__device__ __forceinline__ void append_text_cache(const AttnDecodeArgs& a, const Pair& p, int t, int sub) {
+__device__ __forceinline__ void append_text_cache(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int t, int sub) {
     if (p.on && t < a.beams * 8) {
         const int j = t >> 3;
-        const bf16_t* src = reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + a.d + p.h * HD + sub * 8;
         const size_t dst = ((size_t)(p.row0 + j) * a.T_max + a.pos) * a.d + p.h * HD + sub * 8;
-        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_k) + dst) = *reinterpret_cast<const u32x4_t*>(src);
-        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_v) + dst) = *reinterpret_cast<const u32x4_t*>(src + a.d);
+        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_k) + dst) = *reinterpret_cast<const u32x4_t*>(qs.k(j) + sub * 8);
+        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16_t*>(a.txt_v) + dst) = *reinterpret_cast<const u32x4_t*>(qs.v(j) + sub * 8);
     }
 }
 
 // Q operand of the S MFMAs: lane (row = l15, lg) holds dims ds*32 + lg*8 .. +8 of beam row l15, pre-scaled by 1/8 (exact in bf16)
-__device__ __forceinline__ void load_q_frag(const AttnDecodeArgs& a, const Pair& p, int l15, int lg, bf16x8_t (&qf)[2]) {
+__device__ __forceinline__ void load_q_frag(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int l15, int lg, bf16x8_t (&qf)[2]) {
 #pragma unroll
     for (int ds = 0; ds < 2; ++ds) {
         float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (p.on && l15 < a.beams)
-            ld8bf(reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + l15) * (3 * a.d) + p.h * HD + ds * 32 + lg * 8, qv);
+            ld8bf(qs.q(l15) + ds * 32 + lg * 8, qv);
         u32x4_t t;
 #pragma unroll
         for (int e = 0; e < 4; ++e) t[e] = pack2bf(qv[2 * e] * a.scale, qv[2 * e + 1] * a.scale);
@@ -219,7 +231,7 @@ struct ImagePartial {
 template <int KB>
 struct TextPartial {
     float q[KB][8], m[KB], l[KB], o[KB][8];
-    __device__ __forceinline__ void init(const AttnDecodeArgs& a, const Pair& p, int sub) {
+    __device__ __forceinline__ void init(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int sub) {
 #pragma unroll
         for (int j = 0; j < KB; ++j) {
             m[j] = -INFINITY;
@@ -227,7 +239,7 @@ struct TextPartial {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { q[j][e] = 0.f; o[j][e] = 0.f; }
             if (p.on && j < a.beams) {
-                ld8bf(reinterpret_cast<const bf16_t*>(a.qkv) + (size_t)(p.row0 + j) * (3 * a.d) + p.h * HD + sub * 8, q[j]);
+                ld8bf(qs.q(j) + sub * 8, q[j]);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) q[j][e] *= a.scale;
             }
@@ -266,12 +278,12 @@ struct TextPartial {
     }
     // long texts: the items past the TI up-front ones, on a dependent-load path
     template <int TI>
-    __device__ __forceinline__ void tail(const AttnDecodeArgs& a, const Pair& p, int grp, int ngrp, int sub) {
+    __device__ __forceinline__ void tail(const AttnDecodeArgs& a, const Pair& p, const QkvSrc& qs, int grp, int ngrp, int sub) {
         if (!p.on) return;
         const int nt = a.pos + 1;
         for (int it = grp + ngrp * TI; it < a.beams * nt; it += ngrp) {
             u32x4_t kr, vr;
-            load_text_kv<KB>(a, p, it / nt, it % nt, sub, kr, vr);
+            load_text_kv<KB>(a, p, qs, it / nt, it % nt, sub, kr, vr);
             item(it / nt, kr, vr);
         }
     }
@@ -412,11 +424,12 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
 
     // ---- text items (the 8 * NH eight-lane groups of the pair share them), text-cache append, Q operand -------------
     const int t = tid % PT, grp = t >> 3, sub = tid & 7;
+    const QkvSrc qs = qkv_rows(a, p);
     TextItems<KB, TI> ti;
-    ti.load(a, p, grp, 8 * NH, sub);
-    append_text_cache(a, p, t, sub);
+    ti.load(a, p, qs, grp, 8 * NH, sub);
+    append_text_cache(a, p, qs, t, sub);
     bf16x8_t qf[2];
-    load_q_frag(a, p, l15, lg, qf);
+    load_q_frag(a, p, qs, l15, lg, qf);
 
     // ---- image part on the matrix cores -------------------------------------------------------------------------
     ImagePartial ip;
@@ -451,9 +464,9 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
     ip.finish();
     // ---- text keys ------------------------------------------------------------------------------------------------
     TextPartial<KB> tp;
-    tp.init(a, p, sub);
+    tp.init(a, p, qs, sub);
     tp.items(ti, !(a.dbg & 2));
-    tp.template tail<TI>(a, p, grp, 8 * NH, sub);
+    tp.template tail<TI>(a, p, qs, grp, 8 * NH, sub);
     tp.merge_groups();
     // ---- this wave's partial per beam row = its image keys + its text items, through LDS ----------------------------
     ip.publish(part[hp][half], k, l15, lg);
@@ -463,6 +476,186 @@ __global__ __launch_bounds__(64 * NH * PW) void attn_decode_mfma_kernel(AttnDeco
     if constexpr (NH > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
     if constexpr (NH == 1) write_rows(a, p, part[hp][0], t, PT);
     else write_rows(a, p, part[hp][0], part[hp][NH - 1], t, PT);
+}
+
+// ---- the 8-pair one-wave form with the QKV projection inside ---------------------------------------------------------
+// attn_decode_mfma_kernel<1, TI, 8, 1> preceded, in the same launch, by the part of the QKV GEMM its pairs need.  A
+// (sentence, head) pair reads 192 of the 3 d projected columns of one row -- q, k and v of its head -- and while its first
+// image K/V chunk is on its way (~8 us) the wave has nothing to do.  So a workgroup takes 8 consecutive SENTENCES of ONE head
+// (the packed form above takes 8 consecutive pairs: 8 heads of one sentence); its 8 waves request their pairs' image K, then
+// compute the 8 rows x 192 columns together -- 12 weight strips x 4 K slices, wave w the slice w % 4 of strips 6 (w / 4) .. + 5
+// -- exchange partials and results through LDS, and go on as the form above, with q | k | v of the row coming from LDS
+// instead of the QKV GEMM's output.  One launch per layer less, and no launch boundary between the two.
+// Arithmetic: the projected values are the bits of dgemm_kernel<4, 4, DEPI_BF16> because this kernel calls the same code
+// (dgemm_shared.h): k_slice over 4 slices, mfma_slice with the weights as first operand, sum_waves in slice order,
+// DGEMM_CONSUMER_FINISH under the default contraction, pack2bf.  A row's result does not depend on the rows sharing its MFMA
+// tile, so computing a 16-row tile for 8 of its rows changes nothing.  The head's 295 KB of weights are read by its
+// ceil(B / 8) workgroups: the map from blockIdx to (head, sentence block) keeps them on one blockIdx % 8 residue (one XCD's L2
+// where workgroups are dealt round-robin) -- performance only, any placement gives the same results.
+// Image V^T of the first chunk is requested AFTER the projection's MFMAs: the K and V^T chunks are 64 registers each, the
+// activation slice 24 and two weight strips in flight 48, of 256 (the kernel takes 204); K alone keeps the CU's HBM stream
+// busy for longer than the projection takes.  The weight strips are read by CACHEABLE loads (load_w_slice<false>): the head's
+// other workgroups read them again from the L2 (21.8 us per launch; 23.3 with the chain GEMMs' non-temporal loads, which is what
+// QKV launch + attention took as two launches: docs/LAB_NOTEBOOK.md, profiles/r14_attn_qkv_*).
+constexpr int AQ_PW = 8;                     // pairs = waves = sentences of a workgroup
+constexpr int AQ_STRIPS = 3 * HD / 16;       // weight strips of one head: 4 each of q, k and v
+
+// workgroup-local barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight (vmcnt(0)),
+// here the image K/V chunk the projection is meant to overlap
+__device__ __forceinline__ void attn_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+template <int TI>
+__global__ __launch_bounds__(64 * AQ_PW) void attn_decode_qkv_kernel(AttnDecodeArgs a) {
+    constexpr int KB = 1;
+    __shared__ __attribute__((aligned(16))) f32x4_t red[AQ_STRIPS][4][1][64];     // [strip][K slice][row tile][lane]
+    __shared__ __attribute__((aligned(16))) bf16_t rows[AQ_PW][3 * HD];           // q | k | v of the 8 sentences, this head
+    __shared__ float part[AQ_PW][KB][HD + 2];                                     // [pair][beam]: o[64], m, l
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lg = lane >> 4;
+    const int H = a.d / HD, B = a.n_pairs / H;
+    const int Np = a.N_pad, nsteps = Np >> 5;
+    // (head, sentence block) of this workgroup: the launch has 8 * per workgroups, residue r = blockIdx % 8 takes the `per`
+    // consecutive (head-major) blocks from r * per
+    const int nsb = (B + AQ_PW - 1) / AQ_PW, total = H * nsb, per = (total + 7) >> 3;
+    const int blk = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    if (blk >= total) return;                      // whole workgroup: before any barrier
+    const int b0 = (blk % nsb) * AQ_PW;
+    Pair p;
+    p.h = blk / nsb;
+    p.on = b0 + wave < B;
+    const int b = p.on ? b0 + wave : 0;
+    p.row0 = b;
+    const int bi = a.img_of ? a.img_of[b] : b;
+    const bf16_t* Kf = reinterpret_cast<const bf16_t*>(a.img_k) + ((size_t)bi * H + p.h) * Np * HD;
+    const bf16_t* Vt = reinterpret_cast<const bf16_t*>(a.img_v) + ((size_t)bi * H + p.h) * Np * HD;
+    const int nimg_steps = p.on ? nsteps : 0;
+
+    // ---- image K / V^T of a chunk of key steps (the loads of attn_decode_mfma_kernel's load_chunk, K and V^T apart) -------
+    bf16x8_t kq[ACS][2][2], vq[ACS][4];
+    auto load_k = [&](int s0) {
+#pragma unroll
+        for (int c = 0; c < ACS; ++c) {
+            const bool on = s0 + c < nimg_steps;
+            const bf16_t* kp = Kf + frag_tile(2 * (s0 + c), 0, 2, lane);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int ds = 0; ds < 2; ++ds)
+                    kq[c][t][ds] = !on ? bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}
+                                       : __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(kp + (t * 2 + ds) * 512));
+        }
+    };
+    auto load_v = [&](int s0) {
+#pragma unroll
+        for (int c = 0; c < ACS; ++c) {
+            const bool on = s0 + c < nimg_steps;
+            const bf16_t* vp = Vt + ((size_t)(s0 + c) * 4 * 64 + lane) * 8;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                vq[c][dt] = !on ? bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0}
+                                : __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(vp + dt * 512));
+        }
+    };
+    load_k(0);
+
+    // ---- q | k | v of the workgroup's 8 rows x 192 columns --------------------------------------------------------------
+    const int ksteps = a.d >> 5, N = 3 * a.d;
+    const int slice = wave & 3;
+    const KSlice ks = k_slice(ksteps, 4, slice);
+    const int rt = b0 >> 4;                                    // the 8 sentences are rows (b0 & 15) .. + 7 of row tile rt
+    auto strip_of = [&](int ls) { return (ls >> 2) * (a.d >> 4) + p.h * 4 + (ls & 3); };     // head-local strip -> strip of the 3 d columns
+    bf16x8_t xf[DW_KS][1];
+    load_x_slice(xf, reinterpret_cast<const bf16_t*>(a.x), rt, ks, ksteps, lane);
+#pragma unroll 2
+    for (int u = 0; u < AQ_STRIPS / 2; ++u) {
+        const int ls = (wave >> 2) * (AQ_STRIPS / 2) + u;
+        const WSlice wf = load_w_slice<false>(reinterpret_cast<const bf16_t*>(a.w), strip_of(ls), ks, ksteps, lane);
+        f32x4_t acc[1] = {f32x4_t{0.f, 0.f, 0.f, 0.f}};
+        mfma_slice(acc, wf, xf, ks);
+        red[ls][slice][0][lane] = acc[0];
+    }
+    load_v(0);
+    // wave w finishes strips w and w + 8: its lane (l15, lg) row l15 of the tile, columns lg * 4 .. + 3 of the strip
+    const int fm_raw = rt * 16 + l15;
+    const int fm = fm_raw < a.M ? fm_raw : a.M - 1;
+    const bool second = wave + AQ_PW < AQ_STRIPS;
+    const int fn0 = strip_of(wave) * 16 + lg * 4, fn1 = strip_of(second ? wave + AQ_PW : wave) * 16 + lg * 4;
+    RowStatLoads sl;
+    if (a.stats_in) stats_issue(sl, a.stats_in, a.strips_in, a.M, fm, lg);
+    const float4 bias4[2] = {load_cols4(a.bias, fn0, N), load_cols4(a.bias, fn1, N)};
+    float4 cs4[2] = {float4{0.f, 0.f, 0.f, 0.f}, float4{0.f, 0.f, 0.f, 0.f}};
+    if (a.stats_in) { cs4[0] = load_cols4(a.colsum, fn0, N); cs4[1] = load_cols4(a.colsum, fn1, N); }
+    attn_lds_barrier();
+    {
+#pragma clang fp contract(fast)                    // the chain GEMMs' epilogue, under the contraction they are built with
+        float mean = 0.f, rstd = 1.f;
+        if (a.stats_in) stats_finish(sl, a.inv_d, a.eps_in, mean, rstd);
+        const int i = l15 - (b0 & 15);             // sentence of the workgroup this lane's row is (outside 0..7: another block's)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            if (t == 1 && !second) break;
+            const int ls = wave + t * AQ_PW;
+            const f32x4_t tot = sum_waves<4>(red[ls], 0, lane);
+            DGEMM_CONSUMER_FINISH(v, tot, bias4[t], cs4[t], a.stats_in, mean, rstd, GITMI_ACT_NONE);
+            if (i >= 0 && i < AQ_PW) {
+                uint2 o;
+                o.x = pack2bf(v[0], v[1]);
+                o.y = pack2bf(v[2], v[3]);
+                *reinterpret_cast<uint2*>(&rows[i][ls * 16 + lg * 4]) = o;
+            }
+        }
+    }
+    attn_lds_barrier();
+    const QkvSrc qs{rows[wave], 0, HD};
+
+    // ---- from here on: attn_decode_mfma_kernel<1, TI, 8, 1> --------------------------------------------------------------
+    const int grp = lane >> 3, sub = lane & 7;
+    TextItems<KB, TI> ti;
+    ti.load(a, p, qs, grp, 8, sub);
+    append_text_cache(a, p, qs, lane, sub);
+    bf16x8_t qf[2];
+    load_q_frag(a, p, qs, l15, lg, qf);
+
+    ImagePartial ip;
+    ip.init();
+    for (int s0 = 0; s0 < nimg_steps; s0 += ACS) {
+        if (s0 != 0) { load_k(s0); load_v(s0); }
+        f32x4_t sc[ACS][2];
+        float cm = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < ACS; ++c) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                sc[c][u] = mfma16(kq[c][u][0], qf[0], f32x4_t{0.f, 0.f, 0.f, 0.f});
+                sc[c][u] = mfma16(kq[c][u][1], qf[1], sc[c][u]);
+            }
+            ip.mask_max(sc[c], s0 + c, nimg_steps, a.N_img, lg, cm);
+        }
+        const float mn = ip.new_max(cm, s0 != 0);
+#pragma unroll
+        for (int c = 0; c < ACS; ++c) {
+            const bf16x8_t pf = ip.p_frag(sc[c], mn);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) ip.o[dt] = mfma16(vq[c][dt], pf, ip.o[dt]);
+        }
+    }
+    ip.finish();
+    TextPartial<KB> tp;
+    tp.init(a, p, qs, sub);
+    tp.items(ti, true);
+    tp.template tail<TI>(a, p, qs, grp, 8, sub);
+    tp.merge_groups();
+    ip.publish(part[wave], a.beams, l15, lg);
+    __builtin_amdgcn_wave_barrier();       // a wave reads back only what it wrote itself (its LDS operations complete in order)
+    tp.fold_into(part[wave], a.beams, lane, sub);
+    __builtin_amdgcn_wave_barrier();
+    write_rows(a, p, part[wave], lane, 64);
 }
 
 // ---- streaming form of the one-wave kernel -----------------------------------------------------------------------
@@ -586,11 +779,12 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
 
         // ---- text items (the 8 eight-lane groups of the wave share them), text-cache append, Q operand -------------
         const int grp = lane >> 3, sub = lane & 7;
+        const QkvSrc qs = qkv_rows(a, p);
         TextItems<KB, TI> ti;
-        ti.load(a, p, grp, 8, sub);
-        append_text_cache(a, p, lane, sub);
+        ti.load(a, p, qs, grp, 8, sub);
+        append_text_cache(a, p, qs, lane, sub);
         bf16x8_t qf[2];
-        load_q_frag(a, p, l15, lg, qf);
+        load_q_frag(a, p, qs, l15, lg, qf);
 
         // ---- image part on the matrix cores: operands from the ring ------------------------------------------------
         ImagePartial ip;
@@ -644,9 +838,9 @@ __global__ __launch_bounds__(64 * AS_WAVES) void attn_decode_stream_kernel(AttnD
         ip.finish();
         // ---- text keys, then the wave's partial per beam row = image keys + text items, through its own LDS slot -------
         TextPartial<KB> tp;
-        tp.init(a, p, sub);
+        tp.init(a, p, qs, sub);
         tp.items(ti, true);
-        tp.template tail<TI>(a, p, grp, 8, sub);
+        tp.template tail<TI>(a, p, qs, grp, 8, sub);
         tp.merge_groups();
         ip.publish(part[wave], k, l15, lg);
         __builtin_amdgcn_wave_barrier();       // a wave reads back only what it wrote itself (its LDS operations complete in order)
@@ -673,6 +867,30 @@ static void with_beam_rows(int beams, F&& f) {
     else if (beams <= 2) f(std::integral_constant<int, 2>{});
     else if (beams <= 4) f(std::integral_constant<int, 4>{});
     else f(std::integral_constant<int, 8>{});
+}
+
+int attn_decode_pairs_per_wg(const AttnDecodeArgs& a, int B, int H) {
+    int pw = a.pairs_per_wg >= 8 ? 8 : a.pairs_per_wg >= 4 || a.pairs_per_wg <= 0 ? 4 : a.pairs_per_wg >= 2 ? 2 : 1;
+    while (pw > 1 && B * H / pw < 96) pw >>= 1;
+    if (a.beams > 4 && pw == 8) pw = 4;         // 8 beams: 269 registers, one wave per SIMD: 4 pairs fill a CU
+    return pw;
+}
+
+bool attn_decode_qkv_form(const AttnDecodeArgs& a, int B, int H) {
+    if (B <= 0 || a.beams != 1 || a.waves_per_pair == 2 || a.ntok || a.stream_wgs != 0 || a.dbg) return false;
+    if (a.N_img < 1 || a.N_pad % 32 || a.N_pad < a.N_img || a.N_pad > 8 * 32) return false;
+    if (a.d != H * HD || a.d > 4 * DW_KS * 32 || a.M < B) return false;           // K = d: whole k-steps, a wave's slice in registers
+    if (!a.x || !a.w || !a.bias) return false;
+    return !a.stats_in || (a.colsum && a.strips_in >= 1 && a.strips_in <= 4 * STRIP_SLOTS);
+}
+
+hipError_t launch_attn_decode_qkv(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
+    if (!attn_decode_qkv_form(a, B, H)) return hipErrorInvalidValue;
+    AttnDecodeArgs p = a;
+    p.n_pairs = B * H;
+    const int total = H * ((B + AQ_PW - 1) / AQ_PW);          // (head, block of 8 sentences) per workgroup; the kernel's map
+    hipLaunchKernelGGL((attn_decode_qkv_kernel<3>), dim3(8 * ((total + 7) / 8)), dim3(64 * AQ_PW), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStream_t s) {
@@ -711,9 +929,7 @@ hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStr
     // pairs per workgroup (same per-wave arithmetic whatever the packing): 4 by default, 8 = a full CU under the serving
     // policy (10.58k -> 10.67k captions/s in the mixed schedule, +11 us per decode step alone; profiles/r03_y_*) -- but
     // never fewer than 96 workgroups: a small batch packed onto a handful of CUs streams its K/V through too few of them
-    int pw = a.pairs_per_wg >= 8 ? 8 : a.pairs_per_wg >= 4 || a.pairs_per_wg <= 0 ? 4 : a.pairs_per_wg >= 2 ? 2 : 1;
-    while (pw > 1 && p.n_pairs / pw < 96) pw >>= 1;
-    if (a.beams > 4 && pw == 8) pw = 4;         // 8 beams: 269 registers, one wave per SIMD: 4 pairs fill a CU
+    const int pw = attn_decode_pairs_per_wg(a, B, H);
     with_beam_rows(a.beams, [&](auto kb) {
         constexpr int KB = decltype(kb)::value;
         auto packed = [&](auto pwc) {

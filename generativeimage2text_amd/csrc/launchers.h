@@ -178,6 +178,11 @@ struct AttnDecodeArgs {
     int n_pairs;         // set by the launcher
     const int* ntok;     // ragged batches: image keys of every image ([B images] <= N_img; N_img stays the row stride); nullptr:
                          // all N_img.  The streaming kernel does not serve ragged batches (stream_wgs must be 0).
+    // launch_attn_decode_qkv only (qkv is not read): the rows' q | k | v = the consumer GEMM dgemm_ln(x, w, bias, colsum, ln) over
+    // N = 3 d columns, K = d, M rows, computed inside the attention launch -- DGemmArgs' fields of the same names
+    const unsigned short* x; const unsigned short* w; const float* bias; const float* colsum;
+    const float2* stats_in; int strips_in; float inv_d, eps_in;
+    int M;
 };
 // the f32 mode's decode attention (VALU, kernels_attn.hip) and its head-major fp32 K/V cache
 hipError_t launch_kv_repack(const void* qkv, void* kh, void* vh, int B, int N, int H, int d, hipStream_t s);
@@ -185,6 +190,16 @@ hipError_t launch_attn_decode(const AttnDecodeArgs& a, int B, int H, hipStream_t
 // bf16 decode attention on the matrix cores (kernels_attn_decode.hip) and its cache layouts
 hipError_t launch_kv_repack_frag(const void* qkv, void* kf, void* vt, int B, int N, int N_pad, int H, int d, hipStream_t s);
 hipError_t launch_attn_decode_mfma(const AttnDecodeArgs& a, int B, int H, hipStream_t s);
+int attn_decode_pairs_per_wg(const AttnDecodeArgs& a, int B, int H);   // the packing launch_attn_decode_mfma gives its one-wave register kernel
+// The 8-pair register form with the QKV projection inside (one launch instead of QKV GEMM + attention; bit-identical to the two):
+// one beam, one wave per pair, N_pad <= 256, no ntok, stream_wgs == 0, K = d <= 768.  attn_decode_qkv_form: is this launch of
+// that form?  (the engine adds the policy: only where attn_decode_pairs_per_wg is 8); anything else is hipErrorInvalidValue.
+bool attn_decode_qkv_form(const AttnDecodeArgs& a, int B, int H);
+inline void attn_decode_set_qkv(AttnDecodeArgs& a, const DGemmArgs& g) {          // g: the QKV launch this one replaces (a dgemm_ln)
+    a.x = g.A; a.w = g.W; a.bias = g.bias; a.colsum = g.colsum;
+    a.stats_in = g.stats_in; a.strips_in = g.strips_in; a.inv_d = g.inv_d; a.eps_in = g.eps_in; a.M = g.M;
+}
+hipError_t launch_attn_decode_qkv(const AttnDecodeArgs& a, int B, int H, hipStream_t s);
 
 constexpr int SS_NHMAX = 8;            // num_keep_best supported by the device search
 struct SearchState {

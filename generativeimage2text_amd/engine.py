@@ -45,7 +45,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
-    "gitmi_debug_gemm_form", "gitmi_debug_context_embed",
+    "gitmi_debug_gemm_form", "gitmi_debug_context_embed", "gitmi_debug_attn_decode_qkv",
 ]
 
 
@@ -166,6 +166,8 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_form.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                                      i32, i32, i32, vp]
+        lib.gitmi_debug_attn_decode_qkv.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                                    i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_vocab_topm_rules.argtypes = [vp, vp, vp, vp, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32,
                                                      i32, C.c_float, vp, vp, vp, vp, i32, vp]
         lib.gitmi_debug_search_begin_prefixed.argtypes = [vp, C.POINTER(GitmiSearch), i32, vp, i32, vp, i32, vp]
@@ -1321,6 +1323,32 @@ def op_attn_decode_form(qkv, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_
         qkv.data_ptr(), img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(), kv_src.data_ptr(), out.data_ptr(),
         _ptr(ntok), _ptr(img_of), n_images, B, H, N_img, T_max, pos, beams, _torch_dtype_code(qkv), int(bool(out_frag)),
         int(pairs_per_wg), int(waves_per_pair), int(stream_wgs), _stream()), lib)
+    return out
+
+
+def op_attn_decode_qkv(x, w, bias, img_k, img_v, txt_k, txt_v, kv_src, B, H, N_img, T_max, pos, beams=1, *, colsum=None, stats=None,
+                       eps: float = 1e-12, out=None, img_of=None, ntok=None, out_frag=False, pairs_per_wg=8, waves_per_pair=1,
+                       stream_wgs=0):
+    """The decode attention that computes its own q | k | v (measurement build): op_attn_decode_form without qkv, plus the QKV
+    GEMM's operands as op_dgemm_form(packed=True) takes them -- x fragment-major [>= round_up(B, 16), H * 64], w fragment-major
+    [3 H 64, H 64], bias / colsum [3 H 64], stats [strips, B, 2] or None.  img_k / img_v in kv_repack's layouts (or head-major
+    [images, H, N_img, 64]); txt_k / txt_v are appended to in place.  A call outside the form raises GitmiError."""
+    lib = _exp_library(x.dtype, w.dtype, img_k.dtype, img_v.dtype, txt_k.dtype, txt_v.dtype)
+    d = H * 64
+    n_images = img_k.shape[0] if img_k.dim() == 4 else img_k.numel() // (H * ((N_img + 31) // 32 * 32) * 64)
+    if img_k.dim() == 4:
+        img_k, img_v = kv_repack(img_k, img_v)
+    if img_of is not None:
+        img_of = torch.as_tensor(img_of, dtype=torch.int32).to(x.device)
+    if ntok is not None:
+        ntok = torch.as_tensor(ntok, dtype=torch.int32).to(x.device)
+    if out is None:
+        out = torch.empty((B * beams + 15) // 16 * 16 if out_frag else B * beams, d, device=x.device, dtype=x.dtype)
+    _ck(_experiment_only(lib, "gitmi_debug_attn_decode_qkv")(
+        x.data_ptr(), int(x.shape[0]), w.data_ptr(), _ptr(bias), _ptr(colsum), _ptr(stats), 0 if stats is None else int(stats.shape[0]),
+        eps, img_k.data_ptr(), img_v.data_ptr(), txt_k.data_ptr(), txt_v.data_ptr(), kv_src.data_ptr(), out.data_ptr(), _ptr(ntok),
+        _ptr(img_of), n_images, B, H, N_img, T_max, pos, beams, _torch_dtype_code(x), int(bool(out_frag)), int(pairs_per_wg),
+        int(waves_per_pair), int(stream_wgs), _stream()), lib)
     return out
 
 

@@ -109,6 +109,20 @@ int  gitmi_debug_attn_decode_form(const void* qkv, const void* img_k, const void
                                   const int* kv_src, void* out, const int* ntok, const int* img_of, int n_images, int B, int H,
                                   int N_img, int T_max, int pos, int beams, int dtype, int out_frag, int pairs_per_wg,
                                   int waves_per_pair, int stream_wgs, void* stream);
+/*   attn_decode_qkv:    the decode attention that computes its own q | k | v (tests/test_gpu_attn_decode_qkv.py): attn_decode_form's
+ *                       operands without qkv, plus the QKV GEMM's as gitmi_debug_dgemm_form takes them -- x fragment-major
+ *                       [x_rows >= round_up(B, 16)][K = H * 64], w fragment-major [3 K][K], bias / colsum fp32 [3 K], stats
+ *                       fp32 [strips][B][2] strip partials of the folded LayerNorm or NULL, eps.  `out` and the appended text
+ *                       K/V are, bit for bit, those of gitmi_debug_dgemm_form (C epilogue, N = 3 K) followed by attn_decode_form
+ *                       with pairs_per_wg = 8, waves_per_pair = 1.  An argument check + the launcher the engine calls where its
+ *                       policy packs 8 one-wave pairs per workgroup; the launch is of that form whatever B is.  Refused by name,
+ *                       nothing launched: null pointers, fp32, beams != 1, ntok, waves_per_pair 2, stream_wgs != 0,
+ *                       pairs_per_wg != 8, more than 256 padded image keys, H > 12, x_rows too small, stats without colsum. */
+int  gitmi_debug_attn_decode_qkv(const void* x, int x_rows, const void* w, const float* bias, const float* colsum, const float* stats,
+                                 int strips, float eps, const void* img_k, const void* img_v, void* txt_k, void* txt_v,
+                                 const int* kv_src, void* out, const int* ntok, const int* img_of, int n_images, int B, int H,
+                                 int N_img, int T_max, int pos, int beams, int dtype, int out_frag, int pairs_per_wg,
+                                 int waves_per_pair, int stream_wgs, void* stream);
 
 /* op hooks of the fused decode step (kernels_dgemm.hip vocab_topm_kernel, kernels_search.hip search_step_kernel;
  * tests/test_gpu_search_ops.py).  All list / id / plen pointers are DEVICE memory unless named _host.
