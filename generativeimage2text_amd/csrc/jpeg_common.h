@@ -25,5 +25,16 @@ __host__ __device__ inline size_t jpeg_plane_bytes_bound(long long H, long long 
     return (a + 127) / 128 * 128;
 }
 
+// gitmi_jpeg_entropy_batch: one image of a launch group; all sizes are the CALLER's, the device checks the record against them
+struct JpegScanImg {
+    unsigned long long scan_off, scan_size;         // the scan record in the scan buffer (offset a multiple of 128)
+    unsigned long long coef_off, coef_size;         // the coefficient record to write (offset a multiple of 128)
+    unsigned long long tmp_off;                     // this image's part of the workspace (a multiple of 128)
+    unsigned long long nsub_cap;                    // subsequences that part holds
+};
+struct JpegScanChunk { JpegScanImg d[JPEG_CHUNK]; };
+
+hipError_t launch_jpeg_entropy(const uint8_t* scans, const JpegScanImg* imgs, int n, uint8_t* coef, int* status, uint8_t* tmp,
+                               hipStream_t s);
 hipError_t launch_jpeg_reconstruct(const uint8_t* coef, size_t coef_bytes, const JpegImg* imgs, int n, uint8_t* tmp, uint8_t* rgb,
                                    hipStream_t s);

@@ -210,23 +210,30 @@ inline bool decode_block(Bits& b, const Huff& dc, const Huff& ac, Comp& c, int16
 
 inline unsigned be16(const uint8_t* p) { return ((unsigned)p[0] << 8) | p[1]; }
 
-}  // namespace
-
-extern "C" int gitmi_jpeg_abi_version(void) { return GITMI_JPEG_ABI_VERSION; }
-
-extern "C" int gitmi_jpeg_entropy_decode(const uint8_t* jpg, size_t n, void* out, size_t out_cap, gitmi_jpeg_info* info) {
-    if ((!jpg && n) || (!out && out_cap) || ((uintptr_t)out & 7)) return GITMI_JPEG_BAD_ARGUMENT;
-    if (info) memset(info, 0, sizeof(*info));
-    if (n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return GITMI_JPEG_UNSUPPORTED;
-
-    static_assert(sizeof(gitmi_jpeg_header) == GITMI_JPEG_HEADER_BYTES, "record header layout");
-    gitmi_jpeg_header hdr;
-    memset(&hdr, 0, sizeof(hdr));
+// Everything in front of the entropy-coded segment, shared by gitmi_jpeg_entropy_decode and gitmi_jpeg_scan_prepare: the
+// marker segments, libjpeg's colour-space decision, the sampling factors of the fast path and the layout of the record.
+struct Parsed {
+    gitmi_jpeg_header hdr;                                            // qt[] only; the rest is filled by fill_header()
     Huff huff[2][4];                                                  // [dc / ac][table]
+    gitmi_jpeg_dht dht[2][4];                                         // the same tables as the file has them
+    Comp comp[3];
+    int ncomp, restart;
+    unsigned width, height;
+    const uint8_t* scan;                                              // first byte behind the SOS segment
+    uint32_t mcus_w, mcus_h;
+    uint64_t bytes;                                                   // of the coefficient record
+};
+
+// GITMI_JPEG_OK or GITMI_JPEG_UNSUPPORTED; the caller has checked n >= 4 and the SOI
+int parse_markers(const uint8_t* jpg, size_t n, Parsed& P) {
+    gitmi_jpeg_header& hdr = P.hdr;
+    memset(&hdr, 0, sizeof(hdr));
+    memset(P.dht, 0, sizeof(P.dht));
+    Huff (&huff)[2][4] = P.huff;
     for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 4; ++j) huff[i][j].defined = false;
     bool have_qt[4] = {false, false, false, false};
-    Comp comp[3];
+    Comp (&comp)[3] = P.comp;
     int ncomp = 0, restart = 0;
     bool have_sof = false, jfif = false, adobe = false;
     int adobe_transform = -1;
@@ -276,6 +283,9 @@ extern "C" int gitmi_jpeg_entropy_decode(const uint8_t* jpg, size_t n, void* out
                 for (int i = 0; i < 16; ++i) total += d[o + 1 + i];
                 if (total > 256 || dl - o - 17 < (size_t)total) return GITMI_JPEG_UNSUPPORTED;
                 if (!build_huff(huff[tc][th], d + o + 1, d + o + 17, total, tc == 1)) return GITMI_JPEG_UNSUPPORTED;
+                memset(&P.dht[tc][th], 0, sizeof(gitmi_jpeg_dht));
+                memcpy(P.dht[tc][th].counts, d + o + 1, 16);
+                memcpy(P.dht[tc][th].symbols, d + o + 17, (size_t)total);
                 o += 17 + (size_t)total;
             }
             break;
@@ -354,11 +364,54 @@ extern "C" int gitmi_jpeg_entropy_decode(const uint8_t* jpg, size_t n, void* out
             comp[c].lim[k] = (int16_t)(q ? kCoefLimit / (int)q : kCoefLimit);
         }
     }
-    if (info) {
-        info->width = width; info->height = height; info->ncomp = (uint32_t)ncomp;
-        info->h_samp = (uint32_t)comp[0].h; info->v_samp = (uint32_t)comp[0].v;
-        info->record_bytes = bytes;
+    P.ncomp = ncomp; P.restart = restart; P.width = width; P.height = height; P.scan = scan;
+    P.mcus_w = mcus_w; P.mcus_h = mcus_h; P.bytes = bytes;
+    return GITMI_JPEG_OK;
+}
+
+void fill_info(const Parsed& P, gitmi_jpeg_info* info) {
+    if (!info) return;
+    info->width = P.width; info->height = P.height; info->ncomp = (uint32_t)P.ncomp;
+    info->h_samp = (uint32_t)P.comp[0].h; info->v_samp = (uint32_t)P.comp[0].v;
+    info->record_bytes = P.bytes;
+}
+
+// the header of the coefficient record, complete
+void fill_header(Parsed& P) {
+    gitmi_jpeg_header& hdr = P.hdr;
+    hdr.magic = GITMI_JPEG_MAGIC;
+    hdr.header_bytes = GITMI_JPEG_HEADER_BYTES;
+    hdr.width = P.width; hdr.height = P.height; hdr.ncomp = (uint32_t)P.ncomp;
+    hdr.mcus_w = P.mcus_w; hdr.mcus_h = P.mcus_h;
+    hdr.restart_interval = (uint32_t)P.restart;
+    hdr.record_bytes = P.bytes;
+    for (int c = 0; c < P.ncomp; ++c) {
+        const Comp& k = P.comp[c];
+        hdr.comp[c].h_samp = (uint8_t)k.h; hdr.comp[c].v_samp = (uint8_t)k.v; hdr.comp[c].tq = (uint8_t)k.tq;
+        hdr.comp[c].blocks_w = k.blocks_w; hdr.comp[c].blocks_h = k.blocks_h;
+        hdr.comp[c].plane_offset = k.offset;
     }
+}
+
+}  // namespace
+
+extern "C" int gitmi_jpeg_abi_version(void) { return GITMI_JPEG_ABI_VERSION; }
+
+extern "C" int gitmi_jpeg_entropy_decode(const uint8_t* jpg, size_t n, void* out, size_t out_cap, gitmi_jpeg_info* info) {
+    if ((!jpg && n) || (!out && out_cap) || ((uintptr_t)out & 7)) return GITMI_JPEG_BAD_ARGUMENT;
+    if (info) memset(info, 0, sizeof(*info));
+    if (n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return GITMI_JPEG_UNSUPPORTED;
+
+    static_assert(sizeof(gitmi_jpeg_header) == GITMI_JPEG_HEADER_BYTES, "record header layout");
+    Parsed P;
+    if (parse_markers(jpg, n, P) != GITMI_JPEG_OK) return GITMI_JPEG_UNSUPPORTED;
+    Huff (&huff)[2][4] = P.huff;
+    Comp (&comp)[3] = P.comp;
+    const int ncomp = P.ncomp, restart = P.restart;
+    const uint8_t* scan = P.scan;
+    const uint32_t mcus_w = P.mcus_w, mcus_h = P.mcus_h;
+    const uint64_t bytes = P.bytes;
+    fill_info(P, info);
     if (bytes > out_cap) return GITMI_JPEG_NO_SPACE;
 
     uint8_t* rec = (uint8_t*)out;
@@ -393,17 +446,80 @@ extern "C" int gitmi_jpeg_entropy_decode(const uint8_t* jpg, size_t n, void* out
     const long long rem = b.cnt - b.pad;
     if (rem < 0 || rem >= 8 || b.end - b.p < 2 || b.p[0] != 0xFF || b.p[1] != 0xD9) return GITMI_JPEG_UNSUPPORTED;      // EOI
 
-    hdr.magic = GITMI_JPEG_MAGIC;
-    hdr.header_bytes = GITMI_JPEG_HEADER_BYTES;
-    hdr.width = width; hdr.height = height; hdr.ncomp = (uint32_t)ncomp;
-    hdr.mcus_w = mcus_w; hdr.mcus_h = mcus_h;
-    hdr.restart_interval = (uint32_t)restart;
-    hdr.record_bytes = bytes;
-    for (int c = 0; c < ncomp; ++c) {
-        hdr.comp[c].h_samp = (uint8_t)comp[c].h; hdr.comp[c].v_samp = (uint8_t)comp[c].v; hdr.comp[c].tq = (uint8_t)comp[c].tq;
-        hdr.comp[c].blocks_w = comp[c].blocks_w; hdr.comp[c].blocks_h = comp[c].blocks_h;
-        hdr.comp[c].plane_offset = comp[c].offset;
+    fill_header(P);
+    memcpy(rec, &P.hdr, sizeof(P.hdr));
+    return GITMI_JPEG_OK;
+}
+
+// The parse above, then the entropy-coded segment as it is: FF 00 -> FF, nothing decoded.  The segment must run to an EOI with
+// no other marker in it; restart intervals, which the GPU Huffman decode does not take, are declined here (and decoded by
+// gitmi_jpeg_entropy_decode).
+extern "C" int gitmi_jpeg_scan_prepare(const uint8_t* jpg, size_t n, void* out, size_t out_cap, gitmi_jpeg_info* info,
+                                       uint64_t* scan_record_bytes) {
+    if ((!jpg && n) || (!out && out_cap) || ((uintptr_t)out & 7)) return GITMI_JPEG_BAD_ARGUMENT;
+    if (info) memset(info, 0, sizeof(*info));
+    if (scan_record_bytes) *scan_record_bytes = 0;
+    if (n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return GITMI_JPEG_UNSUPPORTED;
+
+    static_assert(sizeof(gitmi_jpeg_scan) == GITMI_JPEG_SCAN_BYTES, "scan description layout");
+    static_assert(sizeof(gitmi_jpeg_dht) == 272, "scan description layout");
+    Parsed P;
+    if (parse_markers(jpg, n, P) != GITMI_JPEG_OK) return GITMI_JPEG_UNSUPPORTED;
+    if (P.restart != 0) return GITMI_JPEG_UNSUPPORTED;
+    uint32_t per_mcu = 0;
+    for (int c = 0; c < P.ncomp; ++c) {
+        if ((uint64_t)P.comp[c].blocks_w * P.comp[c].blocks_h > GITMI_JPEG_SCAN_MAX_BLOCKS) return GITMI_JPEG_UNSUPPORTED;
+        per_mcu += (uint32_t)(P.comp[c].h * P.comp[c].v);
     }
-    memcpy(rec, &hdr, sizeof(hdr));
+
+    // the length of the unstuffed segment: up to the first FF that no 00 follows, which must be the EOI
+    const uint8_t* const end = jpg + n;
+    const uint8_t* p = P.scan;
+    uint64_t stuffed = 0;
+    for (;;) {
+        p = (const uint8_t*)memchr(p, 0xFF, (size_t)(end - p));
+        if (!p || end - p < 2) return GITMI_JPEG_UNSUPPORTED;          // no EOI
+        if (p[1] == 0x00) { ++stuffed; p += 2; continue; }
+        if (p[1] != 0xD9) return GITMI_JPEG_UNSUPPORTED;              // RSTn, fill bytes, any other marker
+        break;
+    }
+    const uint64_t scan_bytes = (uint64_t)(p - P.scan) - stuffed;
+    if (scan_bytes >= GITMI_JPEG_SCAN_MAX_BYTES) return GITMI_JPEG_UNSUPPORTED;
+    const uint64_t at = GITMI_JPEG_HEADER_BYTES + GITMI_JPEG_SCAN_BYTES;
+    const uint64_t total = at + ((scan_bytes + 8 + 15) & ~(uint64_t)15);
+    fill_info(P, info);
+    if (scan_record_bytes) *scan_record_bytes = total;
+    if (total > out_cap) return GITMI_JPEG_NO_SPACE;
+
+    uint8_t* rec = (uint8_t*)out;
+    fill_header(P);
+    memcpy(rec, &P.hdr, sizeof(P.hdr));
+    gitmi_jpeg_scan sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.magic = GITMI_JPEG_SCAN_MAGIC;
+    sc.scan_struct_bytes = GITMI_JPEG_SCAN_BYTES;
+    sc.ncomp = (uint32_t)P.ncomp;
+    sc.blocks_per_mcu = per_mcu;
+    sc.total_blocks = P.mcus_w * P.mcus_h * per_mcu;
+    sc.scan_bytes = (uint32_t)scan_bytes;
+    sc.scan_offset = at;
+    sc.scan_record_bytes = total;
+    for (int c = 0; c < P.ncomp; ++c) {
+        sc.td[c] = (uint8_t)P.comp[c].td;
+        sc.ta[c] = (uint8_t)P.comp[c].ta;
+        sc.dc[P.comp[c].td] = P.dht[0][P.comp[c].td];
+        sc.ac[P.comp[c].ta] = P.dht[1][P.comp[c].ta];
+    }
+    memcpy(rec + GITMI_JPEG_HEADER_BYTES, &sc, sizeof(sc));
+    uint8_t* w = rec + at;
+    const uint8_t* s = P.scan;
+    while (s < p) {                                                   // runs between the FFs, each FF 00 pair as one FF
+        const uint8_t* f = (const uint8_t*)memchr(s, 0xFF, (size_t)(p - s));
+        const size_t run = (size_t)((f ? f + 1 : p) - s);
+        memcpy(w, s, run);
+        w += run;
+        s += run + (f ? 1 : 0);
+    }
+    memset(w, 0, (size_t)(rec + total - w));
     return GITMI_JPEG_OK;
 }

@@ -1,6 +1,7 @@
 // Entry points of libgitmi_jpeg.so (include/gitmi_jpeg.h): argument checks on the host, then the two launches of
-// kernels_jpeg.hip per JPEG_CHUNK images.  Independent of libgitmi*.so.
+// kernels_jpeg.hip (reconstruction) or the four of kernels_jpeg_entropy.hip (Huffman decode) per JPEG_CHUNK images.  Independent of libgitmi*.so.
 #include "jpeg_common.h"
+#include "jpeg_entropy_dev.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -60,5 +61,51 @@ extern "C" int gitmi_jpeg_reconstruct_batch(const uint8_t* coef, size_t coef_byt
     if (used > tmp_bytes) return fail("jpeg_reconstruct_batch: workspace must hold %zu bytes", used);
     const hipError_t e = launch_jpeg_reconstruct(coef, coef_bytes, imgs.data(), n, tmp, rgb_out, (hipStream_t)stream);
     if (e != hipSuccess) return fail("jpeg_reconstruct_batch: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gitmi_jpeg_entropy_constant(int which) {
+    return which == 0 ? JD_SUB_BITS : which == 1 ? JD_THREADS : which == 2 ? 1 : 0;       // a thread walks subsequences tid, tid + JD_THREADS, ...: one per pass
+}
+
+extern "C" size_t gitmi_jpeg_entropy_workspace_bytes(const int64_t* scan_desc_host, int n) {
+    size_t need = 0;
+    for (int i = 0; scan_desc_host && i < n; ++i) {
+        const int64_t bytes = scan_desc_host[2 * i + 1];
+        if (bytes < 0) return 0;
+        need += (size_t)jd_workspace_bytes(jd_nsub_bound((uint64_t)bytes));
+    }
+    return need;
+}
+
+extern "C" int gitmi_jpeg_entropy_batch(const uint8_t* scans, size_t scans_bytes, const int64_t* scan_desc_host, int n, uint8_t* coef_out,
+                                        size_t coef_bytes, const int64_t* coef_desc_host, int32_t* status, uint8_t* tmp, size_t tmp_bytes,
+                                        void* stream) {
+    if (!scans || !scan_desc_host || !coef_out || !coef_desc_host || !status || !tmp || n < 1) return fail("jpeg_entropy_batch: bad argument");
+    if (((uintptr_t)scans & 127) || ((uintptr_t)coef_out & 127) || ((uintptr_t)tmp & 127) || ((uintptr_t)status & 3))
+        return fail("jpeg_entropy_batch: scans, coef_out and tmp must be 128-byte aligned, status 4-byte aligned");
+    std::vector<JpegScanImg> imgs((size_t)n);
+    size_t used = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t off = scan_desc_host[2 * i], bytes = scan_desc_host[2 * i + 1];
+        const int64_t coff = coef_desc_host[2 * i], cbytes = coef_desc_host[2 * i + 1];
+        if (off < 0 || (off & 127) || bytes < (int64_t)(JD_SCAN_AT + 8) || (uint64_t)off > scans_bytes || scans_bytes - (uint64_t)off < (uint64_t)bytes)
+            return fail("jpeg_entropy_batch: scan record %d (offset %lld, %lld bytes) does not lie 128-byte aligned inside the %zu scan bytes",
+                        i, (long long)off, (long long)bytes, scans_bytes);
+        if (coff < 0 || (coff & 127) || cbytes < GITMI_JPEG_HEADER_BYTES || (cbytes & 127) || (uint64_t)coff > coef_bytes ||
+            coef_bytes - (uint64_t)coff < (uint64_t)cbytes)
+            return fail("jpeg_entropy_batch: coefficient record %d (offset %lld, %lld bytes) does not lie 128-byte aligned inside the %zu "
+                        "output bytes", i, (long long)coff, (long long)cbytes, coef_bytes);
+        imgs[i].scan_off = (unsigned long long)off;
+        imgs[i].scan_size = (unsigned long long)bytes;
+        imgs[i].coef_off = (unsigned long long)coff;
+        imgs[i].coef_size = (unsigned long long)cbytes;
+        imgs[i].tmp_off = used;
+        imgs[i].nsub_cap = jd_nsub_bound((uint64_t)bytes);
+        used += (size_t)jd_workspace_bytes(imgs[i].nsub_cap);
+    }
+    if (used > tmp_bytes) return fail("jpeg_entropy_batch: workspace must hold %zu bytes", used);
+    const hipError_t e = launch_jpeg_entropy(scans, imgs.data(), n, coef_out, status, tmp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail("jpeg_entropy_batch: %s", hipGetErrorString(e));
     return 0;
 }

@@ -19,6 +19,10 @@ jpeg="gpu" (opt-in; the default "host" is the protocol above, unchanged): a work
 record in the slot; the parent uploads it and the GPU reconstructs the pixels (gitmi_jpeg_reconstruct_batch).  Every slot then
 begins with a SLOT_HEADER that says which of the two it holds: the worker falls back to Pillow RGB in the same slot when the
 stream is not one the fast path takes, the row is not a JPEG, the record does not fit the slot, or the library is missing.
+
+jpeg="gpu_entropy" (opt-in): a worker only parses the markers and removes the FF 00 stuffing (jpeg.scan_prepare_into) and leaves
+a SCAN record (SLOT_SCAN) whose Huffman decode the GPU runs too (gitmi_jpeg_entropy_batch).  What scan_prepare alone declines
+(restart intervals, ...) gets the entropy decode above (SLOT_COEF); what that declines gets Pillow (SLOT_RGB).
 """
 from __future__ import annotations
 
@@ -52,10 +56,10 @@ TASK = struct.Struct("<qq")                       # (slot, row); slot < 0: stop
 RESULT_BYTES = 256
 RESULT_HEAD = struct.Struct("<qqiii")             # slot, row, H, W, length of the key (or of an error text when H == W == 0)
 KEY_MAX = RESULT_BYTES - RESULT_HEAD.size
-# jpeg="gpu" only: the first SLOT_HEADER_BYTES of a slot = (kind, 0, payload bytes); the payload follows the header
+# jpeg="gpu" / "gpu_entropy" only: the first SLOT_HEADER_BYTES of a slot = (kind, 0, payload bytes); the payload follows the header
 SLOT_HEADER = struct.Struct("<IIQ")
 SLOT_HEADER_BYTES = 128
-SLOT_RGB, SLOT_COEF = 0, 1
+SLOT_RGB, SLOT_COEF, SLOT_SCAN = 0, 1, 2
 
 
 def _read_exact(fd: int, n: int) -> bytes:
@@ -76,8 +80,8 @@ def worker_main(tsv_path: str, shm_path: str, shm_size: int, slot_bytes: int, ta
     mem = _map_shared(shm_path, shm_size)
     offsets = _offsets_of(tsv_path)
     fp = open(tsv_path, "rb")
-    if jpeg == "gpu":
-        _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes, task_fd, result_fd)
+    if jpeg in ("gpu", "gpu_entropy"):
+        _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes, task_fd, result_fd, scan=jpeg == "gpu_entropy")
         fp.close()
         return
 
@@ -111,8 +115,9 @@ def worker_main(tsv_path: str, shm_path: str, shm_size: int, slot_bytes: int, ta
     fp.close()
 
 
-def _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes: int, task_fd: int, result_fd: int) -> None:
-    """worker_main's loop for jpeg="gpu": coefficient record or Pillow RGB behind a SLOT_HEADER."""
+def _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes: int, task_fd: int, result_fd: int, scan: bool = False) -> None:
+    """worker_main's loop for jpeg="gpu": coefficient record or Pillow RGB behind a SLOT_HEADER; scan (jpeg="gpu_entropy"): a
+    scan record first."""
     import ctypes
     try:                                                        # once per worker; without the library: the Pillow path
         from . import jpeg as J
@@ -141,6 +146,12 @@ def _worker_loop_gpu_jpeg(Image, mem, offsets, fp, slot_bytes: int, task_fd: int
             if len(key) > KEY_MAX:
                 key = b""
             at = slot * slot_bytes
+            if scan and J is not None and raw[:2] == b"\xff\xd8":
+                rc, info, need = J.scan_prepare_into(raw, base + at + SLOT_HEADER_BYTES, room)
+                if rc == J.OK:
+                    SLOT_HEADER.pack_into(mem, at, SLOT_SCAN, 0, need)
+                    reply(slot, row, info.height, info.width, key)
+                    continue
             if J is not None and raw[:2] == b"\xff\xd8":
                 rc, info = J.entropy_decode_into(raw, base + at + SLOT_HEADER_BYTES, room)
                 if rc == J.OK:
@@ -172,8 +183,8 @@ class DecodePool:
     def __init__(self, tsv_path: str, workers: int, slots: int, slot_bytes: int = 1 << 20, jpeg: str = "host"):
         import subprocess
         import sys
-        if jpeg not in ("host", "gpu"):
-            raise ValueError("DecodePool: jpeg must be 'host' or 'gpu', got %r" % (jpeg,))
+        if jpeg not in ("host", "gpu", "gpu_entropy"):
+            raise ValueError("DecodePool: jpeg must be 'host', 'gpu' or 'gpu_entropy', got %r" % (jpeg,))
         self.jpeg = jpeg
         if not os.path.isfile(os.path.splitext(tsv_path)[0] + ".lineidx.8b"):
             from .tsv_io import build_lineidx
@@ -201,8 +212,8 @@ class DecodePool:
         task_r = [r for r, _ in task_pipes]
         cmd = [sys.executable, "-m", "generativeimage2text_amd.decode_pool", tsv_path, self.path, str(size), str(self.slot_bytes),
                str(result_w)] + [str(fd) for fd in task_r]
-        if jpeg == "gpu":
-            cmd.insert(3, "--jpeg-gpu")
+        if jpeg != "host":
+            cmd.insert(3, "--jpeg-gpu" if jpeg == "gpu" else "--jpeg-gpu-entropy")
         self.procs = [subprocess.Popen(cmd, env=env, pass_fds=tuple(task_r) + (result_w,), stdin=subprocess.DEVNULL)]
         for fd in task_r:
             os.close(fd)
@@ -230,7 +241,7 @@ class DecodePool:
         return slot, row, text, h, w
 
     def slot_payload(self, slot: int) -> Tuple[int, np.ndarray]:
-        """jpeg="gpu": (SLOT_RGB or SLOT_COEF, the payload bytes of the slot -- a view of the staging buffer)"""
+        """jpeg="gpu" / "gpu_entropy": (SLOT_RGB, SLOT_COEF or SLOT_SCAN, the payload bytes of the slot -- a view of the staging buffer)"""
         at = slot * self.slot_bytes
         kind, _, n = SLOT_HEADER.unpack_from(self.buffer, at)
         return kind, self.buffer[at + SLOT_HEADER_BYTES: at + SLOT_HEADER_BYTES + n]
@@ -273,8 +284,8 @@ if __name__ == "__main__":
     from PIL import Image  # noqa: F401  (imported once here; the forked workers share it)
     _a = sys.argv[1:]
     _jpeg = "host"
-    if _a[0] == "--jpeg-gpu":
-        _jpeg, _a = "gpu", _a[1:]
+    if _a[0] in ("--jpeg-gpu", "--jpeg-gpu-entropy"):
+        _jpeg, _a = ("gpu" if _a[0] == "--jpeg-gpu" else "gpu_entropy"), _a[1:]
     _result_fd, _task_fds = int(_a[4]), [int(v) for v in _a[5:]]
     _kids = []
     for _i, _fd in enumerate(_task_fds):
@@ -284,8 +295,8 @@ if __name__ == "__main__":
                 if _other != _fd:
                     os.close(_other)
             try:
-                if _jpeg == "gpu":
-                    worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd, jpeg="gpu")
+                if _jpeg != "host":
+                    worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd, jpeg=_jpeg)
                 else:
                     worker_main(_a[0], _a[1], int(_a[2]), int(_a[3]), _fd, _result_fd)
             finally:

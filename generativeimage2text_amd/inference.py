@@ -19,7 +19,7 @@ Differences forced by the environment, not by design:
     shared libraries): GIT_VOCAB (vocabulary file or "ids"), GIT_DECODE_THREADS / GIT_DECODE_PROCS / GIT_DECODE_SLOT_MB (host JPEG decoding of the TSV task: threads of the
     per-image path, worker processes and slot size of the pooled captioning path), GIT_DECODE_JPEG ("gpu": the pooled path's
     workers run only the entropy decode of a JPEG and the GPU reconstructs the pixels, bit for bit Pillow's; same as
-    gpu_jpeg=True; anything else: Pillow decodes on the host, the default), the
+    gpu_jpeg=True; "gpu_entropy": the Huffman decode runs on the GPU too, same as gpu_jpeg="entropy"; anything else: Pillow decodes on the host, the default), the
     launcher's RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* (and OMPI_COMM_WORLD_*).
 """
 from __future__ import annotations
@@ -531,7 +531,7 @@ def run_tsv_inference(image_tsv: str, question_tsv: Optional[str], out_tsv: str,
 
 
 def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int, procs: int, crop: int, in_flight: int,
-                           slot_bytes: int = 2 << 20, stats: Optional[dict] = None, gpu_jpeg: bool = False):
+                           slot_bytes: int = 2 << 20, stats: Optional[dict] = None, gpu_jpeg=False):
     """The host side of the captioning task at the engine's rate: rows [start, end) of `image_tsv` as (keys, fp32 batch
     [n, 3, crop, crop] on the device) in input order.  `procs` worker processes decode straight into a shared staging buffer
     (decode_pool.DecodePool), `in_flight + 2` batches of slots deep; a finished batch is uploaded image by image into ONE
@@ -539,9 +539,12 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
     bit-identical to load_image_by_pil + gpu_image_transform per image.
     gpu_jpeg: the workers leave coefficient records of the JPEGs the fast path takes (DecodePool(jpeg="gpu")); those are
     uploaded as they are and reconstructed on the device straight into the buffer the transform reads
-    (jpeg.decode_batch_to, one launch pair per 64 images); Pillow RGB slots are uploaded into the same buffer as before."""
+    (jpeg.decode_batch_to, one launch pair per 64 images); Pillow RGB slots are uploaded into the same buffer as before.
+    gpu_jpeg="entropy": the workers leave SCAN records (DecodePool(jpeg="gpu_entropy")) where they can; those are uploaded and
+    Huffman-decoded on the device (jpeg.entropy_batch_to) into the coefficient buffer the other records are uploaded to.  The
+    status words of a batch are copied back and waited for once; an image whose word is not 0 is decoded here with Pillow."""
     import time
-    from .decode_pool import DecodePool, SLOT_COEF, SLOT_HEADER_BYTES
+    from .decode_pool import DecodePool, SLOT_COEF, SLOT_SCAN, SLOT_HEADER_BYTES
     from .engine import preprocess_batch
     if gpu_jpeg:
         from . import jpeg as J
@@ -549,7 +552,9 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
     n_rows = end - start
     n_batches = (n_rows + batch_size - 1) // batch_size
     t_pool = time.perf_counter()
-    pool = DecodePool(image_tsv, procs, slots=ring * batch_size, slot_bytes=slot_bytes, **({"jpeg": "gpu"} if gpu_jpeg else {}))
+    entropy = gpu_jpeg == "entropy"
+    pool = DecodePool(image_tsv, procs, slots=ring * batch_size, slot_bytes=slot_bytes,
+                      **({"jpeg": "gpu_entropy" if entropy else "gpu"} if gpu_jpeg else {}))
     host = torch.from_numpy(pool.buffer)
     pinned = False
     try:                                            # page-lock the staging buffer: uploads become asynchronous DMA
@@ -561,6 +566,8 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
                      pool_start_s=time.perf_counter() - t_pool, t_pool_started=time.perf_counter())
         if gpu_jpeg:
             stats.update(jpeg_gpu=0, jpeg_fallback=0)
+        if entropy:
+            stats.update(jpeg_entropy_gpu=0, jpeg_entropy_rejected=0, jpeg_entropy_host=0, status_wait_s=0.0)
     tsv = None
     try:
         meta = {}                                   # batch -> {position: (key, H, W)}
@@ -602,6 +609,7 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
             dev = torch.empty(offs[-1], dtype=torch.uint8, device="cuda")
             desc = []
             coef_items = []                         # gpu_jpeg: (position, payload view) of the slots that hold coefficients
+            scan_items = []                         # gpu_jpeg="entropy": the same of the slots that hold scan records
             for j, (key, h, w, slot) in enumerate(items):
                 if gpu_jpeg and h >= 0:
                     kind, payload = pool.slot_payload(slot)
@@ -609,6 +617,8 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
                     payload = host[at: at + payload.size]           # the same bytes as a view of the (page-locked) staging tensor
                     if kind == SLOT_COEF:
                         coef_items.append((j, payload))
+                    elif kind == SLOT_SCAN:
+                        scan_items.append((j, payload))
                     else:
                         dev[offs[j]: offs[j] + sizes[j]].copy_(payload, non_blocking=True)
                     desc.append((offs[j], h, w))
@@ -622,17 +632,49 @@ def pooled_caption_batches(image_tsv: str, start: int, end: int, batch_size: int
                 else:
                     dev[offs[j]: offs[j] + sizes[j]].copy_(host[slot * slot_bytes: slot * slot_bytes + sizes[j]], non_blocking=True)
                 desc.append((offs[j], h, w))
-            if coef_items:
+            n_host_coef = len(coef_items)
+            if coef_items or scan_items:
+                # one coefficient buffer: the uploaded records first, then room for those the device decodes from the scans
+                csizes = [payload.numel() for _, payload in coef_items] + [J.scan_coef_bytes(payload.numpy()) for _, payload in scan_items]
                 coffs = [0]
-                for _, payload in coef_items:
-                    coffs.append(coffs[-1] + (payload.numel() + 127) // 128 * 128)
+                for n in csizes:
+                    coffs.append(coffs[-1] + (n + 127) // 128 * 128)
                 cbuf = torch.empty(coffs[-1], dtype=torch.uint8, device="cuda")
                 for (_, payload), o in zip(coef_items, coffs):
                     cbuf[o: o + payload.numel()].copy_(payload, non_blocking=True)
+            if scan_items:
+                soffs = [0]
+                for _, payload in scan_items:
+                    soffs.append(soffs[-1] + (payload.numel() + 127) // 128 * 128)
+                sbuf = torch.empty(soffs[-1], dtype=torch.uint8, device="cuda")
+                for (_, payload), o in zip(scan_items, soffs):
+                    sbuf[o: o + payload.numel()].copy_(payload, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             uploaded[b % ring] = ev
             t_c = time.perf_counter()
+            if scan_items:
+                status = torch.empty(len(scan_items), dtype=torch.int32, device="cuda")
+                J.entropy_batch_to(cbuf, list(zip(coffs[n_host_coef:-1], csizes[n_host_coef:])), sbuf,
+                                   [(o, payload.numel()) for (_, payload), o in zip(scan_items, soffs)], status)
+                t_w = time.perf_counter()
+                verdicts = status.tolist()          # the one wait of the batch
+                if stats is not None:
+                    stats["status_wait_s"] += time.perf_counter() - t_w
+                for (j, _), o, v in zip(scan_items, coffs[n_host_coef:-1], verdicts):
+                    if v == 0:
+                        coef_items.append((j, None))
+                        continue
+                    if tsv is None:                 # an anomaly in the Huffman data: Pillow judges the file, as on the other paths
+                        tsv = TSVFile(image_tsv)
+                    arr = decode_to_array(base64.b64decode(tsv[start + b * batch_size + j][1]))
+                    assert arr.shape[0] * arr.shape[1] * 3 == sizes[j], "row %d: Pillow and the frame header disagree" % (start + b * batch_size + j)
+                    dev[offs[j]: offs[j] + sizes[j]].copy_(torch.from_numpy(arr).reshape(-1), non_blocking=False)
+                coffs = coffs[:n_host_coef] + [o for o, v in zip(coffs[n_host_coef:-1], verdicts) if v == 0] + [coffs[-1]]
+                if stats is not None:
+                    stats["jpeg_entropy_gpu"] += sum(1 for v in verdicts if v == 0)
+                    stats["jpeg_entropy_rejected"] += sum(1 for v in verdicts if v != 0)
+                    stats["jpeg_entropy_host"] += n_host_coef
             if coef_items:
                 J.decode_batch_to(dev, [desc[j] for j, _ in coef_items], cbuf, coffs[:-1])
             if gpu_jpeg and stats is not None:
@@ -684,10 +726,16 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
     gpu_jpeg (or GIT_DECODE_JPEG=gpu): on the pooled captioning path the worker processes run only the entropy decode of a
     JPEG and the GPU reconstructs the pixels (include/gitmi_jpeg.h) -- the same bytes Pillow returns, hence the same token ids;
     rows the fast path does not take (progressive, CMYK, PNG, ...) are decoded by Pillow as before.  stats["jpeg_gpu"] /
-    stats["jpeg_fallback"] count the two.  Raises when libgitmi_jpeg*.so have not been built.  The per-image paths (VQA, aspect-
+    stats["jpeg_fallback"] count the two.  gpu_jpeg="entropy" (or GIT_DECODE_JPEG=gpu_entropy): the Huffman decode runs on the GPU
+    too -- the workers only parse the markers and unstuff the scan; restart-interval streams keep the host Huffman decode, and an
+    image whose scan the GPU finds an anomaly in is decoded by Pillow here.  stats["jpeg_entropy_gpu"] / ["jpeg_entropy_rejected"]
+    / ["jpeg_entropy_host"] count those three; jpeg_gpu then counts every image reconstructed on the GPU.  Raises when libgitmi_jpeg*.so have not been built.  The per-image paths (VQA, aspect-
     preserving models, GIT_DECODE_PROCS=0) decode with Pillow either way."""
     import time
-    gpu_jpeg = bool(gpu_jpeg) or os.environ.get("GIT_DECODE_JPEG", "") == "gpu"
+    if gpu_jpeg == "entropy" or (not gpu_jpeg and os.environ.get("GIT_DECODE_JPEG", "") == "gpu_entropy"):
+        gpu_jpeg = "entropy"
+    else:
+        gpu_jpeg = bool(gpu_jpeg) or os.environ.get("GIT_DECODE_JPEG", "") == "gpu"
     if gpu_jpeg:                                # fail here, not in a worker: a missing library is an error, never a quiet fallback
         from . import jpeg as _jpeg
         _jpeg.load_host_library()
@@ -771,7 +819,7 @@ def test_git_inference_single_tsv(image_tsv, model_name, question_tsv, out_tsv, 
         slot = int(os.environ.get("GIT_DECODE_SLOT_MB", "2")) << 20
         batch_source = lambda s_, e_: pooled_caption_batches(image_tsv, s_, e_, batch_size, procs, crop,
                                                              contexts if pipelined else 1, slot_bytes=slot, stats=stats,
-                                                             **({"gpu_jpeg": True} if gpu_jpeg else {}))
+                                                             **({"gpu_jpeg": gpu_jpeg} if gpu_jpeg else {}))
     t_run = time.perf_counter()
     # decode on the pool all the way to the uint8 array the GPU transform uploads (stand-in models of the CPU tests keep PIL images)
     decode = decode_to_array if hasattr(model, "engine") else load_image_by_pil

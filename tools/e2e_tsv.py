@@ -58,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--contexts", type=int, default=4)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--check-rows", type=int, default=64, help="rows compared with the serial one-image-per-call path")
+    ap.add_argument("--jpeg", default="host", help="GIT_DECODE_JPEG settings of the pooled path, e.g. host,gpu,gpu_entropy: every "
+                                                   "worker count is run with each, interleaved")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     os.environ["GIT_VOCAB"] = "ids"
@@ -88,22 +90,27 @@ def main(argv=None):
 
     runs = []
     out_first = None
-    settings = [("procs", int(t)) for t in args.procs.split(",") if t] + [("threads", int(t)) for t in args.threads.split(",") if t]
-    for kind, n in settings:
+    modes = [m for m in args.jpeg.split(",") if m]
+    settings = [("procs", int(t), m) for t in args.procs.split(",") if t for m in modes] + \
+               [("threads", int(t), "host") for t in args.threads.split(",") if t]
+    for kind, n, mode in settings:
+        os.environ["GIT_DECODE_JPEG"] = mode
         os.environ["GIT_DECODE_PROCS"] = str(n) if kind == "procs" else "0"
         os.environ["GIT_DECODE_THREADS"] = str(n) if kind == "threads" else "16"
         st = {}
-        out = os.path.join(tmp, "out_%s_%d.tsv" % (kind, n))
+        out = os.path.join(tmp, "out_%s_%d_%s.tsv" % (kind, n, mode))
         I.test_git_inference_single_tsv(in_tsv, "GIT_BASE", None, out, checkpoint=weights, batch_size=args.batch,
                                         precision=args.precision, contexts=args.contexts, stats=st)
         runs.append({"host_path": "worker processes + batched GPU transform" if kind == "procs" else "thread pool + per-image GPU transform",
-                     kind: n, "captions_per_s": round(st["images"] / st["run_s"], 1), "run_s": round(st["run_s"], 3),
+                     kind: n, "jpeg": mode, "captions_per_s": round(st["images"] / st["run_s"], 1), "run_s": round(st["run_s"], 3),
                      "build_s": round(st["build_s"], 2), "batches": st["batches"], "staging_pinned": st.get("staging_pinned"),
                      "steady_captions_per_s": round(st["steady_captions_per_s"], 1) if "steady_captions_per_s" in st else None,
                      "parent_s": {k: round(st[k], 3) for k in ("pool_start_s", "first_batch_ready_s", "wait_decode_s", "upload_s",
-                                                                "transform_s", "submit_s", "result_s", "device_wait_s") if k in st}})
-        print("%s %3d: %.1f captions/s end to end (%.2f s for %d rows; steady state %s)" % (
-            kind, n, runs[-1]["captions_per_s"], st["run_s"], st["images"], runs[-1]["steady_captions_per_s"]), file=sys.stderr, flush=True)
+                                                                "transform_s", "status_wait_s", "submit_s", "result_s", "device_wait_s",
+                                                                "jpeg_gpu", "jpeg_fallback", "jpeg_entropy_gpu", "jpeg_entropy_rejected",
+                                                                "jpeg_entropy_host") if k in st}})
+        print("%s %3d jpeg=%s: %.1f captions/s end to end (%.2f s for %d rows; steady state %s)" % (
+            kind, n, mode, runs[-1]["captions_per_s"], st["run_s"], st["images"], runs[-1]["steady_captions_per_s"]), file=sys.stderr, flush=True)
         got = [r for r in tsv_io.tsv_reader(out)]
         assert [r[0] for r in got] == [r[0] for r in rows], "row order"
         if out_first is None:

@@ -7,6 +7,10 @@ against the jpeg="gpu" body
 
     base64 -> entropy decode (libgitmi_jpeg_host.so) straight into the slot
 
+and the jpeg="gpu_entropy" body
+
+    base64 -> scan_prepare (marker parse + FF 00 removal) straight into the slot
+
 on 640x480 JPEGs written by Pillow from synthetic content with photographic statistics (smooth + texture + noise), at
 quality 75 / 85 / 95, 4:2:0 and 4:4:4.  One JSON line; --out writes it to a file as well (profiles/).
 
@@ -58,8 +62,13 @@ def main(argv=None):
                     rc, _ = J.entropy_decode_into(base64.b64decode(b64), slot.ctypes.data, slot.size)
                     assert rc == J.OK
 
+            def scan_body():
+                for b64 in rows:
+                    rc, _, _ = J.scan_prepare_into(base64.b64decode(b64), slot.ctypes.data, slot.size)
+                    assert rc == J.OK
+
             best = {}
-            for name, body in (("pillow", pillow_body), ("entropy", entropy_body)):
+            for name, body in (("pillow", pillow_body), ("entropy", entropy_body), ("scan", scan_body)):
                 body()                                        # warm-up
                 ts = []
                 for _ in range(args.repeats):
@@ -69,11 +78,13 @@ def main(argv=None):
                 best[name] = min(ts)
             sets.append({"subsampling": sub_name, "quality": q, "jpeg_kb": round(sum(len(r) for r in raws) * 3 / 4 / len(raws) / 1024, 1),
                          "pillow_body_us": round(best["pillow"], 1), "entropy_body_us": round(best["entropy"], 1),
-                         "ratio": round(best["pillow"] / best["entropy"], 2)})
-            print("%s q%d: Pillow body %.0f us, entropy body %.0f us, ratio %.2f" % (
-                sub_name, q, best["pillow"], best["entropy"], best["pillow"] / best["entropy"]), file=sys.stderr, flush=True)
+                         "ratio": round(best["pillow"] / best["entropy"], 2), "scan_body_us": round(best["scan"], 1),
+                         "scan_record_kb": round(sum(J.scan_prepare_into(base64.b64decode(r), None, 0)[2] for r in raws) / len(raws) / 1024, 1)})
+            print("%s q%d: Pillow body %.0f us, entropy body %.0f us, ratio %.2f, scan body %.0f us" % (
+                sub_name, q, best["pillow"], best["entropy"], best["pillow"] / best["entropy"], best["scan"]), file=sys.stderr, flush=True)
     res = {"what": "host microseconds per 640x480 image of one decode-pool worker body, one thread: default (base64 -> Pillow RGB -> "
-                   "tobytes -> slot copy) vs jpeg='gpu' (base64 -> entropy decode into the slot)",
+                   "tobytes -> slot copy) vs jpeg='gpu' (base64 -> entropy decode into the slot) vs jpeg='gpu_entropy' (base64 -> "
+                   "scan_prepare into the slot)",
            "images": args.images, "distinct": args.distinct, "pillow": Image.__version__, "libjpeg_turbo": features.version("libjpeg_turbo"),
            "sets": sets}
     line = json.dumps(res)
