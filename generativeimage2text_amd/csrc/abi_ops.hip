@@ -508,6 +508,35 @@ GITMI_EXP_EXPORT int gitmi_debug_score_attn_map(const void* qkv, const void* img
     hipFree(ctx); hipFree(stats);
     return rc;
 }
+// tree attention of one layer (GITMI_SEARCH_TREE_SCORE): score_attn's operands with the rows of every "sentence" the nodes of a
+// tree -- packed int64 [Q][Lp] DEVICE (depth << 32 | token), lens int32 [Q] DEVICE node counts, max_depth the depth bound -- and
+// ntok as in score_attn_map: the structure launch, then the attention launch with its end[] table.  bad_out int32 [Q] DEVICE
+// (or NULL) = the structure verdicts.  Synchronises the stream.
+GITMI_EXP_EXPORT int gitmi_debug_score_attn_tree(const void* qkv, const void* img_kv, const int* image_of, const int* ntok,
+                                                 const int64_t* packed, const int* lens, int max_depth, void* out, int* bad_out,
+                                                 int Q, int H, int N_img, int Lp, int dtype, void* stream) {
+    if (!qkv || !img_kv || !image_of || !packed || !lens || !out || Q < 1 || H < 1 || N_img < 1 || Lp < 1 || max_depth < 1)
+        return fail("debug_score_attn_tree: bad argument");
+    if (dtype != GITMI_DTYPE_F32 && dtype != gitmi_operand_dtype()) return fail("debug_score_attn_tree: dtype %d not served by this build", dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)Q * Lp;
+    int* tab = nullptr;
+    auto body = [&]() -> int {
+        HIPCK(hipMalloc(&tab, (4 * M + Q) * sizeof(int)));
+        const TreeNodes nd{tab, tab + M, tab + 2 * M, tab + 3 * M};
+        int* bad = tab + 4 * M;
+        HIPCK(hipMemsetAsync(bad, 0, (size_t)Q * sizeof(int), s));
+        HIPCK(launch_tree_structure((const long long*)packed, Lp, Q, Lp, lens, 1 << 30, max_depth, nd, bad, s));
+        HIPCK(launch_score_attn(qkv, img_kv, image_of, out, Q, H, H * 64, N_img, Lp, 0.125f, dtype == GITMI_DTYPE_F32, s, ntok, nullptr,
+                                nd.end));
+        if (bad_out) HIPCK(hipMemcpyAsync(bad_out, bad, (size_t)Q * sizeof(int), hipMemcpyDefault, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(tab);
+    return rc;
+}
 // head + combine: logits z = A [M][K] W [V][K]^T + bias (never stored in the 16-bit form) -> out fp32 [M][2] =
 // (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) for rows with tgt[m] >= 0, 0 elsewhere.  Synchronises the stream.
 GITMI_EXP_EXPORT int gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K,

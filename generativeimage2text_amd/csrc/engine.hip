@@ -890,6 +890,7 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("%s: GITMI_SEARCH_SCORE is not a search (gitmi_generate_prefixed scores sentences)", who);
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("%s: GITMI_SEARCH_ATTEND is not a search (gitmi_generate_prefixed returns the attention maps of sentences)", who);
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("%s: GITMI_SEARCH_CONTEXT is not a search (gitmi_generate_prefixed puts context tokens into the decoder memory)", who);
+    if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("%s: GITMI_SEARCH_TREE_SCORE is not a search (gitmi_generate_prefixed scores token trees)", who);
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1198,6 +1199,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp && sp->kind == GITMI_SEARCH_SCORE) return fail("generate: GITMI_SEARCH_SCORE scores given sentences: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("generate: GITMI_SEARCH_ATTEND maps given sentences: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("generate: GITMI_SEARCH_CONTEXT takes context segments: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("generate: GITMI_SEARCH_TREE_SCORE scores given token trees: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1214,17 +1216,28 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
 }
 
 // ---- caption scoring (GITMI_SEARCH_SCORE) -------------------------------------------------------------------------
+// Token trees (GITMI_SEARCH_TREE_SCORE, include/gitmi.h): depths are embedding positions and index the root path of the structure walk
+static int tree_max_depth(const gitmi_config& c) { return std::min((int)c.max_text_len, (int)c.max_pos); }
+// Rows (trees x padded nodes) of one tree call.  Every row count, row index and launch grid of the pass is an int and byte offsets
+// are size_t, so the binding widths are grid dimensions: the attention's grid.z = padded nodes of a tree / 64 <= 65535 and the
+// head's grid.y = rows / 128 <= 65535.  The former, for one tree that has all the rows, is the smaller and is the cap.
+constexpr int TREE_MAX_ROWS = 65535 * 64;
 static void score_free(gitmi_engine* e) {
     for (void* p : e->sc_allocs) hipFree(p);
     e->sc_allocs.clear();
     e->sc_rows = 0;
+    e->tr_out_n = 0;
 }
 // Workspaces of a score call with `rows` text rows (Q x Lp): allocated by the first score call and grown when a later call
 // needs more rows, so an engine that never scores keeps its footprint and one that scores short sentences pays for those.
 // Per-sentence buffers are sized for the capacity (max_batch x max_beams sentences x max_text_len; a few hundred KiB).
-static int score_alloc(gitmi_engine* e, size_t rows_needed) {
-    const size_t rows = (size_t)round_up((int)rows_needed, 128);    // the head's 128-row tiles (its loads clamp to M - 1)
-    if (e->sc_rows >= rows) return 0;
+// tree_out > 0 (GITMI_SEARCH_TREE_SCORE): also the node tables of the rows and an output of tree_out (tree, node) elements,
+// kept by later growth; engines that never score trees never hold them.
+static int score_alloc(gitmi_engine* e, size_t rows_needed, size_t tree_out = 0) {
+    size_t rows = (size_t)round_up((int)rows_needed, 128);          // the head's 128-row tiles (its loads clamp to M - 1)
+    if (e->sc_rows >= rows && e->tr_out_n >= tree_out) return 0;
+    rows = std::max(rows, e->sc_rows);
+    tree_out = std::max(tree_out, e->tr_out_n);
     score_free(e);
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden;
@@ -1243,13 +1256,15 @@ static int score_alloc(gitmi_engine* e, size_t rows_needed) {
                     alloc(&e->sc_part, rows * (size_t)(e->pol.f32 ? 1 : score_head_tiles(c.vocab)) * sizeof(float4)) &&
                     alloc(&e->sc_zt, rows * 4) && alloc(&e->sc_tgt, rows * 4) && alloc(&e->sc_lens, Qmax * 4) &&
                     alloc(&e->sc_img, Qmax * 4) && alloc(&e->sc_bad, Qmax * 4) && alloc(&e->sc_info, 16) &&
-                    alloc(&e->sc_out, Qmax * (size_t)c.max_text_len * sizeof(float2));
+                    alloc(&e->sc_out, Qmax * (size_t)c.max_text_len * sizeof(float2)) &&
+                    (!tree_out || (alloc(&e->tr_nodes, rows * 4 * sizeof(int)) && alloc(&e->tr_out, tree_out * sizeof(float2))));
     if (!ok) {
         score_free(e);
         (void)hipGetLastError();
         return fail("score: out of device memory for the workspaces of %zu text rows", rows);
     }
     e->sc_rows = rows;
+    e->tr_out_n = tree_out;
     return 0;
 }
 
@@ -1284,7 +1299,8 @@ static int call_Nimg(const gitmi_engine* e, const float* const* frames, int F) {
 }
 
 // vocabulary head of the score pass over the M text rows in sc_ht, reduced to per-row statistics: sc_part [M][*ntiles], sc_zt
-static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles) {
+// tree (token trees; sc_tgt holds no target): sc_zt[node row] = the logit of the node's token at its parent's row instead
+static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles, const TreeNodes* tree = nullptr, int Lp = 0) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, V = c.vocab;
     *ntiles = 1;
@@ -1296,11 +1312,13 @@ static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles) {
             RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, rows,
                      V, d, 0, TAG_GEMM_OTHER));
             HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
+            if (tree) HIPCK(launch_tree_gather_logits(e->logits, e->ldl, r0, rows, *tree, Lp, M, e->sc_zt, s));
         }
     } else {
         SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
         *ntiles = score_head_tiles(V);
         HIPCK(launch_score_head(e->sc_ht, d, e->w.out_w, e->w.out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
+        if (tree) HIPCK(launch_tree_gather_dot(e->sc_ht, d, e->w.out_w, e->w.out_b, *tree, Lp, M, d, e->sc_zt, s));
     }
     return 0;
 }
@@ -1315,11 +1333,11 @@ static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles) {
 static int text_pass_impl(gitmi_engine* e, const Request& rq, const long long* tokens, int ld, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, V = c.vocab, Q = rq.Q, L = c.dec_layers;
-    const bool attend = rq.sp->kind == GITMI_SEARCH_ATTEND;
+    const bool attend = rq.sp->kind == GITMI_SEARCH_ATTEND, tree = rq.sp->kind == GITMI_SEARCH_TREE_SCORE;
     RCK(images_ready(e, rq, s));
     const int Lp = round_up(rq.maxP, 16), M = Q * Lp;
     const int Nk = e->cur_Nimg, Kc = Nk + ld;
-    void* const out = attend ? (void*)e->at_out : (void*)e->sc_out;
+    void* const out = attend ? (void*)e->at_out : tree ? (void*)e->tr_out : (void*)e->sc_out;
     const size_t out_bytes = attend ? (size_t)Q * ld * L * Kc * sizeof(float) : (size_t)Q * ld * sizeof(float2);
     auto zero_outputs = [&]() -> int {
         HIPCK(hipMemsetAsync(out, 0, out_bytes, s));
@@ -1327,21 +1345,30 @@ static int text_pass_impl(gitmi_engine* e, const Request& rq, const long long* t
         return 0;
     };
     SpanGuard phase(e, s, TAG_DECODE, 0);
-    if (attend) RCK(zero_outputs());       // the map kernels of every layer write into it
+    if (attend || tree) RCK(zero_outputs());       // the map kernels of every layer write into it; the tree verdicts flag sc_bad
+    // token trees: `tokens` is the packed (depth, token) table.  The structure launch is the only reader of its depths; a tree
+    // that fails its rules leaves it as parentless rows, so no later kernel forms an address from what the caller sent.
+    const size_t R = tree ? e->sc_rows : 0;
+    const TreeNodes nodes = tree ? TreeNodes{e->tr_nodes, e->tr_nodes + R, e->tr_nodes + 2 * R, e->tr_nodes + 3 * R} : TreeNodes{};
+    if (tree) HIPCK(launch_tree_structure(tokens, ld, Q, Lp, e->sc_lens, V, tree_max_depth(c), nodes, e->sc_bad, s));
     HIPCK(launch_score_embed_ln(tokens, ld, Q, Lp, e->w.words_f, e->w.positions_f, e->w.emb_lng, e->w.emb_lnb, 1e-8f, e->sc_hf, e->sc_ht,
-                                e->pol.f32, d, V, c.max_pos, s));
+                                e->pol.f32, d, V, c.max_pos, s, tree ? &nodes : nullptr));
     const int* ntok = key_counts(e);
     for (int l = 0; l < L; ++l) {
         const DecLayerW& W = e->w.dec[l];
         RCK(gemm(e, s, e->sc_ht, d, W.wqkv, W.bqkv, nullptr, 0, e->sc_qkv, 3 * d, e->pol.f32, M, 3 * d, d, 0, TAG_GEMM_OTHER));
         HIPCK(launch_score_attn(e->sc_qkv, e->img_kv[l], e->sc_img, e->sc_ctx, Q, c.dec_heads, d, Nk, Lp, 0.125f, e->pol.f32, s, ntok,
-                                attend ? e->at_stats : nullptr));
+                                attend ? e->at_stats : nullptr, tree ? nodes.end : nullptr));
         if (attend)
             HIPCK(launch_score_attn_map(e->sc_qkv, e->img_kv[l], e->sc_img, ntok, e->at_stats, e->sc_lens, e->at_out + (size_t)l * Kc,
                                         (size_t)ld * L * Kc, (size_t)L * Kc, ld, Q, c.dec_heads, Nk, Lp, 0.125f, e->pol.f32, e->sc_bad, s));
         if (!attend || l + 1 < L) RCK(dec_layer_tail(e, s, W, e->sc_ctx, e->sc_hf, e->sc_ht, e->sc_y, e->sc_u, M));
     }
-    if (int ntiles = 1; !attend) {
+    if (int ntiles = 1; tree) {
+        HIPCK(hipMemsetAsync(e->sc_tgt, 0xff, (size_t)M * sizeof(int), s));      // no row has a single target: -1 everywhere
+        RCK(score_head_impl(e, M, s, &ntiles, &nodes, Lp));
+        HIPCK(launch_tree_combine(e->sc_part, ntiles, e->sc_zt, nodes, M, Lp, ld, V, e->tr_out, e->sc_bad, s));
+    } else if (!attend) {
         HIPCK(launch_score_targets(tokens, ld, Lp, e->sc_lens, V, M, e->sc_tgt, s));
         RCK(score_head_impl(e, M, s, &ntiles));
         RCK(zero_outputs());
@@ -1447,20 +1474,29 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     SentenceSpan span;
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT)
         return context_call(e, frames, F, B, (const long long*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
-    if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND)) {
-        const bool attend = sp->kind == GITMI_SEARCH_ATTEND;
-        const char* who = attend ? "attend" : "score";
+    if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {
+        const bool attend = sp->kind == GITMI_SEARCH_ATTEND, tree = sp->kind == GITMI_SEARCH_TREE_SCORE;
+        const char* who = attend ? "attend" : tree ? "tree_score" : "score";
         if (!frames) RCK(check_resident(e, who, B));
         if (attend && !frames && e->has_context)
             return fail("attend: the resident images carry context rows; the attention map over [image | context | text] columns "
                         "is not implemented (run the attend call with frames, or encode without context)");
         if (!logprob_out || !info_out || !prefixes || !prefix_len_host) return fail("%s: null argument", who);
         if (frames) RCK(check_frames(e, who, frames, F, B));
-        if (ld_prefix < 1 || ld_prefix > c.max_text_len) return fail("%s: ld=%d outside [1,%d] (max_text_len)", who, ld_prefix, c.max_text_len);
+        // sentences are bounded by max_text_len positions; a tree by its depths (checked on the device) and the row cap
+        if (tree && tree_max_depth(c) > 8192)
+            return fail("tree_score: the depth bound min(max_text_len, max_pos) = %d exceeds the 8192 entries of the structure walk's "
+                        "root path", tree_max_depth(c));
+        const int ld_max = tree ? TREE_MAX_ROWS : c.max_text_len;
+        if (ld_prefix < 1 || ld_prefix > ld_max)
+            return fail("%s: ld=%d outside [1,%d] (%s)", who, ld_prefix, ld_max, tree ? "the row cap of a tree call" : "max_text_len");
         RCK(read_sentences(e, who, prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch * c.max_beams,
                            "max_batch x max_beams", &span));
         const int Lp = round_up(span.maxP, 16);
-        RCK(score_alloc(e, (size_t)Q * Lp));
+        if (tree && (size_t)Q * Lp > (size_t)TREE_MAX_ROWS)
+            return fail("tree_score: %d trees x %d padded nodes = %zu rows above the cap of %d rows per call", Q, Lp, (size_t)Q * Lp,
+                        TREE_MAX_ROWS);
+        RCK(score_alloc(e, (size_t)Q * Lp, tree ? (size_t)Q * ld_prefix : 0));
         if (attend)
             RCK(attend_alloc(e, (size_t)Q * ld_prefix * c.dec_layers * (call_Nimg(e, frames, F) + ld_prefix),
                              (size_t)Q * c.dec_heads * Lp));

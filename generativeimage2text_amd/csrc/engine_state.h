@@ -255,6 +255,11 @@ struct gitmi_engine {
     float4* sc_part = nullptr;
     int *sc_tgt = nullptr, *sc_lens = nullptr, *sc_img = nullptr, *sc_bad = nullptr, *sc_info = nullptr;
     float2* sc_out = nullptr;
+    // token trees (GITMI_SEARCH_TREE_SCORE): the node tables (int32 [4][sc_rows]: token, depth, parent, end) and the [Q, ld]
+    // output of a call, part of score_alloc's set once a tree call asked for them (tr_out_n: output elements held, 0: none)
+    size_t tr_out_n = 0;
+    int* tr_nodes = nullptr;
+    float2* tr_out = nullptr;
     // attention maps (GITMI_SEARCH_ATTEND): the softmax statistics of one layer's text rows and the [Q, ld, layers, Kc] output,
     // allocated by the first attend call and grown on demand (attend_alloc)
     size_t at_floats = 0, at_stat_rows = 0;

@@ -14,6 +14,11 @@
 // Attention maps (GITMI_SEARCH_ATTEND): the two attention kernels also write the softmax statistics (m, l) of every (sentence,
 // head, text row); score_attn_map_mfma_kernel / score_attn_map_kernel recompute S per key chunk and write the head mean of
 // exp(s - m) / l.  Score calls instantiate the attention kernels without the statistics store: their results are what they were.
+// Token trees (GITMI_SEARCH_TREE_SCORE): the rows are the nodes of trees in DFS pre-order.  tree_structure_kernel turns the
+// caller's depths into (parent, end) tables and rejects a malformed tree; the embedding and the two attention kernels have a
+// third instantiation (position = depth; the causal predicate becomes "ancestor or self", key blocks with no live key are
+// skipped); the head keeps its per-row tiles and tree_gather_*_kernel / tree_combine_kernel add the logit of every child's token
+// at its parent's row.  The score and attend instantiations compile to what they were.
 #include "gitmi_common.h"
 #include "launchers.h"
 
@@ -23,21 +28,30 @@ namespace gitmi {
 
 // ---- embedding + LayerNorm of every text position --------------------------------------------------------------
 // tokens int64 [Q][ld]; positions j >= ld are padding id 0 (text attention is causal: they change nothing before them)
-template <typename TOut>
+// TREE (GITMI_SEARCH_TREE_SCORE): row = node; its token id and position (= depth) come from the node tables
+// tree_structure_kernel wrote, already clamped -- `tokens` is not read.
+template <typename TOut, bool TREE>
 __global__ __launch_bounds__(256) void score_embed_ln_kernel(const long long* __restrict__ tokens, int ld, int Lp,
                                                              const float* __restrict__ words,
                                                              const float* __restrict__ positions,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps,
                                                              float* __restrict__ h_f, TOut* __restrict__ h_t, int D,
-                                                             int vocab, int max_pos) {
+                                                             int vocab, int max_pos, const int* __restrict__ node_tok,
+                                                             const int* __restrict__ node_depth) {
     __shared__ float s_part[8];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row = blockIdx.x;
-    const int q = row / Lp, j = row - q * Lp;
-    long long t = j < ld ? tokens[(size_t)q * ld + j] : 0;
-    const int tok = t < 0 ? 0 : (t >= vocab ? vocab - 1 : (int)t);
-    const int pos = j < max_pos ? j : max_pos - 1;
+    int tok, pos;
+    if constexpr (TREE) {
+        tok = node_tok[row];
+        pos = node_depth[row];
+    } else {
+        const int q = row / Lp, j = row - q * Lp;
+        long long t = j < ld ? tokens[(size_t)q * ld + j] : 0;
+        tok = t < 0 ? 0 : (t >= vocab ? vocab - 1 : (int)t);
+        pos = j < max_pos ? j : max_pos - 1;
+    }
     const int c = tid * 4;
     const bool on = c < D;
     f32x4_t a = {0.f, 0.f, 0.f, 0.f}, g4 = a, b4 = a;
@@ -80,15 +94,21 @@ __global__ __launch_bounds__(256) void score_embed_ln_kernel(const long long* __
 
 hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp, const float* words, const float* positions,
                                  const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
-                                 int D, int vocab, int max_pos, hipStream_t s) {
+                                 int D, int vocab, int max_pos, hipStream_t s, const TreeNodes* tree) {
     if (D > 1024 || (D & 3) || Q < 1 || Lp < 1 || max_pos < 1) return hipErrorInvalidValue;
     const dim3 grid(Q * Lp), block(256);
-    if (t_is_f32)
-        hipLaunchKernelGGL(score_embed_ln_kernel<float>, grid, block, 0, s, tokens, ld, Lp, words, positions, gamma, beta,
-                           eps, h_f, (float*)h_t, D, vocab, max_pos);
-    else
-        hipLaunchKernelGGL(score_embed_ln_kernel<bf16_t>, grid, block, 0, s, tokens, ld, Lp, words, positions, gamma, beta,
-                           eps, h_f, (bf16_t*)h_t, D, vocab, max_pos);
+    const int *ntk = tree ? tree->tok : nullptr, *ndp = tree ? tree->depth : nullptr;
+    auto go = [&](auto kernel, auto* ht) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, tokens, ld, Lp, words, positions, gamma, beta, eps, h_f, ht, D, vocab, max_pos,
+                           ntk, ndp);
+    };
+    if (t_is_f32) {
+        if (tree) go(score_embed_ln_kernel<float, true>, (float*)h_t);
+        else go(score_embed_ln_kernel<float, false>, (float*)h_t);
+    } else {
+        if (tree) go(score_embed_ln_kernel<bf16_t, true>, (bf16_t*)h_t);
+        else go(score_embed_ln_kernel<bf16_t, false>, (bf16_t*)h_t);
+    }
     return hipGetLastError();
 }
 
@@ -124,14 +144,31 @@ __device__ __forceinline__ void ld8(const bf16_t* p, float* o) {
     unpack2op(u.w, o[6], o[7]);
 }
 
+// Visibility of text key t for query row j.  Sentence: causal.  Tree (rows = nodes in DFS pre-order, end = first index past the
+// key's subtree): the key is the query itself or one of its ancestors.
+template <bool TREE>
+__device__ __forceinline__ bool text_key_visible(int t, int j, int end) {
+    if constexpr (TREE) return t <= j && j < end;
+    else return t <= j;
+}
+// Tree rows: does any of the 32 text keys t0 .. t0 + 31 reach the query tile that starts at j0?  A key with end <= j0 has its
+// whole subtree before the tile; one with end > j0 is visible to row j0 (t <= j0) or to itself (t > j0), so the test is exact.
+// Lanes l and l + 32 ask for the same key: every wave of a workgroup gets the same answer without a barrier.
+__device__ __forceinline__ bool tree_block_live(const int* __restrict__ end, int t0, int Lp, int j0, int lane) {
+    const int t = t0 + (lane & 31);
+    return __ballot(t < Lp && end[t] > j0) != 0;
+}
+
 // STATS: also stats[(q * H + h) * Lp + j] = (m, l), the row's score maximum and sum of exp(s - m) over its visible keys
-template <typename T, bool STATS>
+// TREE: node_end [Q * Lp] (tree_structure_kernel) replaces the causal predicate; key chunks past the image with no live key are skipped
+template <typename T, bool STATS, bool TREE>
 __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ img_kv,
                                                         const int* __restrict__ image_of, T* __restrict__ out, int d,
                                                         int N_img, int Lp, float scale, const int* __restrict__ ntok,
-                                                        float2* __restrict__ stats) {
+                                                        float2* __restrict__ stats, const int* __restrict__ node_end) {
     __shared__ float sK[SA_KC][64];
     __shared__ float sV[SA_KC][64];
+    __shared__ int sEnd[TREE ? SA_KC : 1];
     const int lane = threadIdx.x;
     const int q = blockIdx.x, h = blockIdx.y, j0 = blockIdx.z * 64;
     const int j = j0 + lane;
@@ -160,7 +197,16 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
     const int sr = lane >> 3, sc = (lane & 7) * 8;
     for (int k0 = 0; k0 < n_keys; k0 += SA_KC) {
         const int kc = min(SA_KC, n_keys - k0);
+        if constexpr (TREE) {
+            if (k0 >= n_i && !tree_block_live(node_end + row_base, k0 - n_i, Lp, j0, lane) &&
+                !tree_block_live(node_end + row_base, k0 - n_i + 32, Lp, j0, lane))
+                continue;
+        }
         __syncthreads();
+        if constexpr (TREE) {
+            const int t = k0 + lane - n_i;                 // text keys of the chunk are below n_keys - n_i <= Lp
+            sEnd[lane] = lane < kc && t >= 0 ? node_end[row_base + t] : 0;
+        }
         for (int r = sr; r < kc; r += 8) {
             const int key = k0 + r;
             const T* src = key < n_i ? img_kv + ((size_t)img * N_img + key) * ld3
@@ -182,7 +228,7 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
                 const int r = u0 + u;
                 const int key = k0 + r;
                 float sdot = -INFINITY;
-                if (r < kc && (key < n_i || key - n_i <= jq)) {
+                if (r < kc && (key < n_i || text_key_visible<TREE>(key - n_i, jq, TREE ? sEnd[r] : 0))) {
                     sdot = 0.f;
 #pragma unroll
                     for (int c = 0; c < 64; c += 4) {
@@ -248,14 +294,17 @@ __global__ __launch_bounds__(64) void score_attn_kernel(const T* __restrict__ qk
 constexpr int SM_KB = 32;                 // keys per block
 constexpr int SM_KP = 64 + 8;             // padded LDS row of sK (elements)
 constexpr int SM_VP = SM_KB + 8;          // padded LDS row of sVt / sP
-template <bool STATS>
+// TREE: as in score_attn_kernel; the end[] of a key block is staged with its keys (0 for image keys, which need none).
+template <bool STATS, bool TREE>
 __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ img_kv,
                                                               const int* __restrict__ image_of, bf16_t* __restrict__ out,
                                                               int d, int N_img, int Lp, float scale,
-                                                              const int* __restrict__ ntok, float2* __restrict__ stats) {
+                                                              const int* __restrict__ ntok, float2* __restrict__ stats,
+                                                              const int* __restrict__ node_end) {
     __shared__ __attribute__((aligned(16))) bf16_t sK[SM_KB][SM_KP];
     __shared__ __attribute__((aligned(16))) bf16_t sVt[64][SM_VP];
     __shared__ __attribute__((aligned(16))) bf16_t sP[4][16][SM_VP];
+    __shared__ int sEnd[TREE ? SM_KB : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x, h = blockIdx.y, j0 = blockIdx.z * 64;
     const int jw = j0 + wave * 16;                   // first query of this wave
@@ -281,6 +330,9 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
     for (int i = 0; i < 4; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
     const int sk = tid >> 3, sc = (tid & 7) * 8;     // staging: key sk of the block, dims sc .. sc + 8
     for (int k0 = 0; k0 < n_keys; k0 += SM_KB) {
+        if constexpr (TREE) {
+            if (k0 >= n_i && !tree_block_live(node_end + row_base, k0 - n_i, Lp, j0, lane)) continue;   // the same in every wave
+        }
         __syncthreads();
         {
             const int key = k0 + sk;
@@ -289,6 +341,9 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
                 const bf16_t* src = key < n_i ? img_kv + ((size_t)img * N_img + key) * ld3 : qkv + (row_base + (key - n_i)) * ld3;
                 kv = *reinterpret_cast<const uint4*>(src + d + h * 64 + sc);
                 vv = *reinterpret_cast<const uint4*>(src + 2 * d + h * 64 + sc);
+            }
+            if constexpr (TREE) {
+                if (sc == 0) sEnd[sk] = key >= n_i && key < n_keys ? node_end[row_base + (key - n_i)] : 0;
             }
             *reinterpret_cast<uint4*>(&sK[sk][sc]) = kv;
             const bf16_t* v8 = reinterpret_cast<const bf16_t*>(&vv);
@@ -313,7 +368,7 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
                 const int key = k0 + blk * 16 + c;
-                const bool ok = key < n_keys && (key < n_i || key - n_i <= j);
+                const bool ok = key < n_keys && (key < n_i || text_key_visible<TREE>(key - n_i, j, TREE ? sEnd[blk * 16 + c] : 0));
                 x[blk] = ok ? sfr[blk][i] * scale : -INFINITY;
             }
             const float mx = xor16_max(fmaxf(x[0], x[1]));
@@ -350,17 +405,21 @@ __global__ __launch_bounds__(256) void score_attn_mfma_kernel(const bf16_t* __re
 }
 
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
-                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok, float2* stats) {
-    if (d != H * 64 || Q < 1 || Lp < 1 || N_img < 1) return hipErrorInvalidValue;
+                             int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok, float2* stats,
+                             const int* node_end) {
+    if (d != H * 64 || Q < 1 || Lp < 1 || N_img < 1 || (stats && node_end)) return hipErrorInvalidValue;
     const dim3 grid(Q, H, (Lp + 63) / 64);
+    if (grid.y > 65535u || grid.z > 65535u) return hipErrorInvalidValue;
     if (is_f32) {
-        const auto k = stats ? score_attn_kernel<float, true> : score_attn_kernel<float, false>;
+        const auto k = node_end ? score_attn_kernel<float, false, true>
+                                : stats ? score_attn_kernel<float, true, false> : score_attn_kernel<float, false, false>;
         hipLaunchKernelGGL(k, grid, dim3(64), 0, s, (const float*)qkv, (const float*)img_kv, image_of, (float*)out, d, N_img, Lp,
-                           scale, ntok, stats);
+                           scale, ntok, stats, node_end);
     } else {
-        const auto k = stats ? score_attn_mfma_kernel<true> : score_attn_mfma_kernel<false>;
+        const auto k = node_end ? score_attn_mfma_kernel<false, true>
+                                : stats ? score_attn_mfma_kernel<true, false> : score_attn_mfma_kernel<false, false>;
         hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)img_kv, image_of, (bf16_t*)out, d, N_img,
-                           Lp, scale, ntok, stats);
+                           Lp, scale, ntok, stats, node_end);
     }
     return hipGetLastError();
 }
@@ -685,14 +744,8 @@ hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const i
 // ---- combine: per head row with a target, LSE over the tiles -> out[q][j + 1] = (lp, mean_lp); bad[q] = 1 when either
 // value is not finite.  One wave per row.  Tile t covers min(tile_w, V - t tile_w) columns; with M = max over the tiles,
 // S = sum_t se_t exp(m_t - M), D = sum_t (sz_t + n_t (m_t - M)) = sum_c (z_c - M):  LSE = M + log S, mean_lp = D / V - log S.
-__global__ __launch_bounds__(64) void score_combine_kernel(const float4* __restrict__ part, int ntiles, int tile_w,
-                                                           const float* __restrict__ zt, const int* __restrict__ tgt,
-                                                           int Lp, int ld, int V, float2* __restrict__ out,
-                                                           int* __restrict__ bad) {
-    const int lane = threadIdx.x;
-    const int row = blockIdx.x;
-    if (tgt[row] < 0) return;
-    const float4* p = part + (size_t)row * ntiles;
+// (lp, mean_lp) of one head row from its tiles `p` and the logit z at the target, by the whole wave (the value is lane 0's)
+__device__ __forceinline__ float2 combine_row(const float4* __restrict__ p, int ntiles, int tile_w, int V, float z, int lane) {
     float mx = -INFINITY;
     for (int t = lane; t < ntiles; t += 64) mx = fmaxf(mx, p[t].x);
     mx = wave_max(mx);
@@ -705,13 +758,22 @@ __global__ __launch_bounds__(64) void score_combine_kernel(const float4* __restr
     }
     se = wave_sum(se);
     sd = wave_sum(sd);
+    const float ls = logf(se);
+    return make_float2((z - mx) - ls, sd / (float)V - ls);
+}
+
+__global__ __launch_bounds__(64) void score_combine_kernel(const float4* __restrict__ part, int ntiles, int tile_w,
+                                                           const float* __restrict__ zt, const int* __restrict__ tgt,
+                                                           int Lp, int ld, int V, float2* __restrict__ out,
+                                                           int* __restrict__ bad) {
+    const int lane = threadIdx.x;
+    const int row = blockIdx.x;
+    if (tgt[row] < 0) return;
+    const float2 r = combine_row(part + (size_t)row * ntiles, ntiles, tile_w, V, zt[row], lane);
     if (lane == 0) {
-        const float ls = logf(se);
-        const float lp = (zt[row] - mx) - ls;
-        const float mean = sd / (float)V - ls;
         const int q = row / Lp, j = row - q * Lp;
-        out[(size_t)q * ld + j + 1] = make_float2(lp, mean);
-        if (!isfinite(lp) || !isfinite(mean)) bad[q] = 1;
+        out[(size_t)q * ld + j + 1] = r;
+        if (!isfinite(r.x) || !isfinite(r.y)) bad[q] = 1;
     }
 }
 
@@ -736,6 +798,152 @@ __global__ void score_info_kernel(const int* __restrict__ bad, int Q, int ld, in
 
 hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s, int i1, int i2) {
     hipLaunchKernelGGL(score_info_kernel, dim3(1), dim3(256), 0, s, bad, Q, ld, i1, i2, info);
+    return hipGetLastError();
+}
+
+// ---- token trees (GITMI_SEARCH_TREE_SCORE) -------------------------------------------------------------------------------
+// The rows of the text pass are the nodes of Q trees in DFS pre-order: tree q, node i -> row q * Lp + i.  packed [Q][ld] int64 =
+// (depth << 32 | token id); the parent of node i is the last k < i with depth[k] == depth[i] - 1.  In pre-order node k is an
+// ancestor-or-self of node i exactly when k <= i < end[k], end[k] the first index past k's subtree.
+//
+// One wave per tree.  The verdict first, from local rules only (depth[0] == 0, 1 <= depth[i] <= depth[i - 1] + 1, depth <
+// max_depth): a tree that fails gets bad[q] = 1 and the structure of rows past a tree's nodes -- every row a root of its own
+// (depth 0, no parent, end = i + 1: it attends to the image and itself, has no target, and nothing is indexed by its depths).
+// Then lane 0 walks the nodes in order with the current root path in LDS (max_depth entries): node i at depth dp closes the path
+// entries at depths >= dp (their end is i) and takes path[dp - 1] as its parent.  Depths (the validated copies: the caller's table is
+// not read again) and parents pass through LDS in chunks of 64 so that the global accesses of the walk are the whole wave's; every node's end is stored once, when the node is closed.
+__global__ __launch_bounds__(64) void tree_structure_kernel(const long long* __restrict__ packed, int ld, int Lp,
+                                                            const int* __restrict__ lens, int V, int max_depth, TreeNodes nd,
+                                                            int* __restrict__ bad) {
+    extern __shared__ int s_path[];
+    __shared__ int s_dp[64], s_par[64];
+    const int lane = threadIdx.x, q = blockIdx.x;
+    const int n = max(0, min(lens[q], min(ld, Lp)));
+    const long long* src = packed + (size_t)q * ld;
+    const size_t row_base = (size_t)q * Lp;
+    bool wrong = false;
+    for (int i = lane; i < n; i += 64) {
+        const long long dp = src[i] >> 32;
+        const long long up = i ? (src[i - 1] >> 32) + 1 : 0;
+        wrong = wrong || dp >= max_depth || dp > up || dp < (i ? 1 : 0);
+    }
+    const bool ok = __ballot(wrong) == 0;
+    for (int i = lane; i < Lp; i += 64) {
+        const bool live = ok && i < n;
+        const long long v = i < n ? src[i] : 0;
+        const int t = (int)(v & 0xffffffffll);
+        nd.tok[row_base + i] = t < 0 ? 0 : (t >= V ? V - 1 : t);
+        nd.depth[row_base + i] = live ? (int)(v >> 32) : 0;
+        if (!live) { nd.parent[row_base + i] = -1; nd.end[row_base + i] = i + 1; }
+    }
+    if (!ok) {
+        if (lane == 0) bad[q] = 1;
+        return;
+    }
+    int top = -1;                                           // lane 0: depth of the node the path ends in
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int cn = min(64, n - c0);
+        __syncthreads();
+        if (lane < cn) s_dp[lane] = nd.depth[row_base + c0 + lane];      // the validated copy, written above by this very lane
+        __syncthreads();
+        if (lane == 0) {
+            for (int r = 0; r < cn; ++r) {
+                const int i = c0 + r, dp = s_dp[r];
+                for (int k = top; k >= dp; --k) nd.end[row_base + s_path[k]] = i;
+                s_par[r] = dp ? s_path[dp - 1] : -1;
+                s_path[dp] = i;
+                top = dp;
+            }
+        }
+        __syncthreads();
+        if (lane < cn) nd.parent[row_base + c0 + lane] = s_par[lane];
+    }
+    if (lane == 0)
+        for (int k = top; k >= 0; --k) nd.end[row_base + s_path[k]] = n;
+}
+
+hipError_t launch_tree_structure(const long long* packed, int ld, int Q, int Lp, const int* lens, int V, int max_depth,
+                                 const TreeNodes& nd, int* bad, hipStream_t s) {
+    if (Q < 1 || Lp < 1 || ld < 1 || V < 1 || max_depth < 1 || max_depth > 8192) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tree_structure_kernel, dim3(Q), dim3(64), (size_t)max_depth * sizeof(int), s, packed, ld, Lp, lens, V,
+                       max_depth, nd, bad);
+    return hipGetLastError();
+}
+
+// The logit of every node's token at its parent's head row, zt[row of node i] = z[parent(i)][token(i)] (nodes without a parent:
+// not written).  16-bit modes: the head's operands again -- A row of the parent, W row of the token, fp32 accumulation, + bias;
+// one wave per node.
+__global__ __launch_bounds__(256) void tree_gather_dot_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W,
+                                                              const float* __restrict__ bias, TreeNodes nd, int Lp, int M, int K,
+                                                              float* __restrict__ zt) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int par = nd.parent[row];
+    if (par < 0) return;
+    const int tok = nd.tok[row];
+    const bf16_t* a = A + ((size_t)(row / Lp) * Lp + par) * lda;
+    const bf16_t* w = W + (size_t)tok * K;
+    float acc = 0.f;
+    for (int c = lane * 8; c < K; c += 512) {
+        float x[8], y[8];
+        ld8(a + c, x);
+        ld8(w + c, y);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = fmaf(x[i], y[i], acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) zt[row] = acc + bias[tok];
+}
+// f32 mode: from the materialised logits of head rows [row_off, row_off + rows); the children of those rows lie behind them in
+// their own trees: nodes [row_off, first row of the tree after the chunk's last row)
+__global__ void tree_gather_logits_kernel(const float* __restrict__ logits, int ldl, int row_off, int rows, TreeNodes nd, int Lp,
+                                          int row_end, float* __restrict__ zt) {
+    const int row = row_off + blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= row_end) return;
+    const int par = nd.parent[row];
+    if (par < 0) return;
+    const int prow = (row / Lp) * Lp + par;
+    if (prow < row_off || prow >= row_off + rows) return;
+    zt[row] = logits[(size_t)(prow - row_off) * ldl + nd.tok[row]];
+}
+
+hipError_t launch_tree_gather_dot(const void* A, int lda, const void* W, const float* bias, const TreeNodes& nd, int Lp, int M,
+                                  int K, float* zt, hipStream_t s) {
+    if (M < 1 || Lp < 1 || K % 8 || lda % 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tree_gather_dot_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)A, lda, (const bf16_t*)W, bias,
+                       nd, Lp, M, K, zt);
+    return hipGetLastError();
+}
+hipError_t launch_tree_gather_logits(const float* logits, int ldl, int row_off, int rows, const TreeNodes& nd, int Lp, int M,
+                                     float* zt, hipStream_t s) {
+    if (rows < 1) return hipSuccess;
+    const int tree_end = ((row_off + rows - 1) / Lp + 1) * Lp, row_end = tree_end < M ? tree_end : M;
+    hipLaunchKernelGGL(tree_gather_logits_kernel, dim3((row_end - row_off + 255) / 256), dim3(256), 0, s, logits, ldl, row_off,
+                       rows, nd, Lp, row_end, zt);
+    return hipGetLastError();
+}
+
+// combine: node i with a parent -> out[q][i] = (lp, mean_lp) from the tiles of the parent's head row and zt at the node's own row
+__global__ __launch_bounds__(64) void tree_combine_kernel(const float4* __restrict__ part, int ntiles, int tile_w,
+                                                          const float* __restrict__ zt, TreeNodes nd, int Lp, int ld, int V,
+                                                          float2* __restrict__ out, int* __restrict__ bad) {
+    const int lane = threadIdx.x;
+    const int row = blockIdx.x;
+    const int par = nd.parent[row];
+    if (par < 0) return;
+    const int q = row / Lp, i = row - q * Lp;             // a node with a parent is one of the tree's n_q <= ld nodes
+    const float2 r = combine_row(part + ((size_t)q * Lp + par) * ntiles, ntiles, tile_w, V, zt[row], lane);
+    if (lane == 0) {
+        out[(size_t)q * ld + i] = r;
+        if (!isfinite(r.x) || !isfinite(r.y)) bad[q] = 1;
+    }
+}
+
+hipError_t launch_tree_combine(const float4* part, int ntiles, const float* zt, const TreeNodes& nd, int M, int Lp, int ld, int V,
+                               float2* out, int* bad, hipStream_t s) {
+    const int tile_w = ntiles == 1 ? V : SH_COLS;
+    hipLaunchKernelGGL(tree_combine_kernel, dim3(M), dim3(64), 0, s, part, ntiles, tile_w, zt, nd, Lp, ld, V, out, bad);
     return hipGetLastError();
 }
 

@@ -272,15 +272,24 @@ hipError_t launch_fill_start(long long* start, int ld, const long long* prefix, 
 hipError_t launch_load_ids(const long long* tokens, int R, int t, int* ids, int* kv_src, int ld, hipStream_t s);
 
 // caption scoring (kernels_score.hip): rows of the text pass are (sentence q, position j) -> q * Lp + j
+// token trees (GITMI_SEARCH_TREE_SCORE): the rows are tree nodes in DFS pre-order, described by four int32 [Q * Lp] tables
+struct TreeNodes {
+    int* tok;       // token id, clamped into the vocabulary
+    int* depth;     // = position of the embedding
+    int* parent;    // node index within the tree; -1: root, padding row, or any row of a rejected tree
+    int* end;       // first node index past the subtree: k is an ancestor-or-self of i exactly when k <= i < end[k]
+};
+// tree: embed node rows (token / position from its tables; `tokens` is not read) instead of sentence positions
 hipError_t launch_score_embed_ln(const long long* tokens, int ld, int Q, int Lp, const float* words, const float* positions,
                                  const float* gamma, const float* beta, float eps, float* h_f, void* h_t, bool t_is_f32,
-                                 int D, int vocab, int max_pos, hipStream_t s);
+                                 int D, int vocab, int max_pos, hipStream_t s, const TreeNodes* tree = nullptr);
 // qkv [Q * Lp][3d] text rows, img_kv [B * N_img][3d] prefill rows of the same layer, image_of [Q] -> out [Q * Lp][d]
 // ntok (ragged batches): image keys of every image (<= N_img, the row stride of an image's block); nullptr: N_img each
 // stats (attention maps; nullptr: none, the score call's kernels): fp32 [Q][H][Lp] = (m, l), the softmax statistics of every row
+// node_end (token trees; nullptr: sentences, causal): TreeNodes::end -- text key t is visible to row j when t <= j < node_end[t]
 hipError_t launch_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int d,
                              int N_img, int Lp, float scale, bool is_f32, hipStream_t s, const int* ntok = nullptr,
-                             float2* stats = nullptr);
+                             float2* stats = nullptr, const int* node_end = nullptr);
 // attention map of one layer from launch_score_attn's operands and stats: out[q * out_sq + j * out_sj + col] = head mean of the
 // probability text row (q, j) gives column col -- [0, N_img) the image keys of image_of[q] (0 past ntok), N_img + t (t < Tc) its
 // text keys (0 for t > j).  Rows j >= lens[q] (nullptr: Lp rows each) are not written; bad[q] = 1 on a non-finite value (or nullptr).
@@ -298,6 +307,19 @@ hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const i
 hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt, const int* tgt, int M, int Lp, int ld, int V,
                                 float2* out, int* bad, hipStream_t s);
 hipError_t launch_score_info(const int* bad, int Q, int ld, int* info, hipStream_t s, int i1 = 0, int i2 = 0);   // info = {ld, i1, i2, bad}
+// token trees: packed int64 [Q][ld] (depth << 32 | token), lens [Q] node counts -> the node tables; bad[q] = 1 for a tree that
+// breaks the depth rules (its rows, like the rows past a tree's nodes, become parentless roots).  max_depth <= 8192 (LDS).
+hipError_t launch_tree_structure(const long long* packed, int ld, int Q, int Lp, const int* lens, int V, int max_depth,
+                                 const TreeNodes& nd, int* bad, hipStream_t s);
+// zt[node row] = z[parent row][token of the node]: a dot product of the head's 16-bit operands, or read from materialised fp32
+// logits of head rows [row_off, row_off + rows)
+hipError_t launch_tree_gather_dot(const void* A, int lda, const void* W, const float* bias, const TreeNodes& nd, int Lp, int M,
+                                  int K, float* zt, hipStream_t s);
+hipError_t launch_tree_gather_logits(const float* logits, int ldl, int row_off, int rows, const TreeNodes& nd, int Lp, int M,
+                                     float* zt, hipStream_t s);
+// out[q * ld + i] = (lp, mean_lp) of every node with a parent, from the parent row's tiles (launch_score_head / _rowstats) and zt
+hipError_t launch_tree_combine(const float4* part, int ntiles, const float* zt, const TreeNodes& nd, int M, int Lp, int ld, int V,
+                               float2* out, int* bad, hipStream_t s);
 
 // GPU image transform (Pillow-exact bicubic resize + centre crop + CLIP normalisation)
 hipError_t launch_preprocess(const unsigned char* rgb, int H, int W, int crop, unsigned char* tmp, float* out, hipStream_t s);

@@ -25,6 +25,7 @@ SEARCH_AUTOREGRESSIVE, SEARCH_GENERATOR, SEARCH_TRIE = 0, 1, 2
 SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given sentences (Engine.score)
 SEARCH_ATTEND = 4    # not a search: gitmi_generate_prefixed returns the attention maps of given sentences (Engine.attend)
 SEARCH_CONTEXT = 5   # not a search: gitmi_generate_prefixed puts context tokens into the decoder memory (Engine.encode_context)
+SEARCH_TREE_SCORE = 6  # not a search: gitmi_generate_prefixed scores every node of given token trees (Engine.score_tree)
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
 
 EXPORTED_SYMBOLS = [
@@ -45,7 +46,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_vocab_topm_rules", "gitmi_debug_search_begin_prefixed", "gitmi_debug_search_advance_lists", "gitmi_debug_read_hidden",
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
-    "gitmi_debug_gemm_form", "gitmi_debug_context_embed", "gitmi_debug_attn_decode_qkv",
+    "gitmi_debug_gemm_form", "gitmi_debug_context_embed", "gitmi_debug_attn_decode_qkv", "gitmi_debug_score_attn_tree",
 ]
 
 
@@ -162,6 +163,7 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_score_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_score_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
         lib.gitmi_debug_score_attn_map.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        lib.gitmi_debug_score_attn_tree.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attention_ragged.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_attn_decode_form.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
@@ -778,6 +780,30 @@ class Engine:
         self._sentence_call(SEARCH_ATTEND, frames, arr, keep, B, tok, lens, image_of, out)
         return out
 
+    def score_tree(self, frames: Optional[Sequence[torch.Tensor]], tokens, depths, lengths: Optional[Sequence[int]] = None,
+                   image_of: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Log-probability of every node of given token trees (include/gitmi.h GITMI_SEARCH_TREE_SCORE): a closed candidate
+        set as a trie, every shared prefix scored once.  tokens, depths: int [Q, L], tree q in DFS pre-order -- node 0 the root
+        ([CLS]) at depth 0, the parent of node i the last k < i with depths[q, k] == depths[q, i] - 1; lengths: [Q] node counts
+        (default L; L is not bounded by max_text_len, the depths are); image_of as for score.
+        -> fp32 [Q, L, 2] on the device: (lp, mean_lp) at node i = (log_softmax(z)[tokens[q, i]], mean_c log_softmax(z)[c]) with
+        z the logits at the node's parent, computed over [image (| context) | the ancestors]; node 0 and nodes >= length are 0.
+        A chain (depths[q, i] = i) is a sentence and the result is score's.  Raises ValueError naming tree and node when a tree
+        breaks the depth rules.  frames None: a follow-up call over the resident images, nothing is encoded."""
+        arr, keep, B = self._frames_arg(frames)
+        table, lens = pack_trees(tokens, depths, lengths, int(self.c.vocab), min(int(self.c.max_text_len), int(self.c.max_pos)))
+        Q, L = table.shape
+        if Q > self.c.max_batch * self.c.max_beams:
+            raise GitmiError(f"{Q} trees exceed the capacity max_batch x max_beams = {self.c.max_batch * self.c.max_beams}")
+        if image_of is None and Q != B:
+            raise ValueError(f"{Q} trees over {B} images: image_of is required")
+        if image_of is not None and len(image_of) != Q:
+            raise ValueError(f"image_of has {len(image_of)} entries for {Q} trees")
+        table = table.to(torch.device(f"cuda:{self.device}"))
+        out = self._empty((Q, L, 2), torch.float32, table.device)
+        self._sentence_call(SEARCH_TREE_SCORE, frames, arr, keep, B, table, lens, image_of, out)
+        return out
+
     def _sentence_args(self, frames, tokens, lengths, image_of):
         """The argument checks score and attend share -> (frames argument, tensors to keep alive, B, tokens int64 [Q, L] on the
         device with zeros past every length, lengths)."""
@@ -805,15 +831,20 @@ class Engine:
             raise ValueError(f"image_of has {len(image_of)} entries for {Q} sentences")
         return arr, keep, B, tok, lens
 
-    def _sentence_call(self, kind: int, frames, arr, keep, B: int, tok: torch.Tensor, lens, image_of, out: torch.Tensor) -> None:
-        """gitmi_generate_prefixed with a kind that is not a search (score, attend): `out` is its logprob_out."""
+    def _sentence_call(self, kind: int, frames, arr, keep, B: int, tok: torch.Tensor, lens, image_of, out: torch.Tensor,
+                       check: bool = True) -> torch.Tensor:
+        """gitmi_generate_prefixed with a kind that is not a search (score, attend, score_tree): `out` is its logprob_out.
+        -> info int32 [4] of the finished call; check False: info[3] (sentences rejected or non-finite) is the caller's to read."""
         Q, L = tok.shape
         info = self._empty(4, torch.int32, tok.device)
         search = GitmiSearch()
         search.kind = kind
         self._done(self._call(frames, self.lib.gitmi_generate_prefixed(
             self._h, arr, len(keep), B, tok.data_ptr(), L, *_sentence_tables(lens, image_of), Q, C.byref(search), None,
-            out.data_ptr(), None, info.data_ptr(), _stream()), B), info, True)
+            out.data_ptr(), None, info.data_ptr(), _stream()), B), info, check)
+        if not check:
+            torch.cuda.current_stream().synchronize()
+        return info
 
     # -- search seam ---------------------------------------------------------------------------
     def search_begin(self, search: GitmiSearch, start: torch.Tensor, vocab: int) -> None:
@@ -1375,6 +1406,63 @@ def op_score_attn_map(qkv: torch.Tensor, img_kv: torch.Tensor, image_of: torch.T
     _ck(_experiment_only(lib, "gitmi_debug_score_attn_map")(qkv.data_ptr(), img_kv.data_ptr(), img.data_ptr(), _ptr(nt),
                                                             out.data_ptr(), Q, H, N_img, Lp, _torch_dtype_code(qkv), _stream()), lib)
     return out
+
+
+def pack_trees(tokens, depths, lengths, vocab: int, max_depth: int):
+    """Host side of Engine.score_tree: the rules of include/gitmi.h (GITMI_SEARCH_TREE_SCORE) checked on int [Q, L] tokens /
+    depths -- depths[q, 0] == 0, 1 <= depths[q, i] <= depths[q, i - 1] + 1, depth < max_depth, ids in [0, vocab), lengths in [1, L]
+    -- then the packed table.  Raises ValueError naming tree and node.
+    -> (int64 [Q, L] on the CPU with depth << 32 | token, zeros past every length; lengths as a list)"""
+    tok = torch.as_tensor(tokens).detach().to("cpu", torch.int64)
+    dep = torch.as_tensor(depths).detach().to("cpu", torch.int64)
+    if tok.dim() != 2 or tok.shape[1] < 1 or dep.shape != tok.shape:
+        raise ValueError(f"tokens and depths must both be [Q, L], got {tuple(tok.shape)} and {tuple(dep.shape)}")
+    Q, L = int(tok.shape[0]), int(tok.shape[1])
+    lens = [L] * Q if lengths is None else [int(v) for v in lengths]
+    if len(lens) != Q:
+        raise ValueError(f"lengths has {len(lens)} entries for {Q} trees")
+    for q, n in enumerate(lens):
+        if n < 1 or n > L:
+            raise ValueError(f"tree {q}: length {n} outside [1, {L}]")
+    valid = torch.arange(L)[None, :] < torch.as_tensor(lens)[:, None]
+    first = dep[:, 0] != 0
+    if bool(first.any()):
+        q = int(first.nonzero()[0])
+        raise ValueError(f"tree {q}, node 0: the root must have depth 0, got {int(dep[q, 0])}")
+    step = torch.zeros_like(valid)
+    step[:, 1:] = (dep[:, 1:] < 1) | (dep[:, 1:] > dep[:, :-1] + 1)
+    for wrong, what in ((step & valid, "must lie in [1, depth of the node before it + 1] (one root; a child is one level below)"),
+                        ((dep >= max_depth) & valid, f"must be below {max_depth} (min(max_text_len, max_pos))")):
+        if bool(wrong.any()):
+            q, i = (int(v) for v in wrong.nonzero()[0])
+            raise ValueError(f"tree {q}, node {i}: depth {int(dep[q, i])} {what}")
+    ids = tok[valid]
+    if int(ids.min()) < 0 or int(ids.max()) >= vocab:
+        raise ValueError(f"token ids outside [0, {vocab})")
+    table = torch.where(valid, (dep << 32) | tok, torch.zeros_like(tok)).contiguous()
+    return table, lens
+
+
+def op_score_attn_tree(qkv: torch.Tensor, img_kv: torch.Tensor, image_of: torch.Tensor, table: torch.Tensor, lens, max_depth: int,
+                       Q: int, H: int, N_img: int, Lp: int, ntok: Optional[torch.Tensor] = None):
+    """Tree attention of one layer (measurement build): op_score_attn's operands with the rows of every sentence the nodes of a
+    token tree -- table int64 [Q, Lp] (pack_trees), lens int [Q] -> ([Q * Lp, H 64] in the input dtype, int32 [Q] verdicts:
+    1 for a tree the structure launch rejected)."""
+    lib = load_library()
+    dev = qkv.device
+    img = image_of.to(device=dev, dtype=torch.int32).contiguous()
+    nt = None if ntok is None else ntok.to(device=dev, dtype=torch.int32).contiguous()
+    tab = table.to(device=dev, dtype=torch.int64).contiguous()
+    ln = torch.as_tensor(lens).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(tab.shape) != (Q, Lp) or ln.numel() != Q:
+        raise ValueError("table must be [Q, Lp] and lens [Q]")
+    out = torch.empty(Q * Lp, H * 64, device=dev, dtype=qkv.dtype)
+    bad = torch.empty(Q, device=dev, dtype=torch.int32)
+    _ck(_experiment_only(lib, "gitmi_debug_score_attn_tree")(qkv.data_ptr(), img_kv.data_ptr(), img.data_ptr(), _ptr(nt),
+                                                             tab.data_ptr(), ln.data_ptr(), max_depth, out.data_ptr(),
+                                                             bad.data_ptr(), Q, H, N_img, Lp, _torch_dtype_code(qkv), _stream()),
+        lib)
+    return out, bad
 
 
 def op_score_head(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:

@@ -126,6 +126,7 @@ class TokenTrie:
 
     def __init__(self):
         self._children = [{}]                  # node -> {token: child node}; node 0 is the root
+        self._ends = []                        # the node every inserted sequence ends in, in insertion order
         self.curr = 0
 
     @classmethod
@@ -144,6 +145,7 @@ class TokenTrie:
                 self._children.append({})
                 self._children[cur][int(t)] = nxt
             cur = nxt
+        self._ends.append(cur)
 
     def get_valid(self, tokens):
         cur = 0
@@ -162,6 +164,25 @@ class TokenTrie:
     def move(self, t):
         assert int(t) in self._children[self.curr]
         self.curr = self._children[self.curr][int(t)]
+
+    def preorder(self):
+        """The trie below its (token-less) root in DFS pre-order, children in insertion order -- the node order of
+        Engine.score_tree.  -> (tokens, depths, terminal): token id and depth (1 for the first token of a sequence) of every
+        node, and terminal[s] = the index of the node inserted sequence s ends in (duplicates share a node, a sequence that is
+        a prefix of another ends in an inner node; -1 for an empty sequence, which ends in the root)."""
+        tokens, depths, index = [], [], {0: -1}
+        stack = [(0, iter(self._children[0].items()))]
+        while stack:
+            step = next(stack[-1][1], None)
+            if step is None:
+                stack.pop()
+                continue
+            tok, node = step
+            index[node] = len(tokens)
+            tokens.append(tok)
+            depths.append(len(stack))
+            stack.append((node, iter(self._children[node].items())))
+        return tokens, depths, [index[n] for n in self._ends]
 
     def csr(self):
         off, tok, node = [0], [], []
@@ -701,6 +722,61 @@ class CaptioningModel:
         n = sel.sum(1)
         return {"logprobs": lp, "mean_logprobs": mean_lp, "sum": total,
                 "mean": total / n.clamp(min=1).to(total.dtype)}
+
+    def rank(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], candidates, prefixes=None,
+             image_of: Optional[Sequence[int]] = None, on=None, context=None, append_eos: bool = True) -> Dict[str, object]:
+        """Exact log-probability of every candidate of a closed set (VQA answer list, class names, captions to rerank) in ONE
+        engine call: the candidates are merged into a token trie and every trie node is scored once (Engine.score_tree), so
+        a shared question prefix and shared answer prefixes pass through the decoder and the vocabulary head once, and the
+        call is not chunked by max_batch x max_beams candidates.
+        candidates: K id lists (without [CLS]); append_eos adds [SEP] to each, so that the probability of stopping counts, as in
+        the reference's class tries (get_output_vocab_tokens).  prefixes: Q id lists, the question of tree q ([CLS] is put in
+        front unless it is there already; default: none, one tree per image); tree q belongs to image image_of[q] (default:
+        q <-> image q).  images, on and context as for score: images None ranks over the RESIDENT images.
+        -> {'scores' fp32 [Q, K]: the sum of lp over candidate k's own nodes (the prefix does not count); 'best' int64 [Q]: its
+            argmax, ties to the first candidate; 'node_logprobs' fp32 [Q, L, 2]: (lp, mean_lp) of every node; 'tree':
+            {'tokens', 'depths' int64 [Q, L], 'lengths' [Q], 'terminal' int64 [Q, K] the node candidate k ends in}}, on the CPU."""
+        eos = [int(self.cfg.eos)] if append_eos else []
+        cands = [[int(t) for t in c] + eos for c in candidates]
+        if not cands or any(not c for c in cands):
+            raise ValueError("rank needs at least one candidate, each of at least one token")
+        if prefixes is None:
+            n = len(image_of) if image_of is not None else None if images is None else \
+                len(images) if _is_image_list(images) else int((images[0] if isinstance(images, (list, tuple)) else images).shape[0])
+            if n is None:
+                raise ValueError("rank over resident images needs image_of (or prefixes)")
+            prefixes = [[]] * n
+        sos = int(self.cfg.sos)
+        chains = [[int(t) for t in p] for p in prefixes]
+        chains = [c if c[:1] == [sos] else [sos] + c for c in chains]
+        trie_tok, trie_dep, terminal = TokenTrie.construct(cands).preorder()
+        Q, L = len(chains), max(len(c) for c in chains) + len(trie_tok)
+        tokens, depths = torch.zeros(Q, L, dtype=torch.int64), torch.zeros(Q, L, dtype=torch.int64)
+        lengths = []
+        for q, c in enumerate(chains):
+            n = len(c) + len(trie_tok)
+            tokens[q, :n] = torch.tensor(c + trie_tok)
+            depths[q, :n] = torch.tensor(list(range(len(c))) + [len(c) - 1 + d for d in trie_dep])
+            lengths.append(n)
+        out, _ = self._sentence_pass("score_tree", images, tokens, image_of, on, context=context, depths=depths, lengths=lengths)
+        out = out.float()
+        # path sums below the chain, one trie level at a time: own[i] = own[parent(i)] + lp[i]; slot 0 is the chain's last node
+        first = torch.tensor([len(c) for c in chains])
+        own = torch.zeros(Q, len(trie_tok) + 1, dtype=torch.float32)
+        own[:, 1:] = torch.gather(out[..., 0], 1, first[:, None] + torch.arange(len(trie_tok))[None, :])
+        path, parent = [0], []                                                        # slot of the node at every trie depth
+        for i, d in enumerate(trie_dep):
+            del path[d:]
+            parent.append(path[d - 1])
+            path.append(i + 1)
+        dep, parent = torch.tensor(trie_dep), torch.tensor(parent)
+        for d in range(2, max(trie_dep) + 1):
+            level = (dep == d).nonzero()[:, 0]
+            own[:, level + 1] += own[:, parent[level]]
+        scores = own[:, [t + 1 for t in terminal]]
+        term = torch.tensor([[len(c) + t for t in terminal] for c in chains], dtype=torch.int64)
+        return {"scores": scores, "best": torch.from_numpy(scores.numpy().argmax(1)), "node_logprobs": out,
+                "tree": {"tokens": tokens, "depths": depths, "lengths": lengths, "terminal": term}}
 
     def _sentence_pass(self, method: str, images, tokens: torch.Tensor, image_of, on, context=None, **kw):
         """One engine pass over given sentences (Engine.score / Engine.attend) routed like every request: images None -> the

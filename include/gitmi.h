@@ -53,6 +53,8 @@ extern "C" {
                                         * only, see there */
 #define GITMI_SEARCH_CONTEXT        5  /* not a search: context tokens (the reference's batch['context'], decoder.py:861-871) put into
                                         * the decoder memory behind the image tokens; gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_TREE_SCORE 6      /* not a search: score every node of given token trees (a closed candidate set as a trie) in one
+                                        * text pass; gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -299,6 +301,36 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * Like a generate call it replaces the engine's encoded images and prefill (with frames == NULL it scores over the resident
  * images instead: follow-up calls, above gitmi_generate); its workspaces are allocated by the first score call (engines that
  * never score keep their footprint). */
+/* ---- token trees: search->kind == GITMI_SEARCH_TREE_SCORE is GITMI_SEARCH_SCORE with trees in place of sentences: a closed
+ * candidate set (answers of a VQA list, class names, captions to rerank) given as a trie is scored exactly in one call, every
+ * shared prefix passing through the decoder and the vocabulary head once.  "Sentence" q is a tree in DFS pre-order:
+ *   prefixes        : int64 [Q, ld] DEVICE; element i of row q is node i of tree q: low 32 bits = token id (clamped into the
+ *                     vocabulary, as the context kind clamps), high 32 bits = depth.  Node 0 is the root ([CLS]) at depth 0; the
+ *                     parent of node i is the last k < i with depth[k] == depth[i] - 1.
+ *   prefix_len_host : the node counts, 1 <= n_q <= ld.  ld is NOT bounded by max_text_len; the depths are:
+ *                     depth < min(max_text_len, max_pos) (a node's depth is its position embedding); an engine whose bound
+ *                     exceeds 8192 is refused by message (the root path of the structure walk is held on chip).
+ *   image_of_host, Q <= max_batch x max_beams (trees per call), frames or NULL (a follow-up over the resident images, which
+ *                     may carry context: every node then sees [image | context | its ancestors]), ragged image mode: as for score.
+ *   rows            : Q x round_up(max_q n_q, 16) <= 4 194 240 (65535 x 64).  Every row count and launch grid of the pass is a
+ *                     32-bit int and byte offsets are 64-bit; the binding widths are the grids' 65535-block y / z dimensions
+ *                     (attention: padded nodes of a tree / 64, head: rows / 128), and the cap is the smaller, reached by one tree
+ *                     that has all the rows.  A call above it is refused before any launch, the message names the rows asked
+ *                     for; below it, device memory bounds the call (out of memory is an error, nothing is truncated).
+ *   validity        : local -- depth[0] == 0; 1 <= depth[i] <= depth[i-1] + 1 for i >= 1; depth below its bound.  The table is
+ *                     device memory, so the first launch of the call checks it on the device: a tree that fails is rejected --
+ *                     its outputs stay 0, it is counted in info_out[3], and it is given a trivial structure (every node a root)
+ *                     before any other kernel reads it, so no address is ever formed from its depths.  The other trees of the
+ *                     call are not affected.
+ *   logprob_out     : fp32 [Q, ld, 2]; with z the fp32 logits at the row of parent(i), computed over
+ *                     [image (| context) | the ancestors of i, root first]:
+ *                         lp[q, i] = log_softmax(z)[token(i)],   mean_lp[q, i] = sum(z) / V - LSE(z)
+ *                     node 0 and nodes >= n_q: 0.  A tree that is one chain (depth[i] = i) is a sentence and this is score's output.
+ *   tokens_out, sent_out: ignored (may be NULL); info_out = { ld, 0, 0, trees rejected or with a non-finite value }
+ *   the other gitmi_search fields are ignored.  gitmi_generate, gitmi_search_begin and the step seam refuse this kind.
+ * Residency, the eager launch path and the serving schedule are those of a score call.  The node tables and the [Q, ld] output
+ * join the score workspaces at the first tree call and grow on demand: engines that never score trees keep their footprint,
+ * and every other kind returns exactly what it returns without this one. */
 /* ---- attention maps: search->kind == GITMI_SEARCH_ATTEND runs the same text pass over the same inputs with the same checks
  * as GITMI_SEARCH_SCORE (prefixes [Q, ld] DEVICE, prefix_len_host, image_of_host, Q <= max_batch x max_beams, frames or NULL
  * for a follow-up over the resident images) and returns where every token looked instead of how likely it was: the

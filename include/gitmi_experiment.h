@@ -80,13 +80,22 @@ int  gitmi_debug_gemm_form(const void* A, int lda, const void* W, const float* b
  *               the probabilities row (q, j) gives the image keys (columns [0, N_img), 0 past ntok) and its text keys (columns
  *               N_img + t, 0 for t > j).  Runs the attention launch for its softmax statistics first; synchronises the stream.
  *   score_head: out fp32 [M][2] = (log_softmax(z)[tgt[m]], mean_c log_softmax(z)[c]) of z = A [M][K] W [V][K]^T + bias for
- *               rows with tgt[m] >= 0 (0 elsewhere).  Synchronises the stream. */
+ *               rows with tgt[m] >= 0 (0 elsewhere).  Synchronises the stream.
+ *   score_attn_tree: score_attn with the Lp rows of every "sentence" the nodes of a token tree in DFS pre-order
+ *               (GITMI_SEARCH_TREE_SCORE, include/gitmi.h): packed int64 [Q][Lp] DEVICE (depth << 32 | token id), lens int32 [Q]
+ *               DEVICE node counts (<= Lp), max_depth the bound of the depths (<= 8192), ntok as in score_attn_map -> out
+ *               [Q * Lp][H 64]; every row attends to the image keys and to its own ancestors and itself.  Rows past a tree's
+ *               nodes, and every row of a tree that breaks the depth rules, attend to the image and themselves; bad_out int32
+ *               [Q] DEVICE (or NULL) = 1 for such a tree.  Runs the structure launch first; synchronises the stream. */
 int  gitmi_debug_score_attn(const void* qkv, const void* img_kv, const int* image_of, void* out, int Q, int H, int N_img, int Lp,
                             int dtype, void* stream);
 int  gitmi_debug_score_attn_map(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, float* out, int Q, int H,
                                 int N_img, int Lp, int dtype, void* stream);
 int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, const int* tgt, int M, int V, int K, int dtype,
                             float* out, void* stream);
+int  gitmi_debug_score_attn_tree(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, const int64_t* packed,
+                                 const int* lens, int max_depth, void* out, int* bad_out, int Q, int H, int N_img, int Lp, int dtype,
+                                 void* stream);
 
 /* op hooks of the ragged-batch attention (gitmi_set_image_shape(e, 0, 0); tests/test_gpu_ragged_ops.py).  ntok: int32 [B] on the
  * device, the rows of image b (<= N / N_img, which stay the row stride of an image's block); keys past ntok[b] are never used.
