@@ -280,6 +280,7 @@ static void set_resident(gitmi_engine* e, int B, int F_eff, int stride = 0) {
     e->cur_B = B; e->cur_F = F_eff; e->cur_Nimg = stride > 0 ? stride : F_eff * e->N;
     e->have_feats = true; e->have_prefill = false;
     e->keyed = e->ragged; e->has_context = false;
+    e->res_desc.clear();
 }
 // the resident images carry context rows behind their image rows, rg_ntok holds every image's key count
 static void set_context(gitmi_engine* e) { e->keyed = e->has_context = true; }
@@ -316,7 +317,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->sc_allocs) hipFree(p);
-    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab);
+    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -891,6 +892,8 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("%s: GITMI_SEARCH_ATTEND is not a search (gitmi_generate_prefixed returns the attention maps of sentences)", who);
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("%s: GITMI_SEARCH_CONTEXT is not a search (gitmi_generate_prefixed puts context tokens into the decoder memory)", who);
     if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("%s: GITMI_SEARCH_TREE_SCORE is not a search (gitmi_generate_prefixed scores token trees)", who);
+    if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("%s: GITMI_SEARCH_KEEP is not a search (gitmi_generate_prefixed keeps the memory of resident images)", who);
+    if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("%s: GITMI_SEARCH_RECALL is not a search (gitmi_generate_prefixed recalls kept images)", who);
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1200,6 +1203,8 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp && sp->kind == GITMI_SEARCH_ATTEND) return fail("generate: GITMI_SEARCH_ATTEND maps given sentences: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT) return fail("generate: GITMI_SEARCH_CONTEXT takes context segments: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("generate: GITMI_SEARCH_TREE_SCORE scores given token trees: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("generate: GITMI_SEARCH_KEEP keeps the memory of resident images: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("generate: GITMI_SEARCH_RECALL recalls kept images: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1454,9 +1459,208 @@ static int context_call(gitmi_engine* e, const float* const* frames, int F, int 
                                    e->w.emb_lnb, 1e-8f, e->feats, e->pol.f32, nullptr, e->rg_ntok, B, n_img, t.stride, c.vit_width,
                                    c.vocab, c.max_pos, s));
         set_context(e);
+        for (int b = 0; b < B; ++b) e->res_desc.push_back(int4{n_img, t.cnt()[b], e->H, e->W});
         RCK(prefill_impl(e, s));
         HIPCK(hipMemcpyAsync(info_out, tab + 4 * (size_t)Q + B, 4 * sizeof(int), hipMemcpyDefault, s));
         return 0;
+    };
+    const int rc = body();
+    if (rc != 0) drop_resident(e);
+    return rc;
+}
+
+// ---- image memory snapshots (GITMI_SEARCH_KEEP / GITMI_SEARCH_RECALL, include/gitmi.h) ------------------------------------------
+// What a follow-up call reads of an image is its feature rows (a later prefill), the K | V columns of its prefill rows
+// (text pass) and their decode layouts (decode attention; rebuilt by kv_repack), plus its key count.  KEEP copies the first two
+// into a slot of the caller's store, RECALL copies any selection of slots back and rebuilds the third.
+static int memory_cap_rows(const gitmi_engine* e) { return e->cfg.max_frames * e->Nmax; }
+static int memory_elem_dtype(const gitmi_engine* e) { return e->pol.f32 ? GITMI_DTYPE_F32 : gitmi_operand_dtype(); }
+// the geometry of a slot and of the engine's buffers (stride: the rows of an image's block there); fails by message where
+// the configuration does not fit the kernels
+static int memory_args(const gitmi_engine* e, const char* who, int stride, MemoryArgs* out) {
+    const gitmi_config& c = e->cfg;
+    const size_t esz = e->pol.esz, cap = (size_t)memory_cap_rows(e);
+    if (c.dec_layers > MEMORY_MAX_LAYERS) return fail("%s: %d decoder layers, the layer table holds %d", who, c.dec_layers, MEMORY_MAX_LAYERS);
+    if ((c.vit_width * esz) % 16 || (2 * c.dec_hidden * esz) % 16 || (c.dec_hidden * esz) % 16)
+        return fail("%s: rows of %zu and %zu bytes are not multiples of the 16 bytes a lane moves", who, c.vit_width * esz, 2 * c.dec_hidden * esz);
+    MemoryArgs a{};
+    a.feats = e->feats;
+    for (int l = 0; l < c.dec_layers; ++l) a.kv[l] = e->img_kv[l];
+    a.layers = c.dec_layers; a.stride = stride;
+    a.feat_row = (int)(c.vit_width * esz); a.kv_row = (int)(2 * c.dec_hidden * esz);
+    a.kv_ld = (int)(3 * c.dec_hidden * esz); a.kv_col = (int)(c.dec_hidden * esz);
+    a.feat_plane = cap * a.feat_row; a.kv_plane = cap * a.kv_row;
+    a.slot_bytes = (MEMORY_HEADER_BYTES + a.feat_plane + c.dec_layers * a.kv_plane + 255) / 256 * 256;
+    a.ntok = e->rg_ntok; a.meta = nullptr;
+    *out = a;
+    return 0;
+}
+static void memory_fingerprint(const gitmi_engine* e, int* hdr) {
+    const gitmi_config& c = e->cfg;
+    const int fp[MEMW_FP_END - MEMW_FP0] = {c.vit_width, c.dec_hidden, c.dec_layers, c.dec_heads, (int)e->pol.esz, memory_elem_dtype(e),
+                                            memory_cap_rows(e)};
+    for (int i = 0; i < MEMW_FP_END - MEMW_FP0; ++i) hdr[MEMW_FP0 + i] = fp[i];
+}
+static const char* const MEMORY_FP_NAMES[MEMW_FP_END - MEMW_FP0] = {"vit_width", "dec_hidden", "dec_layers", "dec_heads", "element size",
+                                                                     "element dtype", "row capacity"};
+static int memory_table_alloc(gitmi_engine* e, const char* who) {
+    const size_t n = (size_t)e->cfg.max_batch;
+    if (e->mem_tab_n >= n) return 0;
+    hipFree(e->mem_tab);
+    e->mem_tab = nullptr; e->mem_tab_n = 0;
+    // the entries, and behind them room for the first 64 bytes of every slot header of a RECALL (memory_headers)
+    if (hipMalloc((void**)&e->mem_tab, n * (sizeof(MemoryEntry) + MEMORY_HEADER_WORDS * sizeof(int))) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("%s: out of device memory for the table of the call", who);
+    }
+    e->mem_tab_n = n;
+    return 0;
+}
+static int* memory_headers(gitmi_engine* e) { return reinterpret_cast<int*>(e->mem_tab + e->mem_tab_n); }
+// info_out (device or page-locked host) <- four host values; the stream is synchronised so that they may live on the stack
+static int memory_info(const int (&v)[4], int32_t* info_out, hipStream_t s) {
+    HIPCK(hipMemcpyAsync(info_out, v, sizeof(v), hipMemcpyDefault, s));
+    HIPCK(hipStreamSynchronize(s));
+    return 0;
+}
+// the checks KEEP and RECALL share on the store and the slot list
+static int memory_check_store(const char* who, const void* store, int slots, const int32_t* slot_of, int Q) {
+    if (!store) return fail("%s: null store", who);
+    if ((uintptr_t)store & 255) return fail("%s: the store's base address %p is not 256-byte aligned", who, store);
+    if (slots < 1) return fail("%s: a store of %d slots", who, slots);
+    if (!slot_of) return fail("%s: null slot list (prefix_len_host)", who);
+    for (int q = 0; q < Q; ++q)
+        if (slot_of[q] < 0 || slot_of[q] >= slots) return fail("%s: entry %d names slot %d of a store of %d slots", who, q, slot_of[q], slots);
+    return 0;
+}
+
+static int memory_keep(gitmi_engine* e, const float* const* frames, int B, void* store, int slots, const int32_t* slot_of,
+                       const int32_t* image_of, int Q, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    if (!info_out) return fail("keep: null info_out");
+    MemoryArgs a;
+    RCK(memory_args(e, "keep", 1, &a));
+    const int units = (int)(a.slot_bytes / 256);
+    if (Q == 0) return memory_info({units, 0, 0, 0}, info_out, s);         // the size query
+    if (frames) return fail("keep: frames != NULL: KEEP runs over the resident images (encode them with a call of their own)");
+    RCK(check_resident(e, "keep", B));
+    if (Q < 1 || Q > c.max_batch) return fail("keep: Q=%d images outside [1,%d] (max_batch)", Q, c.max_batch);
+    if (!image_of && Q != B) return fail("keep: without image_of, Q must equal B");
+    RCK(memory_check_store("keep", store, slots, slot_of, Q));
+    for (int q = 0; q < Q; ++q) {
+        const int im = image_of ? image_of[q] : q;
+        if (im < 0 || im >= B) return fail("keep: entry %d names image %d of %d", q, im, B);
+        for (int p = 0; p < q; ++p)
+            if (slot_of[p] == slot_of[q]) return fail("keep: entries %d and %d both write slot %d", p, q, slot_of[q]);
+    }
+    RCK(memory_table_alloc(e, "keep"));
+    RCK(images_ready(e, Request{}, s));             // after gitmi_encode_frames alone: the prefill first, as a follow-up does
+    // what the host has to know of every image: a ragged batch keeps it on the device
+    HIPCK(hipStreamSynchronize(s));
+    std::vector<int4> meta;
+    if (e->res_desc.empty() && e->ragged) {
+        meta.resize(B);
+        HIPCK(hipMemcpy(meta.data(), e->rg_meta, (size_t)B * sizeof(int4), hipMemcpyDeviceToHost));
+    }
+    std::vector<MemoryEntry> tab(Q);
+    int max_n = 0, sum_n = 0;
+    for (int q = 0; q < Q; ++q) {
+        const int im = image_of ? image_of[q] : q;
+        MemoryEntry& en = tab[q];
+        memset(&en, 0, sizeof(en));
+        int* h = en.hdr;
+        h[MEMW_MAGIC] = MEMORY_MAGIC; h[MEMW_VERSION] = 1;
+        memory_fingerprint(e, h);
+        h[MEMW_F] = e->cur_F;
+        if (!e->res_desc.empty()) {
+            const int4 d = e->res_desc[im];
+            h[MEMW_IMG_ROWS] = d.x; h[MEMW_CTX_ROWS] = d.y; h[MEMW_H] = d.z; h[MEMW_W] = d.w;
+        } else if (e->ragged) {
+            h[MEMW_IMG_ROWS] = meta[im].z; h[MEMW_H] = meta[im].x; h[MEMW_W] = meta[im].y; h[MEMW_REJECTED] = meta[im].w != 0;
+        } else {
+            h[MEMW_IMG_ROWS] = e->cur_Nimg; h[MEMW_H] = e->H; h[MEMW_W] = e->W;
+        }
+        h[MEMW_N] = h[MEMW_IMG_ROWS] + h[MEMW_CTX_ROWS];
+        if (h[MEMW_N] < 0 || h[MEMW_N] > e->cur_Nimg || h[MEMW_N] > memory_cap_rows(e))
+            return fail("keep: image %d has %d rows, its block holds %d", im, h[MEMW_N], e->cur_Nimg);
+        en.image = im; en.slot = slot_of[q]; en.n = h[MEMW_N];
+        max_n = std::max(max_n, en.n); sum_n += en.n;
+    }
+    HIPCK(hipMemcpy(e->mem_tab, tab.data(), (size_t)Q * sizeof(MemoryEntry), hipMemcpyHostToDevice));
+    a.stride = e->cur_Nimg;
+    HIPCK(launch_memory_pack(a, store, e->mem_tab, Q, max_n, s));
+    return memory_info({units, max_n, sum_n, 0}, info_out, s);
+}
+
+static int memory_recall(gitmi_engine* e, const float* const* frames, int B, const void* store, int slots, const int32_t* slot_of,
+                         const int32_t* image_of, int Q, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    if (frames) return fail("recall: frames != NULL: RECALL forms its images from kept slots");
+    if (!info_out) return fail("recall: null info_out");
+    if (image_of) return fail("recall: image_of_host must be NULL (slot q becomes image q)");
+    if (Q < 1 || Q > c.max_batch) return fail("recall: Q=%d images outside [1,%d] (max_batch)", Q, c.max_batch);
+    if (B != Q) return fail("recall: B=%d must equal Q=%d, the number of images to form", B, Q);
+    RCK(memory_check_store("recall", store, slots, slot_of, Q));
+    const int cap = memory_cap_rows(e);
+    MemoryArgs a;
+    RCK(memory_args(e, "recall", 1, &a));
+    RCK(memory_table_alloc(e, "recall"));
+    // the headers, validated on the host before anything is launched: gathered on the device (one small copy per slot,
+    // enqueued), then one copy to the host and one synchronisation -- not a blocking read per slot
+    const size_t hbytes = MEMORY_HEADER_WORDS * sizeof(int);
+    for (int q = 0; q < Q; ++q)
+        HIPCK(hipMemcpyAsync(memory_headers(e) + (size_t)q * MEMORY_HEADER_WORDS, (const char*)store + (size_t)slot_of[q] * a.slot_bytes,
+                             hbytes, hipMemcpyDefault, s));
+    std::vector<int> headers((size_t)Q * MEMORY_HEADER_WORDS);
+    HIPCK(hipMemcpyAsync(headers.data(), memory_headers(e), (size_t)Q * hbytes, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    std::vector<MemoryEntry> tab(Q);
+    int want[MEMORY_HEADER_WORDS] = {};
+    memory_fingerprint(e, want);
+    int max_n = 0, sum_n = 0, F = 0;
+    bool uniform = !e->ragged, context = false;
+    for (int q = 0; q < Q; ++q) {
+        MemoryEntry& en = tab[q];
+        memset(&en, 0, sizeof(en));
+        const int slot = slot_of[q];
+        int* h = en.hdr;
+        memcpy(h, headers.data() + (size_t)q * MEMORY_HEADER_WORDS, hbytes);
+        if (h[MEMW_MAGIC] != MEMORY_MAGIC || h[MEMW_VERSION] != 1)
+            return fail("recall: slot %d: bad magic 0x%08x / version %d (nothing was kept there)", slot, (unsigned)h[MEMW_MAGIC], h[MEMW_VERSION]);
+        for (int i = MEMW_FP0; i < MEMW_FP_END; ++i)
+            if (h[i] != want[i])
+                return fail("recall: slot %d: fingerprint mismatch: %s is %d in the slot, %d in this engine (kept by another model, "
+                            "precision or capacity)", slot, MEMORY_FP_NAMES[i - MEMW_FP0], h[i], want[i]);
+        const int n = h[MEMW_N];
+        if (n < 1 || n > cap) return fail("recall: slot %d: n=%d rows outside [1,%d], the per-image capacity", slot, n, cap);
+        if (h[MEMW_IMG_ROWS] < 1 || h[MEMW_CTX_ROWS] < 0 || h[MEMW_IMG_ROWS] + h[MEMW_CTX_ROWS] != n)
+            return fail("recall: slot %d: %d image rows + %d context rows do not make n=%d", slot, h[MEMW_IMG_ROWS], h[MEMW_CTX_ROWS], n);
+        if (h[MEMW_REJECTED]) return fail("recall: slot %d: the rejected flag is set (a ragged entry the device refused was kept)", slot);
+        if (h[MEMW_F] < 1 || h[MEMW_F] > c.max_frames) return fail("recall: slot %d: F=%d frames outside [1,%d]", slot, h[MEMW_F], c.max_frames);
+        if (q == 0) F = h[MEMW_F];
+        if (h[MEMW_F] != F) return fail("recall: slot %d: F=%d frames, slot %d has F=%d (one batch, one F)", slot, h[MEMW_F], slot_of[0], F);
+        uniform = uniform && h[MEMW_CTX_ROWS] == 0 && n == F * e->N;
+        context = context || h[MEMW_CTX_ROWS] > 0;
+        en.image = q; en.slot = slot; en.n = n;
+        max_n = std::max(max_n, n); sum_n += n;
+    }
+    // the mode: exactly the state the original call left where that is a uniform batch of the current shape, else key counts
+    const int stride = uniform ? F * e->N : round_up(max_n, 16) <= cap ? round_up(max_n, 16) : max_n;
+    HIPCK(hipMemcpy(e->mem_tab, tab.data(), (size_t)Q * sizeof(MemoryEntry), hipMemcpyHostToDevice));
+    a.stride = stride;
+    a.meta = e->ragged ? e->rg_meta : nullptr;
+    auto body = [&]() -> int {
+        drop_resident(e);               // the workspaces are overwritten from here on
+        HIPCK(launch_memory_unpack(a, store, e->mem_tab, Q, s));
+        for (int l = 0; l < c.dec_layers; ++l) RCK(kv_repack(e, l, Q, stride, s));
+        set_resident(e, Q, F, stride);
+        if (!uniform) {
+            e->keyed = true; e->has_context = context;
+            for (int q = 0; q < Q; ++q)
+                e->res_desc.push_back(int4{tab[q].hdr[MEMW_IMG_ROWS], tab[q].hdr[MEMW_CTX_ROWS], tab[q].hdr[MEMW_H], tab[q].hdr[MEMW_W]});
+        }
+        set_prefilled(e);
+        return memory_info({stride, max_n, sum_n, 0}, info_out, s);
     };
     const int rc = body();
     if (rc != 0) drop_resident(e);
@@ -1474,6 +1678,10 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     SentenceSpan span;
     if (sp && sp->kind == GITMI_SEARCH_CONTEXT)
         return context_call(e, frames, F, B, (const long long*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
+    if (sp && sp->kind == GITMI_SEARCH_KEEP)
+        return memory_keep(e, frames, B, logprob_out, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
+    if (sp && sp->kind == GITMI_SEARCH_RECALL)
+        return memory_recall(e, frames, B, prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {
         const bool attend = sp->kind == GITMI_SEARCH_ATTEND, tree = sp->kind == GITMI_SEARCH_TREE_SCORE;
         const char* who = attend ? "attend" : tree ? "tree_score" : "score";

@@ -169,6 +169,13 @@ struct gitmi_engine {
     bool has_context = false;          // the resident images' blocks are [image rows | context rows | zeros], cur_Nimg rows each
     int* ctx_tab = nullptr;            // segment table of the last context call (engine.hip context_call), grown on demand
     size_t ctx_tab_ints = 0;
+    // image memory snapshots (GITMI_SEARCH_KEEP / _RECALL, engine.hip memory_keep / memory_recall): the device table of a call,
+    // allocated by the first such call, and what only the host knows about the resident images: {image rows, context rows, h, w}
+    // of each after a context call or a recall (empty: every image is cur_Nimg image rows of the current shape, or -- ragged
+    // front end -- what rg_meta says)
+    gitmi::MemoryEntry* mem_tab = nullptr;
+    size_t mem_tab_n = 0;
+    std::vector<int4> res_desc;
 
     // ViT workspaces (one frame of max_batch images at a time)
     void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;

@@ -147,6 +147,36 @@ hipError_t launch_chain_input(const float* x, void* xb_frag, float2* stats, int 
 hipError_t launch_copy_f32(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t s);
 hipError_t launch_fill_i32(int* dst, int value, int n, hipStream_t s);
 
+// ---- image memory snapshots (GITMI_SEARCH_KEEP / _RECALL, include/gitmi.h; kernels_memory.hip) ----
+// A slot of the caller's store: [256-byte header | feature plane: cap rows of feat_row bytes | one plane per decoder layer: cap
+// rows of kv_row bytes, the K | V columns of a prefill row], cap = the engine's per-image row capacity; the first n rows of
+// every plane are valid, the rest of a slot is never read.  Plane offsets depend on the configuration alone.
+constexpr int MEMORY_MAX_LAYERS = 31;       // layer pointers travel by value
+constexpr int MEMORY_HEADER_BYTES = 256, MEMORY_HEADER_WORDS = 16;
+constexpr int MEMORY_MAGIC = 0x4d495447;    // "GTIM"
+// header words: 0 magic, 1 format version, 2..8 the fingerprint (vit_width, dec_hidden, dec_layers, dec_heads, element size,
+// element dtype, row capacity), 9 n, 10 image rows, 11 context rows, 12 frames F, 13 / 14 the image's {h, w}, 15 rejected
+enum { MEMW_MAGIC = 0, MEMW_VERSION = 1, MEMW_FP0 = 2, MEMW_FP_END = 9, MEMW_N = 9, MEMW_IMG_ROWS = 10, MEMW_CTX_ROWS = 11,
+       MEMW_F = 12, MEMW_H = 13, MEMW_W = 14, MEMW_REJECTED = 15 };
+// one table entry per image of a call (DEVICE copy of what the host validated): the kernels take n and the header from here,
+// never from the bytes of a slot
+struct MemoryEntry {
+    int image, slot, n, rsv;                // block of the engine's buffers, slot of the store, valid rows
+    int hdr[MEMORY_HEADER_WORDS + 4];       // the slot header (pack: written as is; unpack: h, w for rg_meta); padded to 16 bytes
+};
+struct MemoryArgs {
+    void* feats;                            // [B][stride][feat_row bytes]
+    void* kv[MEMORY_MAX_LAYERS];            // per layer [B][stride][kv_ld bytes]; the K | V columns start kv_col bytes into a row
+    int layers, stride;                     // stride: rows of an image's block in the engine's buffers
+    int feat_row, kv_row, kv_ld, kv_col;    // bytes, multiples of 16
+    size_t slot_bytes, feat_plane, kv_plane;        // bytes of a slot and of its planes (cap rows each)
+    int* ntok; int4* meta;                  // unpack: ntok[q] = n (and meta[q] = {h, w, n, 0} when not nullptr)
+};
+// grid (row tiles of 16, 1 + layers, entries): slot <- the n valid rows of image `image`, and its header
+hipError_t launch_memory_pack(const MemoryArgs& a, void* store, const MemoryEntry* tab, int entries, int max_n, hipStream_t s);
+// block `image` <- the n rows of slot `slot`, zeros in rows [n, stride), the key count
+hipError_t launch_memory_unpack(const MemoryArgs& a, const void* store, const MemoryEntry* tab, int entries, hipStream_t s);
+
 struct AttnFullArgs {
     const void* q; const void* k; const void* v; void* out;
     int ldq, ldk, ldv, ldo;

@@ -26,6 +26,16 @@ SEARCH_SCORE = 3     # not a search: gitmi_generate_prefixed scores given senten
 SEARCH_ATTEND = 4    # not a search: gitmi_generate_prefixed returns the attention maps of given sentences (Engine.attend)
 SEARCH_CONTEXT = 5   # not a search: gitmi_generate_prefixed puts context tokens into the decoder memory (Engine.encode_context)
 SEARCH_TREE_SCORE = 6  # not a search: gitmi_generate_prefixed scores every node of given token trees (Engine.score_tree)
+SEARCH_KEEP = 7        # not a search: gitmi_generate_prefixed copies the memory of resident images into a caller's store (Engine.keep)
+SEARCH_RECALL = 8      # not a search: gitmi_generate_prefixed makes kept slots the resident images (Engine.recall)
+MEMORY_HEADER_BYTES = 256      # header of a slot of an image store; slots are multiples of this size (include/gitmi.h)
+
+
+def memory_slot_bytes(vit_width: int, dec_hidden: int, dec_layers: int, rows: int, esz: int) -> int:
+    """Bytes of one slot of an image store (include/gitmi.h GITMI_SEARCH_KEEP): the header, then `rows` (the engine's per-image
+    row capacity) feature rows and K | V rows of every decoder layer in elements of esz bytes, rounded up to 256."""
+    raw = MEMORY_HEADER_BYTES + int(rows) * (int(vit_width) + int(dec_layers) * 2 * int(dec_hidden)) * int(esz)
+    return -(-raw // MEMORY_HEADER_BYTES) * MEMORY_HEADER_BYTES
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
 
 EXPORTED_SYMBOLS = [
@@ -634,6 +644,104 @@ class Engine:
             assert max_c == max(counts) and total == sum(counts) and stride >= Nk + max_c
         self._encoded(rc, B)
         return {"stride": stride, "max_context": max_c, "context_rows": total}
+
+    # -- image memory snapshots: keep encoded images in a caller's store, recall any mix of them later ---------------------------
+    @property
+    def memory_rows(self) -> int:
+        """Rows per image the workspaces are sized for (max_frames x max_tokens): the row capacity of a store slot."""
+        return int(self.c.max_frames) * self.max_tokens
+
+    def memory_slot_bytes(self) -> int:
+        """Bytes of one slot of an image store of this engine (include/gitmi.h GITMI_SEARCH_KEEP): a function of the
+        configuration alone, the same for every clone."""
+        esz = 4 if self.precision in ("f32", "fp32") else 2
+        return memory_slot_bytes(self.c.vit_width, self.c.dec_hidden, self.c.dec_layers, self.memory_rows, esz)
+
+    def memory_store(self, slots: int) -> torch.Tensor:
+        """A store of `slots` slots for keep / recall: uint8 [slots, memory_slot_bytes()] on the engine's device (torch's
+        allocator aligns it to 256 bytes and more)."""
+        return torch.empty(int(slots), self.memory_slot_bytes(), dtype=torch.uint8, device=f"cuda:{self.device}")
+
+    def _store_arg(self, store: torch.Tensor) -> int:
+        """-> the slots of `store`, a uint8 tensor [S, slot_bytes] on the engine's device (contiguous, 256-byte aligned)"""
+        nbytes = self.memory_slot_bytes()
+        if not isinstance(store, torch.Tensor) or store.dtype != torch.uint8 or store.dim() != 2 or int(store.shape[1]) != nbytes:
+            raise ValueError(f"an image store is a uint8 tensor [slots, {nbytes}], got {getattr(store, 'dtype', type(store))} "
+                             f"{tuple(getattr(store, 'shape', ()))}")
+        if store.device != torch.device(f"cuda:{self.device}") or not store.is_contiguous():
+            raise ValueError("an image store must be contiguous on the engine's device")
+        return int(store.shape[0])
+
+    def _memory_call(self, kind: int, B: int, store_ptr: Optional[int], S: int, slots, images) -> List[int]:
+        """gitmi_generate_prefixed with GITMI_SEARCH_KEEP / _RECALL -> info [4]; the call synchronises the stream itself."""
+        search = GitmiSearch()
+        search.kind = kind
+        Q = len(slots)
+        info = torch.zeros(4, dtype=torch.int32, device=f"cuda:{self.device}")
+        slot_arr, img_arr = _sentence_tables([int(s) for s in slots], images) if Q else (None, None)
+        keep, recall = (store_ptr, None) if kind == SEARCH_KEEP else (None, store_ptr)
+        self._ck(self.lib.gitmi_generate_prefixed(self._h, None, 0, int(B), recall, int(S), slot_arr, img_arr, Q, C.byref(search),
+                                                  None, keep, None, info.data_ptr(), _stream()))
+        return [int(v) for v in info.tolist()]
+
+    def keep(self, store: torch.Tensor, slots: Sequence[int], images: Optional[Sequence[int]] = None) -> Dict[str, object]:
+        """Copy the encoded memory of resident images into slots of `store` (uint8 [S, memory_slot_bytes()] on the device):
+        resident image images[q] (default: image q, all of them) goes to slot slots[q], every slot at most once per call.
+        Residency does not change.  The blobs are plain bytes: Engine.recall on any context of the same model, precision
+        and capacity -- a clone, or another engine after a copy through the host -- brings the images back.
+        -> {'rows': [n per kept image], 'max_rows', 'total_rows', 'geometry': [per kept image (F, (grid h, grid w), image rows,
+        context rows)], what recall(geometry=...) takes}"""
+        S = self._store_arg(store)
+        B = int(self._resident or 0)                # none resident: the library refuses by name
+        info = self._memory_call(SEARCH_KEEP, B, store.data_ptr(), S, list(slots), images)
+        geo = self._geometry
+        if geo is None:                             # images imported through a debug hook: the host knows no geometry
+            return {"rows": None, "max_rows": info[1], "total_rows": info[2], "geometry": None}
+        per = []
+        for q in range(len(slots)):
+            b = q if images is None else int(images[q])
+            ctx = geo.context[b] if isinstance(geo, Geometry) else 0
+            rows = geo.image_rows if isinstance(geo, Geometry) else geo[0]
+            if getattr(geo, "rows", None):                                   # a recalled mix: every image its own image rows
+                rows = geo.rows[b]
+            if self._hw == (0, 0) and not isinstance(geo, Geometry):       # ragged: every image its own grid inside max_tokens rows
+                rows = geo[2][b][0] * geo[2][b][1] + 1
+            per.append((geo[1], tuple(geo[2][b]), int(rows), int(ctx)))
+        return {"rows": [p[2] + p[3] for p in per], "max_rows": info[1], "total_rows": info[2], "geometry": per}
+
+    def recall(self, store: torch.Tensor, slots: Sequence[int], geometry=None) -> Dict[str, int]:
+        """Make the images kept in `slots` of `store` (any order, repeats, from different earlier calls or contexts) the resident
+        batch of this context: slot slots[q] becomes image q.  Every follow-up call (frames=None) then runs over them.
+        The library validates every slot header on the host before anything is launched; a refusal raises GitmiError naming
+        the slot and the field and leaves the resident set as it was.
+        geometry: per slot what keep returned for it ('geometry': (F, grid, image rows, context rows)); gives
+        resident_geometry its grids (attend's patch_grid) -- without it the grids are unknown (None).
+        -> {'stride', 'max_rows', 'total_rows'}"""
+        S = self._store_arg(store)
+        Q = len(slots)
+        if geometry is not None and len(geometry) != Q:
+            raise ValueError(f"geometry has {len(geometry)} entries for {Q} slots")
+        old = self._resident
+        try:
+            info = self._memory_call(SEARCH_RECALL, Q, store.data_ptr(), S, list(slots), None)
+        except GitmiError as err:
+            # an argument error ("recall: ...") is found before any launch: the images of before stay resident; a failed launch drops them
+            if old is not None and not str(err).startswith("recall:"):
+                self._drop_resident()
+            raise
+        stride, max_n, total, _ = info
+        self._generation += 1
+        self._resident = Q
+        F = int(geometry[0][0]) if geometry else 1
+        grids = [tuple(g[1]) for g in geometry] if geometry else [None] * Q
+        ctx = [int(g[3]) for g in geometry] if geometry else [0] * Q
+        rows = [int(g[2]) for g in geometry] if geometry else [stride] * Q
+        if any(ctx) or any(r != stride for r in rows):
+            self._geometry = Geometry(stride, F, grids, image_rows=max(rows), context=ctx)
+            self._geometry.rows = rows
+        else:
+            self._geometry = (stride, F, grids)
+        return {"stride": stride, "max_rows": max_n, "total_rows": total}
 
     def prefill(self) -> None:
         self._ck(self.lib.gitmi_prefill(self._h, _stream()))

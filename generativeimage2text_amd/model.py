@@ -1002,6 +1002,120 @@ class Pending:
         return self._value
 
 
+class ImageStore:
+    """Encoded images kept beyond the call that encoded them (include/gitmi.h GITMI_SEARCH_KEEP / GITMI_SEARCH_RECALL): one device
+    tensor of `capacity` slots, caller keys mapped to slots, the least recently used key evicted when a new one needs a slot.
+
+        first = model.submit({'image': images}); first.result()
+        store.put(first, keys=['a', 'b', 'c'])                  # after any number of other requests, on any context:
+        h = store.recall(['c', 'a', 'c'])                       # image 0 = 'c', image 1 = 'a', image 2 = 'c' again
+        model.submit_followup({'prefixes': qs, 'image_of': [0, 1, 2]}, on=h).result()
+
+    The handle recall returns is accepted as on= wherever a Pending is (submit_followup, submit_answers(None, ...), score(None, ...),
+    rank(None, ...), attend(None, ...)); StaleImagesError is raised once another call has replaced the images on its context.
+    With a pipelined model (set_pipeline) put reads from the context that produced the result and recall binds its handle to
+    the context that performed it.  The slots are plain bytes of this model's weights: `tensor` may be saved and loaded."""
+
+    def __init__(self, model: "CaptioningModel", capacity: int):
+        if int(capacity) < 1:
+            raise ValueError("an image store needs at least one slot")
+        eng = model.engine
+        self.model, self.capacity = model, int(capacity)
+        self.tensor = eng.memory_store(self.capacity)
+        self._entries: Dict[object, tuple] = {}          # key -> (slot, geometry of the kept image); insertion order = LRU order
+        self._free = list(range(self.capacity - 1, -1, -1))
+
+    def __contains__(self, key) -> bool:
+        return key in self._entries
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    def keys(self):
+        """The keys held, least recently used first."""
+        return list(self._entries)
+
+    def evict(self, key) -> None:
+        slot, _ = self._entries.pop(key)
+        self._free.append(slot)
+
+    def _touch(self, key) -> None:
+        self._entries[key] = self._entries.pop(key)
+
+    def _slot_for(self, key, pinned) -> int:
+        """The slot `key` is (over)written in: its own, a free one, or the least recently used key's that is not in `pinned`."""
+        if key in self._entries:
+            return self._entries[key][0]
+        if not self._free:
+            victim = next((k for k in self._entries if k not in pinned), None)
+            if victim is None:
+                raise ValueError(f"{len(pinned)} keys in one call exceed the {self.capacity} slots of the store")
+            self.evict(victim)
+        return self._free.pop()
+
+    def _on(self, eng, fn):
+        """fn() on the stream of the pipeline context `eng` (ordered behind its own work), or on the caller's stream"""
+        for c, st in zip(getattr(self.model, "_ctxs", None) or [], getattr(self.model, "_streams", None) or []):
+            if c is eng and st is not None:
+                st.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(st):
+                    return fn()
+        return fn()
+
+    def put(self, source, keys: Sequence, images: Optional[Sequence[int]] = None) -> None:
+        """Keep images of a finished call: `source` is the Pending of the call that encoded them (or a recall handle), or the
+        result it returned; key keys[q] names resident image images[q] (default: image q).  A key already held is overwritten
+        in its slot.  Raises StaleImagesError if the context no longer holds the images of `source`."""
+        pending = getattr(source, "pending", source)
+        if not isinstance(pending, Pending) or pending.engine is None:
+            raise TypeError("put takes the Pending of the call that encoded the images, or the result it returned")
+        eng = pending.engine
+        if eng.generation != pending.generation or eng.resident is None:
+            raise StaleImagesError("the images of this handle are no longer resident on its context: another call has replaced "
+                                   "them (or a setter dropped them) since it was issued")
+        keys = list(keys)
+        images = list(range(len(keys))) if images is None else [int(i) for i in images]
+        if len(images) != len(keys) or len(set(keys)) != len(keys):
+            raise ValueError("put needs one image index per key, every key once")
+        if any(i < 0 or i >= eng.resident for i in images):
+            raise ValueError(f"images must name some of the {eng.resident} resident images")
+        if len(keys) > self.capacity:
+            raise ValueError(f"{len(keys)} keys in one call exceed the {self.capacity} slots of the store")
+        slots = [self._slot_for(k, keys) for k in keys]
+        try:
+            kept = self._on(eng, lambda: eng.keep(self.tensor, slots, images))
+        except Exception:
+            for k, s in zip(keys, slots):       # nothing is known about what the slots hold now
+                if k in self._entries:
+                    self.evict(k)
+                else:
+                    self._free.append(s)
+            raise
+        for k, s, g in zip(keys, slots, kept["geometry"]):
+            self._entries.pop(k, None)
+            self._entries[k] = (s, g)
+
+    def recall(self, keys: Sequence, context=None) -> "Pending":
+        """Make the images of `keys` (any order, repeats) the resident batch of an engine context -- `context`, default the next
+        one in the model's rotation -- and return the handle follow-up requests take as on=: image q of the batch is keys[q].
+        `.result()`: {'stride', 'max_rows', 'total_rows'}.  KeyError for a key that is not held (never kept, or evicted)."""
+        keys = list(keys)
+        missing = [k for k in keys if k not in self._entries]
+        if missing:
+            raise KeyError(f"not in the image store (never kept, or evicted): {missing[:4]}")
+        if context is None:
+            eng, _ = self.model._context()
+        else:
+            eng = context
+            self.model._last = eng
+        slots = [self._entries[k][0] for k in keys]
+        geometry = [self._entries[k][1] for k in keys]
+        for k in keys:
+            self._touch(k)
+        info = self._on(eng, lambda: eng.recall(self.tensor, slots, geometry))
+        return Pending(None, lambda: info, lambda out: dict(out), engine=eng)
+
+
 def get_git_model(tokenizer, param: Optional[dict], precision: str = "f16", max_batch: int = 64,
                   decoder=None, device: Optional[int] = None, max_context: int = 0) -> CaptioningModel:
     """Same role as the reference's get_git_model (model.py:9-61): GIT decoder hyper-parameters are

@@ -55,6 +55,10 @@ extern "C" {
                                         * the decoder memory behind the image tokens; gitmi_generate_prefixed only, see there */
 #define GITMI_SEARCH_TREE_SCORE 6      /* not a search: score every node of given token trees (a closed candidate set as a trie) in one
                                         * text pass; gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_KEEP   7          /* not a search: copy the encoded memory of resident images into slots of a caller-owned
+                                        * store; gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_RECALL 8          /* not a search: make any selection of kept slots the resident images of a context;
+                                        * gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -387,6 +391,60 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * (the reference's torch.cat fails there too), a length outside its range.  gitmi_generate and gitmi_search_begin refuse this
  * kind.  The segment table's device copy is allocated by the first context call: engines that never take context keep their
  * footprint. */
+/* ---- image memory snapshots: search->kind == GITMI_SEARCH_KEEP takes the encoded memory of resident images out of a context
+ * into caller-owned device memory; GITMI_SEARCH_RECALL later puts any selection of kept images -- any order, repeats, from
+ * different earlier calls and contexts -- back as the resident batch of any context of the same model.  Every follow-up form
+ * (frames == NULL) then runs over the recalled batch unchanged: a late question about an image costs neither the image encoder
+ * nor the prefill.  Both are "not a search": gitmi_generate and gitmi_search_begin refuse them by name, the other gitmi_search
+ * fields are ignored, both run eagerly (no hipGraph) and synchronise the stream.
+ * The store is the CALLER's: ONE device buffer of slots x slot_bytes, 256-byte aligned.  The engine allocates nothing for it and
+ * keeps no pointer to it after a call returns.  slot_bytes depends on the engine's configuration alone:
+ *     slot_bytes = round_up(256 + cap x (vit_width + dec_layers x 2 x dec_hidden) x esz, 256)
+ * cap = max_frames x max(N, max_image_tokens), the rows per image the workspaces are sized for; esz = 4 (GITMI_PREC_F32) or 2.
+ * A slot is [256-byte header | cap feature rows | per decoder layer: cap rows of the K | V columns of the prefill]; the first n
+ * rows of each are written (n = the image's own key count: image rows + context rows), the rest of a slot is never read.
+ * The header: a magic word and a format version; the fingerprint { vit_width, dec_hidden, dec_layers, dec_heads, element size,
+ * element dtype (GITMI_DTYPE_*), cap }; n, image rows, context rows, frames F; the image's { h, w } and, for a ragged entry,
+ * its rejected flag.  (gitmi_set_ln_fold changes roundings, not what the rows mean: it is not part of the fingerprint.)
+ * The slots are plain bytes: copied through host memory or a file and recalled into any context of the same model, precision and
+ * capacity they mean the same thing; clones are the main case.  Bytes of another model, precision or capacity are caught by the
+ * fingerprint.  The engine CANNOT tell whether the weights are the same: recalling into a context that holds other weights of
+ * the same shape is the caller's error and goes unnoticed.
+ * KEEP, the argument mapping:
+ *   frames          : must be NULL: KEEP runs over the resident images, B = their count (as for every follow-up call).  After
+ *                     gitmi_encode_frames alone it runs the prefill first.
+ *   logprob_out     : the store's base address (written as bytes), 256-byte aligned;  ld_prefix: the slots it has
+ *   image_of_host   : int32 [Q], the resident image entry q keeps, or NULL: Q == B, entry q <-> image q
+ *   prefix_len_host : int32 [Q], the destination slot of entry q, in [0, slots), each slot at most once per call
+ *   Q               : 1 .. max_batch.  Q == 0 is the size query: info_out[0] = slot_bytes / 256, nothing else is read or
+ *                     written (no store, no resident images needed)
+ *   info_out        : { slot_bytes / 256, max_q n_q, sum_q n_q, 0 };  prefixes, tokens_out, sent_out: ignored (may be NULL)
+ *   One launch writes, for every entry, the header, the image's n feature rows and the K | V columns of its n rows of every
+ *   layer (the Q columns are dead after the prefill).  KEEP changes nothing about residency.
+ * RECALL, the argument mapping:
+ *   frames          : must be NULL; no resident images are needed (what is resident is replaced)
+ *   B == Q          : the images to form, 1 .. max_batch;  image_of_host: must be NULL
+ *   prefixes        : the store's base address (read as bytes), 256-byte aligned;  ld_prefix: the slots it has
+ *   prefix_len_host : int32 [Q], the slot that becomes image q; repeats are allowed
+ *   info_out        : { row stride of an image's block, max_q n_q, sum_q n_q, 0 };  tokens_out, logprob_out, sent_out: ignored
+ *   The call synchronises the stream, copies the Q headers to the host and validates them BEFORE any launch: the magic and the
+ *   version, every field of the fingerprint, 1 <= n <= cap, image rows + context rows == n, the rejected flag clear,
+ *   1 <= F <= max_frames and the same F in all slots.  A failure is an argument error whose message names the slot and the
+ *   field: nothing is launched and what was resident stays resident.  The kernels form no address from the bytes of a slot:
+ *   n reaches them through the validated host copy.  Then one launch scatters every slot's rows into image block q of the
+ *   feature tensor and of every layer's prefill K/V, zeroes the rows from n_q up to the block's stride and writes the key
+ *   counts (and, in ragged image mode, the per-image descriptors); the decode layouts are rebuilt by the prefill's own repack
+ *   launch per layer, so they keep a single writer.  Afterwards the engine is in the state of a prefilled encode.
+ *   Mode: if every slot has n == F x N of the engine's current uniform image shape and no context rows, the batch is restored
+ *   WITHOUT key counts: exactly the state the original call left, and a follow-up returns what it returned there bit for bit in
+ *   every precision.  Otherwise (ragged image mode included) it is a key-count batch, as after a context call: stride =
+ *   max_q n_q rounded up to a multiple of 16 where cap allows, attention reads n_q keys of image q, and the batch counts as
+ *   context-carrying if any slot has context rows (GITMI_SEARCH_ATTEND keeps its refusal there).  Each sentence gets what a
+ *   call with its image alone gets (bit for bit in the f32 mode).
+ *   Afterwards gitmi_generate(NULL, ...) with every search, gitmi_generate_prefixed(NULL, ...), GITMI_SEARCH_SCORE, _TREE_SCORE,
+ *   _ATTEND and KEEP itself run over the recalled images; the follow-up graph is keyed on B, the stride and the mode already.
+ * Both kinds allocate one small device table (max_batch entries) at their first call: engines that never keep or recall keep
+ * their footprint. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

@@ -10,7 +10,8 @@
 #     configs  bench lines of the other BASELINE configurations (beam 4, GIT_LARGE bs 32, VATEX 6 frames bs 16), bf16 and f16 builds
 #     smoke    __graft_entry__.smoke()
 #     attrib   tools/error_attribution.py on the benchmark's, the oracle's and the trained-statistics weights -> TAG_error_attribution_*.txt
-# The bench, stats and configs sections write to $BENCH_OUT (default out/), the other sections where their tools write;
+#     memory   tools/memory_bench.py: KEEP / RECALL + follow-up against the full call, GIT_BASE 224 x 224, 64 images, f16 -> TAG_memory_bench.json
+# The bench, stats, configs and memory sections write to $BENCH_OUT (default out/), the other sections where their tools write;
 # copy what is cited into profiles/.
 set -u; mkdir -p gpurun_out; export PYTHONUNBUFFERED=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 R=$PWD; TAG=${1:-collect}; shift || true; SECTIONS=${*:-pmc bench stats suite configs smoke}
@@ -56,6 +57,9 @@ attrib)
     t "error attribution: $wt weights"; timeout 300 python tools/error_attribution.py --weights $wt --out gpurun_out/${TAG}_error_attribution_$wt.txt > gpurun_out/${TAG}_attrib_$wt.log 2>&1; echo "rc=$?"
     cat gpurun_out/${TAG}_error_attribution_$wt.txt | cut -c1-170
   done ;;
+memory)
+  t "memory bench"; timeout 300 python tools/memory_bench.py --out $OUT/${TAG}_memory_bench.json > $OUT/${TAG}_memory_bench.log 2>&1; echo "rc=$?"
+  tail -n 1 $OUT/${TAG}_memory_bench.log | cut -c1-900 ;;
 *) echo "unknown section $sec" ;;
 esac; done
 t done
