@@ -244,6 +244,82 @@ extern "C" int gitmi_op_sample_rows(const float* logits, int R, int V, float tem
     return 0;
 }
 
+// ---- op hooks of the whole-row selection kernels (kernels_search.hip; tests/test_gpu_select_ops.py): an argument check + the
+// launcher the engine calls, so the launcher's own refusals and its choice of instantiation are part of what runs.
+// the rule inputs the three hooks share: ids int32 [R][ld_ids] DEVICE histories of cur_len tokens (NULL: none)
+[[maybe_unused]] static int check_history(const char* op, const int* ids, int ld_ids, int cur_len) {
+    if (ids && (cur_len < 1 || cur_len > ld_ids)) return fail("%s: cur_len=%d outside [1, ld_ids=%d]", op, cur_len, ld_ids);
+    return 0;
+}
+// row_topm_kernel: logits fp32 [R][ldl] -> part_val / part_idx [R][row_topm_slots(M)], part_lse [R] (max, sum exp)
+GITMI_EXP_EXPORT int gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len,
+                                          const int* plen, int beams, int suppress_kind, float rep_penalty, int M, float* part_val,
+                                          int* part_idx, float* part_lse, void* stream) {
+    if (!logits || !part_val || !part_idx || !part_lse) return fail("debug_row_topm: null argument");
+    if (R < 1 || V < 1 || ldl < V) return fail("debug_row_topm: R=%d V=%d ldl=%d", R, V, ldl);
+    if (ids) {
+        if (!plen) return fail("debug_row_topm: ids without plen");
+        if (beams < 1 || R % beams) return fail("debug_row_topm: R=%d is not a multiple of beams=%d", R, beams);
+        RCK(check_history("debug_row_topm", ids, ld_ids, cur_len));
+    } else {
+        suppress_kind = 0;                                  // no histories: no rules (the kernel reads plen for the no-repeat rule)
+    }
+    HIPCK(launch_row_topm(logits, ldl, V, ids, ld_ids, cur_len, plen, ids ? beams : 1, suppress_kind, rep_penalty, M, R, part_val,
+                          part_idx, (float2*)part_lse, (hipStream_t)stream));
+    return 0;
+}
+// trie_select_kernel on a caller's CSR trie (all arrays DEVICE): child_off int32 [n_nodes + 1], child_tok / child_node int32
+// [child_off[n_nodes]], cursor int32 [B] read and updated.  The arrays are checked as gitmi_set_trie checks them, and the
+// cursors against n_nodes (host copies; synchronises the stream first).
+GITMI_EXP_EXPORT int gitmi_debug_trie_select(const float* logits, int ldl, int V, int B, const int* ids, int ld_ids, int cur_len,
+                                             const int* plen, int eos, const int* child_off, const int* child_tok,
+                                             const int* child_node, int n_nodes, int* cursor, float* part_val, int* part_idx,
+                                             float* part_lse, void* stream) {
+    if (!logits || !ids || !plen || !part_val || !part_idx || !part_lse) return fail("debug_trie_select: null argument");
+    if (!child_off || !child_tok || !child_node || !cursor) return fail("debug_trie_select: null trie arrays");
+    if (V < 2) return fail("debug_trie_select: V=%d (at least 2 tokens)", V);
+    if (B < 1 || ldl < V || n_nodes < 1) return fail("debug_trie_select: B=%d V=%d ldl=%d n_nodes=%d", B, V, ldl, n_nodes);
+    RCK(check_history("debug_trie_select", ids, ld_ids, cur_len));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCK(hipStreamSynchronize(s));
+    std::vector<int> off((size_t)n_nodes + 1), cur((size_t)B);
+    HIPCK(hipMemcpy(off.data(), child_off, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (off[0] != 0) return fail("debug_trie_select: child_off must start at 0");
+    for (int n = 0; n < n_nodes; ++n)
+        if (off[n + 1] < off[n]) return fail("debug_trie_select: child_off must be non-decreasing");
+    const int n_edges = off[n_nodes];
+    if (n_edges > 0) {
+        std::vector<int> node((size_t)n_edges);
+        HIPCK(hipMemcpy(node.data(), child_node, node.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n_edges; ++i)
+            if (node[i] < 0 || node[i] >= n_nodes) return fail("debug_trie_select: edge %d leads to node %d of %d", i, node[i], n_nodes);
+    }
+    HIPCK(hipMemcpy(cur.data(), cursor, cur.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b)
+        if (cur[b] < -1 || cur[b] >= n_nodes) return fail("debug_trie_select: cursor %d of sentence %d outside [-1, %d)", cur[b], b, n_nodes);
+    const TrieArgs tr{child_off, child_tok, child_node, cursor};
+    HIPCK(launch_trie_select(logits, ldl, V, ids, ld_ids, cur_len, plen, eos, tr, B, part_val, part_idx, (float2*)part_lse, s));
+    return 0;
+}
+// sample_rows_kernel with everything the engine's sampling step sets: gitmi_op_sample_rows' arguments + the row stride of the
+// logits, the histories of the repetition penalty and the list stride (entries ndraw..stride are padding).  filtered_out [R][V].
+GITMI_EXP_EXPORT int gitmi_debug_sample_rows(const float* logits, int R, int V, float temperature, int top_k, float top_p, int ndraw,
+                                             uint64_t seed, int step, float* draw_logprob, int* draw_token, float* filtered_out,
+                                             int ldl, const int* ids, int ld_ids, int cur_len, float rep_penalty, int stride,
+                                             void* stream) {
+    if (!logits || !draw_logprob || !draw_token) return fail("debug_sample_rows: null argument");
+    if (R < 1 || V < 1 || ldl < V) return fail("debug_sample_rows: R=%d V=%d ldl=%d", R, V, ldl);
+    RCK(check_history("debug_sample_rows", ids, ld_ids, cur_len));
+    float2* lse = nullptr;
+    HIPCK(hipMalloc((void**)&lse, (size_t)R * sizeof(float2)));
+    hipError_t err = launch_sample_rows(logits, ldl, V, R, temperature, top_k, top_p, ndraw, seed, step, draw_logprob, draw_token, lse,
+                                        filtered_out, ids, ld_ids, cur_len, rep_penalty, stride, (hipStream_t)stream);
+    if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(lse);
+    HIPCK(err);
+    return 0;
+}
+
 GITMI_EXP_EXPORT int gitmi_debug_set_gemm_impl(int impl) {
     if (!set_gemm_impl(impl)) return fail("debug_set_gemm_impl: unknown selector %d (low byte: -1, 0 or 9)", impl);
     return 0;

@@ -65,9 +65,10 @@ __global__ __launch_bounds__(NT) void row_topm_kernel(const float* __restrict__ 
     auto feed = [&](float v, int i) {
         if (pen && hist_contains(s_hist, i)) v = rep_penalize(v, rep_penalty);
         if (i == last) v = -10000.f;
-        // online log-sum-exp
+        // online log-sum-exp; while the running maximum is -inf (only masked logits so far) there is no term to add:
+        // exp(-inf - -inf) would be NaN and stay in the sum
         if (v > mx) { sm = sm * __expf(mx - v) + 1.f; mx = v; }
-        else sm += __expf(v - mx);
+        else if (mx != -INFINITY) sm += __expf(v - mx);
         if (v > tv[MMAX - 1]) {
             tv[MMAX - 1] = v; ti[MMAX - 1] = i;
 #pragma unroll

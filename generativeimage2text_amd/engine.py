@@ -57,6 +57,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_im2col", "gitmi_debug_pos_resize", "gitmi_debug_vit_assemble", "gitmi_debug_ragged_front", "gitmi_debug_zero_pad_rows",
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
     "gitmi_debug_gemm_form", "gitmi_debug_context_embed", "gitmi_debug_attn_decode_qkv", "gitmi_debug_score_attn_tree",
+    "gitmi_debug_row_topm", "gitmi_debug_trie_select", "gitmi_debug_sample_rows",
 ]
 
 
@@ -194,6 +195,10 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_layernorm_map.argtypes = [vp, i32, vp, vp, C.c_float, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_context_embed.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_float, vp, i32, vp, vp, i32, i32,
                                                   i32, i32, vp]
+        lib.gitmi_debug_row_topm.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp]
+        lib.gitmi_debug_trie_select.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        lib.gitmi_debug_sample_rows.argtypes = [vp, i32, i32, C.c_float, i32, C.c_float, i32, C.c_uint64, i32, vp, vp, vp, i32, vp, i32,
+                                                i32, C.c_float, i32, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands in _MEASUREMENT_LIBS else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -1659,6 +1664,74 @@ def op_sample_rows(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 
     filt = torch.empty(R, V, device=logits.device, dtype=torch.float32) if want_filtered else None
     _ck(lib.gitmi_op_sample_rows(logits.data_ptr(), R, V, float(temperature), int(top_k), float(top_p), int(ndraw), int(seed),
                                  int(step), lp.data_ptr(), tok.data_ptr(), _ptr(filt), _stream()), lib)
+    return filt, tok, lp
+
+
+# ---- op hooks of the whole-row selection kernels (measurement build; tests/test_gpu_select_ops.py).  logits: an fp32 device
+# view [rows, >= V] with unit column stride; its row stride is ldl and its first V columns are the vocabulary (a padded or
+# misaligned row is a slice of a wider tensor).  out: caller-supplied output tensors (the tests fill them with sentinels).
+def _logit_rows(logits: torch.Tensor, V: int) -> Tuple[int, int]:
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
+        raise ValueError(f"logits must be an fp32 [rows, >= {V}] view with unit column stride")
+    return int(logits.shape[0]), int(logits.stride(0))
+
+
+def row_topm_slots(M: int) -> int:
+    return 1 if M <= 1 else 2 if M <= 2 else 4 if M <= 4 else 8 if M <= 8 else 16
+
+
+def op_row_topm(logits: torch.Tensor, V: int, M: int, ids: Optional[torch.Tensor] = None, cur_len: int = 0,
+                plen: Optional[torch.Tensor] = None, beams: int = 1, suppress_kind: int = 0, rep_penalty: float = 0.0,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, operands: Optional[str] = None):
+    """row_topm_kernel through its launcher: -> (part_val fp32 [R, slots], part_idx int32 [R, slots], part_lse fp32 [R, 2]),
+    slots = row_topm_slots(M).  ids int32 [R, ld_ids] device histories of cur_len tokens (None: no rules), plen int32 [R / beams]."""
+    lib, fn = _front("gitmi_debug_row_topm", operands=operands)
+    R, ldl = _logit_rows(logits, V)
+    slots = row_topm_slots(M)
+    dev = logits.device
+    pv, pi, pl = out if out is not None else (torch.empty(R, slots, device=dev), torch.empty(R, slots, device=dev, dtype=torch.int32),
+                                              torch.empty(R, 2, device=dev))
+    _ck(fn(logits.data_ptr(), ldl, int(V), R, _ptr(ids), 0 if ids is None else int(ids.stride(0)), int(cur_len), _ptr(plen), int(beams),
+           int(suppress_kind), float(rep_penalty), int(M), pv.data_ptr(), pi.data_ptr(), pl.data_ptr(), _stream()), lib)
+    return pv, pi, pl
+
+
+def op_trie_select(logits: torch.Tensor, V: int, ids: torch.Tensor, cur_len: int, plen: torch.Tensor, eos: int,
+                   child_off: Optional[torch.Tensor], child_tok: Optional[torch.Tensor], child_node: Optional[torch.Tensor],
+                   cursor: torch.Tensor, out: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], n_nodes: Optional[int] = None,
+                   operands: Optional[str] = None) -> None:
+    """trie_select_kernel through its launcher on a CSR trie of int32 device tensors; cursor int32 [B] is read and updated, out =
+    (part_val fp32 [B], part_idx int32 [B], part_lse fp32 [B, 2]) written for the rows at or past their prefix."""
+    lib, fn = _front("gitmi_debug_trie_select", operands=operands)
+    B, ldl = _logit_rows(logits, V)
+    pv, pi, pl = out
+    if n_nodes is None:
+        n_nodes = int(child_off.numel()) - 1
+    _ck(fn(logits.data_ptr(), ldl, int(V), B, ids.data_ptr(), int(ids.stride(0)), int(cur_len), plen.data_ptr(), int(eos),
+           _ptr(child_off), _ptr(child_tok), _ptr(child_node), int(n_nodes), cursor.data_ptr(), pv.data_ptr(), pi.data_ptr(),
+           pl.data_ptr(), _stream()), lib)
+
+
+def op_sample_rows_rules(logits: torch.Tensor, V: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, ndraw: int = 2,
+                        seed: int = 0, step: int = 1, stride: Optional[int] = None, ids: Optional[torch.Tensor] = None,
+                        cur_len: int = 0, rep_penalty: float = 0.0, want_filtered: bool = True,
+                        out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
+                        operands: Optional[str] = None):
+    """op_sample_rows with what the engine's sampling step also sets (measurement build): padded logit rows, the repetition
+    penalty over ids int32 [R, ld_ids] (cur_len tokens) and lists of `stride` entries.
+    -> (filtered logits [R, V] or None, tokens int32 [R, stride], log-probs fp32 [R, stride]); out = (log-probs, tokens, filtered)."""
+    lib, fn = _front("gitmi_debug_sample_rows", operands=operands)
+    R, ldl = _logit_rows(logits, V)
+    stride = ndraw if stride is None else int(stride)
+    if out is not None:
+        lp, tok, filt = out
+    else:
+        lp = torch.empty(R, max(stride, 1), device=logits.device, dtype=torch.float32)
+        tok = torch.empty(R, max(stride, 1), device=logits.device, dtype=torch.int32)
+        filt = torch.empty(R, V, device=logits.device, dtype=torch.float32) if want_filtered else None
+    _ck(fn(logits.data_ptr(), R, int(V), float(temperature), int(top_k), float(top_p), int(ndraw), int(seed), int(step), lp.data_ptr(),
+           tok.data_ptr(), _ptr(filt), ldl, _ptr(ids), 0 if ids is None else int(ids.stride(0)), int(cur_len), float(rep_penalty),
+           stride, _stream()), lib)
     return filt, tok, lp
 
 

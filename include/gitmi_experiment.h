@@ -1,7 +1,7 @@
 /* gitmi_experiment.h -- entry points of the MEASUREMENT builds only (`make exp`: libgitmi_exp.so = the product sources compiled
  * with -DGITMI_EXPERIMENT, bf16 operands; libgitmi_f16_exp.so = the same with -DGITMI_OPS_F16, fp16 operands -- the kernels of
  * the benchmarked configuration, the folded-LayerNorm GEMM forms among them).  libgitmi.so / libgitmi_f16.so do not export them.
- * Both measurement builds export the same 63 gitmi_ symbols (the 40 of gitmi.h + the 23 below); gitmi_operand_dtype tells them apart.
+ * Both measurement builds export the same 68 gitmi_ symbols (the 40 of gitmi.h + the 28 below); gitmi_operand_dtype tells them apart.
  *
  * What lives here: debug hooks that exchange stage products between contexts (tools/error_attribution.py), force a GEMM
  * variant (tools/gemm_bench.py, tests of the forced tile heights) or set the timing bits of the decode-chain GEMMs
@@ -197,6 +197,38 @@ int  gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len
                                const float* words, int vocab, const float* positions, int max_pos, const float* gamma,
                                const float* beta, float eps, void* feats, int dtype, float* feats_f32, int* ntok, int B, int n_img,
                                int stride, int D, void* stream);
+
+/* op hooks of the whole-row selection kernels (kernels_search.hip; tests/test_gpu_select_ops.py): an argument check + the
+ * launcher the engine calls, so the launcher's refusals and its choice of instantiation are part of what runs.  All pointers
+ * DEVICE memory.  logits fp32 [rows][ldl], columns [V, ldl) never read; ids int32 [rows][ld_ids] row histories of cur_len
+ * tokens; plen int32 [rows / beams] prefix lengths.
+ *   row_topm:    the parity mode's / caller-supplied-logits selection: per row the M best (logit, token) pairs after the rules
+ *                (suppress_kind 1: the last token to -10000 on rows with cur_len > plen; rep_penalty over the history, 0 or 1:
+ *                off) -> part_val / part_idx [R][row_topm_slots(M)] (1, 2, 4, 8 or 16 slots; value descending, token ascending;
+ *                entries past M hold the next best, entries past V (-inf, 0x7fffffff)), part_lse [R][2] = (max, sum exp(x - max))
+ *                of the ruled row.  ids NULL: no rules.  Refused by name: null logits / outputs, ldl < V, ids without plen, R not
+ *                a multiple of beams, cur_len outside [1, ld_ids]; by the launcher (invalid argument): M outside 1..16, a
+ *                penalty over more than 1024 tokens.  Nothing is launched then.
+ *   trie_select: one step of GITMI_SEARCH_TRIE on a caller's CSR trie -- child_off int32 [n_nodes + 1], child_tok / child_node
+ *                int32 [child_off[n_nodes]], cursor int32 [B] (node of every sentence, -1 unconstrained; read and updated) ->
+ *                part_val / part_idx [B] (log-prob incl. the trie bonus, token), part_lse [B][2] = (0, 1).  Rows with cur_len <
+ *                plen[b] are not written.  Child tokens outside [0, V) are skipped.  Refused by name: null pointers, V < 2,
+ *                ldl < V, a child_off that does not start at 0 or decreases, an edge or a cursor that names no node (checked on
+ *                host copies as gitmi_set_trie checks them; synchronises the stream first).
+ *   sample_rows: gitmi_op_sample_rows with the rest of what the engine's sampling step sets: ldl, the histories of the
+ *                repetition penalty (applied to the raw logits, before the temperature) and the list stride -- draw_logprob /
+ *                draw_token [R][stride], entries ndraw..stride (-inf, 0x7fffffff); filtered_out [R][V] or NULL.  Refused by the
+ *                launcher (invalid argument): V outside 2..32768, ndraw outside 1..16, stride < ndraw, temperature <= 0, a
+ *                penalty over more than 1024 tokens.  Synchronises the stream. */
+int  gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len, const int* plen,
+                          int beams, int suppress_kind, float rep_penalty, int M, float* part_val, int* part_idx, float* part_lse,
+                          void* stream);
+int  gitmi_debug_trie_select(const float* logits, int ldl, int V, int B, const int* ids, int ld_ids, int cur_len, const int* plen,
+                             int eos, const int* child_off, const int* child_tok, const int* child_node, int n_nodes, int* cursor,
+                             float* part_val, int* part_idx, float* part_lse, void* stream);
+int  gitmi_debug_sample_rows(const float* logits, int R, int V, float temperature, int top_k, float top_p, int ndraw, uint64_t seed,
+                             int step, float* draw_logprob, int* draw_token, float* filtered_out, int ldl, const int* ids, int ld_ids,
+                             int cur_len, float rep_penalty, int stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,29 @@ def test_product_libraries_export_the_c_abi_and_nothing_else():
             assert "getenv" in undefined
 
 
+def test_selection_hooks_belong_to_the_measurement_build_only():
+    """The op hooks of row_topm / trie_select / sample_rows: declared in gitmi_experiment.h, named in EXPERIMENT_SYMBOLS, absent
+    from the product ABI (which keeps its 40 entry points), and exported by both measurement libraries where they are built."""
+    names = ("gitmi_debug_row_topm", "gitmi_debug_trie_select", "gitmi_debug_sample_rows")
+    exp = open(os.path.join(ROOT, "include", "gitmi_experiment.h")).read()
+    product = open(os.path.join(ROOT, "include", "gitmi.h")).read()
+    for name in names:
+        assert name + "(" in exp and name in engine.EXPERIMENT_SYMBOLS, name
+        assert name not in engine.EXPORTED_SYMBOLS and name not in product, name
+    assert len(engine.EXPORTED_SYMBOLS) == 40 and len(set(engine.EXPERIMENT_SYMBOLS)) == len(engine.EXPERIMENT_SYMBOLS) == 28
+    assert set(_declared_functions("gitmi_experiment.h")) - set(_declared_functions()) == set(engine.EXPERIMENT_SYMBOLS)
+    for operands, path in (("exp", engine.LIB_PATH_EXP), ("f16_exp", engine.LIB_PATH_F16_EXP)):
+        if os.path.exists(path):
+            lib = engine.load_library(operands)
+            for name in names:
+                assert hasattr(lib, name), (operands, name)
+    for operands, path in (("bf16", engine.LIB_PATH), ("f16", engine.LIB_PATH_F16)):
+        if os.path.exists(path):
+            lib = engine.load_library(operands)
+            for name in names:
+                assert not hasattr(lib, name), (operands, name)
+
+
 def test_measurement_hooks_pick_the_library_of_their_operand_type():
     """_exp_library: fp16 tensors -> libgitmi_f16_exp.so, bf16 or none -> libgitmi_exp.so, `operands` where no tensor can say;
     without use_experiment_build the product library of that type (whose missing hook _experiment_only reports); "f16" itself
