@@ -317,7 +317,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->sc_allocs) hipFree(p);
-    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab);
+    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab); hipFree(e->feat_tab);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -894,6 +894,7 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("%s: GITMI_SEARCH_TREE_SCORE is not a search (gitmi_generate_prefixed scores token trees)", who);
     if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("%s: GITMI_SEARCH_KEEP is not a search (gitmi_generate_prefixed keeps the memory of resident images)", who);
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("%s: GITMI_SEARCH_RECALL is not a search (gitmi_generate_prefixed recalls kept images)", who);
+    if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("%s: GITMI_SEARCH_FEATURES is not a search (gitmi_generate_prefixed installs given feature rows)", who);
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1205,6 +1206,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp && sp->kind == GITMI_SEARCH_TREE_SCORE) return fail("generate: GITMI_SEARCH_TREE_SCORE scores given token trees: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("generate: GITMI_SEARCH_KEEP keeps the memory of resident images: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("generate: GITMI_SEARCH_RECALL recalls kept images: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("generate: GITMI_SEARCH_FEATURES installs given feature rows: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1667,6 +1669,88 @@ static int memory_recall(gitmi_engine* e, const float* const* frames, int B, con
     return rc;
 }
 
+// ---- features in (GITMI_SEARCH_FEATURES, include/gitmi.h) -------------------------------------------------------------------------
+// The other side of gitmi_encode_frames' feats_out: rows the caller holds -- cached, composed from per-frame rows, averaged, of
+// another tower of the same width -- become the resident feature tensor, and the prefill runs over them.  Every check comes
+// before the first launch (an argument error leaves the resident set as it was).
+static int features_call(gitmi_engine* e, const float* const* frames, int F, int B, const void* rows, int dtype, int ld,
+                         const int32_t* pieces_host, const int32_t* image_of_host, int Q, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    if (frames) return fail("features: frames != NULL: the images of this call are formed from the given feature rows");
+    if (!rows || !pieces_host || !info_out) return fail("features: null argument");
+    if ((uintptr_t)rows & 15) return fail("features: the base address %p of the rows is not 16-byte aligned", rows);
+    if (c.vit_width % 8) return fail("features: vit_width %d is not a multiple of the 8 elements a lane moves", c.vit_width);
+    if (dtype != GITMI_DTYPE_F32 && (e->pol.f32 || dtype != gitmi_operand_dtype()))
+        return fail("features: rows of element type %d: this engine takes GITMI_DTYPE_F32 (0)%s", dtype,
+                    e->pol.f32 ? " only (fp32 precision)"
+                               : gitmi_operand_dtype() == GITMI_DTYPE_F16 ? " or GITMI_DTYPE_F16 (2), this library's 16-bit operand type"
+                                                                          : " or GITMI_DTYPE_BF16 (1), this library's 16-bit operand type");
+    if (B < 1 || B > c.max_batch) return fail("features: B=%d outside [1,%d]", B, c.max_batch);
+    if (F < 1 || F > c.max_frames) return fail("features: F=%d outside [1,%d] (max_frames)", F, c.max_frames);
+    if (c.num_frames > 0 && F > c.num_frames) return fail("features: F=%d above the %d frames of the model (num_frames)", F, c.num_frames);
+    const int Qmax = c.max_batch * c.max_frames;
+    if (Q < 1 || Q > Qmax) return fail("features: Q=%d pieces outside [1,%d] (max_batch x max_frames)", Q, Qmax);
+    if (!image_of_host && Q != B) return fail("features: without image_of, Q must equal B");
+    if (ld < 1) return fail("features: a buffer of %d rows (ld_prefix)", ld);
+    const int cap = c.max_frames * e->Nmax;
+    std::vector<FeaturePiece> tab((size_t)Q);
+    std::vector<int> count((size_t)B, 0);
+    for (int q = 0; q < Q; ++q) {
+        const int im = image_of_host ? image_of_host[q] : q;
+        const int src0 = pieces_host[3 * q], n = pieces_host[3 * q + 1], t = pieces_host[3 * q + 2];
+        if (im < 0 || im >= B) return fail("features: piece %d names image %d of %d", q, im, B);
+        if (n < 1) return fail("features: piece %d has %d rows (at least 1)", q, n);
+        if (src0 < 0 || (long long)src0 + n > ld)
+            return fail("features: piece %d reads rows [%d,%lld) of a buffer of %d rows", q, src0, (long long)src0 + n, ld);
+        if (t < -1) return fail("features: piece %d has temporal index %d (-1: none)", q, t);
+        if (t >= 0 && c.num_frames <= 0) return fail("features: piece %d has temporal index %d, but the model has no temporal embeddings", q, t);
+        if (t >= c.num_frames && t >= 0) return fail("features: piece %d has temporal index %d outside [0,%d) (num_frames)", q, t, c.num_frames);
+        if ((long long)count[im] + n > cap)
+            return fail("features: image %d asks for %lld rows, the workspaces hold %d per image (max_frames x max(N, max_image_tokens))",
+                        im, (long long)count[im] + n, cap);
+        tab[q] = FeaturePiece{im, count[im], src0, n, t >= 0 ? e->w.temb[t] : nullptr};
+        count[im] += n;
+    }
+    int max_n = 0, sum_n = 0;
+    bool uniform = !e->ragged;
+    for (int b = 0; b < B; ++b) {
+        if (count[b] < 1) return fail("features: image %d has no piece", b);
+        max_n = std::max(max_n, count[b]); sum_n += count[b];
+        uniform = uniform && count[b] == F * e->N;
+    }
+    // the mode, by RECALL's rule: a uniform batch of the current shape is exactly what gitmi_encode_frames leaves, else key counts
+    const int stride = uniform ? F * e->N : round_up(max_n, 16) <= cap ? round_up(max_n, 16) : max_n;
+    const size_t tab_bytes = (size_t)Qmax * sizeof(FeaturePiece) + (size_t)c.max_batch * sizeof(int);
+    if (!e->feat_tab && hipMalloc((void**)&e->feat_tab, tab_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        e->feat_tab = nullptr;
+        return fail("features: out of device memory for the table of the call");
+    }
+    int* count_dev = reinterpret_cast<int*>(e->feat_tab + Qmax);
+    // staged synchronously, as upload_sentences does: the previous call's work on `s` may still read the table
+    HIPCK(hipStreamSynchronize(s));
+    HIPCK(hipMemcpy(e->feat_tab, tab.data(), (size_t)Q * sizeof(FeaturePiece), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(count_dev, count.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    FeatureArgs a{};
+    a.feats = e->feats; a.src = rows; a.pieces = e->feat_tab; a.pieces_n = Q; a.count = count_dev;
+    a.stride = stride; a.D = c.vit_width;
+    a.ntok = e->rg_ntok; a.meta = e->ragged ? e->rg_meta : nullptr;
+    auto body = [&]() -> int {
+        drop_resident(e);               // the workspaces are overwritten from here on
+        HIPCK(launch_feature_install(a, B, dtype != GITMI_DTYPE_F32, !e->pol.f32, s));
+        set_resident(e, B, F, uniform ? 0 : stride);
+        if (!uniform) {
+            e->keyed = true;
+            for (int b = 0; b < B; ++b) e->res_desc.push_back(int4{count[b], 0, 0, 0});
+        }
+        RCK(prefill_impl(e, s));
+        return memory_info({stride, max_n, sum_n, 0}, info_out, s);
+    };
+    const int rc = body();
+    if (rc != 0) drop_resident(e);
+    return rc;
+}
+
 // Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V)
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
@@ -1682,6 +1766,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         return memory_keep(e, frames, B, logprob_out, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && sp->kind == GITMI_SEARCH_RECALL)
         return memory_recall(e, frames, B, prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
+    if (sp && sp->kind == GITMI_SEARCH_FEATURES)
+        return features_call(e, frames, F, B, prefixes, sp->reserved_, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {
         const bool attend = sp->kind == GITMI_SEARCH_ATTEND, tree = sp->kind == GITMI_SEARCH_TREE_SCORE;
         const char* who = attend ? "attend" : tree ? "tree_score" : "score";

@@ -176,6 +176,9 @@ struct gitmi_engine {
     gitmi::MemoryEntry* mem_tab = nullptr;
     size_t mem_tab_n = 0;
     std::vector<int4> res_desc;
+    // features in (GITMI_SEARCH_FEATURES, engine.hip features_call): the device table of a call -- max_batch x max_frames pieces,
+    // then max_batch row counts --, allocated by the first such call
+    gitmi::FeaturePiece* feat_tab = nullptr;
 
     // ViT workspaces (one frame of max_batch images at a time)
     void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;

@@ -92,10 +92,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TS* __restrict__ x
 // 16-byte bf16 stores -- the one-wave-per-row kernel above moves 8 bytes per lane and instruction and reached 2.8 TB/s on
 // the 36 launches per encode + prefill pass (13.8 us each for 12608 x 768; profiles/r03_a_solo_graph_kernel_stats.txt).
 // Statistics as above (fp32, centred second pass); only the order of the partial sums differs.
-template <typename TS, int NCH>
+// TOut = float: the fp32 copy of the same values (the features handed back to the caller: rounding them to the operand type
+// must give the operand copy bit for bit, so they come from the same order of partial sums).
+template <typename TS, int NCH, typename TOut = bf16_t>
 __global__ __launch_bounds__(256) void layernorm_wide_kernel(const TS* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps,
-                                                             const float* __restrict__ add_after, bf16_t* __restrict__ y_t,
+                                                             const float* __restrict__ add_after, TOut* __restrict__ y_t,
                                                              int ld_t, TS* __restrict__ y_f, int ld_f, int rows, RowMap map) {
     constexpr int D = NCH * 256;
     const int l32 = threadIdx.x & 31;
@@ -158,17 +160,17 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const TS* __restric
 }
 
 // bf16 operand rows out, D = 768 / 1024, 16-byte aligned rows: the wide kernel; false: not applicable
-template <typename TS>
+template <typename TS, typename TOut = bf16_t>
 static bool launch_layernorm_wide(const TS* x, int ldx, const float* gamma, const float* beta, float eps, const float* add_after,
-                                  bf16_t* y_t, int ld_t, TS* y_f, int ld_f, int rows, int D, RowMap m, hipStream_t s) {
+                                  TOut* y_t, int ld_t, TS* y_f, int ld_f, int rows, int D, RowMap m, hipStream_t s) {
     if ((D != 768 && D != 1024) || (ldx & 7) || (ld_t & 7) || (y_f && (ld_f & 7))) return false;
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y_t) & 15) || (reinterpret_cast<uintptr_t>(y_f) & 15) ||
         (reinterpret_cast<uintptr_t>(gamma) & 15) || (reinterpret_cast<uintptr_t>(beta) & 15) ||
         (reinterpret_cast<uintptr_t>(add_after) & 15))
         return false;
     dim3 grid((rows + 7) / 8), block(256);
-    if (D == 768) hipLaunchKernelGGL((layernorm_wide_kernel<TS, 3>), grid, block, 0, s, x, ldx, gamma, beta, eps, add_after, y_t, ld_t, y_f, ld_f, rows, m);
-    else hipLaunchKernelGGL((layernorm_wide_kernel<TS, 4>), grid, block, 0, s, x, ldx, gamma, beta, eps, add_after, y_t, ld_t, y_f, ld_f, rows, m);
+    if (D == 768) hipLaunchKernelGGL((layernorm_wide_kernel<TS, 3, TOut>), grid, block, 0, s, x, ldx, gamma, beta, eps, add_after, y_t, ld_t, y_f, ld_f, rows, m);
+    else hipLaunchKernelGGL((layernorm_wide_kernel<TS, 4, TOut>), grid, block, 0, s, x, ldx, gamma, beta, eps, add_after, y_t, ld_t, y_f, ld_f, rows, m);
     return true;
 }
 
@@ -826,10 +828,13 @@ hipError_t launch_layernorm_s16(const void* x, int ldx, const float* gamma, cons
     if (D > 64 * LN_MAXV || (D & 3) || (ldx & 3) || (ld_t & 3) || (y_s && (ld_s & 3))) return hipErrorInvalidValue;
     RowMap m{map_n_in > 0 ? map_n_in : rows, map_n_in > 0 ? map_n_out : rows, map_off};
     dim3 grid((rows + 3) / 4), block(256);
-    if (t_is_f32)
-        hipLaunchKernelGGL((layernorm_kernel<float, f16_t>), grid, block, 0, s, (const f16_t*)x, ldx, gamma, beta, eps,
-                           add_after, (float*)y_t, ld_t, (f16_t*)y_s, ld_s, rows, D, m);
-    else if (y_t && launch_layernorm_wide<f16_t>((const f16_t*)x, ldx, gamma, beta, eps, add_after, (bf16_t*)y_t, ld_t, (f16_t*)y_s, ld_s,
+    if (t_is_f32) {
+        // the wide kernel where the operand copy of the same rows would take it: the same order of partial sums
+        if (!(y_t && launch_layernorm_wide<f16_t, float>((const f16_t*)x, ldx, gamma, beta, eps, add_after, (float*)y_t, ld_t, (f16_t*)y_s,
+                                                         ld_s, rows, D, m, s)))
+            hipLaunchKernelGGL((layernorm_kernel<float, f16_t>), grid, block, 0, s, (const f16_t*)x, ldx, gamma, beta, eps,
+                               add_after, (float*)y_t, ld_t, (f16_t*)y_s, ld_s, rows, D, m);
+    } else if (y_t && launch_layernorm_wide<f16_t>((const f16_t*)x, ldx, gamma, beta, eps, add_after, (bf16_t*)y_t, ld_t, (f16_t*)y_s, ld_s,
                                                  rows, D, m, s))
         ;
     else

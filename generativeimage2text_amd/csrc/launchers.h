@@ -177,6 +177,21 @@ hipError_t launch_memory_pack(const MemoryArgs& a, void* store, const MemoryEntr
 // block `image` <- the n rows of slot `slot`, zeros in rows [n, stride), the key count
 hipError_t launch_memory_unpack(const MemoryArgs& a, const void* store, const MemoryEntry* tab, int entries, hipStream_t s);
 
+// ---- features in (GITMI_SEARCH_FEATURES, include/gitmi.h; kernels_memory.hip feature_install_kernel) ----
+// one piece of the call (DEVICE copy of what the host validated): rows [src0, src0 + rows) of the caller's buffer become rows
+// [dst0, dst0 + rows) of image `image`'s block; temb: the temporal embedding added to them (fp32 [D]), or nullptr
+struct FeaturePiece { int image, dst0, src0, rows; const float* temb; };
+struct FeatureArgs {
+    void* feats;                            // [B][stride][D], fp32 or the operand type
+    const void* src;                        // the caller's dense rows of D elements, fp32 or the operand type
+    const FeaturePiece* pieces; int pieces_n;
+    const int* count;                       // [B] n_b: the rows of image b; rows [n_b, stride) of its block are written as zeros
+    int stride, D;                          // D % 8 == 0
+    int* ntok; int4* meta;                  // ntok[b] = n_b (and meta[b] = {0, 0, n_b, 0} when not nullptr)
+};
+// grid (row tiles of 16 over the stride, B images); src16 needs dst16 (an fp32 engine takes fp32 rows only)
+hipError_t launch_feature_install(const FeatureArgs& a, int B, bool src16, bool dst16, hipStream_t s);
+
 struct AttnFullArgs {
     const void* q; const void* k; const void* v; void* out;
     int ldq, ldk, ldv, ldo;

@@ -28,6 +28,7 @@ SEARCH_CONTEXT = 5   # not a search: gitmi_generate_prefixed puts context tokens
 SEARCH_TREE_SCORE = 6  # not a search: gitmi_generate_prefixed scores every node of given token trees (Engine.score_tree)
 SEARCH_KEEP = 7        # not a search: gitmi_generate_prefixed copies the memory of resident images into a caller's store (Engine.keep)
 SEARCH_RECALL = 8      # not a search: gitmi_generate_prefixed makes kept slots the resident images (Engine.recall)
+SEARCH_FEATURES = 9    # not a search: gitmi_generate_prefixed makes given feature rows the resident images (Engine.install_features)
 MEMORY_HEADER_BYTES = 256      # header of a slot of an image store; slots are multiples of this size (include/gitmi.h)
 
 
@@ -336,6 +337,56 @@ def context_segments(context, B: int, vocab: int, max_pos: int):
             segments.append(ids)
             image_of.append(b)
     return segments, image_of
+
+
+def feature_pieces(pieces, image_of, rows: int, *, max_batch: int, max_frames: int, cap: int, num_frames: int, F: int = 1):
+    """Host side of Engine.install_features: the rules of include/gitmi.h (GITMI_SEARCH_FEATURES) checked on the piece list.
+    pieces: (first source row, rows, temporal index t or -1 / None) per piece -- a 2-tuple means no temporal index; image_of: the
+    image of every piece (None: piece q <-> image q); rows: the rows the caller's buffer holds.  The pieces of an image are
+    concatenated in the order given.  -> (table [[src0, n, t]], image_of as a list or None, counts [rows of every image]).
+    Raises ValueError naming the piece (or the image) that breaks a rule."""
+    table = []
+    for q, pc in enumerate(pieces):
+        pc = tuple(pc)
+        if len(pc) not in (2, 3):
+            raise ValueError(f"piece {q}: expected (first row, rows[, temporal index]), got {pc!r}")
+        t = -1 if len(pc) == 2 or pc[2] is None else int(pc[2])
+        table.append([int(pc[0]), int(pc[1]), t])
+    Q = len(table)
+    if Q < 1 or Q > max_batch * max_frames:
+        raise ValueError(f"{Q} pieces outside [1, {max_batch * max_frames}] (max_batch x max_frames)")
+    if image_of is not None:
+        image_of = [int(i) for i in image_of]
+        if len(image_of) != Q:
+            raise ValueError(f"image_of has {len(image_of)} entries for {Q} pieces")
+        if min(image_of) < 0:
+            raise ValueError(f"piece {image_of.index(min(image_of))}: image {min(image_of)} is negative")
+    B = Q if image_of is None else max(image_of) + 1
+    if B > max_batch:
+        raise ValueError(f"{B} images exceed max_batch={max_batch}")
+    if F < 1 or F > max_frames or (num_frames > 0 and F > num_frames):
+        raise ValueError(f"F={F} outside [1, {min(max_frames, num_frames) if num_frames > 0 else max_frames}] "
+                         f"(max_frames={max_frames}, num_frames={num_frames})")
+    counts = [0] * B
+    for q, (src0, n, t) in enumerate(table):
+        b = q if image_of is None else image_of[q]
+        if n < 1:
+            raise ValueError(f"piece {q}: {n} rows (at least 1)")
+        if src0 < 0 or src0 + n > rows:
+            raise ValueError(f"piece {q}: rows [{src0}, {src0 + n}) of a buffer of {rows} rows")
+        if t < -1:
+            raise ValueError(f"piece {q}: temporal index {t} (-1 or None: none)")
+        if t >= 0 and num_frames <= 0:
+            raise ValueError(f"piece {q}: temporal index {t}, but the model has no temporal embeddings")
+        if t >= num_frames and t >= 0:
+            raise ValueError(f"piece {q}: temporal index {t} outside [0, {num_frames})")
+        counts[b] += n
+        if counts[b] > cap:
+            raise ValueError(f"piece {q}: image {b} asks for {counts[b]} rows, the engine holds {cap} per image")
+    for b, n in enumerate(counts):
+        if n == 0:
+            raise ValueError(f"image {b} has no piece")
+    return table, image_of, counts
 
 
 def context_capacity(image_size: int, patch: int, max_image_tokens: int, max_frames: int, max_context: int) -> int:
@@ -711,7 +762,7 @@ class Engine:
                 rows = geo.rows[b]
             if self._hw == (0, 0) and not isinstance(geo, Geometry):       # ragged: every image its own grid inside max_tokens rows
                 rows = geo[2][b][0] * geo[2][b][1] + 1
-            per.append((geo[1], tuple(geo[2][b]), int(rows), int(ctx)))
+            per.append((geo[1], None if geo[2][b] is None else tuple(geo[2][b]), int(rows), int(ctx)))
         return {"rows": [p[2] + p[3] for p in per], "max_rows": info[1], "total_rows": info[2], "geometry": per}
 
     def recall(self, store: torch.Tensor, slots: Sequence[int], geometry=None) -> Dict[str, int]:
@@ -738,7 +789,7 @@ class Engine:
         self._generation += 1
         self._resident = Q
         F = int(geometry[0][0]) if geometry else 1
-        grids = [tuple(g[1]) for g in geometry] if geometry else [None] * Q
+        grids = [None if g[1] is None else tuple(g[1]) for g in geometry] if geometry else [None] * Q
         ctx = [int(g[3]) for g in geometry] if geometry else [0] * Q
         rows = [int(g[2]) for g in geometry] if geometry else [stride] * Q
         if any(ctx) or any(r != stride for r in rows):
@@ -746,6 +797,72 @@ class Engine:
             self._geometry.rows = rows
         else:
             self._geometry = (stride, F, grids)
+        return {"stride": stride, "max_rows": max_n, "total_rows": total}
+
+    # -- features in: caller-supplied visual feature rows become the resident images --------------------------------------------
+    def feature_store(self, slots: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """[slots, n_tok, vit_width] on the engine's device: feature rows of `slots` images of the current image shape, the
+        buffer install_features reads pieces from (model.FeatureStore)."""
+        f32 = self.precision in ("f32", "fp32")
+        want = torch.float16 if self.precision in ("f16", "fp16") else torch.bfloat16
+        if dtype != torch.float32 and (f32 or dtype != want):
+            raise ValueError(f"feature rows are torch.float32{'' if f32 else ' or ' + str(want)} on this engine, got {dtype}")
+        return torch.empty(int(slots), int(self.n_tok), int(self.c.vit_width), dtype=dtype, device=f"cuda:{self.device}")
+
+    def install_features(self, rows: torch.Tensor, pieces=None, image_of: Optional[Sequence[int]] = None, F: int = 1) -> Dict[str, int]:
+        """Make visual feature rows the resident image batch of this context and run the prefill (include/gitmi.h
+        GITMI_SEARCH_FEATURES): the input side of encode()'s return value.  rows: a tensor [R, vit_width] on the engine's device
+        with `pieces` = (first row, rows, temporal index or None) per piece and image_of = the image of every piece (default:
+        piece q <-> image q), the pieces of an image concatenated in the order given; or [B, n, vit_width] with the pieces
+        implied (image b = rows[b]).  dtype fp32, or the engine's 16-bit operand type.  F: the frames per image the rows stand
+        for.  Every follow-up call (frames=None) then runs over them.  Grids are known only when every image has the F * n_tok
+        rows of the current image shape; otherwise resident_geometry is a Geometry with grids None (AttentionMaps.patch_grid
+        raises ValueError: the features came without a shape).  An argument error leaves the resident set as it was.
+        -> {'stride', 'max_rows', 'total_rows'}"""
+        if not isinstance(rows, torch.Tensor) or rows.dim() not in (2, 3) or int(rows.shape[-1]) != int(self.c.vit_width):
+            raise ValueError(f"feature rows are a tensor [R, {int(self.c.vit_width)}] or [B, n, {int(self.c.vit_width)}], got "
+                             f"{tuple(getattr(rows, 'shape', ()))}")
+        if rows.dim() == 3:
+            if pieces is not None or image_of is not None:
+                raise ValueError("rows [B, n, D] imply the pieces (image b = rows[b]): pass [R, D] rows with pieces")
+            n = int(rows.shape[1])
+            pieces = [(b * n, n, None) for b in range(int(rows.shape[0]))]
+        elif pieces is None:
+            raise ValueError("rows [R, D] need pieces")
+        f32 = self.precision in ("f32", "fp32")
+        want = torch.float16 if self.precision in ("f16", "fp16") else torch.bfloat16
+        if rows.dtype != torch.float32 and (f32 or rows.dtype != want):
+            raise ValueError(f"feature rows are torch.float32{'' if f32 else ' or ' + str(want)} on this engine, got {rows.dtype}")
+        if rows.device != torch.device(f"cuda:{self.device}") or not rows.is_contiguous():
+            raise ValueError("feature rows must be contiguous on the engine's device")
+        R = int(rows.numel()) // int(self.c.vit_width)
+        table, image_of, counts = feature_pieces(pieces, image_of, R, max_batch=int(self.c.max_batch), max_frames=int(self.c.max_frames),
+                                                 cap=self.memory_rows, num_frames=int(self.c.num_frames), F=int(F))
+        Q, B = len(table), len(counts)
+        search = GitmiSearch()
+        search.kind = SEARCH_FEATURES
+        search.reserved_ = _torch_dtype_code(rows)
+        info = torch.zeros(4, dtype=torch.int32, device=f"cuda:{self.device}")
+        tab = (C.c_int32 * (3 * Q))(*[v for pc in table for v in pc])
+        img = None if image_of is None else (C.c_int32 * Q)(*image_of)
+        old = self._resident
+        try:
+            self._ck(self.lib.gitmi_generate_prefixed(self._h, None, int(F), B, rows.data_ptr(), R, tab, img, Q, C.byref(search),
+                                                      None, None, None, info.data_ptr(), _stream()))
+        except GitmiError as err:
+            # an argument error ("features: ...") is found before any launch: the images of before stay resident; a failed launch drops them
+            if old is not None and not str(err).startswith("features:"):
+                self._drop_resident()
+            raise
+        stride, max_n, total, _ = (int(v) for v in info.tolist())
+        self._generation += 1
+        self._resident = B
+        p = int(self.c.patch)
+        if self._hw != (0, 0) and all(n == int(F) * self.n_tok for n in counts):
+            self._geometry = (stride, int(F), [(self._hw[0] // p, self._hw[1] // p)] * B)
+        else:
+            self._geometry = Geometry(stride, int(F), [None] * B, image_rows=max(counts), context=[0] * B)
+            self._geometry.rows = list(counts)
         return {"stride": stride, "max_rows": max_n, "total_rows": total}
 
     def prefill(self) -> None:

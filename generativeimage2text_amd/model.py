@@ -409,7 +409,11 @@ class AttentionMaps:
     def patch_grid(self, q: int) -> torch.Tensor:
         """[L_q, layers, F, H/p, W/p]: the image columns of caption q's own rows laid out on the patch grid of its image,
         class columns dropped (ragged input: that image's own grid)."""
-        gh, gw = self.grids[self.image_of[q]]
+        grid = self.grids[self.image_of[q]]
+        if grid is None:
+            raise ValueError(f"image {self.image_of[q]} has no patch grid: its features came without a shape (installed feature "
+                             f"rows of another count than the current image shape's, or a recall without geometry)")
+        gh, gw = grid
         n = gh * gw + 1
         rows = self.image[q, :self.lengths[q], :, :self.frames * n]
         Lq, layers = rows.shape[:2]
@@ -829,6 +833,41 @@ class CaptioningModel:
         return AttentionMaps(out, Nk, lengths, list(range(len(lengths))) if image_of is None else [int(i) for i in image_of],
                              F, grids)
 
+    # ---- features out and in: the encoder / head seam of the reference (image_encoder(x) -> visual_features -> textual) --------
+    def features(self, images: torch.Tensor) -> torch.Tensor:
+        """The visual features of `images` [B, 3, H, W]: fp32 [B, N, vit_width] on the device, what the reference's
+        image_encoder(x) returns for a bare tensor (no temporal embedding: install_features / FeatureStore.recall add the one
+        of a frame's position in its window).  Runs on context 0 and the caller's stream; the images are resident there
+        afterwards, as after any encode."""
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if not isinstance(images, torch.Tensor) or images.dim() != 4:
+            raise ValueError("features takes one [B, 3, H, W] tensor (the frames of a video: one call per frame, or stack them)")
+
+        def run():
+            self.engine.set_temporal_embedding(False)
+            feats = self.engine.encode([images])
+            self._last = self.engine
+            return Pending(None, lambda: feats, lambda out: out, engine=self.engine)
+
+        return self._on_context0(run)
+
+    def submit_features(self, rows: torch.Tensor, pieces=None, image_of: Optional[Sequence[int]] = None, F: int = 1,
+                        context=None) -> "Pending":
+        """Make visual feature rows the resident images of an engine context (Engine.install_features: rows [R, D] with pieces, or
+        [B, n, D]) -- `context`, default the next one in the model's rotation -- and return the handle follow-up requests take
+        as on= (submit_followup, submit_answers(None, ...), score / rank / attend(None, ...)).
+        `.result()`: {'stride', 'max_rows', 'total_rows'}."""
+        if not self._loaded:
+            raise RuntimeError("weights not loaded (call load_state_dict first)")
+        if context is None:
+            eng, _ = self._context()
+        else:
+            eng = context
+            self._last = eng
+        info = _on_context_stream(self, eng, lambda: eng.install_features(rows, pieces, image_of, F))
+        return Pending(None, lambda: info, lambda out: dict(out), engine=eng)
+
     def _check_ragged(self) -> None:
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
@@ -1002,6 +1041,16 @@ class Pending:
         return self._value
 
 
+def _on_context_stream(model, eng, fn):
+    """fn() on the stream of the pipeline context `eng` (ordered behind its own work), or on the caller's stream"""
+    for c, st in zip(getattr(model, "_ctxs", None) or [], getattr(model, "_streams", None) or []):
+        if c is eng and st is not None:
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                return fn()
+    return fn()
+
+
 class ImageStore:
     """Encoded images kept beyond the call that encoded them (include/gitmi.h GITMI_SEARCH_KEEP / GITMI_SEARCH_RECALL): one device
     tensor of `capacity` slots, caller keys mapped to slots, the least recently used key evicted when a new one needs a slot.
@@ -1054,13 +1103,7 @@ class ImageStore:
         return self._free.pop()
 
     def _on(self, eng, fn):
-        """fn() on the stream of the pipeline context `eng` (ordered behind its own work), or on the caller's stream"""
-        for c, st in zip(getattr(self.model, "_ctxs", None) or [], getattr(self.model, "_streams", None) or []):
-            if c is eng and st is not None:
-                st.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(st):
-                    return fn()
-        return fn()
+        return _on_context_stream(self.model, eng, fn)
 
     def put(self, source, keys: Sequence, images: Optional[Sequence[int]] = None) -> None:
         """Keep images of a finished call: `source` is the Pending of the call that encoded them (or a recall handle), or the
@@ -1114,6 +1157,113 @@ class ImageStore:
             self._touch(k)
         info = self._on(eng, lambda: eng.recall(self.tensor, slots, geometry))
         return Pending(None, lambda: info, lambda out: dict(out), engine=eng)
+
+
+class FeatureStore:
+    """Visual features kept beyond the call that encoded them (include/gitmi.h GITMI_SEARCH_FEATURES): the sibling of ImageStore
+    that holds the feature rows alone -- [capacity, N, vit_width] for the model's current uniform image shape, 13 x smaller per
+    image than an ImageStore slot in 16-bit -- and pays one prefill at recall.  Caller keys map to slots, the least recently
+    used key is evicted when a new one needs a slot.  A video model slides a window over per-frame features:
+
+        store.put(frame_t, keys=[('video', t)])                                   # one encoder pass per NEW frame
+        h = store.recall([[('video', t - 5 + i) for i in range(6)]])              # image 0 = the window, embedding i on key i
+        model.submit_followup({'prefixes': [[cls]], 'image_of': [0]}, on=h).result()
+
+    dtype: torch.float32 (exact: what the encoder's own store rounds) or the engine's 16-bit operand type (half the bytes; the
+    rows are rounded by torch, which is the same round-to-nearest-even).  The handle recall returns is accepted as on= wherever
+    a Pending is; StaleImagesError is raised once another call has replaced the images on its context."""
+
+    def __init__(self, model: "CaptioningModel", capacity: int, dtype: torch.dtype = torch.float32):
+        if int(capacity) < 1:
+            raise ValueError("a feature store needs at least one slot")
+        eng = model.engine
+        self.model, self.capacity, self.dtype = model, int(capacity), dtype
+        self.rows, self.width = int(eng.n_tok), int(eng.c.vit_width)
+        self.tensor = eng.feature_store(self.capacity, dtype)
+        self._entries: Dict[object, int] = {}            # key -> slot; insertion order = LRU order
+        self._free = list(range(self.capacity - 1, -1, -1))
+
+    def __contains__(self, key) -> bool:
+        return key in self._entries
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    def keys(self):
+        """The keys held, least recently used first."""
+        return list(self._entries)
+
+    @property
+    def bytes_per_image(self) -> int:
+        return self.rows * self.width * self.tensor.element_size()
+
+    def evict(self, key) -> None:
+        self._free.append(self._entries.pop(key))
+
+    def _touch(self, key) -> None:
+        self._entries[key] = self._entries.pop(key)
+
+    def _slot_for(self, key, pinned) -> int:
+        if key in self._entries:
+            return self._entries[key]
+        if not self._free:
+            victim = next((k for k in self._entries if k not in pinned), None)
+            if victim is None:
+                raise ValueError(f"{len(pinned)} keys in one call exceed the {self.capacity} slots of the store")
+            self.evict(victim)
+        return self._free.pop()
+
+    def put(self, frames: torch.Tensor, keys: Sequence) -> None:
+        """Encode `frames` [B, 3, H, W] as a bare tensor (no temporal embedding) and keep image b's feature rows under keys[b]."""
+        if int(frames.shape[0]) != len(list(keys)):
+            raise ValueError(f"{len(list(keys))} keys for {int(frames.shape[0])} frames")
+        self.put_features(self.model.features(frames), keys)
+
+    def put_features(self, rows: torch.Tensor, keys: Sequence) -> None:
+        """Keep feature rows [B, N, vit_width] (fp32, or the store's dtype) under keys[b]; a key already held is overwritten."""
+        keys = list(keys)
+        if tuple(rows.shape) != (len(keys), self.rows, self.width):
+            raise ValueError(f"feature rows must be [{len(keys)}, {self.rows}, {self.width}] for {len(keys)} keys, got {tuple(rows.shape)}")
+        if len(set(keys)) != len(keys):
+            raise ValueError("put needs every key once")
+        if len(keys) > self.capacity:
+            raise ValueError(f"{len(keys)} keys in one call exceed the {self.capacity} slots of the store")
+        slots = [self._slot_for(k, keys) for k in keys]
+        self.tensor[torch.as_tensor(slots, device=self.tensor.device)] = rows.to(device=self.tensor.device, dtype=self.dtype)
+        for k, s in zip(keys, slots):
+            self._entries.pop(k, None)
+            self._entries[k] = s
+
+    def pieces(self, windows: Sequence[Sequence], temporal=None):
+        """(pieces, image_of, F) of recall: image q is the concatenation of the rows of windows[q]'s keys.  temporal: per window
+        the temporal index of every key (None: none); default: index i for the i-th key of a window of more than one key on a
+        model with temporal embeddings, else none.  KeyError for a key that is not held."""
+        windows = [list(w) for w in windows]
+        missing = [k for w in windows for k in w if k not in self._entries]
+        if missing:
+            raise KeyError(f"not in the feature store (never put, or evicted): {missing[:4]}")
+        if not windows or any(len(w) == 0 for w in windows):
+            raise ValueError("recall needs at least one window, every window at least one key")
+        if temporal is not None and ([len(t) for t in temporal] != [len(w) for w in windows]):
+            raise ValueError("temporal needs one index (or None) per key of every window")
+        nf = int(self.model.cfg.num_frames)
+        pieces, image_of = [], []
+        for q, w in enumerate(windows):
+            for i, k in enumerate(w):
+                t = temporal[q][i] if temporal is not None else (i if nf > 0 and len(w) > 1 else None)
+                pieces.append((self._entries[k] * self.rows, self.rows, t))
+                image_of.append(q)
+        return pieces, image_of, max(len(w) for w in windows)
+
+    def recall(self, windows: Sequence[Sequence], temporal=None, context=None) -> "Pending":
+        """Make the windows the resident batch of an engine context -- `context`, default the next one in the model's rotation --
+        and run the prefill over them; returns the handle follow-up requests take as on=.  `.result()`: {'stride', 'max_rows',
+        'total_rows'}."""
+        pieces, image_of, F = self.pieces(windows, temporal)
+        for w in windows:
+            for k in w:
+                self._touch(k)
+        return self.model.submit_features(self.tensor.view(-1, self.width), pieces, image_of, F, context=context)
 
 
 def get_git_model(tokenizer, param: Optional[dict], precision: str = "f16", max_batch: int = 64,

@@ -59,6 +59,8 @@ extern "C" {
                                         * store; gitmi_generate_prefixed only, see there */
 #define GITMI_SEARCH_RECALL 8          /* not a search: make any selection of kept slots the resident images of a context;
                                         * gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_FEATURES 9        /* not a search: make caller-supplied visual feature rows the resident images of a context
+                                        * (the input side of gitmi_encode_frames' feats_out); gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -445,6 +447,53 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  *   _ATTEND and KEEP itself run over the recalled images; the follow-up graph is keyed on B, the stride and the mode already.
  * Both kinds allocate one small device table (max_batch entries) at their first call: engines that never keep or recall keep
  * their footprint. */
+/* ---- features in: search->kind == GITMI_SEARCH_FEATURES is the input side of gitmi_encode_frames' feats_out -- the reference's
+ * textual(hidden_states = visual_features, ...) / CaptioningModel.infer(batch, visual_features, ...) (decoder.py:845-857,
+ * 977-1011).  The caller hands in visual feature rows (what ln_post, plus the temporal embedding of a frame, produces: one row of
+ * vit_width elements per image token) and the engine makes them the resident image batch and runs the prefill: cached features,
+ * video windows composed from per-frame rows, features averaged over augmentations or produced by another tower of the same
+ * width.  Every follow-up form (frames == NULL) then runs unchanged.  "Not a search": gitmi_generate, gitmi_search_begin and the
+ * step seam refuse it by name, the other gitmi_search fields are ignored, it runs eagerly (no hipGraph) and synchronises the
+ * stream.  The argument mapping:
+ *   frames          : must be NULL; no resident images are needed (what is resident is replaced)
+ *   B               : the images to form, 1 .. max_batch
+ *   F               : the frames per image the caller claims, 1 .. max_frames and <= num_frames where that is > 0; recorded as the
+ *                     batch's frame count (KEEP writes it into the slot header), it does not change what is computed
+ *   prefixes        : the base address (read as bytes) of the caller's feature rows: DEVICE memory, 16-byte aligned, dense rows of
+ *                     vit_width elements.  The caller owns it; the engine keeps no pointer to it after the call returns
+ *   search->reserved_ : the element type of the rows: GITMI_DTYPE_F32 (0) or, in a 16-bit engine, gitmi_operand_dtype().  Anything
+ *                     else -- the other 16-bit code, a 16-bit code in an fp32 engine -- is refused by name
+ *   ld_prefix       : the rows the buffer holds; the host checks every piece against it
+ *   Q               : the pieces, 1 .. max_batch x max_frames
+ *   image_of_host   : int32 [Q], the image of piece q (NULL: Q == B, piece q <-> image q).  The pieces of one image are concatenated
+ *                     in increasing q, any interleaving between images is allowed; every image needs at least one piece
+ *   prefix_len_host : int32 [Q][3] = { first source row, rows (>= 1), temporal index t or -1 }.  t >= 0 adds
+ *                     img_temperal_embedding[t] to the rows of the piece (0 <= t < num_frames; refused on a model without temporal
+ *                     embeddings).  This is independent of gitmi_set_temporal_embedding, which only says how frame TENSORS are read
+ *   info_out        : { row stride of an image's block, max_b n_b, sum_b n_b, 0 };  tokens_out, logprob_out, sent_out: ignored
+ * With n_b the rows of image b: 1 <= n_b <= cap = max_frames x max(N, max_image_tokens), the rows per image the workspaces are
+ * sized for; beyond that the call fails before any launch and the message names the rows asked for and the capacity.
+ * vit_width % 8 != 0 is refused by message (a lane moves 8 elements).  Every check comes before the first launch: an argument
+ * error leaves the resident set as it was; a failure after the first launch drops it.
+ * One launch then writes every row of every image's block -- the rows of the pieces, zeros in rows [n_b, stride) --, the key
+ * counts and, in ragged image mode, the per-image descriptors { 0, 0, n_b, 0 }; addresses are formed from the host-validated
+ * table alone.  fp32 rows: the embedding is added in fp32 and the sum is stored as the encoder's own ln_post store does it -- as
+ * is in an fp32 engine, rounded to nearest even to the operand type otherwise.  16-bit rows without t are copied bit for bit;
+ * with t they are widened, added to and rounded once.  The prefill follows, so the engine is in the state of a prefilled encode.
+ * Mode, by RECALL's rule: if the engine is not in ragged image mode and every n_b == F x N of the current uniform image shape, the
+ * batch is installed WITHOUT key counts -- exactly the state gitmi_encode_frames leaves: the fp32 feats_out of an encode, handed
+ * back in, makes every follow-up return what it returns after that encode bit for bit in every precision (so do those rows
+ * rounded to the operand type by the caller).  Rows of per-frame encodes composed with t equal the list-form call bit for bit
+ * when they came from an encoder pass of the same image count and order; rows of passes of another size may differ by the
+ * rounding of another GEMM tile form.  Otherwise it is a key-count batch, as after a context call: stride = max_b n_b rounded up
+ * to a multiple of 16 where cap allows, attention reads n_b keys of image b, no context rows; every image gets what a call with
+ * its rows alone gets.  GITMI_SEARCH_ATTEND works over both (Kc counts the stride's columns; columns >= n_b are 0).
+ * Unlike GITMI_SEARCH_CONTEXT this kind does not need vit_width == dec_hidden: the rows pass through the visual projection.
+ * Serving schedule: as for any follow-up it neither waits for nor signals the gitmi_set_encode_after chain.
+ * The engine CANNOT tell where the rows came from: features of another model of the same width go unnoticed, as for RECALL.
+ * Non-finite or out-of-range values are not looked for here; they surface as info_out[3] of the calls that follow, as today.
+ * The device table (max_batch x max_frames pieces, max_batch counts) is allocated by the first such call: engines that never
+ * take features keep their footprint. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

@@ -11,7 +11,9 @@
 #     smoke    __graft_entry__.smoke()
 #     attrib   tools/error_attribution.py on the benchmark's, the oracle's and the trained-statistics weights -> TAG_error_attribution_*.txt
 #     memory   tools/memory_bench.py: KEEP / RECALL + follow-up against the full call, GIT_BASE 224 x 224, 64 images, f16 -> TAG_memory_bench.json
-# The bench, stats, configs and memory sections write to $BENCH_OUT (default out/), the other sections where their tools write;
+#     features tools/features_bench.py: FeatureStore windows against the list call (GIT_BASE_VATEX, 16 videos) and FeatureStore / ImageStore
+#              recall against the full call (GIT_BASE, 64 images), f16 -> TAG_features_bench.json
+# The bench, stats, configs, memory and features sections write to $BENCH_OUT (default out/), the other sections where their tools write;
 # copy what is cited into profiles/.
 set -u; mkdir -p gpurun_out; export PYTHONUNBUFFERED=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 R=$PWD; TAG=${1:-collect}; shift || true; SECTIONS=${*:-pmc bench stats suite configs smoke}
@@ -60,6 +62,9 @@ attrib)
 memory)
   t "memory bench"; timeout 300 python tools/memory_bench.py --out $OUT/${TAG}_memory_bench.json > $OUT/${TAG}_memory_bench.log 2>&1; echo "rc=$?"
   tail -n 1 $OUT/${TAG}_memory_bench.log | cut -c1-900 ;;
+features)
+  t "features bench"; timeout 300 python tools/features_bench.py --out $OUT/${TAG}_features_bench.json > $OUT/${TAG}_features_bench.log 2>&1; echo "rc=$?"
+  tail -n 1 $OUT/${TAG}_features_bench.log | cut -c1-1200 ;;
 *) echo "unknown section $sec" ;;
 esac; done
 t done
