@@ -317,7 +317,9 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     for (auto ev : e->event_pool) hipEventDestroy(ev);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->sc_allocs) hipFree(p);
-    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab); hipFree(e->feat_tab);
+    hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab); hipFree(e->feat_tab); hipFree(e->ban_words);
+    if (e->ban_stage) hipHostFree(e->ban_stage);
+    if (e->ban_staged) hipEventDestroy(e->ban_staged);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -596,12 +598,24 @@ static int decode_layers_impl(gitmi_engine* e, const int* kv_src, int ld_ids, in
     return 0;
 }
 
-static int sample_candidates(gitmi_engine* e, const float* logits, int ldl, int R, int step, hipStream_t s, StepCands* cands);
+static int sample_candidates(gitmi_engine* e, const float* logits, int ldl, int R, int step, hipStream_t s, StepCands* cands,
+                             const BanArgs* ban);
 static int trie_candidates(gitmi_engine* e, const float* logits, int ldl, int cur_len, hipStream_t s, StepCands* cands);
 // repetition penalty of the current search (GENERATOR only; 0 and 1 both mean "off")
 static float rep_penalty_of(const gitmi_engine* e) {
     const double rp = e->sample.repetition_penalty;
     return (e->ss.kind == GITMI_SEARCH_GENERATOR && rp > 0 && rp != 1.0) ? (float)rp : 0.f;
+}
+
+// decoding constraints of the search in progress (GITMI_SEARCH_CONSTRAIN): the engine's tables, or all null when it runs plain
+static BanArgs ban_args(const gitmi_engine* e) {
+    BanArgs b{};
+    if (!e->ban_live || !e->ban_words) return b;
+    const int mb = e->cfg.max_batch;
+    b.W = (e->cfg.vocab + 31) / 32; b.eos = e->cfg.eos;
+    const int* tab = reinterpret_cast<const int*>(e->ban_words + (size_t)mb * b.W);
+    b.words = e->ban_words; b.set_of = tab; b.min_new = tab + mb; b.ngram = tab + 2 * mb;
+    return b;
 }
 
 // vocabulary head of the step: candidate lists for the search (and optionally the logits themselves)
@@ -614,6 +628,10 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
     const bool sampling = ids != nullptr && e->ss.sampled;
     const bool trie = ids != nullptr && e->trie_search;
     if ((sampling || trie) && !logits_out) { logits_out = e->logits; ldl = e->ldl; }     // the filter / the trie need the whole row
+    // Decoding constraints: every logit is banned exactly ONCE.  Chain: by the fused head -- the logits it stores already carry
+    // the -10000, so the sampling filter that reads them gets no tables.  Otherwise the GEMM stores raw logits and the one
+    // whole-row kernel that consumes them (row_topm or sample_rows) applies the ban.
+    const BanArgs ban = ids ? ban_args(e) : BanArgs{};
     if (chain) {
         VocabArgs v{};
         v.A = (const unsigned short*)e->xo_b; v.lda = d; v.W = (const unsigned short*)e->w.out_f.w; v.bias = e->w.out_f.bias; v.colsum = e->w.out_f.colsum;
@@ -629,6 +647,7 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
         v.max_wgs = e->pol.vocab_wgs >= 0 ? e->pol.vocab_wgs : (e->pol.shared_device && R <= 64) ? 60 : 0;
         v.ids = ids; v.ld_ids = ld_ids; v.cur_len = cur_len; v.plen = e->plen_dev; v.beams = beams; v.suppress_kind = suppress_kind;
         v.rep_penalty = ids ? rep_penalty_of(e) : 0.f;
+        v.ban = ban;
         v.part_val = e->part_val; v.part_idx = e->part_idx; v.part_lse = e->part_lse;
         v.logits_out = logits_out; v.ld_logits = ldl;
         {
@@ -636,17 +655,17 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
             if (!GITMI_SKIPPED(e, 8)) HIPCK(launch_vocab_topm(v, M, s));
         }
         cands->nparts = e->vocab_nparts; cands->slots = vocab_mtop_slots(M);
-        if (sampling) RCK(sample_candidates(e, logits_out, ldl, R, cur_len, s, cands));
+        if (sampling) RCK(sample_candidates(e, logits_out, ldl, R, cur_len, s, cands, nullptr));
         if (trie) RCK(trie_candidates(e, logits_out, ldl, cur_len, s, cands));
     } else {
         RCK(gemm(e, s, e->d_ht, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, R, c.vocab, d, 0, TAG_GEMM_OTHER));
         cands->nparts = 1; cands->slots = row_topm_slots(M);
-        if (sampling) RCK(sample_candidates(e, e->logits, e->ldl, R, cur_len, s, cands));
+        if (sampling) RCK(sample_candidates(e, e->logits, e->ldl, R, cur_len, s, cands, &ban));
         else if (trie) RCK(trie_candidates(e, e->logits, e->ldl, cur_len, s, cands));
         else if (ids)
             HIPCK(launch_row_topm(e->logits, e->ldl, c.vocab, ids, ld_ids, cur_len, e->plen_dev, beams, suppress_kind,
                                   rep_penalty_of(e), M, R,
-                                  e->part_val, e->part_idx, e->part_lse, s));
+                                  e->part_val, e->part_idx, e->part_lse, s, &ban));
         if (logits_out && logits_out != e->logits) HIPCK(launch_copy_f32(e->logits, e->ldl, logits_out, ldl, R, c.vocab, s));
     }
     return 0;
@@ -803,12 +822,13 @@ static int search_mtop(const SearchState& st) {
     return st.kind == GITMI_SEARCH_AUTOREGRESSIVE ? std::max(st.k, st.pn) : st.pn * st.k;
 }
 // sampling branch: filter + draws from the materialised logits of the step (decoder.py:1146-1166)
-static int sample_candidates(gitmi_engine* e, const float* logits, int ldl, int R, int step, hipStream_t s, StepCands* cands) {
+static int sample_candidates(gitmi_engine* e, const float* logits, int ldl, int R, int step, hipStream_t s, StepCands* cands,
+                             const BanArgs* ban) {
     const gitmi_search& sp = e->sample;
     const float temp = sp.temperature > 0 ? (float)sp.temperature : 1.0f;
     HIPCK(launch_sample_rows(logits, ldl, e->ss.V, R, temp, sp.top_k, (float)sp.top_p, e->ss.pn, sp.seed, step,
                              e->part_val, e->part_idx, e->part_lse, nullptr, e->ss.ids[e->ss_cur], e->ss.T, step,
-                             rep_penalty_of(e), row_topm_slots(e->ss.pn), s));
+                             rep_penalty_of(e), row_topm_slots(e->ss.pn), s, ban, e->plen_dev, e->ss.k));
     cands->part_val = e->part_val; cands->part_idx = e->part_idx; cands->part_lse = e->part_lse;
     cands->nparts = 1; cands->slots = row_topm_slots(e->ss.pn);
     return 0;
@@ -895,6 +915,11 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("%s: GITMI_SEARCH_KEEP is not a search (gitmi_generate_prefixed keeps the memory of resident images)", who);
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("%s: GITMI_SEARCH_RECALL is not a search (gitmi_generate_prefixed recalls kept images)", who);
     if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("%s: GITMI_SEARCH_FEATURES is not a search (gitmi_generate_prefixed installs given feature rows)", who);
+    if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN) return fail("%s: GITMI_SEARCH_CONSTRAIN is not a search (gitmi_generate_prefixed arms the constraints of the next search call)", who);
+    if (e->ban_armed)
+        return fail("%s: decoding constraints are armed for %d sentences (GITMI_SEARCH_CONSTRAIN): the seam's caller owns its logits and "
+                    "applies its own -- disarm first (a GITMI_SEARCH_CONSTRAIN call with Q == 0)", who, e->ban_armed);
+    e->ban_live = false;
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -937,7 +962,7 @@ extern "C" int gitmi_search_advance(gitmi_engine* e, const float* logits, void* 
     hipStream_t s = (hipStream_t)stream;
     const int M = search_mtop(st), R = st.B * st.k;
     StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, row_topm_slots(M)};
-    if (st.sampled) RCK(sample_candidates(e, logits, st.V, R, e->ss_len, s, &cands));
+    if (st.sampled) RCK(sample_candidates(e, logits, st.V, R, e->ss_len, s, &cands, nullptr));
     else if (e->trie_search) RCK(trie_candidates(e, logits, st.V, e->ss_len, s, &cands));
     else
         HIPCK(launch_row_topm(logits, st.V, st.V, st.ids[e->ss_cur], st.T, e->ss_len, e->plen_dev, st.k,
@@ -1084,7 +1109,7 @@ static GraphKey graph_key_of(const gitmi_engine* e, const Request& rq, int F_eff
     return {rq.B, rq.Q, F_eff, rq.minP, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, e->H, e->W,
             rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, resident ? 1 : 0,
             resident ? e->cur_Nimg : 0, resident && e->keyed ? 1 : 0, sp.length_penalty,
-            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed};
+            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed, e->ban_live ? 1 : 0};
 }
 
 // Launches the graphs of one call on `x`: `enc` (the whole call, or encode + prefill; nullptr in a follow-up), then `dec`
@@ -1189,11 +1214,19 @@ static int generate_graphed(gitmi_engine* e, const Request& rq, hipStream_t s) {
 
 // common tail of gitmi_generate / gitmi_generate_prefixed: start_dev / plen_dev / img_of_dev are already enqueued on `s`.
 // Eager launches for profiling spans and for long step budgets (which poll the finished count), else captured graphs.
-static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s) {
+// constrained (constrain_check): the call consumes the armed decoding constraints -- here, behind the last step of the entry point
+// that can refuse the call, so that a refused call stays armed; the tables are live for exactly this call
+static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s, bool constrained) {
     const bool long_budget = rq.sp->max_steps - rq.minP > 32;
     const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
-    return settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
+    if (constrained) e->ban_armed = 0;
+    e->ban_live = constrained;
+    const int rc = settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
+    e->ban_live = false;
+    return rc;
 }
+
+static int constrain_check(const gitmi_engine* e, const char* who, const gitmi_search* sp, int Q, bool* constrained);
 
 extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefix, int P,
                               const gitmi_search* sp, int64_t* tokens_out, float* logprob_out, int32_t* info_out,
@@ -1207,6 +1240,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp && sp->kind == GITMI_SEARCH_KEEP) return fail("generate: GITMI_SEARCH_KEEP keeps the memory of resident images: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("generate: GITMI_SEARCH_RECALL recalls kept images: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("generate: GITMI_SEARCH_FEATURES installs given feature rows: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN) return fail("generate: GITMI_SEARCH_CONSTRAIN arms decoding constraints: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1214,12 +1248,14 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (!prefix) P = 1;
     if (P < 1 || P > c.max_text_len) return fail("generate: prefix length %d outside [1,%d]", P, c.max_text_len);
     if (sp->max_steps < P || sp->max_steps > c.max_text_len) return fail("generate: max_steps %d outside [P,%d]", sp->max_steps, c.max_text_len);
+    bool constrained = false;
+    RCK(constrain_check(e, "generate", sp, B, &constrained));
     hipStream_t s = (hipStream_t)stream;
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     // start tokens [B, P] on device (shared prefix, or [CLS]) -- filled by a kernel, no host copy
     RCK(fill_uniform_sentences(e, B, (const long long*)prefix, P, s));
     const Request rq{frames, F, B, B, P, P, false, sp, (long long*)tokens_out, logprob_out, info_out, e->out_sent};
-    return generate_run(e, rq, s);
+    return generate_run(e, rq, s, constrained);
 }
 
 // ---- caption scoring (GITMI_SEARCH_SCORE) -------------------------------------------------------------------------
@@ -1751,6 +1787,88 @@ static int features_call(gitmi_engine* e, const float* const* frames, int F, int
     return rc;
 }
 
+// ---- per-sentence decoding constraints (GITMI_SEARCH_CONSTRAIN, include/gitmi.h; the rule: ban_rules.h) -----------------------
+// Arms the constraints of the NEXT search call of this context: the ban sets (DEVICE words) and the per-sentence table (host) are
+// copied into the engine's own tables.  Every check comes before any launch; a refused call leaves what was armed, and what is
+// resident, as it was.  Q == 0 disarms.
+// info_out of an arming call, enqueued on `s` like the tables (through the staging buffer where there is one: no host wait)
+static int constrain_info(gitmi_engine* e, const int (&v)[4], int32_t* info_out, hipStream_t s) {
+    if (!e->ban_stage) return memory_info(v, info_out, s);          // a disarming call on a context that was never armed
+    HIPCK(hipEventSynchronize(e->ban_staged));
+    int* dst = e->ban_stage + 3 * (size_t)e->cfg.max_batch;
+    for (int i = 0; i < 4; ++i) dst[i] = v[i];
+    HIPCK(hipMemcpyAsync(info_out, dst, 4 * sizeof(int), hipMemcpyDefault, s));
+    HIPCK(hipEventRecord(e->ban_staged, s));
+    return 0;
+}
+static int constrain_call(gitmi_engine* e, const float* const* frames, const unsigned int* sets, int n_sets, const int32_t* table_host,
+                          const int32_t* image_of_host, int Q, int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    const int W = (c.vocab + 31) / 32;
+    if (Q == 0) {                   // disarms and reads nothing else
+        e->ban_armed = 0;
+        return info_out ? constrain_info(e, {0, 0, W, 0}, info_out, s) : 0;
+    }
+    if (frames) return fail("constrain: frames != NULL: constraints belong to the next search call, which brings its own images");
+    if (image_of_host) return fail("constrain: image_of != NULL: row q of the table is sentence q of the call to be constrained");
+    if (Q < 1 || Q > c.max_batch) return fail("constrain: Q=%d sentences outside [0,%d] (max_batch)", Q, c.max_batch);
+    if (n_sets < 0 || n_sets > c.max_batch) return fail("constrain: %d ban sets (ld_prefix) outside [0,%d] (max_batch)", n_sets, c.max_batch);
+    if (n_sets > 0 && !sets) return fail("constrain: %d ban sets, but a null pointer to their words (prefixes)", n_sets);
+    if (!table_host || !info_out) return fail("constrain: null argument");
+    if (c.max_text_len > 1024)      // the whole-row kernels keep the n-gram hits of a row in an LDS set of HIST_SLOTS / 2 tokens
+        return fail("constrain: max_text_len %d: constrained searches support histories up to 1024 tokens", c.max_text_len);
+    for (int q = 0; q < Q; ++q) {
+        const int set = table_host[3 * q], min_new = table_host[3 * q + 1], ngram = table_host[3 * q + 2];
+        if (set < -1 || set >= n_sets) return fail("constrain: sentence %d: set index %d outside [-1,%d)", q, set, n_sets);
+        if (min_new < 0 || min_new > c.max_text_len) return fail("constrain: sentence %d: min_new %d outside [0,%d] (max_text_len)", q, min_new, c.max_text_len);
+        if (ngram < 0 || ngram > 8) return fail("constrain: sentence %d: ngram %d outside [0,8]", q, ngram);
+    }
+    const size_t mb = (size_t)c.max_batch;
+    if (!e->ban_words && hipMalloc((void**)&e->ban_words, (mb * W + 3 * mb) * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        e->ban_words = nullptr;
+        return fail("constrain: out of device memory for the tables of the constraints");
+    }
+    if (!e->ban_stage) {
+        hipError_t err = hipHostMalloc((void**)&e->ban_stage, (3 * mb + 4) * sizeof(int), hipHostMallocDefault);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&e->ban_staged, hipEventDisableTiming);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            if (e->ban_stage) hipHostFree(e->ban_stage);
+            e->ban_stage = nullptr;
+            return fail("constrain: out of page-locked memory for the staging buffer of the constraints");
+        }
+    }
+    // No synchronisation with the work in flight: the table travels through a page-locked staging buffer as a copy ON `s`, behind
+    // whatever on `s` still reads the tables.  The host waits only for the previous arming call's own copy to have left the buffer.
+    HIPCK(hipEventSynchronize(e->ban_staged));
+    e->ban_armed = 0;               // from here on the tables are being overwritten: a copy that fails leaves the context disarmed
+    int* tab = e->ban_stage;
+    for (size_t q = 0; q < mb; ++q) {
+        const bool in = q < (size_t)Q;
+        tab[q] = in ? table_host[3 * q] : -1; tab[mb + q] = in ? table_host[3 * q + 1] : 0; tab[2 * mb + q] = in ? table_host[3 * q + 2] : 0;
+    }
+    HIPCK(hipMemcpyAsync(e->ban_words + mb * W, tab, 3 * mb * sizeof(int), hipMemcpyHostToDevice, s));
+    if (n_sets > 0) HIPCK(hipMemcpyAsync(e->ban_words, sets, (size_t)n_sets * W * sizeof(int), hipMemcpyDeviceToDevice, s));
+    RCK(constrain_info(e, {Q, n_sets, W, 0}, info_out, s));
+    e->ban_armed = Q;
+    return 0;
+}
+// A search call of Q sentences meets the arming: disarmed -> it runs plain; armed for Q -> it will run constrained (generate_run
+// consumes the arming); anything else is refused and stays armed.  Changes nothing: the last argument check of a search call.
+static int constrain_check(const gitmi_engine* e, const char* who, const gitmi_search* sp, int Q, bool* constrained) {
+    *constrained = false;
+    if (!e->ban_armed) return 0;
+    if (sp->kind == GITMI_SEARCH_TRIE)
+        return fail("%s: GITMI_SEARCH_TRIE while decoding constraints are armed (GITMI_SEARCH_CONSTRAIN): constraints on the trie search "
+                    "are not implemented -- disarm first (a GITMI_SEARCH_CONSTRAIN call with Q == 0)", who);
+    if (Q != e->ban_armed)
+        return fail("%s: decoding constraints are armed for %d sentences, this call has %d (they stay armed: run the call they were "
+                    "armed for, arm again, or disarm with Q == 0)", who, e->ban_armed, Q);
+    *constrained = true;
+    return 0;
+}
+
 // Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V)
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
@@ -1766,6 +1884,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         return memory_keep(e, frames, B, logprob_out, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && sp->kind == GITMI_SEARCH_RECALL)
         return memory_recall(e, frames, B, prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
+    if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN)
+        return constrain_call(e, frames, (const unsigned int*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && sp->kind == GITMI_SEARCH_FEATURES)
         return features_call(e, frames, F, B, prefixes, sp->reserved_, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {
@@ -1808,6 +1928,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     RCK(read_sentences(e, "generate_prefixed", prefix_len_host, image_of_host, ld_prefix, B, Q, c.max_batch, "max_batch", &span));
     if (sp->max_steps < span.maxP || sp->max_steps > c.max_text_len)
         return fail("generate_prefixed: max_steps %d outside [%d,%d]", sp->max_steps, span.maxP, c.max_text_len);
+    bool constrained = false;
+    RCK(constrain_check(e, "generate_prefixed", sp, Q, &constrained));
     RCK(upload_sentences(e, e->plen_dev, e->img_of_dev, s));
     HIPCK(hipMemcpy2D(e->start_dev, (size_t)c.max_text_len * sizeof(long long), prefixes, (size_t)ld_prefix * sizeof(long long),
                       (size_t)span.maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
@@ -1815,7 +1937,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, (long long*)tokens_out, logprob_out, info_out,
                      sent_out ? sent_out : e->out_sent};
-    return generate_run(e, rq, s);
+    return generate_run(e, rq, s, constrained);
 }
 
 // ---- profiling --------------------------------------------------------------------------

@@ -57,11 +57,12 @@ enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM
 struct GraphKey {
     int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed; double lp;
     int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
+    int constrained;    // the decode part runs under armed constraints (their VALUES live in the engine's tables, not in the key)
     // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds: Nimg rows per
     // image block, with (keyed) or without per-image key counts; both 0 in a call with frames, which decides them itself
     auto fields() const {
         return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed, lp, smp, top_k, nh, top_p, temp,
-                        rp, seed);
+                        rp, seed, constrained);
     }
     bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
@@ -179,6 +180,16 @@ struct gitmi_engine {
     // features in (GITMI_SEARCH_FEATURES, engine.hip features_call): the device table of a call -- max_batch x max_frames pieces,
     // then max_batch row counts --, allocated by the first such call
     gitmi::FeaturePiece* feat_tab = nullptr;
+    // per-sentence decoding constraints (GITMI_SEARCH_CONSTRAIN, engine.hip constrain_call): the engine's own copy of the ban
+    // sets (uint32 [max_batch][ceil(vocab / 32)]) and, behind them, set_of | min_new | ngram (int [3][max_batch]), allocated
+    // by the first arming call -- the pointers never change afterwards, so captured graphs stay valid whatever the values.
+    // ban_armed: the sentence count the constraints are armed for (0: disarmed); the next search call consumes them.
+    // ban_live: the search in progress runs constrained (decode_head_impl hands the tables to the head); set and cleared by generate_run.
+    unsigned int* ban_words = nullptr;
+    int* ban_stage = nullptr;           // page-locked staging of the table (+ info_out): the arming call enqueues copies, it does not wait
+    hipEvent_t ban_staged = nullptr;    // the last copy out of ban_stage
+    int ban_armed = 0;
+    bool ban_live = false;
 
     // ViT workspaces (one frame of max_batch images at a time)
     void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;

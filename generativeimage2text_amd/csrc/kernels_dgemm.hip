@@ -41,6 +41,7 @@
 #include "gitmi_common.h"
 #include "launchers.h"
 #include "dgemm_shared.h"
+#include "ban_rules.h"
 #include <type_traits>
 #include <utility>
 
@@ -347,7 +348,9 @@ constexpr int VOC_MAX_BLOCKS = 8;      // column blocks a workgroup may walk (bi
 //               memory latency per strip.
 //   VOC_BEAM    several row blocks, K = 768: the rows' activations are re-read (from the L2) per (column block, row
 //               block), which drains the queue once per row block anyway; the refill runs behind the last row block.
-//   VOC_GENERIC any K <= 768, logits output, repetition penalty: conditional loads, stores in the loop.
+//   VOC_GENERIC any K <= 768, logits output, repetition penalty, decoding constraints (VocabArgs::ban, the BAN instantiation):
+//               conditional loads, stores in the loop.  The other two modes never read g.ban: their loops stay free of the
+//               loads and the branch.
 enum { VOC_GENERIC = 0, VOC_BEAM = 1, VOC_GREEDY = 2 };
 
 // x into a descending list tv (ties: the older entry stays ahead; -inf fill), in PLACE and without a dependency chain: every
@@ -381,8 +384,11 @@ template <int B, int N, class F> __device__ __forceinline__ void static_for(F&& 
 
 // ABL (tools/probe/vocab_probe.hip only; 0 in every library): 1 no top-M insertion, 2 no log-sum-exp update, 4 no merge rounds
 // of the four lanes of a row, 8 the row block's activations are not re-read, 16 no MFMAs -- timing decomposition, wrong results
-template <int MTOP, int MODE, int ABL = 0>
+// BAN (VOC_GENERIC only): the decoding constraints of g.ban are applied -- an instantiation of its own, so that the generic form
+// an unconstrained call launches (repetition penalty, sampling, logits output) keeps its registers
+template <int MTOP, int MODE, int ABL = 0, bool BAN = false>
 __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
+    static_assert(!BAN || MODE == VOC_GENERIC, "constraints run in the generic form");
     constexpr int MT = 4, NS = VOC_NS;
     constexpr bool FULLK = MODE != VOC_GENERIC, ONE_RB = MODE == VOC_GREEDY, PARK = MODE == VOC_GREEDY;
     // ONE LDS object (a second __shared__ array makes hipcc drain the vector-memory queue before LDS reads): the exchange
@@ -471,7 +477,7 @@ __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
     }
 
     const bool pen = MODE == VOC_GENERIC && g.ids != nullptr && g.rep_penalty != 0.f && g.rep_penalty != 1.f;
-    int xbuf = 0;      // exchange buffer of the next strip: alternates across row and column blocks (an odd strip count -- the
+    int xbuf = 0;     // exchange buffer of the next strip: alternates across row and column blocks (an odd strip count -- the
                        // vocabulary tail -- must not reuse buffer 0 for the last strip of one pass and the first of the next)
     VOC_LDS_BARRIER();                                       // colc is complete
     // One column block.  REFILL (every block but the workgroup's last) is a COMPILE-TIME property of the call: a branch
@@ -497,6 +503,30 @@ __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
                         const int rel = g.ids[(size_t)fm * g.ld_ids + s2] - c0;
                         if (rel >= 0 && rel < 16 * NS && ((rel >> 2) & 3) == lg) pen_mask |= 1u << ((rel >> 4) * 4 + (rel & 3));
                     }
+                }
+            }
+            // decoding constraints (ban_rules.h): which of this lane's columns are banned for the row, same bit layout.  The set
+            // words of the block's 128 columns are words c0 / 32 .. + 3 (strip st: half (st & 1) of word st >> 1); the length
+            // rule's token and the n-gram hits of the history scan go through the penalty's column -> bit map
+            unsigned int ban_mask = 0u;
+            if constexpr (BAN) {
+                {
+                    const int sent = fm / g.beams;
+                    const BanRow br = ban_row(g.ban, sent, g.plen[sent], g.cur_len);
+                    auto bit_of = [&](int tok) -> unsigned int {
+                        const int rel = tok - c0;
+                        return (rel >= 0 && rel < 16 * NS && ((rel >> 2) & 3) == lg) ? 1u << ((rel >> 4) * 4 + (rel & 3)) : 0u;
+                    };
+#pragma unroll
+                    for (int w = 0; w < NS / 2; ++w) {
+                        const unsigned int sw = ban_set_word(br, (c0 >> 5) + w);
+                        ban_mask |= ((sw >> (lg * 4)) & 0xfu) << (w * 8);
+                        ban_mask |= ((sw >> (16 + lg * 4)) & 0xfu) << (w * 8 + 4);
+                    }
+                    ban_mask |= bit_of(br.eos);
+                    const int* hist = g.ids + (size_t)fm * g.ld_ids;
+                    for (int i = 0; i <= ban_ngram_last(br, g.cur_len); ++i)
+                        if (ban_ngram_hit(br, hist, g.cur_len, i)) ban_mask |= bit_of(hist[i + br.n - 1]);
                 }
             }
             // running per-lane state: sorted top-MTOP of its 4 columns per strip, online log-sum-exp
@@ -540,6 +570,13 @@ __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
                         else v[r] += bb[r];
                     }
                     if constexpr (MODE == VOC_GENERIC) {
+                        // a banned logit is -10000 for everything downstream: the logits_out store (so its readers -- the
+                        // sampling filter -- must NOT apply the ban again: decode_head_impl), the penalty, the candidates, the sum
+                        if constexpr (BAN) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if ((ban_mask >> (st * 4 + r)) & 1u) v[r] = -10000.f;
+                        }
                         if (g.logits_out && fm_raw < g.M) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
@@ -718,8 +755,10 @@ static hipError_t launch_vocab_m(const VocabArgs& g_in, hipStream_t s) {
     int nwg = g.max_wgs > 0 && g.max_wgs < g.nblk ? g.max_wgs : g.nblk;              // each workgroup walks nblk / nwg column blocks
     if ((g.nblk + nwg - 1) / nwg > VOC_MAX_BLOCKS) nwg = (g.nblk + VOC_MAX_BLOCKS - 1) / VOC_MAX_BLOCKS;
     const bool pen = g.ids != nullptr && g.rep_penalty != 0.f && g.rep_penalty != 1.f;
-    const bool fast = (g.K >> 5) == 4 * VKS && !g.logits_out && !pen;
-    if (!fast) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GENERIC>), dim3(nwg), dim3(256), 0, s, g);
+    const bool ban = g.ids != nullptr && g.ban.set_of != nullptr;     // a constrained call: the generic form, like the penalty
+    const bool fast = (g.K >> 5) == 4 * VKS && !g.logits_out && !pen && !ban;
+    if (ban) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GENERIC, 0, true>), dim3(nwg), dim3(256), 0, s, g);
+    else if (!fast) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GENERIC>), dim3(nwg), dim3(256), 0, s, g);
     else if (g.M <= 64) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GREEDY>), dim3(nwg), dim3(256), 0, s, g);
     else hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_BEAM>), dim3(nwg), dim3(256), 0, s, g);     // walks the row blocks too
     return hipGetLastError();

@@ -24,16 +24,33 @@
 // that holds the K/V of text position pos for this row's history) is gathered with them.
 #include "gitmi_common.h"
 #include "launchers.h"
+#include "ban_rules.h"
 
 namespace gitmi {
 
+// Decoding constraints in the whole-row kernels (BAN instantiations only; an unconstrained call launches the plain ones): the
+// tokens the n-gram rule bans for the row, gathered into an LDS token set like the repetition penalty's history.  `tbl` has
+// HIST_SLOTS entries; called by every thread of the workgroup.
+template <int NT>
+__device__ __forceinline__ void ban_fill_ngram(const BanRow& br, const int* hist, int t, int* tbl) {
+    for (int i = threadIdx.x; i < HIST_SLOTS; i += NT) tbl[i] = -1;
+    __syncthreads();
+    for (int i = threadIdx.x; i <= ban_ngram_last(br, t); i += NT)
+        if (ban_ngram_hit(br, hist, t, i)) hist_insert(tbl, hist[i + br.n - 1]);
+    __syncthreads();
+}
+// banned for (row, column c): ban_rules.h, the n-gram rule through the row's token set
+__device__ __forceinline__ bool ban_test(const BanRow& br, const int* tbl, int c) {
+    return ban_static(br, c) || (br.n > 0 && hist_contains(tbl, c));
+}
+
 // ---------------------------------------------------------------------------------------
-template <int MMAX, int NT>
+template <int MMAX, int NT, bool BAN = false>
 __global__ __launch_bounds__(NT) void row_topm_kernel(const float* __restrict__ logits, int ldl, int V,
                                                        const int* __restrict__ ids, int ld_ids, int cur_len,
                                                        const int* __restrict__ plen, int beams, int suppress_kind,
                                                        float rep_penalty, float* __restrict__ part_val,
-                                                       int* __restrict__ part_idx, float2* __restrict__ part_lse) {
+                                                       int* __restrict__ part_idx, float2* __restrict__ part_lse, BanArgs ban) {
     constexpr int NW = NT / 64;
     __shared__ int s_hist[HIST_SLOTS];
     __shared__ float s_val[NT * MMAX];
@@ -57,12 +74,23 @@ __global__ __launch_bounds__(NT) void row_topm_kernel(const float* __restrict__ 
         __syncthreads();
     }
 
+    // decoding constraints (ban_rules.h): -10000 before the penalty and the no-repeat rule
+    BanRow br{};
+    int* s_ban = nullptr;
+    if constexpr (BAN) {
+        __shared__ int s_ban_tbl[HIST_SLOTS];
+        s_ban = s_ban_tbl;
+        br = ban_row(ban, r / beams, plen[r / beams], cur_len);
+        ban_fill_ngram<NT>(br, ids + (size_t)r * ld_ids, cur_len, s_ban);
+    }
+
     float tv[MMAX];
     int ti[MMAX];
 #pragma unroll
     for (int j = 0; j < MMAX; ++j) { tv[j] = -INFINITY; ti[j] = 0x7fffffff; }
     float mx = -INFINITY, sm = 0.f;
     auto feed = [&](float v, int i) {
+        if constexpr (BAN) { if (ban_test(br, s_ban, i)) v = -10000.f; }
         if (pen && hist_contains(s_hist, i)) v = rep_penalize(v, rep_penalty);
         if (i == last) v = -10000.f;
         // online log-sum-exp; while the running maximum is -inf (only masked logits so far) there is no term to add:
@@ -189,13 +217,15 @@ template <typename T> __device__ __forceinline__ T block_sum_1024(T v, T* sh) {
     return t;
 }
 
+template <bool BAN>
 __global__ __launch_bounds__(SMP_NT) void sample_rows_kernel(const float* __restrict__ logits, int ldl, int V,
                                                              float inv_temp, int top_k, float top_p, int ndraw,
                                                              unsigned int seed_lo, unsigned int seed_hi, int step,
                                                              float* __restrict__ part_val, int* __restrict__ part_idx,
                                                              float2* __restrict__ part_lse, float* __restrict__ filtered_out,
                                                              const int* __restrict__ ids, int ld_ids, int cur_len,
-                                                             float rep_penalty, int stride) {
+                                                             float rep_penalty, int stride, BanArgs ban,
+                                                             const int* __restrict__ plen, int beams) {
     __shared__ int s_hist[HIST_SLOTS];
     __shared__ float sh_f[SMP_NT / 64];
     __shared__ int sh_i[SMP_NT / 64];
@@ -211,6 +241,15 @@ __global__ __launch_bounds__(SMP_NT) void sample_rows_kernel(const float* __rest
         for (int s = tid; s < cur_len; s += SMP_NT) hist_insert(s_hist, ids[(size_t)r * ld_ids + s]);
         __syncthreads();
     }
+    // decoding constraints (ban_rules.h) on the raw scores, before the penalty: the filter and the draws see -10000
+    BanRow br{};
+    int* s_ban = nullptr;
+    if constexpr (BAN) {
+        __shared__ int s_ban_tbl[HIST_SLOTS];
+        s_ban = s_ban_tbl;
+        br = ban_row(ban, r / beams, plen[r / beams], cur_len);
+        ban_fill_ngram<SMP_NT>(br, ids + (size_t)r * ld_ids, cur_len, s_ban);
+    }
     float xv[SMP_PER];
     unsigned int key[SMP_PER];
     float mx = -INFINITY;
@@ -218,6 +257,7 @@ __global__ __launch_bounds__(SMP_NT) void sample_rows_kernel(const float* __rest
     for (int i = 0; i < SMP_PER; ++i) {
         const int j = tid + i * SMP_NT;
         float raw = j < V ? x[j] : 0.f;
+        if constexpr (BAN) { if (j < V && ban_test(br, s_ban, j)) raw = -10000.f; }
         if (pen && j < V && hist_contains(s_hist, j)) raw = rep_penalize(raw, rep_penalty);
         xv[i] = j < V ? raw * inv_temp : -INFINITY;
         key[i] = j < V ? f2key(xv[i]) : 0u;
@@ -991,33 +1031,49 @@ int row_topm_slots(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8
 
 hipError_t launch_row_topm(const float* logits, int ldl, int V, const int* ids, int ld_ids, int cur_len,
                            const int* plen, int beams, int suppress_kind, float rep_penalty, int M, int R,
-                           float* part_val, int* part_idx, float2* part_lse, hipStream_t s) {
+                           float* part_val, int* part_idx, float2* part_lse, hipStream_t s, const BanArgs* ban) {
     if (M < 1 || M > 16) return hipErrorInvalidValue;
+    const bool banned = ban && ban->set_of && ids;
+    if (banned && (!plen || cur_len > HIST_SLOTS / 2)) return hipErrorInvalidValue;
+    const BanArgs ba = banned ? *ban : BanArgs{};
     if (rep_penalty != 0.f && rep_penalty != 1.f && ids && cur_len > HIST_SLOTS / 2) return hipErrorInvalidValue;
     // one workgroup per row; more threads per row when the per-thread candidate list is short (LDS: NT*MMAX*8 B)
-#define GITMI_TOPM(MM, NTT)                                                                                         \
-    hipLaunchKernelGGL((row_topm_kernel<MM, NTT>), dim3(R), dim3(NTT), 0, s, logits, ldl, V, ids, ld_ids, cur_len, plen, \
-                       beams, suppress_kind, rep_penalty, part_val, part_idx, part_lse)
+#define GITMI_TOPM_B(MM, NTT, BB)                                                                                           \
+    hipLaunchKernelGGL((row_topm_kernel<MM, NTT, BB>), dim3(R), dim3(NTT), 0, s, logits, ldl, V, ids, ld_ids, cur_len, plen, \
+                       beams, suppress_kind, rep_penalty, part_val, part_idx, part_lse, ba)
+#define GITMI_TOPM(MM, NTT)                           \
+    do {                                              \
+        if (banned) GITMI_TOPM_B(MM, NTT, true);      \
+        else GITMI_TOPM_B(MM, NTT, false);            \
+    } while (0)
     if (M <= 1) GITMI_TOPM(1, 1024);
     else if (M <= 2) GITMI_TOPM(2, 1024);
     else if (M <= 4) GITMI_TOPM(4, 1024);
     else if (M <= 8) GITMI_TOPM(8, 512);
     else GITMI_TOPM(16, 256);
 #undef GITMI_TOPM
+#undef GITMI_TOPM_B
     return hipGetLastError();
 }
 
 hipError_t launch_sample_rows(const float* logits, int ldl, int V, int R, float temperature, int top_k, float top_p,
                               int ndraw, unsigned long long seed, int step, float* part_val, int* part_idx,
                               float2* part_lse, float* filtered_out, const int* ids, int ld_ids, int cur_len,
-                              float rep_penalty, int stride, hipStream_t s) {
+                              float rep_penalty, int stride, hipStream_t s, const BanArgs* ban, const int* plen, int beams) {
     if (R <= 0) return hipSuccess;
+    const bool banned = ban && ban->set_of && ids;
+    if (banned && (!plen || beams < 1 || cur_len > HIST_SLOTS / 2)) return hipErrorInvalidValue;
+    const BanArgs ba = banned ? *ban : BanArgs{};
     if (stride < ndraw) return hipErrorInvalidValue;
     if (rep_penalty != 0.f && rep_penalty != 1.f && ids && cur_len > HIST_SLOTS / 2) return hipErrorInvalidValue;
     if (V > SMP_NT * SMP_PER || V < 2 || ndraw < 1 || ndraw > SS_CMAX || !(temperature > 0.f)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sample_rows_kernel, dim3(R), dim3(SMP_NT), 0, s, logits, ldl, V, 1.0f / temperature, top_k, top_p, ndraw,
-                       (unsigned int)(seed & 0xffffffffu), (unsigned int)(seed >> 32), step, part_val, part_idx, part_lse,
-                       filtered_out, ids, ld_ids, cur_len, rep_penalty, stride);
+#define GITMI_SAMPLE(BB)                                                                                                        \
+    hipLaunchKernelGGL(sample_rows_kernel<BB>, dim3(R), dim3(SMP_NT), 0, s, logits, ldl, V, 1.0f / temperature, top_k, top_p, ndraw, \
+                       (unsigned int)(seed & 0xffffffffu), (unsigned int)(seed >> 32), step, part_val, part_idx, part_lse,         \
+                       filtered_out, ids, ld_ids, cur_len, rep_penalty, stride, ba, plen, beams)
+    if (banned) GITMI_SAMPLE(true);
+    else GITMI_SAMPLE(false);
+#undef GITMI_SAMPLE
     return hipGetLastError();
 }
 

@@ -78,6 +78,14 @@ inline DGemmArgs dgemm_to_stream(const void* A, const void* W, const float* bias
     return g;
 }
 
+// ---- per-sentence decoding constraints (GITMI_SEARCH_CONSTRAIN, include/gitmi.h; the rule itself: ban_rules.h) ----
+// The engine's own tables of an armed call (DEVICE, host-validated): `words` uint32 [n_sets][W] ban sets, bit c % 32 of word
+// c / 32 = token c; per sentence set_of (-1: none), min_new, ngram (0: off, else 1..8).  set_of == nullptr: unconstrained.
+struct BanArgs {
+    const unsigned int* words; const int* set_of; const int* min_new; const int* ngram;
+    int W, eos;
+};
+
 // vocabulary head with the running top-M / log-sum-exp fused: one sorted candidate list per (row, workgroup)
 struct VocabArgs {
     const unsigned short* A; int lda; const unsigned short* W; const float* bias; const float* colsum;
@@ -90,6 +98,9 @@ struct VocabArgs {
     float* logits_out; int ld_logits;                      // optional full logits (teacher-forced parity hook)
     int max_wgs;                // workgroups of the launch (0: one per column block); fewer = each walks several column blocks
     int nblk;                   // column blocks (set by the launcher)
+    // decoding constraints of the rows' sentences (ids / plen / beams / cur_len above describe the rows); VOC_GENERIC only --
+    // the launcher sends a constrained call there, VOC_GREEDY / VOC_BEAM never read these fields
+    BanArgs ban;
 };
 hipError_t launch_vocab_topm(const VocabArgs& g, int mtop, hipStream_t s);
 int vocab_parts(int V, int cols_per_wg);
@@ -292,7 +303,8 @@ int row_topm_slots(int M);
 hipError_t launch_sample_rows(const float* logits, int ldl, int V, int R, float temperature, int top_k, float top_p,
                               int ndraw, unsigned long long seed, int step, float* part_val, int* part_idx,
                               float2* part_lse, float* filtered_out, const int* ids, int ld_ids, int cur_len,
-                              float rep_penalty, int stride, hipStream_t s);      // stride >= ndraw: entries of a row's list
+                              float rep_penalty, int stride, hipStream_t s,       // stride >= ndraw: entries of a row's list
+                              const BanArgs* ban = nullptr, const int* plen = nullptr, int beams = 1);   // ban: rows of plen / beams sentences
 // token trie on the device (CSR: the children of node n are edges child_off[n] .. child_off[n + 1]) + one cursor per sentence
 struct TrieArgs {
     const int* child_off; const int* child_tok; const int* child_node;
@@ -305,7 +317,7 @@ hipError_t launch_trie_select(const float* logits, int ldl, int V, const int* id
                               hipStream_t s);
 hipError_t launch_row_topm(const float* logits, int ldl, int V, const int* ids, int ld_ids, int cur_len,
                            const int* plen, int beams, int suppress_kind, float rep_penalty, int M, int R,
-                           float* part_val, int* part_idx, float2* part_lse, hipStream_t s);
+                           float* part_val, int* part_idx, float2* part_lse, hipStream_t s, const BanArgs* ban = nullptr);
 hipError_t launch_search_step(const SearchState& st, int src, int cur_len, const StepCands& in, const EmbedArgs& em,
                               bool t_is_f32, hipStream_t s);
 hipError_t launch_search_init(const SearchState& st, hipStream_t s);

@@ -29,6 +29,7 @@ SEARCH_TREE_SCORE = 6  # not a search: gitmi_generate_prefixed scores every node
 SEARCH_KEEP = 7        # not a search: gitmi_generate_prefixed copies the memory of resident images into a caller's store (Engine.keep)
 SEARCH_RECALL = 8      # not a search: gitmi_generate_prefixed makes kept slots the resident images (Engine.recall)
 SEARCH_FEATURES = 9    # not a search: gitmi_generate_prefixed makes given feature rows the resident images (Engine.install_features)
+SEARCH_CONSTRAIN = 10  # not a search: gitmi_generate_prefixed arms per-sentence decoding constraints for the next search (Engine.constrain)
 MEMORY_HEADER_BYTES = 256      # header of a slot of an image store; slots are multiples of this size (include/gitmi.h)
 
 
@@ -290,6 +291,78 @@ def _sentence_tables(lens: Sequence[int], image_of: Optional[Sequence[int]]):
     """(prefix_len_host, image_of_host) of gitmi_generate_prefixed as int32 arrays (image_of None: sentence q <-> image q)."""
     Q = len(lens)
     return (C.c_int32 * Q)(*lens), None if image_of is None else (C.c_int32 * Q)(*[int(i) for i in image_of])
+
+
+CONSTRAINT_KEYS = ("min_new_tokens", "no_repeat_ngram_size", "bad_tokens", "allowed_tokens")
+
+
+def constraint_tables(n: int, vocab: int, eos: int, min_new_tokens=0, no_repeat_ngram_size=0, bad_tokens=None, allowed_tokens=None,
+                      max_new: Optional[int] = None):
+    """Host side of Engine.constrain: the per-sentence decoding constraints of `n` sentences in the form of include/gitmi.h
+    (GITMI_SEARCH_CONSTRAIN).  Every argument is one value for all sentences or a list of n values, one per sentence:
+    min_new_tokens an int, no_repeat_ngram_size an int in 0 .. 8, bad_tokens / allowed_tokens a list of token ids (or None:
+    no list for that sentence; for all sentences a flat list of ids, per sentence a list of n lists / Nones).  A sentence bans
+    its bad tokens and everything outside its allowed tokens; [SEP] (`eos`) stays allowed unless it is a bad token.
+    Identical sets are stored once.  max_new: the largest min_new_tokens the engine accepts (its max_text_len).
+    -> (words, table): words a numpy uint32 [n_sets, ceil(vocab / 32)] (bit c % 32 of word c // 32 = token c; the bits at
+    and above `vocab` are clear), table n rows [set index or -1, min_new, ngram]; or None when no sentence is constrained."""
+    import numpy as np
+    n, vocab = int(n), int(vocab)
+    if n < 1:
+        raise ValueError(f"constraints for {n} sentences")
+
+    def per_sentence(name, value, scalar):
+        if scalar(value):
+            return [value] * n
+        value = list(value)
+        if len(value) != n:
+            raise ValueError(f"{name} has {len(value)} entries for {n} sentences (one value for all, or one per sentence)")
+        return value
+
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    is_ids = lambda v: v is None or (isinstance(v, (list, tuple)) and all(is_int(t) for t in v)) or \
+        (hasattr(v, "dim") and v.dim() == 1) or (isinstance(v, np.ndarray) and v.ndim == 1)
+    min_new = per_sentence("min_new_tokens", 0 if min_new_tokens is None else min_new_tokens, is_int)
+    ngram = per_sentence("no_repeat_ngram_size", 0 if no_repeat_ngram_size is None else no_repeat_ngram_size, is_int)
+    bad = per_sentence("bad_tokens", bad_tokens, is_ids)
+    allowed = per_sentence("allowed_tokens", allowed_tokens, is_ids)
+    W = (vocab + 31) // 32
+    sets, index, table = [], {}, []
+    for q in range(n):
+        if not is_int(min_new[q]) or min_new[q] < 0 or (max_new is not None and min_new[q] > max_new):
+            raise ValueError(f"sentence {q}: min_new_tokens {min_new[q]!r} outside [0, {max_new if max_new is not None else 'max_text_len'}]")
+        if not is_int(ngram[q]) or not 0 <= ngram[q] <= 8:
+            raise ValueError(f"sentence {q}: no_repeat_ngram_size {ngram[q]!r} outside [0, 8]")
+        ids = {}
+        for name, lst in (("bad_tokens", bad[q]), ("allowed_tokens", allowed[q])):
+            if lst is None:
+                continue
+            if not is_ids(lst):
+                raise ValueError(f"sentence {q}: {name} must be a list of token ids")
+            ids[name] = [int(t) for t in (lst.tolist() if hasattr(lst, "tolist") else lst)]
+            for t in ids[name]:
+                if t < 0 or t >= vocab:
+                    raise ValueError(f"sentence {q}: {name} holds token {t} outside [0, {vocab})")
+        set_index = -1
+        if ids:
+            bits = np.zeros(W * 32, dtype=bool)
+            if "allowed_tokens" in ids:
+                bits[:vocab] = True
+                bits[ids["allowed_tokens"]] = False
+                bits[int(eos)] = False
+            if "bad_tokens" in ids:
+                bits[ids["bad_tokens"]] = True
+            if bits.any():
+                words = np.packbits(bits.reshape(W, 32), axis=1, bitorder="little").view("<u4").reshape(W).astype(np.uint32)
+                key = words.tobytes()
+                if key not in index:
+                    index[key] = len(sets)
+                    sets.append(words)
+                set_index = index[key]
+        table.append([set_index, int(min_new[q]), int(ngram[q])])
+    if all(row == [-1, 0, 0] for row in table):
+        return None
+    return (np.stack(sets) if sets else np.zeros((0, W), dtype=np.uint32)), table
 
 
 class Geometry(tuple):
@@ -864,6 +937,38 @@ class Engine:
             self._geometry = Geometry(stride, int(F), [None] * B, image_rows=max(counts), context=[0] * B)
             self._geometry.rows = list(counts)
         return {"stride": stride, "max_rows": max_n, "total_rows": total}
+
+    # -- per-sentence decoding constraints ---------------------------------------------------------------------------------------
+    def constrain(self, sets_words, table) -> Dict[str, int]:
+        """Arm per-sentence decoding constraints for the NEXT search call of this context (include/gitmi.h
+        GITMI_SEARCH_CONSTRAIN; constraint_tables builds the arguments): sets_words uint32 [n_sets, ceil(vocab / 32)] (a numpy
+        array or a tensor; None: no sets), table one row [set index or -1, min_new, ngram] per sentence of that call.  One-shot:
+        the call consumes them.  An empty table disarms.  The copies are enqueued on the current stream and nothing is read
+        back: the host does not wait for the context's work in flight.
+        -> {'sentences', 'sets', 'words'}"""
+        import numpy as np
+        table = [[int(v) for v in row] for row in (table or [])]
+        if any(len(row) != 3 for row in table):
+            raise ValueError("a constraint table row is [set index or -1, min_new, ngram]")
+        Q, W = len(table), (int(self.c.vocab) + 31) // 32
+        words, n_sets = None, 0
+        if sets_words is not None and Q:
+            if isinstance(sets_words, torch.Tensor):
+                words = sets_words.view(torch.int32) if sets_words.dtype != torch.int32 else sets_words
+            else:
+                words = torch.from_numpy(np.ascontiguousarray(sets_words, dtype=np.uint32).view(np.int32))
+            if words.dim() != 2 or int(words.shape[1]) != W:
+                raise ValueError(f"ban sets are uint32 [n_sets, {W}] words, got {tuple(words.shape)}")
+            n_sets = int(words.shape[0])
+            words = words.to(torch.device(f"cuda:{self.device}")).contiguous() if n_sets else None
+        search = GitmiSearch()
+        search.kind = SEARCH_CONSTRAIN
+        info = torch.empty(4, dtype=torch.int32, device=f"cuda:{self.device}")
+        tab = (C.c_int32 * max(3 * Q, 1))(*[v for row in table for v in row])
+        self._ck(self.lib.gitmi_generate_prefixed(self._h, None, 0, 0, _ptr(words), n_sets, tab, None, Q, C.byref(search),
+                                                  None, None, None, info.data_ptr(), _stream()))
+        self._ban_keep = (words, info)  # the copies are enqueued on the stream: both outlive the call
+        return {"sentences": Q, "sets": n_sets if Q else 0, "words": W}       # info_out's values (include/gitmi.h), not read back
 
     def prefill(self) -> None:
         self._ck(self.lib.gitmi_prefill(self._h, _stream()))

@@ -13,12 +13,15 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Dict, Mapping, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import torch
 
 from .configs import GitModelConfig, config_from_param
-from .engine import Engine, context_segments, id_table
+from .engine import CONSTRAINT_KEYS, Engine, constraint_tables, context_segments, id_table
+
+# search_param keys of the per-sentence decoding constraints (CaptioningModel._constraints)
+CONSTRAINT_PARAMS = CONSTRAINT_KEYS + ("bad_words",)
 
 
 # ---- decoder.search(start_predictions, step): the reference's search seam as a method ----------------------------
@@ -487,10 +490,12 @@ class CaptioningModel:
 
     def _search_struct(self, search_param: Optional[dict] = None):
         """search_param: the keyword arguments CaptioningModel.infer forwards to decoder.search (decoder.py:1001-1003):
-        do_sample / top_k / top_p for GeneratorWithBeamSearch (decoder.py:1088-1090); `seed` selects the random stream."""
+        do_sample / top_k / top_p for GeneratorWithBeamSearch (decoder.py:1088-1090); `seed` selects the random stream.  The
+        per-sentence decoding constraints (min_new_tokens, no_repeat_ngram_size, bad_tokens, allowed_tokens, bad_words) are not
+        part of the struct: _constraints turns them into the tables the front end arms before the call."""
         d = self.decoder
         sp = dict(search_param or {})
-        unknown = set(sp) - {"do_sample", "top_k", "top_p", "seed", "num_keep_best", "num_return_sequences"}
+        unknown = set(sp) - {"do_sample", "top_k", "top_p", "seed", "num_keep_best", "num_return_sequences"} - set(CONSTRAINT_PARAMS)
         if unknown:
             raise NotImplementedError(f"search parameters {sorted(unknown)} are not implemented")
         if d.kind != "generator" and (int(sp.get("num_keep_best", 1)) != 1 or int(sp.get("num_return_sequences", 1)) != 1):
@@ -502,6 +507,50 @@ class CaptioningModel:
                                   seed=int(sp.get("seed", 0)),
                                   repetition_penalty=getattr(d, "repetition_penalty", 1.0),
                                   num_keep_best=int(sp.get("num_keep_best", 1)))
+
+    def _constraints(self, search_param: Optional[dict], n: int, repeat: int = 1):
+        """The decoding constraints of a request of `n` sentences (include/gitmi.h GITMI_SEARCH_CONSTRAIN) from its search_param:
+        min_new_tokens, no_repeat_ngram_size, bad_tokens, allowed_tokens -- each one value for all sentences or one per sentence
+        (engine.constraint_tables) -- and bad_words, words that are one WordPiece each (one list for all, or one per sentence),
+        banned like bad_tokens.  repeat: every sentence stands for `repeat` consecutive ones (num_return_sequences).
+        -> (words, table) for Engine.constrain, or None: the request is not constrained and nothing is armed."""
+        sp = {k: v for k, v in (search_param or {}).items() if k in CONSTRAINT_PARAMS and v is not None}
+        if not sp:
+            return None
+        if self.decoder.kind == "trie":
+            raise NotImplementedError("decoding constraints on the trie search are not implemented")
+        bad = sp.get("bad_tokens")
+        if "bad_words" in sp:
+            words = sp["bad_words"]
+            flat = all(isinstance(w, str) for w in words)
+            ids = [self._word_ids(words)] * n if flat else [None if ws is None else self._word_ids(ws) for ws in words]
+            if len(ids) != n:
+                raise ValueError(f"bad_words has {len(ids)} entries for {n} sentences (one list for all, or one per sentence)")
+            if bad is not None:
+                flat_ids = all(isinstance(t, int) and not isinstance(t, bool) for t in bad)       # one id list for every sentence
+                per = [list(bad)] * n if flat_ids else list(bad)
+                if len(per) != n:
+                    raise ValueError(f"bad_tokens has {len(per)} entries for {n} sentences (one value for all, or one per sentence)")
+                ids = [None if a is None and b is None else list(a or []) + list(b or []) for a, b in zip(ids, per)]
+            bad = ids
+        out = constraint_tables(n, int(self.cfg.vocab), int(self.cfg.eos), sp.get("min_new_tokens", 0), sp.get("no_repeat_ngram_size", 0),
+                                bad, sp.get("allowed_tokens"), max_new=int(self.engine.c.max_text_len))
+        if out is None or repeat == 1:
+            return out
+        return out[0], [row for row in out[1] for _ in range(repeat)]
+
+    def _word_ids(self, words) -> List[int]:
+        tok = getattr(self, "tokenizer", None)
+        if tok is None:
+            raise ValueError("bad_words needs the model's tokenizer (get_git_model keeps it; or set model.tokenizer)")
+        ids = []
+        for w in words:
+            pieces = tok(w, add_special_tokens=False)["input_ids"]
+            if len(pieces) != 1:
+                raise ValueError(f"bad_words: {w!r} is {len(pieces)} WordPieces; only words that are one WordPiece can be banned "
+                                 f"(multi-token banned sequences are not implemented)")
+            ids.append(int(pieces[0]))
+        return ids
 
     def close(self) -> None:
         """Free the engine contexts (workspaces, KV caches, packed weights) now rather than at garbage collection."""
@@ -628,12 +677,15 @@ class CaptioningModel:
         P = None if prefix is None else int(prefix.numel())
         nret = int((search_param or {}).get("num_return_sequences", 1))
         kind = self.decoder.kind
+        ban = self._constraints(search_param, int(frames[0].shape[0]), repeat=nret)
 
         def launch():
             frames_arg = frames
             if ctx is not None:
                 eng.encode_context(frames, ctx[0], image_of=ctx[1])
                 frames_arg = None
+            if ban is not None:         # armed on this context and stream, immediately before the call that consumes it
+                eng.constrain(*ban)
             if nret != 1:
                 # decoder.py:1093-1097: every image's start tokens num_return_sequences times -- r sentences per image, each
                 # with its own beams (they differ only when sampling); rows b * r + j, as the reference returns them
@@ -671,7 +723,8 @@ class CaptioningModel:
         if int((search_param or {}).get("num_return_sequences", 1)) != 1:
             raise NotImplementedError("num_return_sequences in a follow-up request: repeat the sentence in 'image_of'")
         eng, stream = self._followup_context(on)
-        return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=True)
+        return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=True,
+                                     ban=self._constraints(search_param, len(prefixes)))
 
     def forward(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
                 search_param: Optional[dict] = None, on=None) -> Dict[str, torch.Tensor]:
@@ -897,8 +950,14 @@ class CaptioningModel:
         search = self._search_struct(search_param)
         if int((search_param or {}).get("num_return_sequences", 1)) != 1:
             raise NotImplementedError("num_return_sequences with images of different sizes")
+        ban = self._constraints(search_param, len(images) if prefixes is None else len(prefixes))
         if prefixes is None:
-            return Pending(stream, lambda: eng.generate(packed, search, sync=False, host_out=stream is not None),
+            def launch():
+                if ban is not None:
+                    eng.constrain(*ban)
+                return eng.generate(packed, search, sync=False, host_out=stream is not None)
+
+            return Pending(stream, launch,
                            lambda out: _finish_batch(eng, out, None, self.decoder.kind), keep=(packed,), engine=eng)
         Q = len(prefixes)
         image_of = list(range(Q)) if image_of is None else [int(i) for i in image_of]
@@ -906,7 +965,7 @@ class CaptioningModel:
             raise ValueError(f"{Q} questions exceed max_batch={eng.c.max_batch}")
         if len(image_of) != Q or any(i < 0 or i >= len(images) for i in image_of):
             raise ValueError(f"image_of must name one of the {len(images)} images for each of the {Q} questions")
-        return self._submit_prefixed(eng, stream, packed, prefixes, image_of, search, as_dict=True)
+        return self._submit_prefixed(eng, stream, packed, prefixes, image_of, search, as_dict=True, ban=ban)
 
     def generate_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
                         image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None):
@@ -914,20 +973,22 @@ class CaptioningModel:
         return self._on_context0(lambda: self.submit_ragged(images, prefixes, image_of, search_param))
 
     def submit_answers(self, images: Union[None, torch.Tensor, Sequence[torch.Tensor]], prefixes: Sequence[Sequence[int]],
-                       image_of: Optional[Sequence[int]] = None, on=None) -> "Pending":
+                       image_of: Optional[Sequence[int]] = None, on=None, search_param: Optional[dict] = None) -> "Pending":
         """Questions about SEVERAL images of one resolution in one engine call (batched ragged prefixes): `images` [B,3,H,W]
         (or a list of frames of that shape), question q = token ids starting with [CLS], about image image_of[q] (default: all
         about image 0).  `.result()` returns, per question, the list of predicted token ids exactly as
         ``model({'image': image, 'prefix': [prefix]})['predictions'][0]`` gives them for that image alone -- the reference loop
         of inference.py:172-199 without re-encoding an image per question and without one call per image.
-        images None: further questions about the RESIDENT images of `on`'s context (default: of the most recent call)."""
+        images None: further questions about the RESIDENT images of `on`'s context (default: of the most recent call).
+        search_param: as for submit (sampling, decoding constraints per question)."""
         if not self._loaded:
             raise RuntimeError("weights not loaded (call load_state_dict first)")
         if images is None:
             image_of = [0] * len(prefixes) if image_of is None else [int(i) for i in image_of]
             eng, stream = self._followup_context(on)
             self._prepare(eng, None)
-            return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(), as_dict=False)
+            return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=False,
+                                         ban=self._constraints(search_param, len(prefixes)))
         is_list = isinstance(images, (list, tuple))
         frames = list(images) if is_list else [images]
         Q = len(prefixes)
@@ -936,11 +997,13 @@ class CaptioningModel:
         if Q > eng.c.max_batch or int(frames[0].shape[0]) > eng.c.max_batch:
             raise ValueError(f"{Q} questions / {int(frames[0].shape[0])} images exceed max_batch={eng.c.max_batch}")
         self._prepare(eng, is_list)
-        return self._submit_prefixed(eng, stream, frames, prefixes, image_of, self._search_struct(), as_dict=False)
+        return self._submit_prefixed(eng, stream, frames, prefixes, image_of, self._search_struct(search_param), as_dict=False,
+                                     ban=self._constraints(search_param, Q))
 
-    def _submit_prefixed(self, eng, stream, frames, prefixes, image_of, search, as_dict: bool) -> "Pending":
+    def _submit_prefixed(self, eng, stream, frames, prefixes, image_of, search, as_dict: bool, ban=None) -> "Pending":
         """submit_answers / submit_ragged with questions: one generate_prefixed call on `eng` (frames: a stacked batch or
-        RaggedImages).  .result(): the answers' id lists, and with as_dict {'predictions': them, 'logprobs' [Q, 1]}."""
+        RaggedImages).  .result(): the answers' id lists, and with as_dict {'predictions': them, 'logprobs' [Q, 1]}.
+        ban: the decoding constraints of the sentences (_constraints), armed on the context's stream right before the call."""
         kind = self.decoder.kind
         if frames is None:
             self._prepare(eng, None)
@@ -951,6 +1014,8 @@ class CaptioningModel:
                                  f"{len(prefixes)} sentences")
 
         def launch():
+            if ban is not None:
+                eng.constrain(*ban)
             return eng.generate_prefixed(frames, search, prefixes, image_of=image_of, sync=False, host_out=stream is not None)
 
         def finish(out):
@@ -1280,5 +1345,7 @@ def get_git_model(tokenizer, param: Optional[dict], precision: str = "f16", max_
     if decoder is None:
         decoder = GeneratorWithBeamSearch(eos_index=cfg.eos, max_steps=1024, beam_size=4, length_penalty=0.6)
     logging.info("building GIT engine: %s, search %s", cfg, type(decoder).__name__)
-    return CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch, device=device, max_context=max_context,
-                           context_not_share_embedding=bool((param or {}).get("context_not_share_embedding", False)))
+    model = CaptioningModel(cfg, decoder, precision=precision, max_batch=max_batch, device=device, max_context=max_context,
+                            context_not_share_embedding=bool((param or {}).get("context_not_share_embedding", False)))
+    model.tokenizer = tokenizer        # search_param['bad_words'] goes through it
+    return model

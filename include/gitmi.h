@@ -61,6 +61,8 @@ extern "C" {
                                         * gitmi_generate_prefixed only, see there */
 #define GITMI_SEARCH_FEATURES 9        /* not a search: make caller-supplied visual feature rows the resident images of a context
                                         * (the input side of gitmi_encode_frames' feats_out); gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_CONSTRAIN 10      /* not a search: arm per-sentence decoding constraints (banned tokens, a minimum length, no
+                                        * repeated n-grams) for the next search call of a context; gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -494,6 +496,41 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * Non-finite or out-of-range values are not looked for here; they surface as info_out[3] of the calls that follow, as today.
  * The device table (max_batch x max_frames pieces, max_batch counts) is allocated by the first such call: engines that never
  * take features keep their footprint. */
+/* ---- per-sentence decoding constraints: search->kind == GITMI_SEARCH_CONSTRAIN arms the constraints of the NEXT search call on
+ * this context.  It is one-shot: that call consumes them.  Defined against the reference's `step` callable: let row r belong to
+ * sentence s = r / beams and hold tokens x[0 .. t), start tokens and prefix (P_s tokens) included.  The constrained step returns
+ * the reference's logits with z[c] = -10000 for every token c banned for (r, t); the search class then does what it does after
+ * `step` (repetition penalty, the no-immediate-repeat rule, the forced [SEP] of an ended beam, temperature, the sampling filter,
+ * log-softmax).  c is banned if any of
+ *   set     bit c % 32 of word c / 32 of ban set set_of[s] is set (set_of[s] == -1: no set; an allowed-token list is the
+ *           complement, built by the caller),
+ *   length  c == eos and t - P_s < min_new[s]: at least min_new[s] generated tokens before [SEP] (0: off),
+ *   n-gram  n = ngram[s] in 1 .. 8 (0: off), t >= n, and some i in [0, t - n] has x[i .. i + n - 1) == x[t - n + 1 .. t) and
+ *           x[i + n - 1] == c: no n-gram of the row occurs twice (n == 1 bans every token of the history; the history includes
+ *           the start tokens, as it does for repetition_penalty)
+ * holds.  While a sentence is inside its prefix (t < P_s) the step appends the given token, as always.  -10000 keeps every number
+ * finite, so info_out[3] keeps its meaning; a set that bans the whole vocabulary leaves a flat distribution and is the caller's
+ * error.  "Not a search": gitmi_generate, gitmi_search_begin and the step seam refuse the kind by name, the other gitmi_search
+ * fields are ignored.  The argument mapping:
+ *   frames          : must be NULL; F and B are ignored.  Residency is neither needed nor touched
+ *   prefixes        : a DEVICE pointer read as uint32 [n_sets][W], W = ceil(vocab / 32); may be NULL when ld_prefix == 0.  The engine
+ *                     copies the words into a table of its own on `stream` and keeps no pointer; bits at or above vocab are ignored
+ *   ld_prefix       : n_sets, 0 .. max_batch
+ *   prefix_len_host : int32 [Q][3] = { set index or -1, min_new, ngram }
+ *   image_of_host   : must be NULL
+ *   Q               : the sentence count of the call to be constrained, 1 .. max_batch; Q == 0 disarms and reads nothing else
+ *   info_out        : { Q, n_sets, W, 0 };  tokens_out, logprob_out, sent_out: ignored
+ * Checked on the host before any launch, by message naming sentence and field: set index in [-1, n_sets), 0 <= min_new <=
+ * max_text_len, 0 <= ngram <= 8.  A refused call leaves what was armed and what is resident unchanged.
+ * Consumption: the next gitmi_generate (kinds 0 and 1) with B == Q, or the next gitmi_generate_prefixed search with that Q, runs
+ * constrained and disarms; a follow-up (frames == NULL) works like any other.  Another sentence count is an argument error that
+ * names both numbers and stays armed.  While armed, GITMI_SEARCH_TRIE and gitmi_search_begin refuse by name (the seam's caller
+ * owns its logits; constraints on the trie search are not implemented).  The other "not a search" kinds run unconstrained and
+ * leave the arming alone.  A clone starts disarmed.
+ * The tables (the set words and three int [max_batch] arrays) are allocated by the first arming call: engines that never
+ * constrain keep their footprint.  The hipGraph key of the decode part gains "constrained"; the values live in those tables, whose
+ * pointers never change, so armed calls of equal shape and different values replay one graph.  A constrained 16-bit call runs
+ * the vocabulary head in its generic form (the form the repetition penalty uses); an unconstrained call launches what it did. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,
