@@ -14,6 +14,8 @@ using namespace gitmi;
 #include "../../include/gitmi_experiment.h"
 #define GITMI_EXP_EXPORT extern "C"
 #else
+#define GITMI_EXPERIMENT_TYPES_ONLY          // the hooks are unused statics here: their argument types, not their declarations
+#include "../../include/gitmi_experiment.h"
 #define GITMI_EXP_EXPORT [[maybe_unused]] static
 #endif
 
@@ -202,17 +204,49 @@ extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bi
     return 0;
 }
 
+// the decoding constraints of a hook call (include/gitmi_experiment.h: gitmi_debug_ban) -> the BanArgs the launchers take, after
+// the checks gitmi_generate_constrained makes of a caller's tables -- on host copies, the stream synchronised first; rows / beams
+// sentences.  Everything the kernels form an address from (set_of, W, the table lengths) is validated here.
+[[maybe_unused]] static int fill_ban(const char* op, const gitmi_debug_ban* ban, const int* ids, const int* plen, int rows, int beams, int V,
+                    hipStream_t s, BanArgs* out) {
+    if (!ids || !plen) return fail("%s: ban without ids or plen", op);
+    if (beams < 1 || rows % beams) return fail("%s: %d rows are not a multiple of beams=%d", op, rows, beams);
+    if (ban->W != (V + 31) / 32) return fail("%s: ban W=%d, but (V + 31) / 32 = %d", op, ban->W, (V + 31) / 32);
+    if (ban->n_sets < 0) return fail("%s: ban n_sets=%d", op, ban->n_sets);
+    if (!ban->set_of || !ban->min_new || !ban->ngram) return fail("%s: ban with a null table", op);
+    if (ban->eos < 0 || ban->eos >= V) return fail("%s: ban eos=%d outside [0, V=%d)", op, ban->eos, V);
+    const int S = rows / beams;
+    HIPCK(hipStreamSynchronize(s));
+    std::vector<int> tab((size_t)3 * S);
+    HIPCK(hipMemcpy(tab.data(), ban->set_of, (size_t)S * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(tab.data() + S, ban->min_new, (size_t)S * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(tab.data() + 2 * S, ban->ngram, (size_t)S * sizeof(int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < S; ++i) {
+        const int so = tab[i], mn = tab[S + i], ng = tab[2 * S + i];
+        if (so < -1 || so >= ban->n_sets) return fail("%s: ban set_of[%d]=%d outside [-1, n_sets=%d)", op, i, so, ban->n_sets);
+        if (so >= 0 && !ban->words) return fail("%s: ban words are null, but set_of[%d]=%d", op, i, so);
+        if (mn < 0) return fail("%s: ban min_new[%d]=%d is negative", op, i, mn);
+        if (ng < 0 || ng > 8) return fail("%s: ban ngram[%d]=%d outside [0, 8]", op, i, ng);
+    }
+    out->words = ban->words; out->set_of = ban->set_of; out->min_new = ban->min_new; out->ngram = ban->ngram;
+    out->W = ban->W; out->eos = ban->eos;
+    return 0;
+}
+
 // the fused head with the REAL rule inputs of a search step (tests/test_gpu_search_ops.py): VocabArgs exactly as the engine's
 // decode_head_impl fills them -- ids int32 [M][ld_ids] (DEVICE) the rows' histories, cur_len tokens each, plen int32 [M / beams]
 // (DEVICE) the sentences' prefix lengths, suppress_kind 1 = the no-immediate-repeat rule on rows with cur_len > plen,
 // rep_penalty the GENERATOR repetition penalty over ids[row][0..cur_len) (0 or 1: off).  ids == NULL: no rules.  A penalty over
 // more than HIST_SLOTS / 2 tokens is refused HERE, as search_begin_impl refuses it for the engine (the row_topm / sample_rows
 // launchers hold the history as a set of that capacity; launch_vocab_topm walks the ids and has no such check of its own).
+// ban: the decoding constraints of the rows (VocabArgs::ban); the head walks the ids for the n-gram rule too, so a constrained
+// call has no cap on cur_len.
 GITMI_EXP_EXPORT int gitmi_debug_vocab_topm_rules(const void* A, const void* W, const float* bias, const float* colsum,
                                                   const float* stats, int strips, float eps, int M, int V, int K, int cols_per_wg,
                                                   int mtop, const int* ids, int ld_ids, int cur_len, const int* plen, int beams,
                                                   int suppress_kind, float rep_penalty, float* part_val, int* part_idx,
-                                                  float* part_lse, float* logits_out, int max_wgs, void* stream) {
+                                                  float* part_lse, float* logits_out, int max_wgs, void* stream,
+                                                  const gitmi_debug_ban* ban) {
     if (!A || !W || !bias || !part_val || !part_idx || !part_lse) return fail("debug_vocab_topm_rules: null argument");
     if (cols_per_wg != 128) return fail("debug_vocab_topm_rules: cols_per_wg must be 128");
     VocabArgs v = vocab_op_args(A, W, bias, colsum, stats, strips, eps, M, V, K, cols_per_wg, part_val, part_idx, part_lse, logits_out, max_wgs);
@@ -225,6 +259,7 @@ GITMI_EXP_EXPORT int gitmi_debug_vocab_topm_rules(const void* A, const void* W, 
         v.ids = ids; v.ld_ids = ld_ids; v.cur_len = cur_len; v.plen = plen; v.beams = beams; v.suppress_kind = suppress_kind;
         v.rep_penalty = rep_penalty;
     }
+    if (ban) RCK(fill_ban("debug_vocab_topm_rules", ban, ids, plen, M, beams, V, (hipStream_t)stream, &v.ban));
     HIPCK(launch_vocab_topm(v, mtop, (hipStream_t)stream));
     return 0;
 }
@@ -254,7 +289,7 @@ extern "C" int gitmi_op_sample_rows(const float* logits, int R, int V, float tem
 // row_topm_kernel: logits fp32 [R][ldl] -> part_val / part_idx [R][row_topm_slots(M)], part_lse [R] (max, sum exp)
 GITMI_EXP_EXPORT int gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len,
                                           const int* plen, int beams, int suppress_kind, float rep_penalty, int M, float* part_val,
-                                          int* part_idx, float* part_lse, void* stream) {
+                                          int* part_idx, float* part_lse, void* stream, const gitmi_debug_ban* ban) {
     if (!logits || !part_val || !part_idx || !part_lse) return fail("debug_row_topm: null argument");
     if (R < 1 || V < 1 || ldl < V) return fail("debug_row_topm: R=%d V=%d ldl=%d", R, V, ldl);
     if (ids) {
@@ -264,8 +299,10 @@ GITMI_EXP_EXPORT int gitmi_debug_row_topm(const float* logits, int ldl, int V, i
     } else {
         suppress_kind = 0;                                  // no histories: no rules (the kernel reads plen for the no-repeat rule)
     }
+    BanArgs ba{};
+    if (ban) RCK(fill_ban("debug_row_topm", ban, ids, plen, R, beams, V, (hipStream_t)stream, &ba));
     HIPCK(launch_row_topm(logits, ldl, V, ids, ld_ids, cur_len, plen, ids ? beams : 1, suppress_kind, rep_penalty, M, R, part_val,
-                          part_idx, (float2*)part_lse, (hipStream_t)stream));
+                          part_idx, (float2*)part_lse, (hipStream_t)stream, ban ? &ba : nullptr));
     return 0;
 }
 // trie_select_kernel on a caller's CSR trie (all arrays DEVICE): child_off int32 [n_nodes + 1], child_tok / child_node int32
@@ -303,17 +340,21 @@ GITMI_EXP_EXPORT int gitmi_debug_trie_select(const float* logits, int ldl, int V
 }
 // sample_rows_kernel with everything the engine's sampling step sets: gitmi_op_sample_rows' arguments + the row stride of the
 // logits, the histories of the repetition penalty and the list stride (entries ndraw..stride are padding).  filtered_out [R][V].
+// ban: the decoding constraints of the rows, with plen int32 [R / beams] (DEVICE) and beams -- read under a ban only.
 GITMI_EXP_EXPORT int gitmi_debug_sample_rows(const float* logits, int R, int V, float temperature, int top_k, float top_p, int ndraw,
                                              uint64_t seed, int step, float* draw_logprob, int* draw_token, float* filtered_out,
                                              int ldl, const int* ids, int ld_ids, int cur_len, float rep_penalty, int stride,
-                                             void* stream) {
+                                             void* stream, const int* plen, int beams, const gitmi_debug_ban* ban) {
     if (!logits || !draw_logprob || !draw_token) return fail("debug_sample_rows: null argument");
     if (R < 1 || V < 1 || ldl < V) return fail("debug_sample_rows: R=%d V=%d ldl=%d", R, V, ldl);
     RCK(check_history("debug_sample_rows", ids, ld_ids, cur_len));
+    BanArgs ba{};
+    if (ban) RCK(fill_ban("debug_sample_rows", ban, ids, plen, R, beams, V, (hipStream_t)stream, &ba));
     float2* lse = nullptr;
     HIPCK(hipMalloc((void**)&lse, (size_t)R * sizeof(float2)));
     hipError_t err = launch_sample_rows(logits, ldl, V, R, temperature, top_k, top_p, ndraw, seed, step, draw_logprob, draw_token, lse,
-                                        filtered_out, ids, ld_ids, cur_len, rep_penalty, stride, (hipStream_t)stream);
+                                        filtered_out, ids, ld_ids, cur_len, rep_penalty, stride, (hipStream_t)stream,
+                                        ban ? &ba : nullptr, ban ? plen : nullptr, ban ? beams : 1);
     if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t)stream);
     hipFree(lse);
     HIPCK(err);

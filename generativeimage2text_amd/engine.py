@@ -184,7 +184,7 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_attn_decode_qkv.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
                                                     i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_vocab_topm_rules.argtypes = [vp, vp, vp, vp, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32,
-                                                     i32, C.c_float, vp, vp, vp, vp, i32, vp]
+                                                     i32, C.c_float, vp, vp, vp, vp, i32, vp, vp]
         lib.gitmi_debug_search_begin_prefixed.argtypes = [vp, C.POINTER(GitmiSearch), i32, vp, i32, vp, i32, vp]
         lib.gitmi_debug_search_advance_lists.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
         lib.gitmi_debug_read_hidden.argtypes = [vp, i32, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
@@ -197,10 +197,10 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_layernorm_map.argtypes = [vp, i32, vp, vp, C.c_float, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
         lib.gitmi_debug_context_embed.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, C.c_float, vp, i32, vp, vp, i32, i32,
                                                   i32, i32, vp]
-        lib.gitmi_debug_row_topm.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp]
+        lib.gitmi_debug_row_topm.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp]
         lib.gitmi_debug_trie_select.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         lib.gitmi_debug_sample_rows.argtypes = [vp, i32, i32, C.c_float, i32, C.c_float, i32, C.c_uint64, i32, vp, vp, vp, i32, vp, i32,
-                                                i32, C.c_float, i32, vp]
+                                                i32, C.c_float, i32, vp, vp, i32, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands in _MEASUREMENT_LIBS else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -1587,10 +1587,13 @@ def op_vocab_topm_rules(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mt
                         cur_len: int, plen: Optional[torch.Tensor], beams: int = 1, suppress_kind: int = 0,
                         rep_penalty: float = 0.0, cols_per_wg: int = 128, colsum: Optional[torch.Tensor] = None,
                         stats: Optional[torch.Tensor] = None, eps: float = 1e-12, want_logits: bool = False, packed: bool = False,
-                        rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0):
+                        rows: Optional[int] = None, V: Optional[int] = None, max_wgs: int = 0, ban: Optional["DebugBan"] = None,
+                        out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None):
     """op_vocab_topm with the rule inputs of a real search step (measurement build): ids int32 [M, ld_ids] row histories of
     cur_len tokens, plen int32 [M / beams] prefix lengths, suppress_kind (no immediate repeat on rows with cur_len > plen),
-    rep_penalty.  Same outputs; the materialised logits are taken before the rules."""
+    rep_penalty.  Same outputs; the materialised logits are taken before the rules -- but after the ban of `ban` (DebugBan: the
+    rows' decoding constraints), which they carry as -10000.  out: caller-supplied (part_val, part_idx, part_lse, logits or None)
+    in place of fresh ones."""
     lib, M, ops, shape, outs, result, keep = _vocab_head_call(A, W, bias, mtop, cols_per_wg, colsum, stats, want_logits, packed, rows, V,
                                                               measurement=True)
     if ids is not None:
@@ -1598,9 +1601,11 @@ def op_vocab_topm_rules(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, mt
         plen = plen.to(device=A.device, dtype=torch.int32).contiguous()
         if ids.dim() != 2 or ids.shape[0] != M or plen.numel() * beams != M:
             raise ValueError(f"ids {tuple(ids.shape)} / plen {tuple(plen.shape)} do not describe {M} rows of {beams} beams")
+    if out is not None:
+        result, outs = out, tuple(_ptr(t) for t in out)
     _ck(_experiment_only(lib, "gitmi_debug_vocab_topm_rules")(
         *ops, eps, *shape, _ptr(ids), 0 if ids is None else int(ids.shape[1]), int(cur_len), _ptr(plen), int(beams),
-        int(suppress_kind), float(rep_penalty), *outs, int(max_wgs), _stream()), lib)
+        int(suppress_kind), float(rep_penalty), *outs, int(max_wgs), _stream(), _ban_ref(ban)), lib)
     return result
 
 
@@ -1892,6 +1897,27 @@ def op_sample_rows(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 
 # ---- op hooks of the whole-row selection kernels (measurement build; tests/test_gpu_select_ops.py).  logits: an fp32 device
 # view [rows, >= V] with unit column stride; its row stride is ldl and its first V columns are the vocabulary (a padded or
 # misaligned row is a slice of a wider tensor).  out: caller-supplied output tensors (the tests fill them with sentinels).
+class _GitmiDebugBan(C.Structure):
+    _fields_ = [("words", C.c_void_p), ("n_sets", C.c_int), ("W", C.c_int), ("set_of", C.c_void_p), ("min_new", C.c_void_p),
+                ("ngram", C.c_void_p), ("eos", C.c_int)]
+
+
+class DebugBan:
+    """gitmi_debug_ban (include/gitmi_experiment.h) for op_vocab_topm_rules / op_row_topm / op_sample_rows_rules: words uint32
+    [n_sets, W] as an int32 device tensor of the same bits (or None), set_of / min_new / ngram int32 device tensors with one entry
+    per sentence, eos.  The hooks check the tables; nothing is checked here.  Keeps the tensors alive."""
+
+    def __init__(self, words: Optional[torch.Tensor], n_sets: int, W: int, set_of: Optional[torch.Tensor],
+                 min_new: Optional[torch.Tensor], ngram: Optional[torch.Tensor], eos: int):
+        self.tensors = (words, set_of, min_new, ngram)
+        self.struct = _GitmiDebugBan(_ptr(words) or None, int(n_sets), int(W), _ptr(set_of) or None, _ptr(min_new) or None,
+                                     _ptr(ngram) or None, int(eos))
+
+
+def _ban_ref(ban: Optional[DebugBan]):
+    return None if ban is None else C.addressof(ban.struct)
+
+
 def _logit_rows(logits: torch.Tensor, V: int) -> Tuple[int, int]:
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
         raise ValueError(f"logits must be an fp32 [rows, >= {V}] view with unit column stride")
@@ -1904,9 +1930,11 @@ def row_topm_slots(M: int) -> int:
 
 def op_row_topm(logits: torch.Tensor, V: int, M: int, ids: Optional[torch.Tensor] = None, cur_len: int = 0,
                 plen: Optional[torch.Tensor] = None, beams: int = 1, suppress_kind: int = 0, rep_penalty: float = 0.0,
-                out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, operands: Optional[str] = None):
+                out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, operands: Optional[str] = None,
+                ban: Optional[DebugBan] = None):
     """row_topm_kernel through its launcher: -> (part_val fp32 [R, slots], part_idx int32 [R, slots], part_lse fp32 [R, 2]),
-    slots = row_topm_slots(M).  ids int32 [R, ld_ids] device histories of cur_len tokens (None: no rules), plen int32 [R / beams]."""
+    slots = row_topm_slots(M).  ids int32 [R, ld_ids] device histories of cur_len tokens (None: no rules), plen int32 [R / beams];
+    ban: the rows' decoding constraints."""
     lib, fn = _front("gitmi_debug_row_topm", operands=operands)
     R, ldl = _logit_rows(logits, V)
     slots = row_topm_slots(M)
@@ -1914,7 +1942,7 @@ def op_row_topm(logits: torch.Tensor, V: int, M: int, ids: Optional[torch.Tensor
     pv, pi, pl = out if out is not None else (torch.empty(R, slots, device=dev), torch.empty(R, slots, device=dev, dtype=torch.int32),
                                               torch.empty(R, 2, device=dev))
     _ck(fn(logits.data_ptr(), ldl, int(V), R, _ptr(ids), 0 if ids is None else int(ids.stride(0)), int(cur_len), _ptr(plen), int(beams),
-           int(suppress_kind), float(rep_penalty), int(M), pv.data_ptr(), pi.data_ptr(), pl.data_ptr(), _stream()), lib)
+           int(suppress_kind), float(rep_penalty), int(M), pv.data_ptr(), pi.data_ptr(), pl.data_ptr(), _stream(), _ban_ref(ban)), lib)
     return pv, pi, pl
 
 
@@ -1938,9 +1966,11 @@ def op_sample_rows_rules(logits: torch.Tensor, V: int, temperature: float = 1.0,
                         seed: int = 0, step: int = 1, stride: Optional[int] = None, ids: Optional[torch.Tensor] = None,
                         cur_len: int = 0, rep_penalty: float = 0.0, want_filtered: bool = True,
                         out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None,
-                        operands: Optional[str] = None):
+                        operands: Optional[str] = None, plen: Optional[torch.Tensor] = None, beams: int = 1,
+                        ban: Optional[DebugBan] = None):
     """op_sample_rows with what the engine's sampling step also sets (measurement build): padded logit rows, the repetition
-    penalty over ids int32 [R, ld_ids] (cur_len tokens) and lists of `stride` entries.
+    penalty over ids int32 [R, ld_ids] (cur_len tokens) and lists of `stride` entries; ban: the rows' decoding constraints, with
+    plen int32 [R / beams] and beams.
     -> (filtered logits [R, V] or None, tokens int32 [R, stride], log-probs fp32 [R, stride]); out = (log-probs, tokens, filtered)."""
     lib, fn = _front("gitmi_debug_sample_rows", operands=operands)
     R, ldl = _logit_rows(logits, V)
@@ -1953,7 +1983,7 @@ def op_sample_rows_rules(logits: torch.Tensor, V: int, temperature: float = 1.0,
         filt = torch.empty(R, V, device=logits.device, dtype=torch.float32) if want_filtered else None
     _ck(fn(logits.data_ptr(), R, int(V), float(temperature), int(top_k), float(top_p), int(ndraw), int(seed), int(step), lp.data_ptr(),
            tok.data_ptr(), _ptr(filt), ldl, _ptr(ids), 0 if ids is None else int(ids.stride(0)), int(cur_len), float(rep_penalty),
-           stride, _stream()), lib)
+           stride, _stream(), _ptr(plen), int(beams), _ban_ref(ban)), lib)
     return filt, tok, lp
 
 

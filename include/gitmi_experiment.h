@@ -19,6 +19,25 @@
 extern "C" {
 #endif
 
+/* decoding constraints for the three hooks that see logits together with the rows' histories (vocab_topm_rules, row_topm,
+ * sample_rows; tests/test_gpu_constraints_ops.py): the tables of GITMI_SEARCH_CONSTRAIN (include/gitmi.h; the rule itself:
+ * csrc/ban_rules.h) as the engine keeps them for an armed call.  Row r belongs to sentence r / beams.  The hook fills the
+ * launcher's BanArgs from it, so the launcher's choice of the BAN instantiation and its refusals are part of what runs.  NULL:
+ * the hook behaves and launches exactly as without the argument.  Checked on host copies (the hook synchronises the stream
+ * first) and refused by name, nothing launched: ban without ids or plen, W != (V + 31) / 32, n_sets < 0, null set_of / min_new /
+ * ngram, words null while some set_of >= 0, a set_of outside [-1, n_sets), min_new < 0, ngram outside [0, 8], eos outside
+ * [0, V). */
+typedef struct gitmi_debug_ban {
+    const uint32_t* words;      /* DEVICE uint32 [n_sets][W]; token c <-> bit c % 32 of word c / 32 */
+    int n_sets, W;
+    const int32_t *set_of, *min_new, *ngram;   /* DEVICE int32 [rows / beams] */
+    int eos;
+} gitmi_debug_ban;
+
+/* GITMI_EXPERIMENT_TYPES_ONLY: the types above without the entry points (csrc/abi_ops.hip in the product builds, which compile
+ * the hooks as unused statics) */
+#ifndef GITMI_EXPERIMENT_TYPES_ONLY
+
 /* ---- error attribution hooks (tools/error_attribution.py; not part of the serving path).  Two contexts of the SAME
  * model in different precisions: import_stage hands the products of the image encoder (stage 1) or of encoder + prefill
  * (stage 2: the image K/V of every decoder layer) from `src` to `dst`, converted, so that gitmi_step_logits on `dst`
@@ -138,6 +157,10 @@ int  gitmi_debug_attn_decode_qkv(const void* x, int x_rows, const void* w, const
  *   vocab_topm_rules:      gitmi_op_vocab_topm with the rule inputs of a real search step in place of suppress_tok: ids int32
  *                          [M][ld_ids] row histories (cur_len tokens each), plen int32 [M / beams] prefix lengths, suppress_kind
  *                          (1: no immediate repeat on rows with cur_len > plen), rep_penalty (0 or 1: off).  ids NULL: no rules.
+ *                          ban (or NULL): the rows' decoding constraints, applied before the penalty and the no-repeat rule;
+ *                          logits_out then carries the -10000 of the ban (and nothing of the other rules).  The head walks ids
+ *                          per column block and keeps no history set: a constrained call has NO cap on cur_len (the penalty's
+ *                          cap of 1024 tokens is the hook's own, as before).
  *   search_begin_prefixed: gitmi_search_begin with one prefix length per sentence (start_host int64 [B][ld], plen_host int32 [B]);
  *                          every sentence stands for its own batch-1 reference call, as in gitmi_generate_prefixed.
  *   search_advance_lists:  gitmi_search_advance on caller-supplied candidate lists in the fused head's format (part_val / part_idx
@@ -149,7 +172,8 @@ int  gitmi_debug_attn_decode_qkv(const void* x, int x_rows, const void* w, const
 int  gitmi_debug_vocab_topm_rules(const void* A, const void* W, const float* bias, const float* colsum, const float* stats,
                                   int strips, float eps, int M, int V, int K, int cols_per_wg, int mtop, const int* ids, int ld_ids,
                                   int cur_len, const int* plen, int beams, int suppress_kind, float rep_penalty, float* part_val,
-                                  int* part_idx, float* part_lse, float* logits_out, int max_wgs, void* stream);
+                                  int* part_idx, float* part_lse, float* logits_out, int max_wgs, void* stream,
+                                  const gitmi_debug_ban* ban);
 int  gitmi_debug_search_begin_prefixed(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host, int ld,
                                        const int32_t* plen_host, int vocab, void* stream);
 int  gitmi_debug_search_advance_lists(gitmi_engine* e, const float* part_val, const int* part_idx, const float* part_lse,
@@ -208,7 +232,8 @@ int  gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len
  *                entries past M hold the next best, entries past V (-inf, 0x7fffffff)), part_lse [R][2] = (max, sum exp(x - max))
  *                of the ruled row.  ids NULL: no rules.  Refused by name: null logits / outputs, ldl < V, ids without plen, R not
  *                a multiple of beams, cur_len outside [1, ld_ids]; by the launcher (invalid argument): M outside 1..16, a
- *                penalty over more than 1024 tokens.  Nothing is launched then.
+ *                penalty or a ban over more than 1024 tokens.  Nothing is launched then.  ban (or NULL): the rows' decoding
+ *                constraints, -10000 before the penalty and the no-repeat rule.
  *   trie_select: one step of GITMI_SEARCH_TRIE on a caller's CSR trie -- child_off int32 [n_nodes + 1], child_tok / child_node
  *                int32 [child_off[n_nodes]], cursor int32 [B] (node of every sentence, -1 unconstrained; read and updated) ->
  *                part_val / part_idx [B] (log-prob incl. the trie bonus, token), part_lse [B][2] = (0, 1).  Rows with cur_len <
@@ -219,17 +244,21 @@ int  gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len
  *                repetition penalty (applied to the raw logits, before the temperature) and the list stride -- draw_logprob /
  *                draw_token [R][stride], entries ndraw..stride (-inf, 0x7fffffff); filtered_out [R][V] or NULL.  Refused by the
  *                launcher (invalid argument): V outside 2..32768, ndraw outside 1..16, stride < ndraw, temperature <= 0, a
- *                penalty over more than 1024 tokens.  Synchronises the stream. */
+ *                penalty or a ban over more than 1024 tokens.  ban (or NULL): the rows' decoding constraints on the raw
+ *                logits, before the penalty, with plen int32 [R / beams] and beams (both read under a ban only; R a multiple of
+ *                beams).  Synchronises the stream. */
 int  gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len, const int* plen,
                           int beams, int suppress_kind, float rep_penalty, int M, float* part_val, int* part_idx, float* part_lse,
-                          void* stream);
+                          void* stream, const gitmi_debug_ban* ban);
 int  gitmi_debug_trie_select(const float* logits, int ldl, int V, int B, const int* ids, int ld_ids, int cur_len, const int* plen,
                              int eos, const int* child_off, const int* child_tok, const int* child_node, int n_nodes, int* cursor,
                              float* part_val, int* part_idx, float* part_lse, void* stream);
 int  gitmi_debug_sample_rows(const float* logits, int R, int V, float temperature, int top_k, float top_p, int ndraw, uint64_t seed,
                              int step, float* draw_logprob, int* draw_token, float* filtered_out, int ldl, const int* ids, int ld_ids,
-                             int cur_len, float rep_penalty, int stride, void* stream);
+                             int cur_len, float rep_penalty, int stride, void* stream, const int* plen, int beams,
+                             const gitmi_debug_ban* ban);
 
+#endif /* GITMI_EXPERIMENT_TYPES_ONLY */
 #ifdef __cplusplus
 }
 #endif

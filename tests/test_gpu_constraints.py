@@ -177,8 +177,9 @@ def test_f32_ids_equal_the_reference(name):
 # build must return identical to the reference although no margin certifies them.  Measured on the MI355X: 4 of 4
 # (constraints_tiny_beam4) and 1 of 1 (constraints_tiny_prefix_beam4) in every run so far, f16 and bf16 alike.  The four-row floor
 # sits one row under the measurement (a re-ordered fp32 sum may move one near-tie row: margins down to 0.0015 against an fp16 logit
-# bound of 0.0069); a one-row fixture has no room under it.  This is the only place where the f16 ids of a constrained beam call --
-# vocab_topm_kernel<8, VOC_GENERIC, 0, BAN> -- meet the reference's.
+# bound of 0.0069); a one-row fixture has no room under it.  This is where the f16 ids of a whole constrained beam call meet the
+# reference's; its kernel -- vocab_topm_kernel<8, VOC_GENERIC, 0, BAN> -- and the other BAN instantiations meet an fp64 reference
+# launch by launch in tests/test_gpu_constraints_ops.py.
 F16_BEAM_IDENTICAL_FLOOR = {"constraints_tiny_beam4": 3, "constraints_tiny_prefix_beam4": 1}
 
 
