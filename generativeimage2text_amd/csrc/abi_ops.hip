@@ -786,4 +786,98 @@ GITMI_EXP_EXPORT int gitmi_debug_context_embed(const int64_t* tokens, int ld, co
     hipFree(tab);
     return rc;
 }
+
+// ---- op hooks of the text pass around its attention (kernels_score.hip; tests/test_gpu_text_pass_ops.py) ---------------------
+// Each one is an argument check + the launchers text_pass_impl calls, in its order.
+GITMI_EXP_EXPORT int gitmi_debug_score_embed(const int64_t* tokens, int Q, int ld, int Lp, const float* words, int vocab,
+                                             const float* positions, int max_pos, const float* gamma, const float* beta, float eps,
+                                             int D, float* h_f, void* h_t, int dtype, const int* node_tok, const int* node_depth,
+                                             void* stream) {
+    if (!tokens || !words || !positions || !gamma || !beta || !h_f || !h_t) return fail("debug_score_embed: null argument");
+    RCK(check_dtype("debug_score_embed", "dtype", dtype));
+    if (Q < 1 || ld < 1 || Lp < 1 || vocab < 1 || max_pos < 1 || D < 4 || D > 1024 || D % 4)
+        return fail("debug_score_embed: bad shape (D a multiple of 4 up to 1024)");
+    if (!node_tok != !node_depth) return fail("debug_score_embed: the node tables come together");
+    if (((uintptr_t)words | (uintptr_t)positions | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)h_f | (uintptr_t)h_t) & 15)
+        return fail("debug_score_embed: tables and rows must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (node_tok) {       // the tree instantiation forms its addresses from the tables as they are (the structure kernel's output)
+        const size_t M = (size_t)Q * Lp;
+        std::vector<int> host(2 * M);
+        HIPCK(hipMemcpyAsync(host.data(), node_tok, M * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCK(hipMemcpyAsync(host.data() + M, node_depth, M * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        for (size_t i = 0; i < M; ++i)
+            if (host[i] < 0 || host[i] >= vocab || host[M + i] < 0 || host[M + i] >= max_pos)
+                return fail("debug_score_embed: node row %zu (token %d, depth %d) outside the tables", i, host[i], host[M + i]);
+    }
+    const TreeNodes nd{const_cast<int*>(node_tok), const_cast<int*>(node_depth), nullptr, nullptr};
+    HIPCK(launch_score_embed_ln((const long long*)tokens, ld, Q, Lp, words, positions, gamma, beta, eps, h_f, h_t, dtype == GITMI_DTYPE_F32,
+                                D, vocab, max_pos, s, node_tok ? &nd : nullptr));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_tree_tables(const int64_t* packed, const int* lens, int Q, int ld, int Lp, int V, int max_depth,
+                                             int* tok, int* depth, int* parent, int* end, int* bad, void* stream) {
+    if (!packed || !lens || !tok || !depth || !parent || !end || !bad) return fail("debug_tree_tables: null argument");
+    if (Q < 1 || ld < 1 || Lp < 1 || V < 1 || max_depth < 1 || max_depth > 8192) return fail("debug_tree_tables: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCK(hipMemsetAsync(bad, 0, (size_t)Q * sizeof(int), s));
+    HIPCK(launch_tree_structure((const long long*)packed, ld, Q, Lp, lens, V, max_depth, TreeNodes{tok, depth, parent, end}, bad, s));
+    return 0;
+}
+GITMI_EXP_EXPORT int gitmi_debug_score_tail(const void* A, const void* W, const float* bias, const int64_t* tokens, const int* lens,
+                                            int Q, int ld, int Lp, int V, int K, int dtype, int chunk_rows, int tree_max_depth,
+                                            float* out, int* bad, int* info, int* tgt_out, float* zt_out, void* stream) {
+    if (!A || !W || !bias || !tokens || !lens || !out || !bad || !info) return fail("debug_score_tail: null argument");
+    RCK(check_dtype("debug_score_tail", "dtype", dtype));
+    const bool f32 = dtype == GITMI_DTYPE_F32, tree = tree_max_depth > 0;
+    if (Q < 1 || ld < 1 || Lp < 1 || V < 2 || K < 32 || K % 32 || (size_t)Q * Lp > (1u << 20))
+        return fail("debug_score_tail: bad shape (K a multiple of 32, at most 2^20 rows)");
+    if (tree_max_depth < 0 || tree_max_depth > 8192) return fail("debug_score_tail: tree_max_depth=%d outside [0,8192]", tree_max_depth);
+    if (f32 && (chunk_rows < 1 || chunk_rows > Q * Lp))
+        return fail("debug_score_tail: the fp32 head needs chunk_rows in [1, Q * Lp = %d], got %d", Q * Lp, chunk_rows);
+    if (((uintptr_t)A | (uintptr_t)W) & 15) return fail("debug_score_tail: A and W must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // sentences: the target and combine kernels index the caller's tables by the lengths, as the engine's calls do after
+    // read_sentences has checked them.  (Trees: the structure kernel clamps the node count itself.)
+    if (!tree) {
+        std::vector<int> len_host(Q);
+        HIPCK(hipMemcpyAsync(len_host.data(), lens, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        for (int q = 0; q < Q; ++q)
+            if (len_host[q] < 1 || len_host[q] > ld) return fail("debug_score_tail: length %d of sentence %d outside [1,%d]", len_host[q], q, ld);
+    }
+    const int M = Q * Lp, ldl = round_up(V, 8);
+    int* tab = nullptr; float4* part = nullptr; float* zt = nullptr; float* logits = nullptr;
+    auto body = [&]() -> int {
+        HIPCK(hipMalloc(&tab, (size_t)(tree ? 5 : 1) * M * sizeof(int)));
+        HIPCK(hipMalloc(&part, (size_t)M * (f32 ? 1 : score_head_tiles(V)) * sizeof(float4)));
+        HIPCK(hipMalloc(&zt, (size_t)M * sizeof(float)));
+        if (f32) HIPCK(hipMalloc(&logits, (size_t)chunk_rows * ldl * sizeof(float)));
+        int* tgt = tab;
+        const TreeNodes nd{tab + M, tab + 2 * (size_t)M, tab + 3 * (size_t)M, tab + 4 * (size_t)M};
+        const ScoreHeadArgs h{A, W, bias, tgt, part, zt, logits, ldl, chunk_rows};
+        int ntiles = 1;
+        HIPCK(hipMemsetAsync(bad, 0, (size_t)Q * sizeof(int), s));
+        HIPCK(hipMemsetAsync(zt, 0xff, (size_t)M * sizeof(float), s));         // a logit nobody gathered is a NaN, not a stale value
+        if (tree) {
+            HIPCK(launch_tree_structure((const long long*)tokens, ld, Q, Lp, lens, V, tree_max_depth, nd, bad, s));
+            HIPCK(hipMemsetAsync(tgt, 0xff, (size_t)M * sizeof(int), s));
+            HIPCK(launch_score_head_rows(h, f32, M, V, K, &nd, Lp, &ntiles, s));
+            HIPCK(launch_tree_combine(part, ntiles, zt, nd, M, Lp, ld, V, (float2*)out, bad, s));
+        } else {
+            HIPCK(launch_score_targets((const long long*)tokens, ld, Lp, lens, V, M, tgt, s));
+            HIPCK(launch_score_head_rows(h, f32, M, V, K, nullptr, 0, &ntiles, s));
+            HIPCK(launch_score_combine(part, ntiles, zt, tgt, M, Lp, ld, V, (float2*)out, bad, s));
+        }
+        HIPCK(launch_score_info(bad, Q, ld, info, s));
+        if (tgt_out) HIPCK(hipMemcpyAsync(tgt_out, tgt, (size_t)M * sizeof(int), hipMemcpyDefault, s));
+        if (zt_out) HIPCK(hipMemcpyAsync(zt_out, zt, (size_t)M * sizeof(float), hipMemcpyDefault, s));
+        HIPCK(hipStreamSynchronize(s));
+        return 0;
+    };
+    const int rc = body();
+    hipFree(tab); hipFree(part); hipFree(zt); hipFree(logits);
+    return rc;
+}
 #endif

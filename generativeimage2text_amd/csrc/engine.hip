@@ -1346,23 +1346,13 @@ static int call_Nimg(const gitmi_engine* e, const float* const* frames, int F) {
 static int score_head_impl(gitmi_engine* e, int M, hipStream_t s, int* ntiles, const TreeNodes* tree = nullptr, int Lp = 0) {
     const gitmi_config& c = e->cfg;
     const int d = c.dec_hidden, V = c.vocab;
-    *ntiles = 1;
-    if (e->pol.f32) {
-        // parity mode: logits in chunks of the decode workspace's rows, then one statistics row each
-        const int chunk = round_up(c.max_batch * c.max_beams, 64);
-        for (int r0 = 0; r0 < M; r0 += chunk) {
-            const int rows = std::min(chunk, M - r0);
-            RCK(gemm(e, s, (const float*)e->sc_ht + (size_t)r0 * d, d, e->w.out_w, e->w.out_b, nullptr, 0, e->logits, e->ldl, true, rows,
-                     V, d, 0, TAG_GEMM_OTHER));
-            HIPCK(launch_score_rowstats(e->logits, e->ldl, V, e->sc_tgt, r0, rows, e->sc_part, e->sc_zt, s));
-            if (tree) HIPCK(launch_tree_gather_logits(e->logits, e->ldl, r0, rows, *tree, Lp, M, e->sc_zt, s));
-        }
-    } else {
-        SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
-        *ntiles = score_head_tiles(V);
-        HIPCK(launch_score_head(e->sc_ht, d, e->w.out_w, e->w.out_b, e->sc_tgt, M, V, d, e->sc_part, e->sc_zt, s));
-        if (tree) HIPCK(launch_tree_gather_dot(e->sc_ht, d, e->w.out_w, e->w.out_b, *tree, Lp, M, d, e->sc_zt, s));
-    }
+    // launch_score_head_rows (gitmi_debug_score_tail runs it on a caller's buffers): 16-bit modes the fused head; the parity mode
+    // materialises the logits in e->logits, the decode workspace's rows at a time (the last three fields, unused otherwise).
+    // One span over the whole head: in parity mode it times the row statistics and the tree gather with the GEMM chunks.
+    const ScoreHeadArgs h{e->sc_ht, e->w.out_w, e->w.out_b, e->sc_tgt, e->sc_part, e->sc_zt, e->logits, e->ldl,
+                          round_up(c.max_batch * c.max_beams, 64)};
+    SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(M, V, d));
+    HIPCK(launch_score_head_rows(h, e->pol.f32, M, V, d, tree, Lp, ntiles, s));
     return 0;
 }
 // The text pass of GITMI_SEARCH_SCORE / _ATTEND: the textual head over whole sentences (CaptioningModel.forward_one_ce,

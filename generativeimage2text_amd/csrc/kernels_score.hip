@@ -947,4 +947,31 @@ hipError_t launch_tree_combine(const float4* part, int ntiles, const float* zt, 
     return hipGetLastError();
 }
 
+// ---- the head of a whole text pass (launchers.h) -----------------------------------------------------------------------------
+// f32: a chunk's logits are overwritten by the next chunk's, so a tree's children are gathered chunk by chunk, each when the
+// chunk that holds its parent's row is materialised
+hipError_t launch_score_head_rows(const ScoreHeadArgs& h, bool f32, int M, int V, int K, const TreeNodes* tree, int Lp, int* ntiles,
+                                  hipStream_t s) {
+    if (M < 1 || V < 1 || K < 1 || (tree && Lp < 1)) return hipErrorInvalidValue;
+    *ntiles = 1;
+    if (!f32) {
+        *ntiles = score_head_tiles(V);
+        const hipError_t err = launch_score_head(h.A, K, h.W, h.bias, h.tgt, M, V, K, h.part, h.zt, s);
+        if (err != hipSuccess || !tree) return err;
+        return launch_tree_gather_dot(h.A, K, h.W, h.bias, *tree, Lp, M, K, h.zt, s);
+    }
+    if (!h.logits || h.chunk_rows < 1 || h.ldl < V) return hipErrorInvalidValue;
+    for (int r0 = 0; r0 < M; r0 += h.chunk_rows) {
+        const int rows = h.chunk_rows < M - r0 ? h.chunk_rows : M - r0;
+        GemmArgs g{};
+        g.A = (const float*)h.A + (size_t)r0 * K; g.W = h.W; g.bias = h.bias; g.C = h.logits;
+        g.M = rows; g.N = V; g.K = K; g.lda = K; g.ldc = h.ldl;
+        hipError_t err = launch_gemm(g, true, true, s);
+        if (err == hipSuccess) err = launch_score_rowstats(h.logits, h.ldl, V, h.tgt, r0, rows, h.part, h.zt, s);
+        if (err == hipSuccess && tree) err = launch_tree_gather_logits(h.logits, h.ldl, r0, rows, *tree, Lp, M, h.zt, s);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 }  // namespace gitmi

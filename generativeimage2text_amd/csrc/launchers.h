@@ -359,6 +359,17 @@ hipError_t launch_score_head(const void* A, int lda, const void* W, const float*
                              float4* part, float* zt, hipStream_t s);
 hipError_t launch_score_rowstats(const float* logits, int ldl, int V, const int* tgt, int row_off, int rows, float4* part,
                                  float* zt, hipStream_t s);
+// The head of a whole text pass, as the score / tree-score calls and gitmi_debug_score_tail run it: A [M][K] text rows, W [V][K],
+// tgt [M] -> part [M][*ntiles], zt [M].  f32: GEMM into `logits` [chunk_rows][ldl], launch_score_rowstats (one statistics row
+// each, *ntiles = 1) and, with a tree, launch_tree_gather_logits, chunk_rows rows at a time; 16-bit: launch_score_head and, with
+// a tree, launch_tree_gather_dot (logits and chunk_rows unused).  tree: zt[node row] = the node's token at its parent's row.
+struct ScoreHeadArgs {
+    const void* A; const void* W; const float* bias; const int* tgt;
+    float4* part; float* zt;
+    float* logits; int ldl, chunk_rows;
+};
+hipError_t launch_score_head_rows(const ScoreHeadArgs& h, bool f32, int M, int V, int K, const TreeNodes* tree, int Lp, int* ntiles,
+                                  hipStream_t s);
 hipError_t launch_score_targets(const long long* tokens, int ld, int Lp, const int* lens, int V, int M, int* tgt,
                                 hipStream_t s);
 hipError_t launch_score_combine(const float4* part, int ntiles, const float* zt, const int* tgt, int M, int Lp, int ld, int V,

@@ -60,6 +60,7 @@ EXPERIMENT_SYMBOLS = [
     "gitmi_debug_layernorm_map", "gitmi_debug_score_attn_map", "gitmi_debug_attn_decode_form", "gitmi_debug_dgemm_form",
     "gitmi_debug_gemm_form", "gitmi_debug_context_embed", "gitmi_debug_attn_decode_qkv", "gitmi_debug_score_attn_tree",
     "gitmi_debug_row_topm", "gitmi_debug_trie_select", "gitmi_debug_sample_rows",
+    "gitmi_debug_score_embed", "gitmi_debug_tree_tables", "gitmi_debug_score_tail",
 ]
 
 
@@ -201,6 +202,9 @@ def load_library(operands: str = "bf16") -> C.CDLL:
         lib.gitmi_debug_trie_select.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         lib.gitmi_debug_sample_rows.argtypes = [vp, i32, i32, C.c_float, i32, C.c_float, i32, C.c_uint64, i32, vp, vp, vp, i32, vp, i32,
                                                 i32, C.c_float, i32, vp, vp, i32, vp]
+        lib.gitmi_debug_score_embed.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, C.c_float, i32, vp, vp, i32, vp, vp, vp]
+        lib.gitmi_debug_tree_tables.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.gitmi_debug_score_tail.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS + (EXPERIMENT_SYMBOLS if operands in _MEASUREMENT_LIBS else []):
         if name not in ("gitmi_last_error", "gitmi_destroy"):
             getattr(lib, name).restype = C.c_int
@@ -1817,6 +1821,50 @@ def op_score_head(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tgt: tor
                                                         t.data_ptr(), M, V, K, _torch_dtype_code(A), out.data_ptr(),
                                                         _stream()), lib)
     return out
+
+
+# ---- op hooks of the text pass around its attention and head (measurement build; tests/test_gpu_text_pass_ops.py).  Every
+# output is a caller-supplied device tensor, as for the front-end hooks below; operands as there.
+def op_score_embed(tokens: torch.Tensor, Lp: int, words: torch.Tensor, positions: torch.Tensor, gamma: torch.Tensor,
+                   beta: torch.Tensor, eps: float, h_f: torch.Tensor, h_t: torch.Tensor, node_tok: Optional[torch.Tensor] = None,
+                   node_depth: Optional[torch.Tensor] = None, operands: Optional[str] = None) -> None:
+    """tokens int64 [Q, ld] -> h_f fp32 / h_t (fp32 or the operand type) [Q * Lp, D]: the embedding + LayerNorm of every row of
+    the text pass; node_tok / node_depth int32 [Q * Lp]: the tree instantiation (tokens is not read)."""
+    lib, fn = _front("gitmi_debug_score_embed", h_t.dtype, operands=operands)
+    Q, ld = tokens.shape
+    _ck(fn(tokens.data_ptr(), Q, ld, Lp, words.data_ptr(), int(words.shape[0]), positions.data_ptr(), int(positions.shape[0]),
+           gamma.data_ptr(), beta.data_ptr(), eps, int(words.shape[1]), h_f.data_ptr(), h_t.data_ptr(), _torch_dtype_code(h_t),
+           _ptr(node_tok), _ptr(node_depth), _stream()), lib)
+
+
+def op_tree_tables(packed: torch.Tensor, lens: torch.Tensor, Lp: int, V: int, max_depth: int, tables: torch.Tensor,
+                   bad: torch.Tensor, operands: Optional[str] = None) -> None:
+    """packed int64 [Q, ld] (depth << 32 | token), lens int32 [Q] -> tables int32 [4, Q * Lp] = (tok, depth, parent, end) of the
+    structure launch and bad int32 [Q]."""
+    lib, fn = _front("gitmi_debug_tree_tables", operands=operands)
+    Q, ld = packed.shape
+    if tuple(tables.shape) != (4, Q * Lp) or tables.dtype != torch.int32 or not tables.is_contiguous():
+        raise ValueError("tables must be a contiguous int32 [4, Q * Lp]")
+    _ck(fn(packed.data_ptr(), lens.data_ptr(), Q, ld, Lp, V, max_depth, tables[0].data_ptr(), tables[1].data_ptr(),
+           tables[2].data_ptr(), tables[3].data_ptr(), bad.data_ptr(), _stream()), lib)
+
+
+def op_score_tail(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, tokens: torch.Tensor, lens: torch.Tensor, Lp: int,
+                  out: torch.Tensor, bad: torch.Tensor, info: torch.Tensor, chunk_rows: int = 0, tree_max_depth: int = 0,
+                  tgt_out: Optional[torch.Tensor] = None, zt_out: Optional[torch.Tensor] = None,
+                  operands: Optional[str] = None) -> None:
+    """Everything behind the last decoder layer of a score (tree_max_depth = 0) or tree-score call: A [Q * Lp, K] text rows,
+    W [V, K] (fp32 or the operand type), bias fp32 [V], tokens int64 [Q, ld] (or the packed tree table), lens int32 [Q] -> out
+    fp32 [Q, ld, 2] (only the entries with a target / a parent are written), bad int32 [Q], info int32 [4]; tgt_out int32 /
+    zt_out fp32 [Q * Lp]: the head rows' targets and gathered logits."""
+    lib, fn = _front("gitmi_debug_score_tail", A.dtype, W.dtype, operands=operands)
+    Q, ld = tokens.shape
+    V, K = W.shape
+    if tuple(A.shape) != (Q * Lp, K) or tuple(out.shape) != (Q, ld, 2) or bias.numel() != V or lens.numel() != Q:
+        raise ValueError("A must be [Q * Lp, K], out [Q, ld, 2], bias [V], lens [Q]")
+    _ck(fn(A.data_ptr(), W.data_ptr(), bias.data_ptr(), tokens.data_ptr(), lens.data_ptr(), Q, ld, Lp, V, K, _torch_dtype_code(A),
+           int(chunk_rows), int(tree_max_depth), out.data_ptr(), bad.data_ptr(), info.data_ptr(), _ptr(tgt_out), _ptr(zt_out),
+           _stream()), lib)
 
 
 # ---- op hooks of the encoder's image front end (measurement build; tests/test_gpu_frontend_ops.py).  Every output is a

@@ -1,7 +1,7 @@
 /* gitmi_experiment.h -- entry points of the MEASUREMENT builds only (`make exp`: libgitmi_exp.so = the product sources compiled
  * with -DGITMI_EXPERIMENT, bf16 operands; libgitmi_f16_exp.so = the same with -DGITMI_OPS_F16, fp16 operands -- the kernels of
  * the benchmarked configuration, the folded-LayerNorm GEMM forms among them).  libgitmi.so / libgitmi_f16.so do not export them.
- * Both measurement builds export the same 68 gitmi_ symbols (the 40 of gitmi.h + the 28 below); gitmi_operand_dtype tells them apart.
+ * Both measurement builds export the same 71 gitmi_ symbols (the 40 of gitmi.h + the 31 below); gitmi_operand_dtype tells them apart.
  *
  * What lives here: debug hooks that exchange stage products between contexts (tools/error_attribution.py), force a GEMM
  * variant (tools/gemm_bench.py, tests of the forced tile heights) or set the timing bits of the decode-chain GEMMs
@@ -115,6 +115,34 @@ int  gitmi_debug_score_head(const void* A, const void* W, const float* bias, con
 int  gitmi_debug_score_attn_tree(const void* qkv, const void* img_kv, const int* image_of, const int* ntok, const int64_t* packed,
                                  const int* lens, int max_depth, void* out, int* bad_out, int Q, int H, int N_img, int Lp, int dtype,
                                  void* stream);
+
+/* op hooks of the text pass around its attention and head (kernels_score.hip; tests/test_gpu_text_pass_ops.py): an argument
+ * check + the launchers the score / tree-score calls run, in their order.  All pointers DEVICE memory.
+ *   score_embed: tokens int64 [Q][ld] -> h_f fp32 [Q * Lp][D] and h_t [Q * Lp][D] (dtype) = LayerNorm(words[id] +
+ *                positions[min(j, max_pos - 1)], eps) of row (q, j); ids clamp into [0, vocab), positions j >= ld embed id 0.
+ *                node_tok / node_depth int32 [Q * Lp] (both or neither): the tree instantiation -- row i embeds words[node_tok[i]]
+ *                + positions[node_depth[i]] and `tokens` is not read; the hook checks both tables on host copies (synchronises).
+ *                Refused by name: null or misaligned pointers, D not a multiple of 4 up to 1024, a node outside the tables.
+ *   tree_tables: packed int64 [Q][ld] (depth << 32 | token), lens int32 [Q] -> the structure launch's tok / depth / parent / end
+ *                int32 [Q * Lp] and bad int32 [Q] (zeroed first).
+ *   score_tail:  everything behind the last decoder layer.  A [Q * Lp][K] text rows, W [V][K] (dtype), bias fp32 [V], tokens
+ *                int64 [Q][ld] (tree_max_depth > 0: the packed tree table), lens int32 [Q] -> out float2 [Q][ld] (NOT zeroed: only
+ *                the entries the combine kernel writes change), bad int32 [Q] (zeroed first), info int32 [4] = {ld, 0, 0, bad
+ *                sentences}; tgt_out int32 [Q * Lp] (or NULL): the target of every head row (-1: none; trees: -1 everywhere);
+ *                zt_out fp32 [Q * Lp] (or NULL): the logit at the row's target (trees: of the node's token at its parent's row),
+ *                NaN where none was stored.  Sentences: targets, head, combine, info; trees: structure, head with the gather,
+ *                tree combine, info.  The head is launch_score_head_rows, the engine's own: fp32 in chunks of chunk_rows rows
+ *                (GEMM, row statistics, gather), 16-bit the fused head (+ the gather dot).  Refused by name: null pointers, A or W
+ *                not 16-byte aligned, K % 32, a dtype of the other build, fp32 with chunk_rows outside [1, Q * Lp], tree_max_depth outside [0, 8192], (sentences) a
+ *                length outside [1, ld].  Synchronises the stream. */
+int  gitmi_debug_score_embed(const int64_t* tokens, int Q, int ld, int Lp, const float* words, int vocab, const float* positions,
+                             int max_pos, const float* gamma, const float* beta, float eps, int D, float* h_f, void* h_t, int dtype,
+                             const int* node_tok, const int* node_depth, void* stream);
+int  gitmi_debug_tree_tables(const int64_t* packed, const int* lens, int Q, int ld, int Lp, int V, int max_depth, int* tok, int* depth,
+                             int* parent, int* end, int* bad, void* stream);
+int  gitmi_debug_score_tail(const void* A, const void* W, const float* bias, const int64_t* tokens, const int* lens, int Q, int ld,
+                            int Lp, int V, int K, int dtype, int chunk_rows, int tree_max_depth, float* out, int* bad, int* info,
+                            int* tgt_out, float* zt_out, void* stream);
 
 /* op hooks of the ragged-batch attention (gitmi_set_image_shape(e, 0, 0); tests/test_gpu_ragged_ops.py).  ntok: int32 [B] on the
  * device, the rows of image b (<= N / N_img, which stay the row stride of an image's block); keys past ntok[b] are never used.

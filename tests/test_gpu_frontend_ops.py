@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from ln_reference import ln_ref_and_bound
 from test_gpu_dgemm_forms import on_both_operand_builds
 
 pytestmark = pytest.mark.gpu
@@ -254,27 +255,7 @@ def test_pos_resize_to_the_stored_grid_returns_the_table(experiment_build, g, D)
     assert torch.equal(_bits(out), _bits(pos))
 
 
-# ---- LayerNorm bound shared by ln_pre and ln_post ----------------------------------------------------------------------
-def _ln_ref_and_bound(v, gamma, beta, eps, add=None):
-    """fp64 LayerNorm of the rows v (+ add) and the bound of the kernels' fp32 evaluation, element by element.  With V = max |v|
-    of the row, d = v - mean, s = sqrt(var + eps), u = 2^-24:
-      v itself (ln_pre: src + pos) rounds once: u V.  The mean is a sum of D <= 1024 terms in at most 40 sequential roundings
-      (<= 32 per lane + the 5 or 6 shuffle levels + the division) of partial sums <= D V / D: 40 u V, + the u V of its terms.
-      d: |dd| <= 42 u V + u |d|.
-      var: each d^2 moves by 2 |d| dd, the sum rounds 42 times: relative 84 u V / s + 44 u; rstd = rsqrt(var + eps) half of that
-      + 3 u (the add and a 2-ulp rsqrtf): 42 u V / s + 25 u.
-      y = d rstd gamma + beta (+ add): |gamma| / s * dd + |d / s gamma| (42 u V / s + 25 u + 4 u) + 2 u (|y| + |add|)."""
-    v, g, b = v.double(), gamma.double(), beta.double()
-    mean = v.mean(-1, keepdim=True)
-    d = v - mean
-    s = torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
-    yhat = d / s * g
-    y = yhat + b
-    a = torch.zeros_like(y) if add is None else add.double().expand_as(y)
-    y = y + a
-    V = v.abs().amax(-1, keepdim=True)
-    bound = g.abs() / s * (42 * U * V + U * d.abs()) + yhat.abs() * (42 * U * V / s + 29 * U) + 2 * U * (y.abs() + a.abs())
-    return y, bound
+# ---- LayerNorm bound shared by ln_pre and ln_post: ln_reference.py (the text pass's embedding uses it too) ------------------
 
 
 # ---- token assembly + ln_pre ----------------------------------------------------------------------------------------
@@ -292,7 +273,7 @@ def _assemble_ref(patch, cls, pos, gamma, beta, eps, B, N):
     D = cls.numel()
     src = torch.cat([cls.double().expand(B, 1, D), patch.double().reshape(B, N - 1, D)], 1)
     v = (src + pos.double()[None]).reshape(B * N, D)
-    return _ln_ref_and_bound(v, gamma, beta, eps)
+    return ln_ref_and_bound(v, gamma, beta, eps)
 
 
 def _check_partials(part, x16, what):
@@ -592,7 +573,7 @@ def _run_ln_post(D, src, mode, with_temb, temb_shift=0):
     bound = torch.empty_like(ref)
     for fr in range(LNF):
         # input row fr B N + b N + n -> output row b F N + fr N + n; the embedding is added AFTER gamma and beta
-        y, bd_ = _ln_ref_and_bound(x[fr * rows:(fr + 1) * rows], gamma, beta, 1e-5, temb[fr] if with_temb else None)
+        y, bd_ = ln_ref_and_bound(x[fr * rows:(fr + 1) * rows], gamma, beta, 1e-5, temb[fr] if with_temb else None)
         ref[:, fr] = y.reshape(LNB, LNN, D)
         bound[:, fr] = bd_.reshape(LNB, LNN, D)
     got = {name: o.cpu().reshape(LNB, LNF, LNN, D) for name, o in outs.items()}
@@ -613,7 +594,7 @@ def _check_ln_post(got, ref, bound, what):
 def test_ln_post_scatter(experiment_build, D, src, mode, with_temb):
     """F = 3, B = 2, N = 5.  D = 768 / 1024 with a 16-bit operand output run the wide kernel, D = 192 and every fp32 output the
     one-wave-per-row kernel; src f16: the fp16 residual stream (layernorm_kernel<*, f16_t>, layernorm_wide_kernel<f16_t, *>).
-    Bound: the fp32 LayerNorm evaluation (_ln_ref_and_bound), + half an ulp of a 16-bit output."""
+    Bound: the fp32 LayerNorm evaluation (ln_ref_and_bound), + half an ulp of a 16-bit output."""
     got, ref, bound = _run_ln_post(D, src, mode, with_temb)
     _check_ln_post(got, ref, bound, f"D={D} src={src} {mode} temb={with_temb}")
 

@@ -82,13 +82,14 @@ def test_score_head(experiment_build, dtype, V, offset):
     tgt[4] = -1
     tgt[-1] = V - 2
     got = op_score_head(A.cuda(), W.cuda(), bias.cuda(), tgt).double().cpu()
-    ref, z = _head_ref(A, W, bias, tgt)
+    ref, _ = _head_ref(A, W, bias, tgt)
     assert torch.all(got[4] == 0)
-    # the logits themselves carry fp32 rounding at their magnitude (|z| ~ offset): the bound scales with it
-    span = float((z - z.mean(-1, keepdim=True)).abs().max())
-    base = 2e-4 if dtype == "f32" else 2e-3 * span
-    tol = base + 16 * max(1.0, offset) * 2.0 ** -23                 # 16 fp32 ulps of the logits' magnitude
+    # the logits themselves carry fp32 rounding at their magnitude (|z| ~ offset): the bound scales with it.  One base for both
+    # operand types: the operands arrive already rounded and both paths accumulate in fp32 (a tile-wise fp32 emulation of the
+    # 16-bit head is within 1e-6 of fp64, 3e-5 at offset 1e3; a last tile counted as 128 columns moves mean_lp by 2e-3 and more)
+    tol = 2e-4 + 16 * max(1.0, offset) * 2.0 ** -23                 # 16 fp32 ulps of the logits' magnitude
     err_lp = (got[:, 0] - ref[:, 0]).abs().max().item()
     err_mean = (got[:, 1] - ref[:, 1]).abs().max().item()
+    print(f"score head {dtype} V={V} offset={offset}: lp max error {err_lp:.3e}, mean_lp max error {err_mean:.3e}, bound {tol:.3e}")
     assert err_lp <= tol, (dtype, V, offset, err_lp, tol)
     assert err_mean <= tol, (dtype, V, offset, err_mean, tol)

@@ -450,6 +450,22 @@ def _check_hidden(eng, w, rows):
 
 
 @pytest.mark.parametrize("hidden", [768, 320])
+def test_prefill_embedding(hidden):
+    """embed_ln_kernel, the embedding of the teacher-forced positions (gitmi_step_logits embeds position after position; the
+    search step's fused embedding takes over behind them): one call over t = 3 tokens on encoded frames leaves the rows of the
+    last position, LayerNorm(words[token] + positions[2]), the 16-bit copy h_f rounded to the operand type."""
+    eng, cfg, w = _engine("p", hidden=hidden, max_batch=4, max_beams=4)
+    B, t = 3, 3
+    eng.encode([f.cuda() for f in O.make_images(cfg, B, 1, seed=5)], return_features=False)
+    g = torch.Generator().manual_seed(hidden + 1)
+    rows = torch.randint(0, V_SMALL, (B, t), generator=g, dtype=torch.int64)
+    rows[:, 0] = cfg.sos
+    rows[0, -1], rows[1, -1] = 0, V_SMALL - 1                       # the first and the last row of the word table
+    assert bool(torch.isfinite(eng.step_logits(rows)).all())
+    _check_hidden(eng, w, rows)
+
+
+@pytest.mark.parametrize("hidden", [768, 320])
 def test_search_step_embedding(hidden):
     """embed = 1: h_f = LayerNorm(words[token] + positions[position], eps 1e-8) of the tokens the step appended, the 16-bit copy
     (fragment-major, read back row-major) is h_f rounded to the operand type -- the one-row form (greedy: the whole workgroup on

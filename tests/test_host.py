@@ -72,7 +72,7 @@ def test_selection_hooks_belong_to_the_measurement_build_only():
     for name in names:
         assert name + "(" in exp and name in engine.EXPERIMENT_SYMBOLS, name
         assert name not in engine.EXPORTED_SYMBOLS and name not in product, name
-    assert len(engine.EXPORTED_SYMBOLS) == 40 and len(set(engine.EXPERIMENT_SYMBOLS)) == len(engine.EXPERIMENT_SYMBOLS) == 28
+    assert len(engine.EXPORTED_SYMBOLS) == 40 and len(set(engine.EXPERIMENT_SYMBOLS)) == len(engine.EXPERIMENT_SYMBOLS) == 31
     assert set(_declared_functions("gitmi_experiment.h")) - set(_declared_functions()) == set(engine.EXPERIMENT_SYMBOLS)
     for operands, path in (("exp", engine.LIB_PATH_EXP), ("f16_exp", engine.LIB_PATH_F16_EXP)):
         if os.path.exists(path):
