@@ -50,6 +50,49 @@ inline int context_table(const char* who, const int32_t* len, const int32_t* ima
     info[0] = t.stride; info[1] = t.max_rows; info[2] = t.total; info[3] = 0;
     return 0;
 }
+
+// Host side of the banned-sequence pool (GITMI_SEARCH_CONSTRAIN's extension, include/gitmi.h, and its op hook): pool int32 [n] =
+// { L, S, T, 0, list_of[Q], list_off[L + 1], seq_off[S + 1], tok[T] }.  Everything ban_rows_kernel forms an address from is
+// checked here, before any launch: the sizes add up to n, L <= max_lists, S and T within the caps (launchers.h BAN_SEQ_MAX_*),
+// list_of in [-1, L), both offset arrays start at 0, never decrease and end at S / T, every sequence has 2 .. max_len tokens,
+// every token lies in [0, vocab).  Fails by message naming `who` and the sentence, list and sequence.
+struct BanPoolView {
+    int L = 0, S = 0, T = 0;
+    const int32_t *list_of = nullptr, *list_off = nullptr, *seq_off = nullptr, *tok = nullptr;
+};
+inline int ban_pool_check(const char* who, const int32_t* pool, int n, int Q, int vocab, int max_lists, int max_seqs, int max_toks,
+                          int max_len, BanPoolView* out) {
+    if (!pool || n < 4) return fail("%s: a sequence pool of %d words (at least the 4 of its header)", who, n);
+    const int L = pool[0], S = pool[1], T = pool[2];
+    if (L < 0 || L > max_lists) return fail("%s: %d sequence lists outside [0,%d] (max_batch)", who, L, max_lists);
+    if (S < 0 || S > max_seqs) return fail("%s: %d sequences above the cap of %d per call", who, S, max_seqs);
+    if (T < 0 || T > max_toks) return fail("%s: %d sequence tokens above the cap of %d per call", who, T, max_toks);
+    const long long need = 4LL + Q + (L + 1) + (S + 1) + T;
+    if (pool[3] != 0 || need != (long long)n)
+        return fail("%s: the sequence pool has %d words, but { L=%d, S=%d, T=%d, 0 } with %d sentences needs %lld", who, n, L, S, T, Q, need);
+    BanPoolView v;
+    v.L = L; v.S = S; v.T = T;
+    v.list_of = pool + 4; v.list_off = v.list_of + Q; v.seq_off = v.list_off + L + 1; v.tok = v.seq_off + S + 1;
+    for (int q = 0; q < Q; ++q)
+        if (v.list_of[q] < -1 || v.list_of[q] >= L) return fail("%s: sentence %d: sequence list %d outside [-1,%d)", who, q, v.list_of[q], L);
+    if (v.list_off[0] != 0 || v.list_off[L] != S) return fail("%s: list offsets run from %d to %d, not from 0 to S=%d", who, v.list_off[0], v.list_off[L], S);
+    for (int l = 0; l < L; ++l)
+        if (v.list_off[l + 1] < v.list_off[l]) return fail("%s: list %d: offsets decrease (%d after %d)", who, l, v.list_off[l + 1], v.list_off[l]);
+    if (v.seq_off[0] != 0 || v.seq_off[S] != T) return fail("%s: sequence offsets run from %d to %d, not from 0 to T=%d", who, v.seq_off[0], v.seq_off[S], T);
+    for (int l = 0; l < L; ++l)
+        for (int j = v.list_off[l]; j < v.list_off[l + 1]; ++j) {
+            const long long m = (long long)v.seq_off[j + 1] - v.seq_off[j];
+            if (m < 2 || m > max_len) return fail("%s: list %d: sequence %d has %lld tokens, outside [2,%d]", who, l, j, m, max_len);
+        }
+    // with list_off ending at S and every length >= 2, seq_off is strictly increasing from 0 to T: every token index is in [0, T)
+    for (int l = 0; l < L; ++l)
+        for (int j = v.list_off[l]; j < v.list_off[l + 1]; ++j)
+            for (int i = v.seq_off[j]; i < v.seq_off[j + 1]; ++i)
+                if (v.tok[i] < 0 || v.tok[i] >= vocab)
+                    return fail("%s: list %d: sequence %d holds token %d outside [0,%d)", who, l, j, v.tok[i], vocab);
+    *out = v;
+    return 0;
+}
 }  // namespace gitmi
 
 #define HIPCK(expr)                                                                                   \

@@ -207,9 +207,14 @@ extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bi
 // the decoding constraints of a hook call (include/gitmi_experiment.h: gitmi_debug_ban) -> the BanArgs the launchers take, after
 // the checks gitmi_generate_constrained makes of a caller's tables -- on host copies, the stream synchronised first; rows / beams
 // sentences.  Everything the kernels form an address from (set_of, W, the table lengths) is validated here.
+[[maybe_unused]] static int fill_ban_tables(const char* op, const gitmi_debug_ban* ban, int rows, int beams, int V, hipStream_t s, BanArgs* out);
 [[maybe_unused]] static int fill_ban(const char* op, const gitmi_debug_ban* ban, const int* ids, const int* plen, int rows, int beams, int V,
                     hipStream_t s, BanArgs* out) {
     if (!ids || !plen) return fail("%s: ban without ids or plen", op);
+    return fill_ban_tables(op, ban, rows, beams, V, s, out);
+}
+// row_words (the rows' own sets, uint32 [rows][W]: the caller's to size) is taken as it is
+static int fill_ban_tables(const char* op, const gitmi_debug_ban* ban, int rows, int beams, int V, hipStream_t s, BanArgs* out) {
     if (beams < 1 || rows % beams) return fail("%s: %d rows are not a multiple of beams=%d", op, rows, beams);
     if (ban->W != (V + 31) / 32) return fail("%s: ban W=%d, but (V + 31) / 32 = %d", op, ban->W, (V + 31) / 32);
     if (ban->n_sets < 0) return fail("%s: ban n_sets=%d", op, ban->n_sets);
@@ -224,12 +229,46 @@ extern "C" int gitmi_op_vocab_topm(const void* A, const void* W, const float* bi
     for (int i = 0; i < S; ++i) {
         const int so = tab[i], mn = tab[S + i], ng = tab[2 * S + i];
         if (so < -1 || so >= ban->n_sets) return fail("%s: ban set_of[%d]=%d outside [-1, n_sets=%d)", op, i, so, ban->n_sets);
-        if (so >= 0 && !ban->words) return fail("%s: ban words are null, but set_of[%d]=%d", op, i, so);
+        if (so >= 0 && !ban->words && !ban->row_words) return fail("%s: ban words are null, but set_of[%d]=%d", op, i, so);
         if (mn < 0) return fail("%s: ban min_new[%d]=%d is negative", op, i, mn);
         if (ng < 0 || ng > 8) return fail("%s: ban ngram[%d]=%d outside [0, 8]", op, i, ng);
     }
     out->words = ban->words; out->set_of = ban->set_of; out->min_new = ban->min_new; out->ngram = ban->ngram;
-    out->W = ban->W; out->eos = ban->eos;
+    out->W = ban->W; out->eos = ban->eos; out->row_words = ban->row_words;
+    return 0;
+}
+
+// ban_rows_kernel alone (tests/test_gpu_ban_sequences_ops.py).  An entry point of its own in all but the export: the measurement
+// builds' symbol list is pinned by a host test, so it is reached through gitmi_debug_row_topm with ban->row_words_out set, which
+// does nothing else then.  When that list is next revised this becomes gitmi_debug_ban_rows and the three fields leave the struct:
+// the per-row sets of one step under banned sequences.  ban: the
+// static sets as for the other hooks (words / n_sets / W / set_of are read; min_new, ngram and eos are checked like theirs);
+// pool_host int32 [n_pool] the HOST pool of GITMI_SEARCH_CONSTRAIN's extension for rows / beams sentences, validated by the
+// engine's own check (abi_common.h ban_pool_check; max_lists = the sentence count); ids int32 [rows][ld_ids] DEVICE histories of
+// cur_len tokens -> row_words_out uint32 [rows][W] DEVICE.  The pool travels to a device buffer of the hook's own.  Synchronises.
+[[maybe_unused]] static int debug_ban_rows(const gitmi_debug_ban* ban, const int32_t* pool_host, int n_pool, const int* ids, int ld_ids,
+                                           int cur_len, int rows, int beams, int V, uint32_t* row_words_out, void* stream) {
+    if (!ban || !ids || !row_words_out) return fail("debug_ban_rows: null argument");
+    if (ban->row_words) return fail("debug_ban_rows: ban->row_words together with row_words_out (the words are this form's output, not an input)");
+    if (rows < 1 || beams < 1 || rows % beams) return fail("debug_ban_rows: %d rows are not a positive multiple of beams=%d", rows, beams);
+    if (cur_len < 1 || cur_len > ld_ids) return fail("debug_ban_rows: cur_len=%d outside [1, ld_ids=%d]", cur_len, ld_ids);
+    hipStream_t s = (hipStream_t)stream;
+    BanArgs ba{};
+    RCK(fill_ban_tables("debug_ban_rows", ban, rows, beams, V, s, &ba));
+    ba.row_words = nullptr;
+    if (ba.W > BAN_ROW_MAX_WORDS) return fail("debug_ban_rows: W=%d above the %d words the kernel holds in LDS", ba.W, BAN_ROW_MAX_WORDS);
+    const int Q = rows / beams;
+    BanPoolView pool;
+    RCK(ban_pool_check("debug_ban_rows", pool_host, n_pool, Q, V, Q, BAN_SEQ_MAX_SEQS, BAN_SEQ_MAX_TOKS, BAN_SEQ_MAX_LEN, &pool));
+    int* dev = nullptr;
+    HIPCK(hipMalloc((void**)&dev, (size_t)n_pool * sizeof(int)));
+    hipError_t err = hipMemcpyAsync(dev, pool_host, (size_t)n_pool * sizeof(int), hipMemcpyHostToDevice, s);
+    const BanSeqArgs sq{dev + (pool.list_of - pool_host), dev + (pool.list_off - pool_host), dev + (pool.seq_off - pool_host),
+                        dev + (pool.tok - pool_host)};
+    if (err == hipSuccess) err = launch_ban_rows(ba, sq, ids, ld_ids, cur_len, rows, beams, row_words_out, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    hipFree(dev);
+    HIPCK(err);
     return 0;
 }
 
@@ -290,6 +329,8 @@ extern "C" int gitmi_op_sample_rows(const float* logits, int R, int V, float tem
 GITMI_EXP_EXPORT int gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len,
                                           const int* plen, int beams, int suppress_kind, float rep_penalty, int M, float* part_val,
                                           int* part_idx, float* part_lse, void* stream, const gitmi_debug_ban* ban) {
+    if (ban && ban->row_words_out)
+        return debug_ban_rows(ban, ban->pool_host, ban->n_pool, ids, ld_ids, cur_len, R, beams, V, ban->row_words_out, stream);
     if (!logits || !part_val || !part_idx || !part_lse) return fail("debug_row_topm: null argument");
     if (R < 1 || V < 1 || ldl < V) return fail("debug_row_topm: R=%d V=%d ldl=%d", R, V, ldl);
     if (ids) {

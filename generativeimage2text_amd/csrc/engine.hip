@@ -320,6 +320,8 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab); hipFree(e->feat_tab); hipFree(e->ban_words);
     if (e->ban_stage) hipHostFree(e->ban_stage);
     if (e->ban_staged) hipEventDestroy(e->ban_staged);
+    hipFree(e->ban_seq); hipFree(e->ban_row_words);
+    if (e->ban_seq_stage) hipHostFree(e->ban_seq_stage);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
     if (e->trie_child) hipFree(e->trie_child);
@@ -615,8 +617,16 @@ static BanArgs ban_args(const gitmi_engine* e) {
     b.W = (e->cfg.vocab + 31) / 32; b.eos = e->cfg.eos;
     const int* tab = reinterpret_cast<const int*>(e->ban_words + (size_t)mb * b.W);
     b.words = e->ban_words; b.set_of = tab; b.min_new = tab + mb; b.ngram = tab + 2 * mb;
+    if (e->ban_seq_live) b.row_words = e->ban_row_words;
     return b;
 }
+// the banned sequences of the search in progress: the fixed regions of the engine's device table (engine_state.h)
+static BanSeqArgs ban_seq_args(const gitmi_engine* e) {
+    const int mb = e->cfg.max_batch;
+    const int* t = e->ban_seq;
+    return {t, t + mb, t + 2 * mb + 1, t + 2 * mb + 1 + BAN_SEQ_MAX_SEQS + 1};
+}
+static size_t ban_seq_ints(const gitmi_engine* e) { return (size_t)2 * e->cfg.max_batch + 1 + BAN_SEQ_MAX_SEQS + 1 + BAN_SEQ_MAX_TOKS; }
 
 // vocabulary head of the step: candidate lists for the search (and optionally the logits themselves)
 static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur_len, int R, int beams, int suppress_kind,
@@ -632,6 +642,9 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
     // the -10000, so the sampling filter that reads them gets no tables.  Otherwise the GEMM stores raw logits and the one
     // whole-row kernel that consumes them (row_topm or sample_rows) applies the ban.
     const BanArgs ban = ids ? ban_args(e) : BanArgs{};
+    // banned sequences: the rows' own sets of this step, behind the search step that wrote position cur_len - 1 and reordered the
+    // beams (same stream) and before whichever kernel below applies the ban
+    if (ban.row_words) HIPCK(launch_ban_rows(ban, ban_seq_args(e), ids, ld_ids, cur_len, R, beams, e->ban_row_words, s));
     if (chain) {
         VocabArgs v{};
         v.A = (const unsigned short*)e->xo_b; v.lda = d; v.W = (const unsigned short*)e->w.out_f.w; v.bias = e->w.out_f.bias; v.colsum = e->w.out_f.colsum;
@@ -919,7 +932,7 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (e->ban_armed)
         return fail("%s: decoding constraints are armed for %d sentences (GITMI_SEARCH_CONSTRAIN): the seam's caller owns its logits and "
                     "applies its own -- disarm first (a GITMI_SEARCH_CONSTRAIN call with Q == 0)", who, e->ban_armed);
-    e->ban_live = false;
+    e->ban_live = e->ban_seq_live = false;
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -1109,7 +1122,7 @@ static GraphKey graph_key_of(const gitmi_engine* e, const Request& rq, int F_eff
     return {rq.B, rq.Q, F_eff, rq.minP, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, e->H, e->W,
             rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, resident ? 1 : 0,
             resident ? e->cur_Nimg : 0, resident && e->keyed ? 1 : 0, sp.length_penalty,
-            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed, e->ban_live ? 1 : 0};
+            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed, e->ban_live ? (e->ban_seq_live ? 2 : 1) : 0};
 }
 
 // Launches the graphs of one call on `x`: `enc` (the whole call, or encode + prefill; nullptr in a follow-up), then `dec`
@@ -1221,8 +1234,9 @@ static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s, bool 
     const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
     if (constrained) e->ban_armed = 0;
     e->ban_live = constrained;
+    e->ban_seq_live = constrained && e->ban_seq_armed;
     const int rc = settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
-    e->ban_live = false;
+    e->ban_live = e->ban_seq_live = false;
     return rc;
 }
 
@@ -1791,12 +1805,14 @@ static int constrain_info(gitmi_engine* e, const int (&v)[4], int32_t* info_out,
     HIPCK(hipEventRecord(e->ban_staged, s));
     return 0;
 }
+// n_pool > 0 (search->reserved_): pool_host is the HOST pool of banned token sequences, int32 [n_pool] (abi_common.h ban_pool_check)
 static int constrain_call(gitmi_engine* e, const float* const* frames, const unsigned int* sets, int n_sets, const int32_t* table_host,
-                          const int32_t* image_of_host, int Q, int32_t* info_out, hipStream_t s) {
+                          const int32_t* image_of_host, int Q, int32_t* info_out, const int32_t* pool_host, int n_pool, hipStream_t s) {
     const gitmi_config& c = e->cfg;
     const int W = (c.vocab + 31) / 32;
     if (Q == 0) {                   // disarms and reads nothing else
         e->ban_armed = 0;
+        e->ban_seq_armed = false;
         return info_out ? constrain_info(e, {0, 0, W, 0}, info_out, s) : 0;
     }
     if (frames) return fail("constrain: frames != NULL: constraints belong to the next search call, which brings its own images");
@@ -1814,6 +1830,15 @@ static int constrain_call(gitmi_engine* e, const float* const* frames, const uns
         if (ngram < 0 || ngram > 8) return fail("constrain: sentence %d: ngram %d outside [0,8]", q, ngram);
     }
     const size_t mb = (size_t)c.max_batch;
+    BanPoolView pool;
+    if (n_pool < 0) return fail("constrain: search->reserved_ = %d: 0, or the word count of the sequence pool in sent_out", n_pool);
+    if (n_pool > 0) {
+        if (!pool_host) return fail("constrain: search->reserved_ = %d words of banned sequences, but sent_out is NULL", n_pool);
+        RCK(ban_pool_check("constrain", pool_host, n_pool, Q, c.vocab, c.max_batch, BAN_SEQ_MAX_SEQS, BAN_SEQ_MAX_TOKS, BAN_SEQ_MAX_LEN, &pool));
+        if (W > BAN_ROW_MAX_WORDS)
+            return fail("constrain: banned sequences need the %d words of a ban set in LDS, the kernel holds %d (vocabularies up to %d)",
+                        W, BAN_ROW_MAX_WORDS, BAN_ROW_MAX_WORDS * 32);
+    }
     if (!e->ban_words && hipMalloc((void**)&e->ban_words, (mb * W + 3 * mb) * sizeof(int)) != hipSuccess) {
         (void)hipGetLastError();
         e->ban_words = nullptr;
@@ -1829,6 +1854,19 @@ static int constrain_call(gitmi_engine* e, const float* const* frames, const uns
             return fail("constrain: out of page-locked memory for the staging buffer of the constraints");
         }
     }
+    // the three buffers of the sequence rule: all of them or none
+    if (n_pool > 0 && !e->ban_seq) {
+        int *seq_tab = nullptr, *stage = nullptr; unsigned int* rows = nullptr;
+        hipError_t err = hipMalloc((void**)&seq_tab, ban_seq_ints(e) * sizeof(int));
+        if (err == hipSuccess) err = hipMalloc((void**)&rows, mb * c.max_beams * W * sizeof(int));
+        if (err == hipSuccess) err = hipHostMalloc((void**)&stage, ban_seq_ints(e) * sizeof(int), hipHostMallocDefault);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(seq_tab); hipFree(rows);
+            return fail("constrain: out of memory for the tables of the banned sequences");
+        }
+        e->ban_seq = seq_tab; e->ban_row_words = rows; e->ban_seq_stage = stage;
+    }
     // No synchronisation with the work in flight: the table travels through a page-locked staging buffer as a copy ON `s`, behind
     // whatever on `s` still reads the tables.  The host waits only for the previous arming call's own copy to have left the buffer.
     HIPCK(hipEventSynchronize(e->ban_staged));
@@ -1840,8 +1878,22 @@ static int constrain_call(gitmi_engine* e, const float* const* frames, const uns
     }
     HIPCK(hipMemcpyAsync(e->ban_words + mb * W, tab, 3 * mb * sizeof(int), hipMemcpyHostToDevice, s));
     if (n_sets > 0) HIPCK(hipMemcpyAsync(e->ban_words, sets, (size_t)n_sets * W * sizeof(int), hipMemcpyDeviceToDevice, s));
+    e->ban_seq_armed = false;
+    if (n_pool > 0) {               // the pool's four arrays, each into its fixed region of the staging twin and from there on `s`
+        const BanSeqArgs at = ban_seq_args(e);
+        const int* src[4] = {pool.list_of, pool.list_off, pool.seq_off, pool.tok};
+        const int* dst[4] = {at.list_of, at.list_off, at.seq_off, at.tok};
+        const size_t cnt[4] = {(size_t)Q, (size_t)pool.L + 1, (size_t)pool.S + 1, (size_t)pool.T};
+        for (int i = 0; i < 4; ++i) {
+            if (!cnt[i]) continue;
+            int* st = e->ban_seq_stage + (dst[i] - e->ban_seq);
+            memcpy(st, src[i], cnt[i] * sizeof(int));
+            HIPCK(hipMemcpyAsync(const_cast<int*>(dst[i]), st, cnt[i] * sizeof(int), hipMemcpyHostToDevice, s));
+        }
+    }
     RCK(constrain_info(e, {Q, n_sets, W, 0}, info_out, s));
     e->ban_armed = Q;
+    e->ban_seq_armed = n_pool > 0;
     return 0;
 }
 // A search call of Q sentences meets the arming: disarmed -> it runs plain; armed for Q -> it will run constrained (generate_run
@@ -1875,7 +1927,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     if (sp && sp->kind == GITMI_SEARCH_RECALL)
         return memory_recall(e, frames, B, prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN)
-        return constrain_call(e, frames, (const unsigned int*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
+        return constrain_call(e, frames, (const unsigned int*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, sent_out,
+                              sp->reserved_, s);
     if (sp && sp->kind == GITMI_SEARCH_FEATURES)
         return features_call(e, frames, F, B, prefixes, sp->reserved_, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {

@@ -57,7 +57,9 @@ enum { TAG_VIT = 0, TAG_PREFILL = 1, TAG_DECODE = 2, TAG_GEMM_VIT = 10, TAG_GEMM
 struct GraphKey {
     int B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed; double lp;
     int smp, top_k, nh; double top_p, temp, rp; unsigned long long seed;
-    int constrained;    // the decode part runs under armed constraints (their VALUES live in the engine's tables, not in the key)
+    // 0 plain, 1 the decode part runs under armed constraints, 2 under constraints with banned sequences (one more launch per
+    // step); their VALUES live in the engine's tables, not in the key
+    int constrained;
     // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds: Nimg rows per
     // image block, with (keyed) or without per-image key counts; both 0 in a call with frames, which decides them itself
     auto fields() const {
@@ -190,6 +192,17 @@ struct gitmi_engine {
     hipEvent_t ban_staged = nullptr;    // the last copy out of ban_stage
     int ban_armed = 0;
     bool ban_live = false;
+    // banned token sequences (the extension of GITMI_SEARCH_CONSTRAIN selected by search->reserved_): the device table ban_seq =
+    // list_of [max_batch] | list_off [max_batch + 1] | seq_off [BAN_SEQ_MAX_SEQS + 1] | tok [BAN_SEQ_MAX_TOKS] at fixed offsets, its
+    // page-locked staging twin (guarded by ban_staged, like ban_stage) and the per-row sets ban_row_words (uint32 [max_batch x
+    // max_beams][W], written by ban_rows_kernel before the head of every step) -- allocated by the first arming call that
+    // carries sequences, pointers fixed afterwards.  ban_seq_armed: the armed constraints carry sequences; ban_seq_live: so does
+    // the search in progress.
+    int* ban_seq = nullptr;
+    int* ban_seq_stage = nullptr;
+    unsigned int* ban_row_words = nullptr;
+    bool ban_seq_armed = false;
+    bool ban_seq_live = false;
 
     // ViT workspaces (one frame of max_batch images at a time)
     void *patches = nullptr, *v_h = nullptr, *v_qkv = nullptr, *v_ctx = nullptr, *v_u = nullptr;

@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void vocab_topm_kernel(VocabArgs g) {
             if constexpr (BAN) {
                 {
                     const int sent = fm / g.beams;
-                    const BanRow br = ban_row(g.ban, sent, g.plen[sent], g.cur_len);
+                    const BanRow br = ban_row(g.ban, fm, sent, g.plen[sent], g.cur_len);
                     auto bit_of = [&](int tok) -> unsigned int {
                         const int rel = tok - c0;
                         return (rel >= 0 && rel < 16 * NS && ((rel >> 2) & 3) == lg) ? 1u << ((rel >> 4) * 4 + (rel & 3)) : 0u;

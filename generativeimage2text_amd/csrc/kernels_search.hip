@@ -44,6 +44,35 @@ __device__ __forceinline__ bool ban_test(const BanRow& br, const int* tbl, int c
     return ban_static(br, c) || (br.n > 0 && hist_contains(tbl, c));
 }
 
+// The per-row ban set of a step under banned token sequences (ban_rules.h, the sequence rule): one workgroup per row.  The W
+// words of the sentence's static set (zeros without one) go into LDS; the threads stride over the sentence's sequences, compare
+// each one's head with the tail of the history, and a hit sets the bit of its last token with an LDS atomic OR; then the W words
+// are stored to row_words[row].  Addresses come from the host-validated offsets, the row index and history positions in [0, t);
+// history and sequence tokens are compared and set bits, and a token indexes LDS only after the host has bounded it by vocab.
+constexpr int BAN_ROWS_NT = 256;
+__global__ __launch_bounds__(BAN_ROWS_NT) void ban_rows_kernel(BanArgs ban, BanSeqArgs seq, const int* __restrict__ ids, int ld_ids,
+                                                               int t, int beams, unsigned int* __restrict__ row_words) {
+    extern __shared__ unsigned int s_row_words[];
+    const int row = blockIdx.x, sent = row / beams, tid = threadIdx.x;
+    const int si = ban.set_of ? ban.set_of[sent] : -1;
+    const unsigned int* set = si >= 0 ? ban.words + (size_t)si * ban.W : nullptr;
+    for (int w = tid; w < ban.W; w += BAN_ROWS_NT) s_row_words[w] = set ? set[w] : 0u;
+    __syncthreads();
+    const int li = seq.list_of[sent];
+    if (li >= 0) {
+        const int* x = ids + (size_t)row * ld_ids;
+        for (int q = seq.list_off[li] + tid; q < seq.list_off[li + 1]; q += BAN_ROWS_NT) {
+            const int o = seq.seq_off[q], m = seq.seq_off[q + 1] - o;
+            if (ban_seq_hit(x, t, seq.tok + o, m)) {
+                const int c = seq.tok[o + m - 1];
+                atomicOr(&s_row_words[c >> 5], 1u << (c & 31));
+            }
+        }
+    }
+    __syncthreads();
+    for (int w = tid; w < ban.W; w += BAN_ROWS_NT) row_words[(size_t)row * ban.W + w] = s_row_words[w];
+}
+
 // ---------------------------------------------------------------------------------------
 template <int MMAX, int NT, bool BAN = false>
 __global__ __launch_bounds__(NT) void row_topm_kernel(const float* __restrict__ logits, int ldl, int V,
@@ -80,7 +109,7 @@ __global__ __launch_bounds__(NT) void row_topm_kernel(const float* __restrict__ 
     if constexpr (BAN) {
         __shared__ int s_ban_tbl[HIST_SLOTS];
         s_ban = s_ban_tbl;
-        br = ban_row(ban, r / beams, plen[r / beams], cur_len);
+        br = ban_row(ban, r, r / beams, plen[r / beams], cur_len);
         ban_fill_ngram<NT>(br, ids + (size_t)r * ld_ids, cur_len, s_ban);
     }
 
@@ -247,7 +276,7 @@ __global__ __launch_bounds__(SMP_NT) void sample_rows_kernel(const float* __rest
     if constexpr (BAN) {
         __shared__ int s_ban_tbl[HIST_SLOTS];
         s_ban = s_ban_tbl;
-        br = ban_row(ban, r / beams, plen[r / beams], cur_len);
+        br = ban_row(ban, r, r / beams, plen[r / beams], cur_len);
         ban_fill_ngram<SMP_NT>(br, ids + (size_t)r * ld_ids, cur_len, s_ban);
     }
     float xv[SMP_PER];
@@ -1028,6 +1057,16 @@ hipError_t launch_load_ids(const long long* tokens, int R, int t, int* ids, int*
 }
 
 int row_topm_slots(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16; }
+
+hipError_t launch_ban_rows(const BanArgs& ban, const BanSeqArgs& seq, const int* ids, int ld_ids, int t, int rows, int beams,
+                           unsigned int* row_words, hipStream_t s) {
+    if (rows <= 0) return hipSuccess;
+    if (ban.W < 1 || ban.W > BAN_ROW_MAX_WORDS || beams < 1 || t < 1 || t > ld_ids) return hipErrorInvalidValue;
+    if (!ids || !row_words || !seq.list_of || !seq.list_off || !seq.seq_off || !seq.tok) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ban_rows_kernel, dim3(rows), dim3(BAN_ROWS_NT), (size_t)ban.W * sizeof(unsigned int), s, ban, seq, ids, ld_ids,
+                       t, beams, row_words);
+    return hipGetLastError();
+}
 
 hipError_t launch_row_topm(const float* logits, int ldl, int V, const int* ids, int ld_ids, int cur_len,
                            const int* plen, int beams, int suppress_kind, float rep_penalty, int M, int R,

@@ -81,10 +81,27 @@ inline DGemmArgs dgemm_to_stream(const void* A, const void* W, const float* bias
 // ---- per-sentence decoding constraints (GITMI_SEARCH_CONSTRAIN, include/gitmi.h; the rule itself: ban_rules.h) ----
 // The engine's own tables of an armed call (DEVICE, host-validated): `words` uint32 [n_sets][W] ban sets, bit c % 32 of word
 // c / 32 = token c; per sentence set_of (-1: none), min_new, ngram (0: off, else 1..8).  set_of == nullptr: unconstrained.
+// row_words (or nullptr: as without it) uint32 [rows][W]: the row's own set for this step -- its sentence's set OR the last tokens
+// of the banned sequences its history ends with (ban_rows_kernel) -- read in place of words[set_of].
 struct BanArgs {
     const unsigned int* words; const int* set_of; const int* min_new; const int* ngram;
     int W, eos;
+    const unsigned int* row_words;
 };
+// Banned token sequences of an armed call (the host-validated pool of GITMI_SEARCH_CONSTRAIN's extension, DEVICE): sentence q
+// names list list_of[q] (-1: none) = sequences list_off[l] .. list_off[l + 1] - 1, sequence j = tokens tok[seq_off[j] ..
+// seq_off[j + 1]), 2 .. BAN_SEQ_MAX_LEN of them, every token in [0, vocab).
+struct BanSeqArgs {
+    const int* list_of; const int* list_off; const int* seq_off; const int* tok;
+};
+constexpr int BAN_SEQ_MAX_LEN = 16;         // tokens of one banned sequence
+constexpr int BAN_SEQ_MAX_SEQS = 4096;      // sequences of one arming call (all lists)
+constexpr int BAN_SEQ_MAX_TOKS = 32768;     // their tokens
+constexpr int BAN_ROW_MAX_WORDS = 8192;     // set words ban_rows_kernel holds in LDS (32 KB: vocabularies up to 262144 tokens)
+// one workgroup per row: row_words[row] = set of the row's sentence | last tokens of the sequences its history ids[row][0 .. t) ends
+// with.  ban: words / set_of / W are read.  Refuses (invalid value) W outside [1, BAN_ROW_MAX_WORDS], beams < 1, t < 1.
+hipError_t launch_ban_rows(const BanArgs& ban, const BanSeqArgs& seq, const int* ids, int ld_ids, int t, int rows, int beams,
+                           unsigned int* row_words, hipStream_t s);
 
 // vocabulary head with the running top-M / log-sum-exp fused: one sorted candidate list per (row, workgroup)
 struct VocabArgs {

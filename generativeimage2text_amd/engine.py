@@ -369,6 +369,81 @@ def constraint_tables(n: int, vocab: int, eos: int, min_new_tokens=0, no_repeat_
     return (np.stack(sets) if sets else np.zeros((0, W), dtype=np.uint32)), table
 
 
+SEQUENCE_MAX_LEN = 16          # tokens of one banned sequence (include/gitmi.h)
+SEQUENCE_MAX_SEQS = 4096       # sequences of one arming call, all lists together
+SEQUENCE_MAX_TOKENS = 32768    # their tokens
+
+
+def banned_sequence_tables(n: int, vocab: int, sequences):
+    """Host side of Engine.constrain(..., sequences=): the banned token sequences of `n` sentences in the form of include/gitmi.h
+    (the extension of GITMI_SEARCH_CONSTRAIN).  sequences: one list of id sequences for all sentences, or n entries that are each
+    None or such a list; an element that is a list of ints is a sequence.  A sequence of one token is a banned token: it comes
+    back in `singles` for the sentence's bit set and never reaches the engine; the others have 2 .. SEQUENCE_MAX_LEN tokens.
+    Identical lists (the same sequences in the same order, duplicates within a list dropped) are stored once.
+    -> (singles, pool): singles n entries, each None or the list of single-token ids of the sentence; pool a numpy int32 array
+    { L, S, T, 0, list_of[n], list_off[L + 1], seq_off[S + 1], tok[T] }, or None when no sentence has a longer sequence."""
+    import numpy as np
+    n, vocab = int(n), int(vocab)
+    if n < 1:
+        raise ValueError(f"banned sequences for {n} sentences")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    is_seq = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and all(is_int(t) for t in v)
+    if sequences is None:
+        return [None] * n, None
+    if not isinstance(sequences, (list, tuple)):
+        raise ValueError("bad_sequences must be a list of id sequences, or one such list (or None) per sentence")
+    if all(is_seq(v) for v in sequences):           # one list for every sentence (the empty list among them)
+        per = [list(sequences)] * n
+    else:
+        per = list(sequences)
+        if len(per) != n:
+            raise ValueError(f"bad_sequences has {len(per)} entries for {n} sentences (one list for all, or one per sentence)")
+    singles, list_of, lists, index = [], [], [], {}
+    for q, lst in enumerate(per):
+        if lst is None:
+            singles.append(None)
+            list_of.append(-1)
+            continue
+        if not isinstance(lst, (list, tuple)):
+            raise ValueError(f"sentence {q}: bad_sequences must be a list of id sequences or None, got {type(lst).__name__}")
+        one, many = [], []
+        for j, seq in enumerate(lst):
+            if not is_seq(seq):
+                raise ValueError(f"sentence {q}: sequence {j} must be a non-empty list of token ids, got {seq!r}")
+            seq = tuple(int(t) for t in seq)
+            for t in seq:
+                if t < 0 or t >= vocab:
+                    raise ValueError(f"sentence {q}: sequence {j} holds token {t} outside [0, {vocab})")
+            if len(seq) > SEQUENCE_MAX_LEN:
+                raise ValueError(f"sentence {q}: sequence {j} has {len(seq)} tokens, at most {SEQUENCE_MAX_LEN} are supported")
+            if len(seq) == 1:
+                one.append(seq[0])
+            elif seq not in many:
+                many.append(seq)
+        singles.append(one or None)
+        if not many:
+            list_of.append(-1)
+            continue
+        key = tuple(many)
+        if key not in index:
+            index[key] = len(lists)
+            lists.append(many)
+        list_of.append(index[key])
+    if not lists:
+        return singles, None
+    list_off, seq_off, tok = [0], [0], []
+    for many in lists:
+        for seq in many:
+            tok.extend(seq)
+            seq_off.append(len(tok))
+        list_off.append(len(seq_off) - 1)
+    S, T = len(seq_off) - 1, len(tok)
+    if S > SEQUENCE_MAX_SEQS or T > SEQUENCE_MAX_TOKENS:
+        raise ValueError(f"bad_sequences: {S} distinct sequences with {T} tokens in {len(lists)} lists; one call carries at most "
+                         f"{SEQUENCE_MAX_SEQS} sequences and {SEQUENCE_MAX_TOKENS} tokens")
+    return singles, np.array([len(lists), S, T, 0] + list_of + list_off + seq_off + tok, dtype=np.int32)
+
+
 class Geometry(tuple):
     """Engine.resident_geometry: the tuple (Nk, F, grids) -- Nk key rows of an image's block (its row stride), F frames, the token
     grid of every image -- plus, for a batch that carries context tokens (Engine.encode_context): image_rows, the F * n_tok image
@@ -943,12 +1018,14 @@ class Engine:
         return {"stride": stride, "max_rows": max_n, "total_rows": total}
 
     # -- per-sentence decoding constraints ---------------------------------------------------------------------------------------
-    def constrain(self, sets_words, table) -> Dict[str, int]:
+    def constrain(self, sets_words, table, sequences=None) -> Dict[str, int]:
         """Arm per-sentence decoding constraints for the NEXT search call of this context (include/gitmi.h
         GITMI_SEARCH_CONSTRAIN; constraint_tables builds the arguments): sets_words uint32 [n_sets, ceil(vocab / 32)] (a numpy
         array or a tensor; None: no sets), table one row [set index or -1, min_new, ngram] per sentence of that call.  One-shot:
         the call consumes them.  An empty table disarms.  The copies are enqueued on the current stream and nothing is read
         back: the host does not wait for the context's work in flight.
+        sequences: the int32 pool of banned_sequence_tables for the same sentences (None: no banned sequences -- the C call is
+        then exactly the one made without the keyword).
         -> {'sentences', 'sets', 'words'}"""
         import numpy as np
         table = [[int(v) for v in row] for row in (table or [])]
@@ -969,8 +1046,15 @@ class Engine:
         search.kind = SEARCH_CONSTRAIN
         info = torch.empty(4, dtype=torch.int32, device=f"cuda:{self.device}")
         tab = (C.c_int32 * max(3 * Q, 1))(*[v for row in table for v in row])
+        pool = None
+        if sequences is not None and Q:
+            seq = np.ascontiguousarray(sequences, dtype=np.int32).reshape(-1)
+            if seq.size < 4 + Q:
+                raise ValueError(f"a sequence pool for {Q} sentences has at least {4 + Q} words, got {seq.size}")
+            pool = (C.c_int32 * int(seq.size))(*seq.tolist())      # host memory: read before the call returns
+            search.reserved_ = int(seq.size)
         self._ck(self.lib.gitmi_generate_prefixed(self._h, None, 0, 0, _ptr(words), n_sets, tab, None, Q, C.byref(search),
-                                                  None, None, None, info.data_ptr(), _stream()))
+                                                  None, None, pool, info.data_ptr(), _stream()))
         self._ban_keep = (words, info)  # the copies are enqueued on the stream: both outlive the call
         return {"sentences": Q, "sets": n_sets if Q else 0, "words": W}       # info_out's values (include/gitmi.h), not read back
 
@@ -1947,23 +2031,47 @@ def op_sample_rows(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 
 # misaligned row is a slice of a wider tensor).  out: caller-supplied output tensors (the tests fill them with sentinels).
 class _GitmiDebugBan(C.Structure):
     _fields_ = [("words", C.c_void_p), ("n_sets", C.c_int), ("W", C.c_int), ("set_of", C.c_void_p), ("min_new", C.c_void_p),
-                ("ngram", C.c_void_p), ("eos", C.c_int)]
+                ("ngram", C.c_void_p), ("eos", C.c_int), ("row_words", C.c_void_p),
+                ("pool_host", C.c_void_p), ("n_pool", C.c_int), ("row_words_out", C.c_void_p)]
 
 
 class DebugBan:
     """gitmi_debug_ban (include/gitmi_experiment.h) for op_vocab_topm_rules / op_row_topm / op_sample_rows_rules: words uint32
     [n_sets, W] as an int32 device tensor of the same bits (or None), set_of / min_new / ngram int32 device tensors with one entry
-    per sentence, eos.  The hooks check the tables; nothing is checked here.  Keeps the tensors alive."""
+    per sentence, eos; row_words int32 [rows, W] (or None: as without it) the rows' own sets of the step, which the kernels then
+    read in place of words[set_of] (op_ban_rows computes them).  The hooks check the tables; nothing is checked here.  Keeps the
+    tensors alive."""
 
     def __init__(self, words: Optional[torch.Tensor], n_sets: int, W: int, set_of: Optional[torch.Tensor],
-                 min_new: Optional[torch.Tensor], ngram: Optional[torch.Tensor], eos: int):
-        self.tensors = (words, set_of, min_new, ngram)
+                 min_new: Optional[torch.Tensor], ngram: Optional[torch.Tensor], eos: int,
+                 row_words: Optional[torch.Tensor] = None):
+        self.tensors = (words, set_of, min_new, ngram, row_words)
         self.struct = _GitmiDebugBan(_ptr(words) or None, int(n_sets), int(W), _ptr(set_of) or None, _ptr(min_new) or None,
-                                     _ptr(ngram) or None, int(eos))
+                                     _ptr(ngram) or None, int(eos), _ptr(row_words) or None)
 
 
 def _ban_ref(ban: Optional[DebugBan]):
     return None if ban is None else C.addressof(ban.struct)
+
+
+def op_ban_rows(ban: DebugBan, pool, ids: torch.Tensor, cur_len: int, beams: int, V: int, out: Optional[torch.Tensor] = None,
+                operands: Optional[str] = None) -> torch.Tensor:
+    """ban_rows_kernel through its launcher (measurement build; the form of gitmi_debug_row_topm that ban.row_words_out selects,
+    include/gitmi_experiment.h): the per-row ban sets of one step under banned token sequences.
+    ban: the static sets (words / n_sets / W / set_of); pool: the int32 host pool of banned_sequence_tables for ids.shape[0] /
+    beams sentences; ids int32 [rows, ld_ids] device histories of cur_len tokens.  -> row_words int32 [rows, W] (the bits of the
+    uint32 words), or `out`."""
+    import numpy as np
+    lib, fn = _front("gitmi_debug_row_topm", operands=operands)
+    pool = np.ascontiguousarray(pool, dtype=np.int32)
+    rows = int(ids.shape[0])
+    rw = out if out is not None else torch.empty(rows, int(ban.struct.W), device=ids.device, dtype=torch.int32)
+    f = {n: getattr(ban.struct, n) for n, _ in _GitmiDebugBan._fields_}
+    f.update(row_words=None, pool_host=int(pool.ctypes.data), n_pool=int(pool.size), row_words_out=rw.data_ptr())
+    call = _GitmiDebugBan(**f)
+    _ck(fn(None, 0, int(V), rows, ids.data_ptr(), int(ids.stride(0)), int(cur_len), None, int(beams), 0, 0.0, 1, None, None, None,
+           _stream(), C.addressof(call)), lib)
+    return rw
 
 
 def _logit_rows(logits: torch.Tensor, V: int) -> Tuple[int, int]:

@@ -18,10 +18,19 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 import torch
 
 from .configs import GitModelConfig, config_from_param
-from .engine import CONSTRAINT_KEYS, Engine, constraint_tables, context_segments, id_table
+from .engine import CONSTRAINT_KEYS, Engine, banned_sequence_tables, constraint_tables, context_segments, id_table
 
 # search_param keys of the per-sentence decoding constraints (CaptioningModel._constraints)
-CONSTRAINT_PARAMS = CONSTRAINT_KEYS + ("bad_words",)
+CONSTRAINT_PARAMS = CONSTRAINT_KEYS + ("bad_words", "bad_sequences", "bad_phrases")
+
+
+def _arm(eng, ban) -> None:
+    """Arm the constraints of a request (CaptioningModel._constraints) on `eng`: (words, table), or with banned sequences
+    (words, table, pool) -- only then does the call carry the `sequences` keyword."""
+    if len(ban) == 2:
+        eng.constrain(ban[0], ban[1])
+    else:
+        eng.constrain(ban[0], ban[1], sequences=ban[2])
 
 
 # ---- decoder.search(start_predictions, step): the reference's search seam as a method ----------------------------
@@ -512,32 +521,87 @@ class CaptioningModel:
         """The decoding constraints of a request of `n` sentences (include/gitmi.h GITMI_SEARCH_CONSTRAIN) from its search_param:
         min_new_tokens, no_repeat_ngram_size, bad_tokens, allowed_tokens -- each one value for all sentences or one per sentence
         (engine.constraint_tables) -- and bad_words, words that are one WordPiece each (one list for all, or one per sentence),
-        banned like bad_tokens.  repeat: every sentence stands for `repeat` consecutive ones (num_return_sequences).
-        -> (words, table) for Engine.constrain, or None: the request is not constrained and nothing is armed."""
+        banned like bad_tokens.  bad_sequences (id sequences) and bad_phrases (strings of any number of WordPieces, through the
+        tokenizer) ban token sequences: one list for all sentences or one per sentence (engine.banned_sequence_tables); their
+        one-token entries join the sentence's bad tokens.  repeat: every sentence stands for `repeat` consecutive ones
+        (num_return_sequences).
+        -> (words, table) for Engine.constrain -- (words, table, pool) when some sentence bans a sequence of two or more tokens --
+        or None: the request is not constrained and nothing is armed."""
         sp = {k: v for k, v in (search_param or {}).items() if k in CONSTRAINT_PARAMS and v is not None}
         if not sp:
             return None
         if self.decoder.kind == "trie":
             raise NotImplementedError("decoding constraints on the trie search are not implemented")
         bad = sp.get("bad_tokens")
+        pool = None
+        if "bad_sequences" in sp or "bad_phrases" in sp:
+            singles, pool = banned_sequence_tables(n, int(self.cfg.vocab), self._sequences(sp, n))
+            if any(one is not None for one in singles):
+                bad = self._merge_ids("bad_tokens", bad, singles, n)
         if "bad_words" in sp:
             words = sp["bad_words"]
             flat = all(isinstance(w, str) for w in words)
             ids = [self._word_ids(words)] * n if flat else [None if ws is None else self._word_ids(ws) for ws in words]
             if len(ids) != n:
                 raise ValueError(f"bad_words has {len(ids)} entries for {n} sentences (one list for all, or one per sentence)")
-            if bad is not None:
-                flat_ids = all(isinstance(t, int) and not isinstance(t, bool) for t in bad)       # one id list for every sentence
-                per = [list(bad)] * n if flat_ids else list(bad)
-                if len(per) != n:
-                    raise ValueError(f"bad_tokens has {len(per)} entries for {n} sentences (one value for all, or one per sentence)")
-                ids = [None if a is None and b is None else list(a or []) + list(b or []) for a, b in zip(ids, per)]
-            bad = ids
+            bad = ids if bad is None else self._merge_ids("bad_tokens", bad, ids, n)
         out = constraint_tables(n, int(self.cfg.vocab), int(self.cfg.eos), sp.get("min_new_tokens", 0), sp.get("no_repeat_ngram_size", 0),
                                 bad, sp.get("allowed_tokens"), max_new=int(self.engine.c.max_text_len))
-        if out is None or repeat == 1:
-            return out
-        return out[0], [row for row in out[1] for _ in range(repeat)]
+        if pool is None:
+            if out is None or repeat == 1:
+                return out
+            return out[0], [row for row in out[1] for _ in range(repeat)]
+        import numpy as np
+        if out is None:             # sequences alone: no set, no length rule, no n-gram rule
+            out = np.zeros((0, (int(self.cfg.vocab) + 31) // 32), dtype=np.uint32), [[-1, 0, 0] for _ in range(n)]
+        if repeat != 1:             # list_of is the pool's only per-sentence array
+            pool = np.concatenate([pool[:4], np.repeat(pool[4:4 + n], repeat), pool[4 + n:]]).astype(np.int32)
+        return out[0], [row for row in out[1] for _ in range(repeat)], pool
+
+    @staticmethod
+    def _merge_ids(name: str, given, more, n: int):
+        """given: a search_param id list for all sentences or one (or None) per sentence; more: n entries, None or ids -> n entries"""
+        flat_ids = all(isinstance(t, int) and not isinstance(t, bool) for t in given or [])       # one id list for every sentence
+        per = [None if given is None else list(given)] * n if flat_ids else list(given)
+        if len(per) != n:
+            raise ValueError(f"{name} has {len(per)} entries for {n} sentences (one value for all, or one per sentence)")
+        return [None if a is None and b is None else list(a or []) + list(b or []) for a, b in zip(more, per)]
+
+    def _sequences(self, sp: dict, n: int):
+        """bad_sequences and bad_phrases of a request -> one entry per sentence: None or its list of id sequences"""
+        def per_sentence(name, value, is_leaf):
+            if not isinstance(value, (list, tuple)):
+                raise ValueError(f"{name} must be a list (one for all sentences, or one list or None per sentence)")
+            if all(is_leaf(v) for v in value):
+                return [list(value)] * n
+            if len(value) != n:
+                raise ValueError(f"{name} has {len(value)} entries for {n} sentences (one list for all, or one per sentence)")
+            return list(value)
+
+        import numpy as np
+        is_int = lambda t: isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+        is_ids = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and all(is_int(t) for t in v)
+        per = [None] * n
+        if sp.get("bad_sequences") is not None:
+            per = per_sentence("bad_sequences", sp["bad_sequences"], is_ids)
+        if sp.get("bad_phrases") is not None:
+            tok = getattr(self, "tokenizer", None)
+            if tok is None:
+                raise ValueError("bad_phrases needs the model's tokenizer (get_git_model keeps it; or set model.tokenizer)")
+            phrases = per_sentence("bad_phrases", sp["bad_phrases"], lambda v: isinstance(v, str))
+            for q, lst in enumerate(phrases):
+                if lst is None:
+                    continue
+                seqs = []
+                for ph in lst:
+                    if not isinstance(ph, str):
+                        raise ValueError(f"sentence {q}: bad_phrases holds {ph!r}, not a string")
+                    ids = [int(t) for t in tok(ph, add_special_tokens=False)["input_ids"]]
+                    if not ids:
+                        raise ValueError(f"sentence {q}: bad_phrases: {ph!r} has no WordPiece")
+                    seqs.append(ids)
+                per[q] = seqs if per[q] is None else list(per[q]) + seqs
+        return per
 
     def _word_ids(self, words) -> List[int]:
         tok = getattr(self, "tokenizer", None)
@@ -548,7 +612,7 @@ class CaptioningModel:
             pieces = tok(w, add_special_tokens=False)["input_ids"]
             if len(pieces) != 1:
                 raise ValueError(f"bad_words: {w!r} is {len(pieces)} WordPieces; only words that are one WordPiece can be banned "
-                                 f"(multi-token banned sequences are not implemented)")
+                                 f"(multi-token banned sequences are not implemented for bad_words: use bad_phrases)")
             ids.append(int(pieces[0]))
         return ids
 
@@ -685,7 +749,7 @@ class CaptioningModel:
                 eng.encode_context(frames, ctx[0], image_of=ctx[1])
                 frames_arg = None
             if ban is not None:         # armed on this context and stream, immediately before the call that consumes it
-                eng.constrain(*ban)
+                _arm(eng, ban)
             if nret != 1:
                 # decoder.py:1093-1097: every image's start tokens num_return_sequences times -- r sentences per image, each
                 # with its own beams (they differ only when sampling); rows b * r + j, as the reference returns them
@@ -954,7 +1018,7 @@ class CaptioningModel:
         if prefixes is None:
             def launch():
                 if ban is not None:
-                    eng.constrain(*ban)
+                    _arm(eng, ban)
                 return eng.generate(packed, search, sync=False, host_out=stream is not None)
 
             return Pending(stream, launch,
@@ -1015,7 +1079,7 @@ class CaptioningModel:
 
         def launch():
             if ban is not None:
-                eng.constrain(*ban)
+                _arm(eng, ban)
             return eng.generate_prefixed(frames, search, prefixes, image_of=image_of, sync=False, host_out=stream is not None)
 
         def finish(out):

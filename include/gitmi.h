@@ -530,7 +530,31 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * The tables (the set words and three int [max_batch] arrays) are allocated by the first arming call: engines that never
  * constrain keep their footprint.  The hipGraph key of the decode part gains "constrained"; the values live in those tables, whose
  * pointers never change, so armed calls of equal shape and different values replay one graph.  A constrained 16-bit call runs
- * the vocabulary head in its generic form (the form the repetition penalty uses); an unconstrained call launches what it did. */
+ * the vocabulary head in its generic form (the form the repetition penalty uses); an unconstrained call launches what it did.
+ *
+ * Banned token sequences (an optional extension of the arming call, selected by search->reserved_).  The rule: sentence s may name
+ * one list of sequences a = (a_0 .. a_{m-1}), 2 <= m <= 16.  Token c is additionally banned for (r, t) if some sequence of the
+ * list has a_{m-1} == c, t >= m - 1 and x[t - m + 1 .. t) == a[0 .. m - 1): the last token of a banned sequence is banned
+ * exactly when the row's history (start tokens and prefix included, as for the n-gram rule) ends with the tokens before it.
+ * Several sequences may hit at once; the union is banned.  Sequences of one token are bits of the sentence's set and are not
+ * part of the extension.
+ *   search->reserved_ == 0 is the call above, exactly.
+ *   search->reserved_ = n > 0 : sent_out is read as a HOST const int32 [n] pool
+ *                     { L, S, T, 0, list_of[Q], list_off[L + 1], seq_off[S + 1], tok[T] }: L lists, S sequences, T tokens;
+ *                     list_of[q] the list of sentence q or -1; list l = sequences list_off[l] .. list_off[l + 1] - 1; sequence j =
+ *                     tok[seq_off[j] .. seq_off[j + 1]).  Read before the call returns; the engine keeps no pointer.
+ * Checked on the host before any launch, by message naming sentence, list and sequence: the sizes add up to n, both offset
+ * arrays start at 0, never decrease and end at S and T, every length in [2, 16], every token in [0, vocab), list_of in [-1, L),
+ * L <= max_batch, and at most 4096 sequences and 32768 tokens per call.  A vocabulary above 262144 tokens (8192 set words, the LDS
+ * budget of the kernel below) is refused too.  A refused call leaves what was armed and what is resident unchanged.
+ * The pool travels through page-locked staging to a device table of the engine's own, enqueued on `stream` with no host wait.
+ * That table and a buffer of max_batch x max_beams x W words are allocated by the first arming call that carries sequences (their
+ * pointers never change afterwards): engines that never use sequences keep their footprint.  info_out is as above.
+ * A search armed with sequences launches one more kernel per decode step, before the vocabulary head: one workgroup per row ORs
+ * the sentence's set and the last tokens of the sequences the row's history ends with into the row's own W words, which the
+ * set rule of that step then reads.  The hipGraph key's "constrained" tells plain, armed and armed with sequences apart; calls of
+ * equal shape armed with other sequences replay one graph.  Plain calls and set-only armed calls launch what they did; a set-only
+ * arming after one with sequences carries none.  The trie search and the step seam keep refusing while armed. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,

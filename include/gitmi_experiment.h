@@ -32,6 +32,13 @@ typedef struct gitmi_debug_ban {
     int n_sets, W;
     const int32_t *set_of, *min_new, *ngram;   /* DEVICE int32 [rows / beams] */
     int eos;
+    const uint32_t* row_words;  /* DEVICE uint32 [rows][W] or NULL (as before the field existed): the rows' own sets of the step
+                                 * (banned sequences; the row_words_out form of gitmi_debug_row_topm computes them), read in place of words[set_of]; set_of
+                                 * is still checked, words may then be NULL */
+    /* gitmi_debug_row_topm only: row_words_out != NULL turns the call into ban_rows_kernel alone (see there) */
+    const int32_t* pool_host;   /* HOST int32 [n_pool]: the sequence pool of GITMI_SEARCH_CONSTRAIN's extension */
+    int n_pool;
+    uint32_t* row_words_out;    /* DEVICE uint32 [rows][W] */
 } gitmi_debug_ban;
 
 /* GITMI_EXPERIMENT_TYPES_ONLY: the types above without the entry points (csrc/abi_ops.hip in the product builds, which compile
@@ -275,6 +282,16 @@ int  gitmi_debug_context_embed(const int64_t* tokens, int ld, const int32_t* len
  *                penalty or a ban over more than 1024 tokens.  ban (or NULL): the rows' decoding constraints on the raw
  *                logits, before the penalty, with plen int32 [R / beams] and beams (both read under a ban only; R a multiple of
  *                beams).  Synchronises the stream. */
+/*   row_topm with ban->row_words_out != NULL: ban_rows_kernel ALONE, no selection (the measurement builds keep their symbol
+ *                list, so the hook of the new kernel is a form of this one) -- the per-row ban sets of one step under banned token
+ *                sequences (include/gitmi.h, the extension of GITMI_SEARCH_CONSTRAIN): row_words_out uint32 [R][W] DEVICE = the
+ *                static set of the row's sentence (ban->words / n_sets / W / set_of; zeros without one) OR the last tokens of the
+ *                sequences that the row's history ids[row][0 .. cur_len) ends with.  ban->pool_host int32 [n_pool]: the HOST pool
+ *                { L, S, T, 0, list_of[R / beams], list_off[L + 1], seq_off[S + 1], tok[T] }, validated by the check the arming
+ *                call makes (L at most the sentence count) and refused by the same messages; W above the kernel's LDS budget
+ *                (8192 words) and ban->row_words together with row_words_out are refused.  Reads ids, ld_ids, cur_len, R, beams,
+ *                V, stream; logits, plen, the rules and the list outputs are ignored.  Synchronises.  (To become a hook of its
+ *                own, gitmi_debug_ban_rows, when the symbol list of the measurement builds is next revised.) */
 int  gitmi_debug_row_topm(const float* logits, int ldl, int V, int R, const int* ids, int ld_ids, int cur_len, const int* plen,
                           int beams, int suppress_kind, float rep_penalty, int M, float* part_val, int* part_idx, float* part_lse,
                           void* stream, const gitmi_debug_ban* ban);

@@ -28,13 +28,22 @@ def ngram_banned(history, n: int):
     return {history[i + n - 1] for i in range(t - n + 1) if list(history[i:i + n - 1]) == tail}
 
 
-def wrap_step(step, sets, table, eos: int, plen):
+def sequence_banned(history, seqs):
+    """The last tokens of the sequences of `seqs` (2 or more tokens each) whose other tokens the `history` ends with"""
+    t = len(history)
+    return {int(a[-1]) for a in seqs if t >= len(a) - 1 and list(history[t - len(a) + 1:]) == [int(v) for v in a[:-1]]}
+
+
+def wrap_step(step, sets, table, eos: int, plen, sequences=None, list_of=None):
     """step: [rows, t] token ids -> [rows, vocab] logits, rows = sentences x beams with the rows of a sentence contiguous.
     sets: uint32 [n_sets, W]; table: one [set index or -1, min_new, ngram] per sentence; plen: the prefix length of every
-    sentence (start tokens included)."""
+    sentence (start tokens included).  sequences: lists of banned token sequences, list_of: the list of every sentence or -1
+    (None with sequences: sentence s <-> list s)."""
     table = [[int(v) for v in row] for row in table]
     plen = [int(p) for p in plen]
     S = len(table)
+    if sequences is not None and list_of is None:
+        list_of = list(range(S))
 
     def constrained(tokens: torch.Tensor) -> torch.Tensor:
         z = step(tokens).clone()
@@ -50,6 +59,9 @@ def wrap_step(step, sets, table, eos: int, plen):
                 z[r, eos] = BANNED
             for c in ngram_banned(tokens[r].tolist(), n):
                 z[r, c] = BANNED
+            if sequences is not None and list_of[s] >= 0:
+                for c in sequence_banned(tokens[r].tolist(), sequences[list_of[s]]):
+                    z[r, c] = BANNED
         return z
 
     return constrained
