@@ -267,8 +267,10 @@ int CapturedGraph::capture(hipStream_t s, const std::function<int()>& fn) {
 }
 // both hipGraph slots: full calls (one graph, or encode + prefill | decode) and follow-up calls (decode alone)
 static void destroy_graph(gitmi_engine* e) {
-    for (CapturedGraph* g : {&e->graph_full, &e->graph_decode, &e->graph_follow}) g->reset();
-    e->full_slot.valid = e->follow_slot.valid = false;
+    for (auto& gs : e->graphs) {
+        for (CapturedGraph* g : {&gs.graph_full, &gs.graph_decode, &gs.graph_follow}) g->reset();
+        gs.full_slot.valid = gs.follow_slot.valid = false;
+    }
 }
 // ---- residency (include/gitmi.h: what a follow-up call runs over): the only writers of cur_* / have_* ----
 // the engine's images stop being resident: an encode starts (or failed), or a setter changed what an encode would produce
@@ -320,7 +322,7 @@ extern "C" void gitmi_destroy(gitmi_engine* e) {
     hipFree(e->at_out); hipFree(e->at_stats); hipFree(e->ctx_tab); hipFree(e->mem_tab); hipFree(e->feat_tab); hipFree(e->ban_words);
     if (e->ban_stage) hipHostFree(e->ban_stage);
     if (e->ban_staged) hipEventDestroy(e->ban_staged);
-    hipFree(e->ban_seq); hipFree(e->ban_row_words);
+    hipFree(e->ban_seq); hipFree(e->ban_row_words); hipFree(e->trace_buf);
     if (e->ban_seq_stage) hipHostFree(e->ban_seq_stage);
     if (e->trie_off) hipFree(e->trie_off);
     if (e->trie_tok) hipFree(e->trie_tok);
@@ -628,6 +630,70 @@ static BanSeqArgs ban_seq_args(const gitmi_engine* e) {
 }
 static size_t ban_seq_ints(const gitmi_engine* e) { return (size_t)2 * e->cfg.max_batch + 1 + BAN_SEQ_MAX_SEQS + 1 + BAN_SEQ_MAX_TOKS; }
 
+// per-token trace (GITMI_SEARCH_TRACE): the carving of trace_buf for a call of Q sentences returning nout sequences each, T
+// positions, n alternatives -- byte offsets of the log (rows = Q x max_beams, whatever the beam count of the call), the
+// hypotheses' side of it, and the engine's output copies (the graph outputs, copied to the caller's buffers after the launch)
+struct TraceLayout { int rows; size_t log_lp, log_tok, hyp_src, fin_lp, fin_tok, out_lp, out_tok, lse, total; };
+static TraceLayout trace_layout(const gitmi_engine* e, int Q, int nout, int T, int n) {
+    TraceLayout L{};
+    L.rows = Q * e->cfg.max_beams;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t recs = (size_t)T * L.rows, seqs = (size_t)Q * nout;
+    L.log_lp = take(recs * (1 + n) * sizeof(float)); L.log_tok = take(recs * n * sizeof(int));
+    L.hyp_src = take(seqs * T * sizeof(int));
+    L.fin_lp = take(seqs * (1 + n) * sizeof(float)); L.fin_tok = take(seqs * n * sizeof(int));
+    L.out_lp = take(seqs * T * (1 + n) * sizeof(float)); L.out_tok = take(seqs * T * n * sizeof(long long));
+    L.lse = take((size_t)L.rows * sizeof(float2));          // row_topm_traced's scratch
+    L.total = at;
+    return L;
+}
+static TraceLayout trace_layout_live(const gitmi_engine* e) { return trace_layout(e, e->trace_Q, e->trace_nout, e->trace_T, e->trace_n); }
+// the log of the search in progress, or all null when it is not traced
+static TraceArgs trace_args(const gitmi_engine* e) {
+    TraceArgs t{};
+    if (!e->trace_live || !e->trace_buf) return t;
+    const TraceLayout L = trace_layout_live(e);
+    char* p = e->trace_buf;
+    t.n = e->trace_n; t.rows = L.rows;
+    t.log_lp = (float*)(p + L.log_lp); t.log_tok = (int*)(p + L.log_tok); t.hyp_src = (int*)(p + L.hyp_src);
+    t.fin_lp = (float*)(p + L.fin_lp); t.fin_tok = (int*)(p + L.fin_tok);
+    return t;
+}
+// candidates per row the head of a step lists: what the search reads, and the n alternatives of a traced search
+static int search_mtop(const SearchState& st);
+static int head_mtop(const gitmi_engine* e) { return std::max(search_mtop(e->ss), e->trace_live ? e->trace_n : 0); }
+// The whole-row top-M of a step (f32 mode, step seam) of a TRACED search.  The instantiation that holds max(M, n) candidates per
+// row sums the row's exp in another order than the one the plain call launches, so the step's (max, sum exp) -- and with it every
+// log-prob the search adds -- comes from the launch the plain call makes, and the longer lists from a second launch whose
+// statistics go to a scratch: the list values are the logits themselves either way, and traced == plain bit for bit.
+static int row_topm_traced(gitmi_engine* e, const float* logits, int ldl, int V, const int* ids, int ld_ids, int cur_len, int beams,
+                           int suppress_kind, int R, hipStream_t s, const BanArgs* ban) {
+    const int Mp = search_mtop(e->ss), M = head_mtop(e);
+    HIPCK(launch_row_topm(logits, ldl, V, ids, ld_ids, cur_len, e->plen_dev, beams, suppress_kind, rep_penalty_of(e), Mp, R, e->part_val,
+                          e->part_idx, e->part_lse, s, ban));
+    if (row_topm_slots(M) != row_topm_slots(Mp))
+        HIPCK(launch_row_topm(logits, ldl, V, ids, ld_ids, cur_len, e->plen_dev, beams, suppress_kind, rep_penalty_of(e), M, R,
+                              e->part_val, e->part_idx, (float2*)(e->trace_buf + trace_layout_live(e).lse), s, ban));
+    return 0;
+}
+// behind launch_search_finish: the trace of the returned sequences into the engine's output copies
+static int trace_gather(gitmi_engine* e, hipStream_t s) {
+    const TraceLayout L = trace_layout_live(e);
+    HIPCK(launch_search_trace_gather(e->ss, e->ss_cur, e->ss_len, trace_args(e), (float*)(e->trace_buf + L.out_lp),
+                                     e->trace_n > 0 ? (long long*)(e->trace_buf + L.out_tok) : nullptr, s));
+    return 0;
+}
+// the engine's output copies to the buffers of the arming call (device or page-locked host memory), like the ids of a graphed call
+static int trace_deliver(gitmi_engine* e, hipStream_t s) {
+    const TraceLayout L = trace_layout_live(e);
+    const size_t elems = (size_t)e->trace_Q * e->trace_nout * e->trace_T;
+    HIPCK(hipMemcpyAsync(e->trace_user_lp, e->trace_buf + L.out_lp, elems * (1 + e->trace_n) * sizeof(float), hipMemcpyDefault, s));
+    if (e->trace_n > 0)
+        HIPCK(hipMemcpyAsync(e->trace_user_tok, e->trace_buf + L.out_tok, elems * e->trace_n * sizeof(long long), hipMemcpyDefault, s));
+    return 0;
+}
+
 // vocabulary head of the step: candidate lists for the search (and optionally the logits themselves)
 static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur_len, int R, int beams, int suppress_kind,
                             int M, float* logits_out, int ldl, hipStream_t s, StepCands* cands) {
@@ -665,7 +731,7 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
         v.logits_out = logits_out; v.ld_logits = ldl;
         {
             SpanGuard sp(e, s, TAG_GEMM_OTHER, gemm_flops(R, c.vocab, d));
-            if (!GITMI_SKIPPED(e, 8)) HIPCK(launch_vocab_topm(v, M, s));
+            if (!GITMI_SKIPPED(e, 8)) HIPCK(launch_vocab_topm(v, M, s, ids != nullptr && e->trace_live));
         }
         cands->nparts = e->vocab_nparts; cands->slots = vocab_mtop_slots(M);
         if (sampling) RCK(sample_candidates(e, logits_out, ldl, R, cur_len, s, cands, nullptr));
@@ -675,6 +741,8 @@ static int decode_head_impl(gitmi_engine* e, const int* ids, int ld_ids, int cur
         cands->nparts = 1; cands->slots = row_topm_slots(M);
         if (sampling) RCK(sample_candidates(e, e->logits, e->ldl, R, cur_len, s, cands, &ban));
         else if (trie) RCK(trie_candidates(e, e->logits, e->ldl, cur_len, s, cands));
+        else if (ids && e->trace_live)
+            RCK(row_topm_traced(e, e->logits, e->ldl, c.vocab, ids, ld_ids, cur_len, beams, suppress_kind, R, s, &ban));
         else if (ids)
             HIPCK(launch_row_topm(e->logits, e->ldl, c.vocab, ids, ld_ids, cur_len, e->plen_dev, beams, suppress_kind,
                                   rep_penalty_of(e), M, R,
@@ -830,6 +898,7 @@ static int search_begin_impl(gitmi_engine* e, const Request& rq, int V, hipStrea
     return 0;
 }
 
+static int trace_check(const gitmi_engine* e, const char* who, const gitmi_search* sp, int Q, bool* traced);
 static int search_mtop(const SearchState& st) {
     if (st.sampled) return st.pn;
     return st.kind == GITMI_SEARCH_AUTOREGRESSIVE ? std::max(st.k, st.pn) : st.pn * st.k;
@@ -863,7 +932,8 @@ static int search_step_impl(gitmi_engine* e, const StepCands& cands, bool embed,
     const SearchState& st = e->ss;
     const int cur_len = e->ss_len;
     if (cur_len >= st.T) return fail("search_advance: sequence already at max_steps");
-    HIPCK(launch_search_step(st, e->ss_cur, cur_len, cands, embed_args(e, embed), e->pol.f32, s));
+    const TraceArgs tr = trace_args(e);
+    HIPCK(launch_search_step(st, e->ss_cur, cur_len, cands, embed_args(e, embed), e->pol.f32, s, tr.log_lp ? &tr : nullptr));
     e->ss_cur ^= 1;
     e->ss_len = cur_len + 1;
     return 0;
@@ -929,10 +999,14 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("%s: GITMI_SEARCH_RECALL is not a search (gitmi_generate_prefixed recalls kept images)", who);
     if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("%s: GITMI_SEARCH_FEATURES is not a search (gitmi_generate_prefixed installs given feature rows)", who);
     if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN) return fail("%s: GITMI_SEARCH_CONSTRAIN is not a search (gitmi_generate_prefixed arms the constraints of the next search call)", who);
+    if (sp && sp->kind == GITMI_SEARCH_TRACE) return fail("%s: search->kind GITMI_SEARCH_TRACE is not a search (gitmi_generate_prefixed arms the per-token trace of the next search call)", who);
     if (e->ban_armed)
         return fail("%s: decoding constraints are armed for %d sentences (GITMI_SEARCH_CONSTRAIN): the seam's caller owns its logits and "
                     "applies its own -- disarm first (a GITMI_SEARCH_CONSTRAIN call with Q == 0)", who, e->ban_armed);
     e->ban_live = e->ban_seq_live = false;
+    bool traced = false;
+    if (sp) RCK(trace_check(e, who, sp, B, &traced));
+    e->trace_live = false;
     int minP = ld, maxP = ld;
     if (plen_host) {
         maxP = 1;
@@ -951,7 +1025,10 @@ static int search_begin_host(gitmi_engine* e, const char* who, const gitmi_searc
     e->img_identity = true;
     Request rq{};
     rq.Q = B; rq.minP = minP; rq.maxP = maxP; rq.prefixed = plen_host != nullptr; rq.sp = sp;
-    return search_begin_impl(e, rq, vocab, s);
+    RCK(search_begin_impl(e, rq, vocab, s));
+    // the seam search consumes an armed trace under the kind of the search it starts; gitmi_search_finish fills the buffers
+    if (traced) { e->trace_armed = 0; e->trace_live = true; }
+    return 0;
 }
 
 extern "C" int gitmi_search_begin(gitmi_engine* e, const gitmi_search* sp, int B, const int64_t* start_host, int P,
@@ -973,10 +1050,13 @@ extern "C" int gitmi_search_advance(gitmi_engine* e, const float* logits, void* 
     if (!logits) return fail("search_advance: null logits");
     const SearchState& st = e->ss;
     hipStream_t s = (hipStream_t)stream;
-    const int M = search_mtop(st), R = st.B * st.k;
+    const int M = head_mtop(e), R = st.B * st.k;
     StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, row_topm_slots(M)};
     if (st.sampled) RCK(sample_candidates(e, logits, st.V, R, e->ss_len, s, &cands, nullptr));
     else if (e->trie_search) RCK(trie_candidates(e, logits, st.V, e->ss_len, s, &cands));
+    else if (e->trace_live)
+        RCK(row_topm_traced(e, logits, st.V, st.V, st.ids[e->ss_cur], st.T, e->ss_len, st.k,
+                            st.kind == GITMI_SEARCH_AUTOREGRESSIVE ? 1 : 0, R, s, nullptr));
     else
         HIPCK(launch_row_topm(logits, st.V, st.V, st.ids[e->ss_cur], st.T, e->ss_len, e->plen_dev, st.k,
                               st.kind == GITMI_SEARCH_AUTOREGRESSIVE ? 1 : 0, rep_penalty_of(e), M, R, e->part_val,
@@ -1000,6 +1080,11 @@ extern "C" int gitmi_search_finish(gitmi_engine* e, int64_t* tokens_out, float* 
     const SearchState& st = e->ss;
     HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, (long long*)tokens_out, logprob_out, info_out, nullptr,
                                (hipStream_t)stream));
+    if (e->trace_live) {
+        RCK(trace_gather(e, (hipStream_t)stream));
+        RCK(trace_deliver(e, (hipStream_t)stream));
+        e->trace_live = false;          // delivered: a second finish returns the ids alone, and the context may be armed again
+    }
     return 0;
 }
 
@@ -1025,7 +1110,9 @@ GITMI_EXP_EXPORT int gitmi_debug_search_advance_lists(gitmi_engine* e, const flo
     if (nparts < 1 || nparts > 256) return fail("debug_search_advance_lists: nparts=%d outside [1,256]", nparts);
     if (slots != 1 && slots != 2 && slots != 4 && slots != 8 && slots != 16)
         return fail("debug_search_advance_lists: slots=%d is not one of 1, 2, 4, 8, 16", slots);
-    if (slots < search_mtop(st)) return fail("debug_search_advance_lists: slots=%d, but the step reads %d candidates per row", slots, search_mtop(st));
+    if (slots < head_mtop(e))
+        return fail("debug_search_advance_lists: slots=%d, but the step reads %d candidates per row (the search's, or the n alternatives "
+                    "of its trace)", slots, head_mtop(e));
     const StepCands cands{part_val, part_idx, (const float2*)part_lse, nparts, slots};
     return search_step_impl(e, cands, embed != 0, (hipStream_t)stream);
 }
@@ -1068,14 +1155,17 @@ static int generate_decode(gitmi_engine* e, const Request& rq, hipStream_t s, bo
     RCK(search_begin_impl(e, rq, c.vocab, s));
     const int Q = rq.Q, minP = rq.minP, maxP = rq.maxP, T = sp->max_steps, k = sp->beam_size, R = Q * k;
     const SearchState& st = e->ss;
-    const int M = search_mtop(st);
+    const int M = head_mtop(e);
     const int suppress = sp->kind != GITMI_SEARCH_GENERATOR ? 1 : 0;
     {
         SpanGuard phase(e, s, TAG_DECODE, 0);
         // position 0 is embedded here; every later position by the search step that appends its token
         RCK(embed_position(e, st.ids[0], T, 0, R, s));
         e->ss_len = 1;
-        StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, 1};
+        // Steps below minP only append given tokens and read no list.  A traced step still checks that its lists hold n
+        // alternatives, so the shape the head will give them stands from the first step on.
+        const bool chain = e->pol.skinny && !e->pol.f32;
+        StepCands cands{e->part_val, e->part_idx, e->part_lse, 1, e->trace_live ? (chain ? vocab_mtop_slots(M) : row_topm_slots(M)) : 1};
         while (e->ss_len < T) {
             const int cur_len = e->ss_len;
             SpanGuard step(e, s, TAG_STEP, 0);
@@ -1096,6 +1186,7 @@ static int generate_decode(gitmi_engine* e, const Request& rq, hipStream_t s, bo
         }
     }
     HIPCK(launch_search_finish(st, e->ss_cur, e->ss_len, rq.tokens, rq.logprob, rq.info, rq.sent, s));
+    if (e->trace_live) RCK(trace_gather(e, s));
     if (e->ragged)      // sentences over a rejected image: NaN log-probs, counted with the non-finite ones (info[3])
         HIPCK(launch_ragged_report(e->rg_meta, e->img_identity ? nullptr : e->img_of_dev, Q, keep_best(*sp), rq.logprob, rq.info,
                                    nullptr, s));
@@ -1122,7 +1213,8 @@ static GraphKey graph_key_of(const gitmi_engine* e, const Request& rq, int F_eff
     return {rq.B, rq.Q, F_eff, rq.minP, sp.kind, sp.beam_size, sp.per_node_beam_size, sp.max_steps, e->H, e->W,
             rq.prefixed ? 1 : 0, e->img_identity ? 1 : 0, e->pol.use_temb ? 1 : 0, resident ? 1 : 0,
             resident ? e->cur_Nimg : 0, resident && e->keyed ? 1 : 0, sp.length_penalty,
-            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed, e->ban_live ? (e->ban_seq_live ? 2 : 1) : 0};
+            sp.do_sample, sp.top_k, keep_best(sp), sp.top_p, sp.temperature, sp.repetition_penalty, sp.seed, e->ban_live ? (e->ban_seq_live ? 2 : 1) : 0,
+            e->trace_live ? 1 + e->trace_n : 0};
 }
 
 // Launches the graphs of one call on `x`: `enc` (the whole call, or encode + prefill; nullptr in a follow-up), then `dec`
@@ -1179,35 +1271,36 @@ static int generate_graphed(gitmi_engine* e, const Request& rq, hipStream_t s) {
     own.tokens = e->out_tokens; own.logprob = e->out_lp; own.info = e->out_info; own.sent = e->out_sent;
     const GraphKey key = graph_key_of(e, rq, F_eff);
     const CapturedGraph *enc = nullptr, *dec = nullptr;
+    gitmi_engine::GraphSet& gs = e->graphs[e->trace_live ? 1 : 0];
     if (resident) {
         RCK(images_ready(e, rq, x));        // the prefill, after gitmi_encode_frames alone: outside the graph
-        if (!e->follow_slot.valid || !(key == e->follow_slot.key)) {
-            e->follow_slot.valid = false;
-            RCK(e->graph_follow.capture(x, [&] { return generate_decode(e, own, x, false); }));
-            e->follow_slot = {key, true};
+        if (!gs.follow_slot.valid || !(key == gs.follow_slot.key)) {
+            gs.follow_slot.valid = false;
+            RCK(gs.graph_follow.capture(x, [&] { return generate_decode(e, own, x, false); }));
+            gs.follow_slot = {key, true};
         }
-        dec = &e->graph_follow;
+        dec = &gs.graph_follow;
     } else {
         // two graphs (encode + prefill | decode) whenever something has to happen between them: profiling events or the
         // enc_done record other contexts wait for
         const bool split = e->profile_mode == 2 || e->enc_after != nullptr || !e->enc_watchers.empty();
-        if (!e->full_slot.valid || !(key == e->full_slot.key) || split != e->graph_is_split) {
-            e->full_slot.valid = false;
-            e->graph_decode.reset();
+        if (!gs.full_slot.valid || !(key == gs.full_slot.key) || split != gs.graph_is_split) {
+            gs.full_slot.valid = false;
+            gs.graph_decode.reset();
             if (!split) {
-                RCK(e->graph_full.capture(x, [&] { return generate_body(e, own, x, false); }));
+                RCK(gs.graph_full.capture(x, [&] { return generate_body(e, own, x, false); }));
             } else {
-                RCK(e->graph_full.capture(x, [&] { return generate_encode(e, own, x); }));
-                RCK(e->graph_decode.capture(x, [&] { return generate_decode(e, own, x, false); }));
+                RCK(gs.graph_full.capture(x, [&] { return generate_encode(e, own, x); }));
+                RCK(gs.graph_decode.capture(x, [&] { return generate_decode(e, own, x, false); }));
             }
-            e->full_slot = {key, true}; e->graph_is_split = split;
+            gs.full_slot = {key, true}; gs.graph_is_split = split;
         } else {
             // a replay: the host-side state that enqueueing the encode and the prefill leaves behind
             set_resident(e, rq.B, F_eff);
             set_prefilled(e);
         }
-        enc = &e->graph_full;
-        if (split) dec = &e->graph_decode;
+        enc = &gs.graph_full;
+        if (split) dec = &gs.graph_decode;
     }
     RCK(replay(e, rq, x, enc, dec));
     // ---- results to the caller's buffers: device memory or PAGE-LOCKED host memory (hipMemcpyDefault: the results then arrive on
@@ -1229,14 +1322,18 @@ static int generate_graphed(gitmi_engine* e, const Request& rq, hipStream_t s) {
 // Eager launches for profiling spans and for long step budgets (which poll the finished count), else captured graphs.
 // constrained (constrain_check): the call consumes the armed decoding constraints -- here, behind the last step of the entry point
 // that can refuse the call, so that a refused call stays armed; the tables are live for exactly this call
-static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s, bool constrained) {
+// traced (trace_check): likewise the armed per-token trace; its output copies go to the caller's buffers behind the call
+static int generate_run(gitmi_engine* e, const Request& rq, hipStream_t s, bool constrained, bool traced) {
     const bool long_budget = rq.sp->max_steps - rq.minP > 32;
     const bool graph = e->pol.use_graph && !e->profiling && !long_budget;
     if (constrained) e->ban_armed = 0;
     e->ban_live = constrained;
     e->ban_seq_live = constrained && e->ban_seq_armed;
-    const int rc = settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
-    e->ban_live = e->ban_seq_live = false;
+    if (traced) e->trace_armed = 0;
+    e->trace_live = traced;
+    int rc = settle_residency(e, rq, graph ? generate_graphed(e, rq, s) : generate_body(e, rq, s, long_budget && !e->profiling));
+    if (rc == 0 && traced) rc = trace_deliver(e, s);
+    e->ban_live = e->ban_seq_live = e->trace_live = false;
     return rc;
 }
 
@@ -1255,6 +1352,7 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp && sp->kind == GITMI_SEARCH_RECALL) return fail("generate: GITMI_SEARCH_RECALL recalls kept images: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_FEATURES) return fail("generate: GITMI_SEARCH_FEATURES installs given feature rows: call gitmi_generate_prefixed");
     if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN) return fail("generate: GITMI_SEARCH_CONSTRAIN arms decoding constraints: call gitmi_generate_prefixed");
+    if (sp && sp->kind == GITMI_SEARCH_TRACE) return fail("generate: GITMI_SEARCH_TRACE arms the per-token trace: call gitmi_generate_prefixed");
     // follow-up call over the resident images (F is ignored); asked first: without images there is nothing to size buffers by
     if (!frames) RCK(check_resident(e, "generate", B));
     if (!sp || !tokens_out || !logprob_out || !info_out) return fail("generate: null argument");
@@ -1264,12 +1362,14 @@ extern "C" int gitmi_generate(gitmi_engine* e, const float* const* frames, int F
     if (sp->max_steps < P || sp->max_steps > c.max_text_len) return fail("generate: max_steps %d outside [P,%d]", sp->max_steps, c.max_text_len);
     bool constrained = false;
     RCK(constrain_check(e, "generate", sp, B, &constrained));
+    bool traced = false;
+    RCK(trace_check(e, "generate", sp, B, &traced));
     hipStream_t s = (hipStream_t)stream;
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     // start tokens [B, P] on device (shared prefix, or [CLS]) -- filled by a kernel, no host copy
     RCK(fill_uniform_sentences(e, B, (const long long*)prefix, P, s));
     const Request rq{frames, F, B, B, P, P, false, sp, (long long*)tokens_out, logprob_out, info_out, e->out_sent};
-    return generate_run(e, rq, s, constrained);
+    return generate_run(e, rq, s, constrained, traced);
 }
 
 // ---- caption scoring (GITMI_SEARCH_SCORE) -------------------------------------------------------------------------
@@ -1911,6 +2011,77 @@ static int constrain_check(const gitmi_engine* e, const char* who, const gitmi_s
     return 0;
 }
 
+// ---- per-token trace (GITMI_SEARCH_TRACE, include/gitmi.h) -------------------------------------------------------------------
+// Arms the trace of the NEXT search call of this context: its shape (Q sentences x nout sequences, T positions, n alternatives)
+// and the caller's output buffers.  Every check comes before the first change, so a refused call leaves the arming as it was.
+static int trace_call(gitmi_engine* e, const float* const* frames, const int64_t* prefixes, const int32_t* prefix_len_host,
+                      const int32_t* image_of_host, int Q, const gitmi_search* sp, int64_t* tokens_out, float* logprob_out,
+                      int32_t* info_out, hipStream_t s) {
+    const gitmi_config& c = e->cfg;
+    if (Q == 0) {
+        e->trace_armed = 0;
+        return info_out ? memory_info({0, 0, 0, 0}, info_out, s) : 0;
+    }
+    if (e->trace_live)
+        return fail("trace: a traced seam search is in progress (gitmi_search_begin without gitmi_search_finish): its log is carved by "
+                    "the arming it consumed -- finish it, or begin another search, before arming again");
+    if (frames) return fail("trace: frames != NULL: the trace belongs to the next search call, which brings its own images");
+    if (prefixes) return fail("trace: prefixes != NULL: the call to be traced brings its own");
+    if (prefix_len_host) return fail("trace: prefix_len_host != NULL: the call to be traced brings its own");
+    if (image_of_host) return fail("trace: image_of != NULL: the call to be traced brings its own");
+    if (Q < 1 || Q > c.max_batch) return fail("trace: Q=%d sentences outside [0,%d] (max_batch)", Q, c.max_batch);
+    if (sp->num_keep_best < 0 || sp->num_keep_best > SS_NHMAX)
+        return fail("trace: search->num_keep_best %d outside [0,%d]", sp->num_keep_best, SS_NHMAX);
+    if (sp->max_steps < 1 || sp->max_steps > c.max_text_len)
+        return fail("trace: search->max_steps %d outside [1,%d] (max_text_len)", sp->max_steps, c.max_text_len);
+    const int n = sp->reserved_, nout = keep_best(*sp), T = sp->max_steps;
+    if (n < 0 || n > TRACE_NMAX) return fail("trace: search->reserved_ = %d alternatives outside [0,%d]", n, TRACE_NMAX);
+    if (n >= c.vocab) return fail("trace: search->reserved_ = %d alternatives, the vocabulary has %d tokens", n, c.vocab);
+    if (!logprob_out) return fail("trace: logprob_out is NULL (fp32 [Q * nout][T][1 + n])");
+    if (n > 0 && !tokens_out) return fail("trace: tokens_out is NULL with search->reserved_ = %d alternatives (int64 [Q * nout][T][n])", n);
+    const TraceLayout L = trace_layout(e, Q, nout, T, n);
+    if (L.total > e->trace_bytes) {
+        // captured traced graphs hold pointers into the old allocation, a traced search in flight writes it
+        HIPCK(hipDeviceSynchronize());
+        char* buf = nullptr;
+        if (hipMalloc((void**)&buf, L.total) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("trace: out of device memory for the log of the trace (%zu bytes)", L.total);
+        }
+        for (CapturedGraph* g : {&e->graphs[1].graph_full, &e->graphs[1].graph_decode, &e->graphs[1].graph_follow}) g->reset();
+        e->graphs[1].full_slot.valid = e->graphs[1].follow_slot.valid = false;
+        hipFree(e->trace_buf);
+        e->trace_buf = buf; e->trace_bytes = L.total;
+    }
+    if (info_out) RCK(memory_info({Q, nout, T, n}, info_out, s));       // (waits for the stream; NULL: the host does not wait)
+    e->trace_armed = e->trace_Q = Q; e->trace_nout = nout; e->trace_T = T; e->trace_n = n;
+    e->trace_user_lp = logprob_out; e->trace_user_tok = (long long*)tokens_out;
+    return 0;
+}
+// A search call of Q sentences meets the arming: disarmed -> it runs plain; armed for its shape -> it will run traced (generate_run
+// or the seam's begin consumes the arming); anything else is refused and stays armed.  Changes nothing.
+static int trace_check(const gitmi_engine* e, const char* who, const gitmi_search* sp, int Q, bool* traced) {
+    *traced = false;
+    if (!e->trace_armed) return 0;
+    if (sp->kind == GITMI_SEARCH_TRIE)
+        return fail("%s: GITMI_SEARCH_TRIE while the per-token trace is armed (GITMI_SEARCH_TRACE): traces of the trie search are not "
+                    "implemented -- disarm first (a GITMI_SEARCH_TRACE call with Q == 0)", who);
+    if (sp->do_sample && e->trace_n > 0)
+        return fail("%s: do_sample while the per-token trace is armed with %d alternatives (GITMI_SEARCH_TRACE): alternatives under "
+                    "sampling are not implemented -- arm with search->reserved_ = 0, or disarm with Q == 0", who, e->trace_n);
+    if (Q != e->trace_armed)
+        return fail("%s: the per-token trace is armed for %d sentences, this call has %d (it stays armed: run the call it was armed "
+                    "for, arm again, or disarm with Q == 0)", who, e->trace_armed, Q);
+    const int nout = sp->kind == GITMI_SEARCH_GENERATOR ? keep_best(*sp) : 1;
+    if (nout != e->trace_nout)
+        return fail("%s: the per-token trace is armed for %d sequences per sentence (num_keep_best), this call returns %d (it stays "
+                    "armed)", who, e->trace_nout, nout);
+    if (sp->max_steps != e->trace_T)
+        return fail("%s: the per-token trace is armed for max_steps %d, this call has %d (it stays armed)", who, e->trace_T, sp->max_steps);
+    *traced = true;
+    return 0;
+}
+
 // Q sentences with their own prefixes over B encoded images (batched VQA: the questions of one image share its K/V)
 extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B, const int64_t* prefixes,
                                        int ld_prefix, const int32_t* prefix_len_host, const int32_t* image_of_host, int Q,
@@ -1929,6 +2100,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     if (sp && sp->kind == GITMI_SEARCH_CONSTRAIN)
         return constrain_call(e, frames, (const unsigned int*)prefixes, ld_prefix, prefix_len_host, image_of_host, Q, info_out, sent_out,
                               sp->reserved_, s);
+    if (sp && sp->kind == GITMI_SEARCH_TRACE)
+        return trace_call(e, frames, prefixes, prefix_len_host, image_of_host, Q, sp, tokens_out, logprob_out, info_out, s);
     if (sp && sp->kind == GITMI_SEARCH_FEATURES)
         return features_call(e, frames, F, B, prefixes, sp->reserved_, ld_prefix, prefix_len_host, image_of_host, Q, info_out, s);
     if (sp && (sp->kind == GITMI_SEARCH_SCORE || sp->kind == GITMI_SEARCH_ATTEND || sp->kind == GITMI_SEARCH_TREE_SCORE)) {
@@ -1973,6 +2146,8 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
         return fail("generate_prefixed: max_steps %d outside [%d,%d]", sp->max_steps, span.maxP, c.max_text_len);
     bool constrained = false;
     RCK(constrain_check(e, "generate_prefixed", sp, Q, &constrained));
+    bool traced = false;
+    RCK(trace_check(e, "generate_prefixed", sp, Q, &traced));
     RCK(upload_sentences(e, e->plen_dev, e->img_of_dev, s));
     HIPCK(hipMemcpy2D(e->start_dev, (size_t)c.max_text_len * sizeof(long long), prefixes, (size_t)ld_prefix * sizeof(long long),
                       (size_t)span.maxP * sizeof(long long), (size_t)Q, hipMemcpyDeviceToDevice));
@@ -1980,7 +2155,7 @@ extern "C" int gitmi_generate_prefixed(gitmi_engine* e, const float* const* fram
     if (frames) RCK(ragged_prepare(e, frames, F, B, s));
     const Request rq{frames, F, B, Q, span.minP, span.maxP, true, sp, (long long*)tokens_out, logprob_out, info_out,
                      sent_out ? sent_out : e->out_sent};
-    return generate_run(e, rq, s, constrained);
+    return generate_run(e, rq, s, constrained, traced);
 }
 
 // ---- profiling --------------------------------------------------------------------------

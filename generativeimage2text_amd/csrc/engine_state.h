@@ -60,11 +60,12 @@ struct GraphKey {
     // 0 plain, 1 the decode part runs under armed constraints, 2 under constraints with banned sequences (one more launch per
     // step); their VALUES live in the engine's tables, not in the key
     int constrained;
+    int trace;          // 0, or 1 + n: the decode part logs its picks (GITMI_SEARCH_TRACE) and the head lists hold max(M, n) candidates
     // resident: a follow-up call (frames == NULL) -- the decode part alone, over the images the engine holds: Nimg rows per
     // image block, with (keyed) or without per-image key counts; both 0 in a call with frames, which decides them itself
     auto fields() const {
         return std::tie(B, Q, F, P, kind, k, pn, T, H, W, prefixed, ident, temb, resident, Nimg, keyed, lp, smp, top_k, nh, top_p, temp,
-                        rp, seed, constrained);
+                        rp, seed, constrained, trace);
     }
     bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
@@ -192,6 +193,15 @@ struct gitmi_engine {
     hipEvent_t ban_staged = nullptr;    // the last copy out of ban_stage
     int ban_armed = 0;
     bool ban_live = false;
+    // per-token trace (GITMI_SEARCH_TRACE, engine.hip trace_call): trace_armed = the sentence count the trace is armed for (0:
+    // disarmed) with the nout / T / n and the caller's buffers of the arming; the next search call consumes them.  trace_live: the
+    // search in progress is traced (the fields then describe it).  trace_buf: one device allocation, made by the first arming call
+    // and grown by a larger one (captured traced graphs go with it), carved by trace_args / trace_out_*.
+    int trace_armed = 0, trace_nout = 0, trace_T = 0, trace_n = 0;
+    int trace_Q = 0;                    // the sentence count of the arming, kept when a call consumes it (the carving depends on it)
+    float* trace_user_lp = nullptr; long long* trace_user_tok = nullptr;
+    bool trace_live = false;
+    char* trace_buf = nullptr; size_t trace_bytes = 0;
     // banned token sequences (the extension of GITMI_SEARCH_CONSTRAIN selected by search->reserved_): the device table ban_seq =
     // list_of [max_batch] | list_off [max_batch + 1] | seq_off [BAN_SEQ_MAX_SEQS + 1] | tok [BAN_SEQ_MAX_TOKS] at fixed offsets, its
     // page-locked staging twin (guarded by ban_staged, like ban_stage) and the per-row sets ban_row_words (uint32 [max_batch x
@@ -269,9 +279,12 @@ struct gitmi_engine {
     // between the two (graph_is_split), graph_full (encode + prefill) and graph_decode; both belong to full_slot.  A
     // follow-up call replays graph_follow (the decode part alone, GraphKey::resident) of follow_slot, so that full and
     // follow-up calls with unchanged arguments alternate without re-capturing either
-    CapturedGraph graph_full, graph_decode, graph_follow;
-    GraphSlot full_slot, follow_slot;
-    bool graph_is_split = false;
+    // graphs[1]: the same for traced calls (GITMI_SEARCH_TRACE), so that plain and traced calls alternate without re-capturing
+    struct GraphSet {
+        CapturedGraph graph_full, graph_decode, graph_follow;
+        GraphSlot full_slot, follow_slot;
+        bool graph_is_split = false;
+    } graphs[2];
     std::vector<float*> frame_stage;   // engine-owned copies of the input frames (graph inputs)
     long long* out_tokens = nullptr;   // graph outputs, copied to the caller's buffers after the launch
     float* out_lp = nullptr;

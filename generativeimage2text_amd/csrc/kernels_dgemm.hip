@@ -749,14 +749,14 @@ int vocab_parts(int V, int cols_per_wg) { return (V + cols_per_wg - 1) / cols_pe
 int vocab_mtop_slots(int mtop) { return mtop <= 1 ? 1 : mtop <= 2 ? 2 : mtop <= 4 ? 4 : mtop <= 8 ? 8 : 16; }
 
 template <int MTOP>
-static hipError_t launch_vocab_m(const VocabArgs& g_in, hipStream_t s) {
+static hipError_t launch_vocab_m(const VocabArgs& g_in, hipStream_t s, bool generic) {
     VocabArgs g = g_in;
     g.nblk = vocab_parts(g.N, 16 * VOC_NS);
     int nwg = g.max_wgs > 0 && g.max_wgs < g.nblk ? g.max_wgs : g.nblk;              // each workgroup walks nblk / nwg column blocks
     if ((g.nblk + nwg - 1) / nwg > VOC_MAX_BLOCKS) nwg = (g.nblk + VOC_MAX_BLOCKS - 1) / VOC_MAX_BLOCKS;
     const bool pen = g.ids != nullptr && g.rep_penalty != 0.f && g.rep_penalty != 1.f;
     const bool ban = g.ids != nullptr && g.ban.set_of != nullptr;     // a constrained call: the generic form, like the penalty
-    const bool fast = (g.K >> 5) == 4 * VKS && !g.logits_out && !pen && !ban;
+    const bool fast = (g.K >> 5) == 4 * VKS && !g.logits_out && !pen && !ban && !generic;
     if (ban) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GENERIC, 0, true>), dim3(nwg), dim3(256), 0, s, g);
     else if (!fast) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GENERIC>), dim3(nwg), dim3(256), 0, s, g);
     else if (g.M <= 64) hipLaunchKernelGGL((vocab_topm_kernel<MTOP, VOC_GREEDY>), dim3(nwg), dim3(256), 0, s, g);
@@ -766,16 +766,16 @@ static hipError_t launch_vocab_m(const VocabArgs& g_in, hipStream_t s) {
 
 // 128 columns per column block (cols_per_wg, kept in the argument list as a check); bias / colsum / the packed weight rows
 // must be readable up to the next multiple of 128; activations up to the next multiple of 64 rows
-hipError_t launch_vocab_topm(const VocabArgs& g, int mtop, hipStream_t s) {
+hipError_t launch_vocab_topm(const VocabArgs& g, int mtop, hipStream_t s, bool generic) {
     if (g.M <= 0) return hipSuccess;
     if (g.K % 32 != 0 || (g.K >> 5) > 4 * VKS || g.cols_per_wg != 16 * VOC_NS || mtop < 1 || mtop > 16)
         return hipErrorInvalidValue;
     if (g.stats_in && (!g.colsum || g.strips_in > 4 * STRIP_SLOTS)) return hipErrorInvalidValue;
-    if (mtop <= 1) return launch_vocab_m<1>(g, s);
-    if (mtop <= 2) return launch_vocab_m<2>(g, s);
-    if (mtop <= 4) return launch_vocab_m<4>(g, s);
-    if (mtop <= 8) return launch_vocab_m<8>(g, s);
-    return launch_vocab_m<16>(g, s);
+    if (mtop <= 1) return launch_vocab_m<1>(g, s, generic);
+    if (mtop <= 2) return launch_vocab_m<2>(g, s, generic);
+    if (mtop <= 4) return launch_vocab_m<4>(g, s, generic);
+    if (mtop <= 8) return launch_vocab_m<8>(g, s, generic);
+    return launch_vocab_m<16>(g, s, generic);
 }
 
 }  // namespace gitmi

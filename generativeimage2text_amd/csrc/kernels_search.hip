@@ -15,6 +15,8 @@
 //                    AUTOREGRESSIVE: decoder.py:257-298 (first step), 313-417
 //                    GENERATOR     : decoder.py:1169-1232 + BeamHypotheses 1292-1341 (n_hyp = num_keep_best <= SS_NHMAX)
 //   finish       : select outputs.
+//   trace        : (GITMI_SEARCH_TRACE) a traced instantiation of search_step logs every pick's log-prob and its row's n best;
+//                  trace_gather, beside finish, reads the records of the returned sequences back through kv_src.
 //
 // Sentences may carry their own prefix (VQA questions of different lengths in one batch; the reference runs them
 // one at a time, decoder.py:984-989): while cur_len < plen[b] the step simply appends the given token.  All
@@ -541,9 +543,13 @@ __device__ __forceinline__ int ids_at(const SearchState& st, int buf, int r, int
 
 // grid = B (one workgroup per sentence), block = 256.  cur_len = tokens currently in ids (before appending).
 // SLOTS = entries per partial list (compile time: the per-lane lists live in registers and are popped by static shifts)
-template <typename TOut, int SLOTS>
-__global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int src, int cur_len, StepCands in,
-                                                          EmbedArgs em) {
+// TRACE (GITMI_SEARCH_TRACE; an instantiation of its own, the plain one keeps its code under if constexpr): phase A merges max(M, tr.n) candidates,
+// phase B carries every pick's own c_val and the beam it was picked from, phase C stores the records of the new rows at
+// log[cur_len][row] -- addresses from the step, the row index and tr.n / tr.rows alone, which the host has checked against the
+// log's size.
+template <typename TOut, int SLOTS, bool TRACE>
+__device__ __forceinline__ void search_step_body(const SearchState& st, int src, int cur_len, const StepCands& in,
+                                                 const EmbedArgs& em, const TraceArgs& tr) {
     __shared__ float c_val[SS_KMAX][SS_CMAX];  // merged top-M log-probabilities per beam row
     __shared__ int c_idx[SS_KMAX][SS_CMAX];
     __shared__ int sel_src[SS_KMAX], sel_word[SS_KMAX];
@@ -559,6 +565,9 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
     __shared__ double s_hscore[SS_NHMAX];
     __shared__ int s_hseq[SS_NHMAX];
     __shared__ float s_part[8];
+    // TRACE: log-prob and beam (-1: none, a given or padding token) of the k picks and of the hypotheses added this step
+    __shared__ float sel_lp[TRACE ? SS_KMAX : 1], s_add_lp[TRACE ? SS_CMAX * 2 : 1];
+    __shared__ int sel_par[TRACE ? SS_KMAX : 1], s_add_par[TRACE ? SS_CMAX * 2 : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
@@ -568,6 +577,8 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
     const bool forced = cur_len < P;                       // still inside this sentence's prefix
     const bool first = cur_len == P;                       // first search step of this sentence
     const int M = st.kind == 0 ? (first ? k : pn) : (st.sampled ? pn : pn * k);   // candidates needed per row
+    int MA = M;                                            // candidates merged per row
+    if constexpr (TRACE) MA = tr.n > M ? tr.n : M;
 
     if (tid == 0) s_nadd = 0;
     {   // staging loads: one thread per value, all in flight together with the candidate lists of phase A
@@ -601,7 +612,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
             const int last = ids_at(st, src, r, cur_len - 1);
             if (st.kind == 0 && !first && last == st.eos) {
                 // one-hot distribution on EOS (decoder.py:300-310, 347-351): log-prob 0, everything else -inf
-                if (lane < M) {
+                if (lane < MA) {
                     c_val[j][lane] = lane == 0 ? 0.f : -INFINITY;
                     c_idx[j][lane] = lane == 0 ? st.eos : (lane - 1 < st.eos ? lane - 1 : lane);
                 }
@@ -630,7 +641,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
             const float bm = wave_max(pm);
             const float part = wave_sum(pm == -INFINITY ? 0.f : ps * __expf(pm - bm));
             const float lse = bm + logf(part);
-            for (int round = 0; round < M; ++round) {
+            for (int round = 0; round < MA; ++round) {
                 float v = hv[0][0];
                 int id = hi[0][0], who = 0;
 #pragma unroll
@@ -667,6 +678,8 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
         if (forced) {
             const int word = (int)st.start[(size_t)b * st.ld_start + cur_len];
             for (int j = 0; j < k; ++j) { sel_src[j] = b * k + j; sel_word[j] = word; sel_score[j] = st.score[src][b * k + j]; }
+            if constexpr (TRACE)
+                for (int j = 0; j < k; ++j) { sel_lp[j] = 0.f; sel_par[j] = -1; }
         } else if (st.kind == 0) {
             // ---- AutoRegressiveBeamSearch -------------------------------------------------------------------
             if (!first && s_stop == 0) {
@@ -679,6 +692,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
             if (first) {
                 for (int j = 0; j < k; ++j) {
                     sel_src[j] = b * k; sel_word[j] = c_idx[0][j]; sel_score[j] = c_val[0][j];
+                    if constexpr (TRACE) { sel_lp[j] = c_val[0][j]; sel_par[j] = 0; }
                 }
                 // decoder.py:279-291: every first prediction is EOS (k == 1) -> early return
                 if (k == 1) st.early[b] = c_idx[0][0] == st.eos ? 1 : 0;
@@ -694,6 +708,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
                     }
                     used |= 1ull << bc;
                     sel_src[j] = b * k + bc / pn; sel_word[j] = c_idx[bc / pn][bc % pn]; sel_score[j] = best;
+                    if constexpr (TRACE) { sel_lp[j] = c_val[bc / pn][bc % pn]; sel_par[j] = bc / pn; }
                 }
             }
         } else {
@@ -704,6 +719,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
             int headp[SS_KMAX];
             for (int j = 0; j < k; ++j) headp[j] = 0;
             float n_score[SS_CMAX * 2]; int n_beam[SS_CMAX * 2], n_word[SS_CMAX * 2];
+            float n_lp[TRACE ? SS_CMAX * 2 : 1]; int n_par[TRACE ? SS_CMAX * 2 : 1];      // the candidate's own c_val and its row's beam
             float n_max = -INFINITY;
             for (int c = 0; c < ncand; ++c) {
                 if (st.sampled) {
@@ -713,6 +729,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
                     // (beam_indices.repeat(batch, per_node_beam_size), decoder.py:1161-1164).  Reproduced as is.
                     const int j = c / pn, d = c % pn;
                     n_score[c] = c_val[j][d] + s_score[j]; n_beam[c] = c % k; n_word[c] = c_idx[j][d];
+                    if constexpr (TRACE) { n_lp[c] = c_val[j][d]; n_par[c] = j; }
                 } else {
                     float best = 0.f; int bj = -1; long long bflat = 0;
                     for (int j = 0; j < k; ++j) {
@@ -722,6 +739,7 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
                         if (bj < 0 || v > best || (v == best && flat < bflat)) { best = v; bj = j; bflat = flat; }
                     }
                     n_score[c] = best; n_beam[c] = bj; n_word[c] = c_idx[bj][headp[bj]];
+                    if constexpr (TRACE) { n_lp[c] = c_val[bj][headp[bj]]; n_par[c] = bj; }
                     headp[bj]++;
                 }
                 n_max = fmaxf(n_max, n_score[c]);
@@ -769,10 +787,12 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
                             h_len[slot] = cur_len;
                             h_seq[slot] = hyp_cnt++;
                             s_add_slot[s_nadd] = slot; s_add_row[s_nadd] = b * k + n_beam[c];
+                            if constexpr (TRACE) { s_add_lp[s_nadd] = n_lp[c]; s_add_par[s_nadd] = n_par[c]; }
                             ++s_nadd;
                         }
                     } else {
                         sel_score[nb] = n_score[c]; sel_word[nb] = word; sel_src[nb] = b * k + n_beam[c];
+                        if constexpr (TRACE) { sel_lp[nb] = n_lp[c]; sel_par[nb] = n_par[c]; }
                         ++nb;
                     }
                 }
@@ -786,6 +806,8 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
                 // stands for its own batch-1 reference call, whose row 0 is the sentence's own first row.
                 const int pad_row = st.prefixed ? b * k : 0;
                 for (int j = 0; j < k; ++j) { sel_score[j] = 0.f; sel_word[j] = st.eos; sel_src[j] = pad_row; }
+                if constexpr (TRACE)
+                    for (int j = 0; j < k; ++j) { sel_lp[j] = 0.f; sel_par[j] = -1; }
             }
         }
         if (b == 0) st.info[2] += 1;
@@ -796,6 +818,19 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
     for (int a = 0; a < s_nadd; ++a) {           // in the order of the adds: a slot refilled twice in one step keeps the later history
         int* ht = st.hyp_tok + ((size_t)b * st.nh + s_add_slot[a]) * T;
         for (int s = tid; s < cur_len; s += 256) ht[s] = ids_at(st, src, s_add_row[a], s);
+        if constexpr (TRACE) {
+            // where hyp_tok is copied: the K/V rows of the history name its records; the finishing candidate's record stays with the slot
+            const size_t hs = (size_t)b * st.nh + s_add_slot[a];
+            for (int s = tid; s < cur_len; s += 256) tr.hyp_src[hs * T + s] = st.kv_src[src][(size_t)s_add_row[a] * T + s];
+            if (tid <= tr.n) {
+                const int par = s_add_par[a];
+                tr.fin_lp[hs * (1 + tr.n) + tid] = tid == 0 ? s_add_lp[a] : par >= 0 ? c_val[par][tid - 1] : 0.f;
+                if (tid > 0) tr.fin_tok[hs * tr.n + tid - 1] = par >= 0 ? c_idx[par][tid - 1] : -1;
+            }
+            // A slot refilled twice in one step: the same thread stores the same element again, in the order of the adds.  Only the
+            // sampling branch can get there (its candidates are in draw order; the greedy-beam branch's arrive in descending order, so
+            // a second add never beats the first into the same slot), and no test reaches it.
+        }
     }
     // all k rows in one sweep (one round trip, not k: the compiler cannot move row j + 1's loads above row j's stores)
     for (int idx = tid; idx < k * cur_len; idx += 256) {
@@ -809,6 +844,14 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
         st.ids[dst][(size_t)r * T + cur_len] = sel_word[tid];
         st.kv_src[dst][(size_t)r * T + cur_len] = r;
         st.score[dst][r] = sel_score[tid];
+    }
+    if constexpr (TRACE) {
+        if (tid < k * (1 + tr.n)) {
+            const int j = tid / (1 + tr.n), i = tid - j * (1 + tr.n), par = sel_par[j];
+            const size_t rec = (size_t)cur_len * tr.rows + (size_t)(b * k + j);
+            tr.log_lp[rec * (1 + tr.n) + i] = i == 0 ? sel_lp[j] : par >= 0 ? c_val[par][i - 1] : 0.f;
+            if (i > 0) tr.log_tok[rec * tr.n + i - 1] = par >= 0 ? c_idx[par][i - 1] : -1;
+        }
     }
 
     // ---- phase D: embedding + LayerNorm of the chosen tokens = input of the next decode step -----------------------
@@ -921,6 +964,16 @@ __global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int sr
     }
 }
 
+template <typename TOut, int SLOTS>
+__global__ __launch_bounds__(256) void search_step_kernel(SearchState st, int src, int cur_len, StepCands in, EmbedArgs em) {
+    search_step_body<TOut, SLOTS, false>(st, src, cur_len, in, em, TraceArgs{});
+}
+template <typename TOut, int SLOTS>
+__global__ __launch_bounds__(256) void search_step_trace_kernel(SearchState st, int src, int cur_len, StepCands in, EmbedArgs em,
+                                                                TraceArgs tr) {
+    search_step_body<TOut, SLOTS, true>(st, src, cur_len, in, em, tr);
+}
+
 // ---------------------------------------------------------------------------------------
 __global__ void search_init_kernel(SearchState st) {
     const int R = st.B * st.k;
@@ -944,6 +997,17 @@ __global__ void search_init_kernel(SearchState st) {
         // single bookkeeping thread otherwise evaluates several double-precision pow() per step
         for (int len = threadIdx.x; len <= st.T; len += blockDim.x) st.len_norm[len] = length_norm(len, st.length_penalty);
     }
+}
+
+// the next hypothesis of a sentence in output order (decoder.py:1264-1290): the best score not yet taken, equal scores in list
+// order; -1 when the list holds no more
+__device__ __forceinline__ int hyp_next(const double* h_score, const int* h_seq, int have, unsigned taken) {
+    int best = -1;
+    for (int j = 0; j < have; ++j) {
+        if ((taken >> j) & 1u) continue;
+        if (best < 0 || h_score[j] > h_score[best] || (h_score[j] == h_score[best] && h_seq[j] < h_seq[best])) best = j;
+    }
+    return best;
 }
 
 // AUTOREGRESSIVE: best beam (index 0), log-prob / num_valid (decoder.py:429-438)
@@ -984,11 +1048,7 @@ __global__ void search_finish_kernel(SearchState st, int cur, int cur_len, long 
             const int* h_seq = st.hyp_seq + (size_t)b * nh;
             unsigned taken = 0u;
             for (int i = 0; i < nh; ++i) {
-                int best = -1;
-                for (int j = 0; j < have; ++j) {
-                    if ((taken >> j) & 1u) continue;
-                    if (best < 0 || h_score[j] > h_score[best] || (h_score[j] == h_score[best] && h_seq[j] < h_seq[best])) best = j;
-                }
+                const int best = hyp_next(h_score, h_seq, have, taken);
                 const int n = best >= 0 ? st.hyp_len[(size_t)b * nh + best] : 0;
                 const int* ht = st.hyp_tok + ((size_t)b * nh + (best >= 0 ? best : 0)) * st.T;
                 for (int s = 0; s < st.T; ++s) out[(size_t)i * st.T + s] = s < n ? ht[s] : st.eos;
@@ -1013,6 +1073,57 @@ __global__ void search_finish_kernel(SearchState st, int cur, int cur_len, long 
         int bad = 0;
         for (int i = 0; i < st.B * nout; ++i) bad += !isfinite(logprob_out[i]);
         info_out[3] = bad;
+    }
+}
+
+// The trace of the returned sequences (GITMI_SEARCH_TRACE), in search_finish_kernel's output order: grid = B * nout workgroups,
+// sequence o = b * nout + i, a thread per position.  Every element of out_lp [o][T][1 + n] and out_tok [o][T][n] is written.
+// Record indices come from kv_src / hyp_src, which hold row indices < B * k written by this search; they are clamped into the log.
+__global__ __launch_bounds__(256) void search_trace_gather_kernel(SearchState st, int cur, int cur_len, TraceArgs tr,
+                                                                  float* __restrict__ out_lp, long long* __restrict__ out_tok) {
+    const int nout = st.kind == 0 ? 1 : st.nh;
+    const int b = blockIdx.x / nout, i = blockIdx.x - b * nout;
+    const int T = st.T, n = tr.n, P = st.plen[b];
+    int first = P, end = 0, slot = -1;            // records of the log: positions [first, end); slot >= 0: its record at position end
+    const int* src_row = nullptr;
+    if (st.kind == 0) {
+        const int stop = st.stop[b];
+        end = stop > 0 ? stop : cur_len;
+        src_row = st.kv_src[cur] + (size_t)b * st.k * T;
+    } else {
+        const double* h_score = st.hyp_score + (size_t)b * st.nh;
+        const int* h_seq = st.hyp_seq + (size_t)b * st.nh;
+        const int have = st.hyp_n[b];
+        unsigned taken = 0u;
+        for (int q = 0; q <= i; ++q) {
+            slot = hyp_next(h_score, h_seq, have, taken);
+            if (slot >= 0) taken |= 1u << slot;
+        }
+        if (slot >= 0) {
+            end = st.hyp_len[(size_t)b * st.nh + slot];
+            src_row = tr.hyp_src + ((size_t)b * st.nh + slot) * T;
+        }
+    }
+    const int R = st.B * st.k;
+    for (int s = threadIdx.x; s < T; s += blockDim.x) {
+        const float* lp = nullptr;
+        const int* tok = nullptr;
+        if (s >= first && s < end) {
+            int r = src_row[s];
+            r = r < 0 ? 0 : (r >= R ? R - 1 : r);
+            const size_t rec = (size_t)s * tr.rows + r;
+            lp = tr.log_lp + rec * (1 + n); tok = tr.log_tok + rec * n;
+        } else if (slot >= 0 && s == end && s >= first) {
+            const size_t hs = (size_t)b * st.nh + slot;
+            lp = tr.fin_lp + hs * (1 + n); tok = tr.fin_tok + hs * n;
+        }
+        float* o_lp = out_lp + ((size_t)blockIdx.x * T + s) * (1 + n);
+        o_lp[0] = lp ? lp[0] : 0.f;
+        for (int j = 0; j < n; ++j) {
+            const float v = lp ? lp[1 + j] : 0.f;
+            o_lp[1 + j] = v;
+            out_tok[((size_t)blockIdx.x * T + s) * n + j] = (lp && v != -INFINITY) ? (long long)tok[j] : -1ll;
+        }
     }
 }
 
@@ -1127,10 +1238,34 @@ hipError_t launch_trie_select(const float* logits, int ldl, int V, const int* id
 }
 
 hipError_t launch_search_step(const SearchState& st, int src, int cur_len, const StepCands& in, const EmbedArgs& em,
-                              bool t_is_f32, hipStream_t s) {
+                              bool t_is_f32, hipStream_t s, const TraceArgs* tr) {
     if (st.k > SS_KMAX || in.slots < 1 || in.slots > SS_CMAX || in.nparts < 1 || in.nparts > 256) return hipErrorInvalidValue;
     if (st.k * st.pn > SS_CMAX) return hipErrorInvalidValue;
     if (em.words && (em.D > 1024 || (em.D & 3))) return hipErrorInvalidValue;
+    const bool traced = tr && tr->log_lp;
+    if (traced) {
+        if (tr->n < 0 || tr->n > TRACE_NMAX || tr->n > in.slots || tr->rows < st.B * st.k || cur_len < 0 || cur_len >= st.T)
+            return hipErrorInvalidValue;
+        if (tr->n > 0 && !tr->log_tok) return hipErrorInvalidValue;
+        if (st.kind != 0 && (!tr->hyp_src || !tr->fin_lp || (tr->n > 0 && !tr->fin_tok))) return hipErrorInvalidValue;
+    }
+#define GITMI_SSTEP_T(SL)                                                                                               \
+    do {                                                                                                                \
+        if (t_is_f32) hipLaunchKernelGGL((search_step_trace_kernel<float, SL>), dim3(st.B), dim3(256), 0, s, st, src, cur_len, in, em, *tr); \
+        else hipLaunchKernelGGL((search_step_trace_kernel<bf16_t, SL>), dim3(st.B), dim3(256), 0, s, st, src, cur_len, in, em, *tr);          \
+    } while (0)
+    if (traced) {
+        switch (in.slots) {
+            case 1: GITMI_SSTEP_T(1); break;
+            case 2: GITMI_SSTEP_T(2); break;
+            case 4: GITMI_SSTEP_T(4); break;
+            case 8: GITMI_SSTEP_T(8); break;
+            case 16: GITMI_SSTEP_T(16); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+#undef GITMI_SSTEP_T
 #define GITMI_SSTEP(SL)                                                                                               \
     do {                                                                                                                \
         if (t_is_f32) hipLaunchKernelGGL((search_step_kernel<float, SL>), dim3(st.B), dim3(256), 0, s, st, src, cur_len, in, em); \
@@ -1155,6 +1290,15 @@ hipError_t launch_search_finish(const SearchState& st, int cur, int cur_len, lon
                                 float* logprob_out, int* info_out, int* sent_out, hipStream_t s) {
     hipLaunchKernelGGL(search_finish_kernel, dim3(1), dim3(256), 0, s, st, cur, cur_len, tokens_out, logprob_out,
                        info_out, sent_out);
+    return hipGetLastError();
+}
+hipError_t launch_search_trace_gather(const SearchState& st, int cur, int cur_len, const TraceArgs& tr, float* out_lp,
+                                      long long* out_tok, hipStream_t s) {
+    if (!tr.log_lp || !out_lp || tr.n < 0 || tr.n > TRACE_NMAX || (tr.n > 0 && (!out_tok || !tr.log_tok))) return hipErrorInvalidValue;
+    if (tr.rows < st.B * st.k || cur_len > st.T) return hipErrorInvalidValue;
+    if (st.kind != 0 && (!tr.hyp_src || !tr.fin_lp)) return hipErrorInvalidValue;
+    const int nout = st.kind == 0 ? 1 : st.nh;
+    hipLaunchKernelGGL(search_trace_gather_kernel, dim3(st.B * nout), dim3(256), 0, s, st, cur, cur_len, tr, out_lp, out_tok);
     return hipGetLastError();
 }
 hipError_t launch_search_rows(const SearchState& st, int cur, int cur_len, long long* out, hipStream_t s) {

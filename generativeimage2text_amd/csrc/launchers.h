@@ -119,7 +119,8 @@ struct VocabArgs {
     // the launcher sends a constrained call there, VOC_GREEDY / VOC_BEAM never read these fields
     BanArgs ban;
 };
-hipError_t launch_vocab_topm(const VocabArgs& g, int mtop, hipStream_t s);
+// generic: run the generic form whatever the shape (a traced call, whose lists hold max(M, n) candidates)
+hipError_t launch_vocab_topm(const VocabArgs& g, int mtop, hipStream_t s, bool generic = false);
 int vocab_parts(int V, int cols_per_wg);
 int vocab_mtop_slots(int mtop);
 
@@ -312,6 +313,17 @@ struct EmbedArgs {
     float* h_f; void* h_t; int D, vocab;
     int frag;            // h_t in the fragment-major operand layout of the decode chain
 };
+// per-token trace of a search (GITMI_SEARCH_TRACE, include/gitmi.h): the engine-owned log.  The step that writes position s of
+// new row r stores one record at [s][r]: the log-prob of the pick and the n best (token, log-prob) of the row it was picked from.
+// A position is written once per search, so the record of position s of any later row is log[s][kv_src[row][s]]; a GENERATOR
+// hypothesis keeps the kv_src of its history and the record of the candidate that finished it.  log_lp == nullptr: no trace.
+constexpr int TRACE_NMAX = 8;
+struct TraceArgs {
+    int n, rows;                        // alternatives per position (0 .. TRACE_NMAX); row stride of the log (>= B * k)
+    float* log_lp; int* log_tok;        // [T][rows][1 + n], [T][rows][n]
+    int* hyp_src;                       // [B][nh][T]
+    float* fin_lp; int* fin_tok;        // [B][nh][1 + n], [B][nh][n]
+};
 int row_topm_slots(int M);
 // sampling branch (decoder.py:1146-1166, 1343-1375): per row scores / temperature -> top-k / top-p filter (min 2 tokens
 // kept) -> `ndraw` draws without replacement (Gumbel-top-k on a counter-based generator) -> their log-probabilities under
@@ -335,8 +347,13 @@ hipError_t launch_trie_select(const float* logits, int ldl, int V, const int* id
 hipError_t launch_row_topm(const float* logits, int ldl, int V, const int* ids, int ld_ids, int cur_len,
                            const int* plen, int beams, int suppress_kind, float rep_penalty, int M, int R,
                            float* part_val, int* part_idx, float2* part_lse, hipStream_t s, const BanArgs* ban = nullptr);
+// tr (or nullptr: the plain kernel): the traced instantiation, which merges max(M, tr->n) candidates per row and logs the picks
 hipError_t launch_search_step(const SearchState& st, int src, int cur_len, const StepCands& in, const EmbedArgs& em,
-                              bool t_is_f32, hipStream_t s);
+                              bool t_is_f32, hipStream_t s, const TraceArgs* tr = nullptr);
+// beside launch_search_finish, in the order of its tokens_out: out_lp fp32 [B * nout][T][1 + n], out_tok int64 [B * nout][T][n]
+// (nullptr when n == 0); every element is written
+hipError_t launch_search_trace_gather(const SearchState& st, int cur, int cur_len, const TraceArgs& tr, float* out_lp,
+                                      long long* out_tok, hipStream_t s);
 hipError_t launch_search_init(const SearchState& st, hipStream_t s);
 hipError_t launch_search_finish(const SearchState& st, int cur, int cur_len, long long* tokens_out,
                                 float* logprob_out, int* info_out, int* sent_out, hipStream_t s);

@@ -30,6 +30,8 @@ SEARCH_KEEP = 7        # not a search: gitmi_generate_prefixed copies the memory
 SEARCH_RECALL = 8      # not a search: gitmi_generate_prefixed makes kept slots the resident images (Engine.recall)
 SEARCH_FEATURES = 9    # not a search: gitmi_generate_prefixed makes given feature rows the resident images (Engine.install_features)
 SEARCH_CONSTRAIN = 10  # not a search: gitmi_generate_prefixed arms per-sentence decoding constraints for the next search (Engine.constrain)
+SEARCH_TRACE = 11  # not a search: gitmi_generate_prefixed arms the per-token trace of the next search (Engine.trace)
+TRACE_MAX_ALTERNATIVES = 8
 MEMORY_HEADER_BYTES = 256      # header of a slot of an image store; slots are multiples of this size (include/gitmi.h)
 
 
@@ -1057,6 +1059,44 @@ class Engine:
                                                   None, None, pool, info.data_ptr(), _stream()))
         self._ban_keep = (words, info)  # the copies are enqueued on the stream: both outlive the call
         return {"sentences": Q, "sets": n_sets if Q else 0, "words": W}       # info_out's values (include/gitmi.h), not read back
+
+    # -- per-token trace ---------------------------------------------------------------------------------------------------------
+    def trace(self, Q: int, nout: int = 1, T: int = 0, n: int = 0, out_lp: Optional[torch.Tensor] = None,
+              out_tok: Optional[torch.Tensor] = None, host_out: bool = False):
+        """Arm the per-token trace of the NEXT search call of this context (include/gitmi.h GITMI_SEARCH_TRACE): that call -- Q
+        sentences, nout returned sequences each (num_keep_best), max_steps T -- also fills
+            out_lp  fp32 [Q * nout, T, 1 + n]: column 0 the log-prob of the token at every position (0 inside the prefix and past
+                    the end), columns 1 .. n the log-probs of the n likeliest alternatives there, descending
+            out_tok int64 [Q * nout, T, n]: their tokens (-1: none), or None when n == 0
+        in the order of its tokens.  One-shot; Q == 0 disarms.  The buffers (made here when not given; host_out: page-locked host
+        tensors) are valid once the stream has reached the end of the traced call.  Nothing is read back, the host does not wait.
+        -> (out_lp, out_tok)"""
+        Q, nout, T, n = int(Q), max(1, int(nout)), int(T), int(n)
+        search = GitmiSearch()
+        search.kind = SEARCH_TRACE
+        if Q == 0:
+            self._ck(self.lib.gitmi_generate_prefixed(self._h, None, 0, 0, None, 0, None, None, 0, C.byref(search), None, None, None,
+                                                      None, _stream()))
+            self._trace_keep = None
+            return None, None
+        if not 0 <= n <= TRACE_MAX_ALTERNATIVES:
+            raise ValueError(f"top_logprobs={n} outside [0, {TRACE_MAX_ALTERNATIVES}]")
+        if Q < 0 or T < 1:
+            raise ValueError(f"a trace of {Q} sentences and {T} positions")
+        dev = torch.device(f"cuda:{self.device}")
+        if out_lp is None:
+            out_lp = self._empty((Q * nout, T, 1 + n), torch.float32, dev, host_out)
+        if out_tok is None and n > 0:
+            out_tok = self._empty((Q * nout, T, n), torch.int64, dev, host_out)
+        if out_lp.dtype != torch.float32 or out_lp.numel() != Q * nout * T * (1 + n) or not out_lp.is_contiguous():
+            raise ValueError(f"out_lp is a contiguous fp32 [{Q * nout}, {T}, {1 + n}] tensor, got {out_lp.dtype} {tuple(out_lp.shape)}")
+        if n > 0 and (out_tok.dtype != torch.int64 or out_tok.numel() != Q * nout * T * n or not out_tok.is_contiguous()):
+            raise ValueError(f"out_tok is a contiguous int64 [{Q * nout}, {T}, {n}] tensor, got {out_tok.dtype} {tuple(out_tok.shape)}")
+        search.num_keep_best, search.max_steps, search.reserved_ = nout, T, n
+        self._ck(self.lib.gitmi_generate_prefixed(self._h, None, 0, 0, None, 0, None, None, Q, C.byref(search),
+                                                  _ptr(out_tok) if n > 0 else None, out_lp.data_ptr(), None, None, _stream()))
+        self._trace_keep = (out_lp, out_tok)    # the traced call writes them: both outlive it
+        return out_lp, (out_tok if n > 0 else None)
 
     def prefill(self) -> None:
         self._ck(self.lib.gitmi_prefill(self._h, _stream()))

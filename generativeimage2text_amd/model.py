@@ -18,10 +18,76 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 import torch
 
 from .configs import GitModelConfig, config_from_param
-from .engine import CONSTRAINT_KEYS, Engine, banned_sequence_tables, constraint_tables, context_segments, id_table
+from .engine import CONSTRAINT_KEYS, TRACE_MAX_ALTERNATIVES, Engine, banned_sequence_tables, constraint_tables, context_segments, id_table
 
 # search_param keys of the per-sentence decoding constraints (CaptioningModel._constraints)
 CONSTRAINT_PARAMS = CONSTRAINT_KEYS + ("bad_words", "bad_sequences", "bad_phrases")
+
+
+# search_param keys of the per-token trace (CaptioningModel._trace)
+TRACE_PARAMS = ("output_scores", "top_logprobs")
+
+
+def trace_param(search_param: Optional[dict], kind: str) -> Optional[int]:
+    """The per-token trace a request asks for (include/gitmi.h GITMI_SEARCH_TRACE) from its search_param: output_scores (bool)
+    asks for the log-prob of every returned token, top_logprobs (0 .. 8; above 0 implies output_scores) for that many
+    alternatives per position as well.  `kind`: the decoder's search.  -> the number of alternatives n, or None: no trace, the
+    request builds nothing and arms nothing."""
+    sp = search_param or {}
+    n = sp.get("top_logprobs", 0)
+    n = 0 if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= TRACE_MAX_ALTERNATIVES:
+        raise ValueError(f"top_logprobs {n!r} outside [0, {TRACE_MAX_ALTERNATIVES}]")
+    if not sp.get("output_scores", False) and n == 0:
+        return None
+    if kind == "trie":
+        raise NotImplementedError("output_scores / top_logprobs on the trie search are not implemented")
+    if n > 0 and sp.get("do_sample", False):
+        raise NotImplementedError("top_logprobs with do_sample: alternatives under sampling are not implemented (output_scores alone works)")
+    return n
+
+
+def _arm_trace(eng, n: Optional[int], Q: int, search, host: bool):
+    """Arm the trace of a request (trace_param) of Q sentences on `eng`, right before the call that consumes it -> its buffers, or None"""
+    if n is None:
+        return None
+    return eng.trace(Q, max(1, int(search.num_keep_best)), int(search.max_steps), n, host_out=host)
+
+
+def format_trace(trace, spans):
+    """The trace of a finished call (Engine.trace's buffers: lp [S, T, 1 + n], tokens [S, T, n] or None) cut like its predictions:
+    spans[o] = (first, end) positions of returned sequence o.  -> {'token_logprobs': per sequence the log-prob of every token,
+    'top_tokens' / 'top_logprobs': per sequence [len, n] lists (n > 0 only)}"""
+    lp, tok = trace
+    lp = lp.cpu()
+    out = {"token_logprobs": [lp[o, a:b, 0].tolist() for o, (a, b) in enumerate(spans)]}
+    if tok is not None:
+        tok = tok.cpu()
+        out["top_tokens"] = [tok[o, a:b].tolist() for o, (a, b) in enumerate(spans)]
+        out["top_logprobs"] = [lp[o, a:b, 1:].tolist() for o, (a, b) in enumerate(spans)]
+    return out
+
+
+def trace_spans(n_seq: int, nout: int, T: int, sent, prefix, kind: str):
+    """The positions format_predictions keeps of every returned sequence (n_seq sentences x nout sequences, T positions): the
+    same arguments, the same rule -> [(first, end)] per returned sequence"""
+    autoregressive = kind in ("autoregressive", "trie")
+    spans = []
+    for q in range(n_seq):
+        if isinstance(prefix, (list, tuple)):
+            P, L, early = int(prefix[q]), int(sent[q][0]), int(sent[q][1])
+            first = P
+        else:
+            P, L, early = (1 if prefix is None else int(prefix)), int(sent[0]), int(sent[1])
+            first = 0 if prefix is None else P
+        if autoregressive:
+            # the early-[SEP] return keeps position P alone, and a given prefix is then removed from THAT one-token row
+            # (format_predictions, as decoder.py:1004-1006 does): nothing is left of it
+            span = ((P, P + 1) if first == 0 else (P + 1, P + 1)) if early else (first, L)
+        else:
+            span = (first, T)
+        spans.extend([span] * nout)
+    return spans
 
 
 def _arm(eng, ban) -> None:
@@ -391,12 +457,17 @@ def format_predictions(tokens, logprobs, sent, prefix, kind: str):
 
 
 def _finish_batch(eng, out, prefix, kind: str):
-    """Pending.finish of a batch-uniform request (model(batch), captioning ragged batches)."""
-    tokens, logprobs, info = out
+    """Pending.finish of a batch-uniform request (model(batch), captioning ragged batches); a traced request's `out` carries
+    Engine.trace's buffers as a fourth entry."""
+    tokens, logprobs, info = out[:3]
     info_h = info.tolist()                                              # ONE small read-back for the four fields
     eng.check_finite(info_h)
     predictions, logprobs = format_predictions(tokens, logprobs, info_h[:2], prefix, kind)
-    return {"predictions": predictions, "logprobs": logprobs}
+    res = {"predictions": predictions, "logprobs": logprobs}
+    if len(out) > 3:
+        nout = 1 if tokens.dim() == 2 else int(tokens.shape[1])
+        res.update(format_trace(out[3], trace_spans(int(tokens.shape[0]), nout, int(tokens.shape[-1]), info_h[:2], prefix, kind)))
+    return res
 
 
 def _is_image_list(images) -> bool:
@@ -504,7 +575,8 @@ class CaptioningModel:
         part of the struct: _constraints turns them into the tables the front end arms before the call."""
         d = self.decoder
         sp = dict(search_param or {})
-        unknown = set(sp) - {"do_sample", "top_k", "top_p", "seed", "num_keep_best", "num_return_sequences"} - set(CONSTRAINT_PARAMS)
+        unknown = set(sp) - {"do_sample", "top_k", "top_p", "seed", "num_keep_best", "num_return_sequences"} - set(CONSTRAINT_PARAMS) \
+            - set(TRACE_PARAMS)
         if unknown:
             raise NotImplementedError(f"search parameters {sorted(unknown)} are not implemented")
         if d.kind != "generator" and (int(sp.get("num_keep_best", 1)) != 1 or int(sp.get("num_return_sequences", 1)) != 1):
@@ -742,6 +814,7 @@ class CaptioningModel:
         nret = int((search_param or {}).get("num_return_sequences", 1))
         kind = self.decoder.kind
         ban = self._constraints(search_param, int(frames[0].shape[0]), repeat=nret)
+        trace_n = trace_param(search_param, kind)
 
         def launch():
             frames_arg = frames
@@ -750,6 +823,7 @@ class CaptioningModel:
                 frames_arg = None
             if ban is not None:         # armed on this context and stream, immediately before the call that consumes it
                 _arm(eng, ban)
+            trace = _arm_trace(eng, trace_n, int(frames[0].shape[0]) * nret, search, stream is not None)
             if nret != 1:
                 # decoder.py:1093-1097: every image's start tokens num_return_sequences times -- r sentences per image, each
                 # with its own beams (they differ only when sampling); rows b * r + j, as the reference returns them
@@ -763,7 +837,7 @@ class CaptioningModel:
             else:
                 # requests in flight on other streams: results straight into page-locked host memory (no read-back to enqueue)
                 tokens, logprobs, info = eng.generate(frames_arg, search, prefix=prefix, sync=False, host_out=stream is not None)
-            return tokens, logprobs, info
+            return (tokens, logprobs, info) if trace is None else (tokens, logprobs, info, trace)
 
         return Pending(stream, launch, lambda out: _finish_batch(eng, out, P, kind), keep=(frames, prefix), engine=eng)
 
@@ -788,7 +862,8 @@ class CaptioningModel:
             raise NotImplementedError("num_return_sequences in a follow-up request: repeat the sentence in 'image_of'")
         eng, stream = self._followup_context(on)
         return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=True,
-                                     ban=self._constraints(search_param, len(prefixes)))
+                                     ban=self._constraints(search_param, len(prefixes)),
+                                     trace_n=trace_param(search_param, self.decoder.kind))
 
     def forward(self, batch: Mapping[str, Union[torch.Tensor, Sequence[torch.Tensor]]],
                 search_param: Optional[dict] = None, on=None) -> Dict[str, torch.Tensor]:
@@ -1015,11 +1090,14 @@ class CaptioningModel:
         if int((search_param or {}).get("num_return_sequences", 1)) != 1:
             raise NotImplementedError("num_return_sequences with images of different sizes")
         ban = self._constraints(search_param, len(images) if prefixes is None else len(prefixes))
+        trace_n = trace_param(search_param, self.decoder.kind)
         if prefixes is None:
             def launch():
                 if ban is not None:
                     _arm(eng, ban)
-                return eng.generate(packed, search, sync=False, host_out=stream is not None)
+                trace = _arm_trace(eng, trace_n, len(images), search, stream is not None)
+                out = eng.generate(packed, search, sync=False, host_out=stream is not None)
+                return out if trace is None else (*out, trace)
 
             return Pending(stream, launch,
                            lambda out: _finish_batch(eng, out, None, self.decoder.kind), keep=(packed,), engine=eng)
@@ -1029,7 +1107,7 @@ class CaptioningModel:
             raise ValueError(f"{Q} questions exceed max_batch={eng.c.max_batch}")
         if len(image_of) != Q or any(i < 0 or i >= len(images) for i in image_of):
             raise ValueError(f"image_of must name one of the {len(images)} images for each of the {Q} questions")
-        return self._submit_prefixed(eng, stream, packed, prefixes, image_of, search, as_dict=True, ban=ban)
+        return self._submit_prefixed(eng, stream, packed, prefixes, image_of, search, as_dict=True, ban=ban, trace_n=trace_n)
 
     def generate_ragged(self, images: Sequence[torch.Tensor], prefixes: Optional[Sequence[Sequence[int]]] = None,
                         image_of: Optional[Sequence[int]] = None, search_param: Optional[dict] = None):
@@ -1052,7 +1130,8 @@ class CaptioningModel:
             eng, stream = self._followup_context(on)
             self._prepare(eng, None)
             return self._submit_prefixed(eng, stream, None, prefixes, image_of, self._search_struct(search_param), as_dict=False,
-                                         ban=self._constraints(search_param, len(prefixes)))
+                                         ban=self._constraints(search_param, len(prefixes)),
+                                         trace_n=trace_param(search_param, self.decoder.kind))
         is_list = isinstance(images, (list, tuple))
         frames = list(images) if is_list else [images]
         Q = len(prefixes)
@@ -1062,12 +1141,13 @@ class CaptioningModel:
             raise ValueError(f"{Q} questions / {int(frames[0].shape[0])} images exceed max_batch={eng.c.max_batch}")
         self._prepare(eng, is_list)
         return self._submit_prefixed(eng, stream, frames, prefixes, image_of, self._search_struct(search_param), as_dict=False,
-                                     ban=self._constraints(search_param, Q))
+                                     ban=self._constraints(search_param, Q), trace_n=trace_param(search_param, self.decoder.kind))
 
-    def _submit_prefixed(self, eng, stream, frames, prefixes, image_of, search, as_dict: bool, ban=None) -> "Pending":
+    def _submit_prefixed(self, eng, stream, frames, prefixes, image_of, search, as_dict: bool, ban=None, trace_n=None) -> "Pending":
         """submit_answers / submit_ragged with questions: one generate_prefixed call on `eng` (frames: a stacked batch or
         RaggedImages).  .result(): the answers' id lists, and with as_dict {'predictions': them, 'logprobs' [Q, 1]}.
-        ban: the decoding constraints of the sentences (_constraints), armed on the context's stream right before the call."""
+        ban: the decoding constraints of the sentences (_constraints), armed on the context's stream right before the call.
+        trace_n (trace_param): the request is traced -- the result is then the dict whatever as_dict says, with the trace's keys."""
         kind = self.decoder.kind
         if frames is None:
             self._prepare(eng, None)
@@ -1080,12 +1160,20 @@ class CaptioningModel:
         def launch():
             if ban is not None:
                 _arm(eng, ban)
-            return eng.generate_prefixed(frames, search, prefixes, image_of=image_of, sync=False, host_out=stream is not None)
+            trace = _arm_trace(eng, trace_n, len(prefixes), search, stream is not None)
+            out = eng.generate_prefixed(frames, search, prefixes, image_of=image_of, sync=False, host_out=stream is not None)
+            return out if trace is None else (*out, trace)
 
         def finish(out):
-            tokens, logprobs, sent, info = out
+            tokens, logprobs, sent, info = out[:4]
             eng.check_finite(info.tolist())
-            preds, logprobs = format_predictions(tokens.cpu(), logprobs, sent.cpu(), [len(p) for p in prefixes], kind)
+            plens = [len(p) for p in prefixes]
+            preds, logprobs = format_predictions(tokens.cpu(), logprobs, sent.cpu(), plens, kind)
+            if len(out) > 4:
+                nout = 1 if tokens.dim() == 2 else int(tokens.shape[1])
+                res = {"predictions": preds, "logprobs": logprobs.cpu()}
+                res.update(format_trace(out[4], trace_spans(len(prefixes), nout, int(tokens.shape[-1]), sent.cpu(), plens, kind)))
+                return res
             return {"predictions": preds, "logprobs": logprobs.cpu()} if as_dict else preds
 
         return Pending(stream, launch, finish, keep=(frames,), engine=eng)

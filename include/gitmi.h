@@ -63,6 +63,8 @@ extern "C" {
                                         * (the input side of gitmi_encode_frames' feats_out); gitmi_generate_prefixed only, see there */
 #define GITMI_SEARCH_CONSTRAIN 10      /* not a search: arm per-sentence decoding constraints (banned tokens, a minimum length, no
                                         * repeated n-grams) for the next search call of a context; gitmi_generate_prefixed only, see there */
+#define GITMI_SEARCH_TRACE 11          /* not a search: arm the per-token trace (log-prob of every emitted token and the n likeliest
+                                        * alternatives) of the next search call of a context; gitmi_generate_prefixed only, see there */
 
 typedef struct gitmi_engine gitmi_engine;
 
@@ -555,6 +557,46 @@ int  gitmi_generate(gitmi_engine* e, const float* const* frames, int F, int B,
  * set rule of that step then reads.  The hipGraph key's "constrained" tells plain, armed and armed with sequences apart; calls of
  * equal shape armed with other sequences replay one graph.  Plain calls and set-only armed calls launch what they did; a set-only
  * arming after one with sequences carries none.  The trie search and the step seam keep refusing while armed. */
+/* ---- per-token trace: search->kind == GITMI_SEARCH_TRACE arms the trace of the NEXT search call on this context.  One-shot: that
+ * call consumes it and fills the buffers given here.  The rule, for returned sequence o of sentence q (prefix length P_q) and
+ * position s: lp[o][s] is the entry of the search class's own class_logprobs for the token at position s, taken from the row
+ * whose history is seq[0 .. s), after everything the class does before its log-softmax (the -10000 on the previous token and
+ * the forced one-hot [SEP] of an ended beam, decoder.py:330-358; the repetition penalty, temperature and sampling filter of the
+ * GENERATOR, decoder.py:1135-1175; armed constraint bans).  lp is 0 for s < P_q (given tokens) and past the end of the sequence.
+ *   AUTOREGRESSIVE : positions [P_q, L_q), L_q the returned length (sent_out[2q]); a forced [SEP] after the first one has lp 0.
+ *   GENERATOR      : positions [P_q, n_h) of the hypothesis; position n_h, where the output appends [SEP], holds the lp of the
+ *                    candidate that finished the hypothesis: [SEP] itself, or the last word when cur_len + 1 == max_steps (the
+ *                    reference scores that word and drops it).  Sequences the list could not fill (log-prob -1e5): all 0 / -1.
+ *   alternatives   : alt_tok[o][s][j], alt_lp[o][s][j], j < n: the n likeliest tokens of that same distribution, descending, ties
+ *                    to the lower token id.  An entry whose lp is -inf (the one-hot rows) is token -1 with lp -inf; prefix positions
+ *                    and positions past the end are token -1, lp 0.
+ * Sum: sum_s lp[o][s] reproduces logprob_out -- divided by num_valid (AUTOREGRESSIVE) or by len_norm(n_h) (GENERATOR) -- up to
+ * the rounding of a sequential fp32 sum.  NOT for a sampled GENERATOR call with beam_size > 1: the reference attaches candidate c
+ * to beam c % k but takes its score from beam c / per_node_beam_size (decoder.py:1161-1164); the engine reproduces that, so the
+ * running sum does not follow the history there.  The lps themselves are still the scores the search added.
+ * If the chosen token ranks below n it appears among the alternatives with the bit-identical lp.
+ * The argument mapping:
+ *   frames, prefixes, prefix_len_host, image_of_host : must be NULL; F, B, ld_prefix are ignored.  Residency is untouched
+ *   Q                     : the sentence count of the call to trace, 1 .. max_batch; Q == 0 disarms and reads nothing else
+ *   search->num_keep_best : sequences per sentence that call returns (nout; 0 and 1 both mean one)
+ *   search->max_steps     : its max_steps T;   search->reserved_ : n, 0 .. 8
+ *   logprob_out           : fp32 [Q * nout][T][1 + n]: column 0 the chosen lp, columns 1 .. n alt_lp
+ *   tokens_out            : int64 [Q * nout][T][n] alt_tok, or NULL when n == 0
+ *                           both DEVICE or page-locked host buffers, alive until the stream reaches the end of the traced call
+ *   info_out              : { Q, nout, T, n }, or NULL: nothing is written and the host does not wait for the stream;  sent_out: ignored
+ * Checked on the host before any launch, by message naming the field; a refused call leaves the arming and what is resident
+ * unchanged.  Consumption: the next gitmi_generate (kinds 0 and 1), the next gitmi_generate_prefixed search, or the next seam
+ * search (gitmi_search_begin consumes it under the kind of the search it starts; gitmi_search_finish fills the buffers).  Another
+ * sentence count, nout or T is an argument error that names both numbers and stays armed.  Refused by name: GITMI_SEARCH_TRIE
+ * while armed, and n > 0 with do_sample.  Composes with armed constraints (the lps are those after the bans).  A clone starts
+ * disarmed.  gitmi_generate and gitmi_search_begin refuse the kind by name.
+ * The step of a traced search logs one record per new row (its pick's lp and its parent row's n best) at [position][row]; the
+ * beam reordering moves nothing more than it does in a plain call, the record of position s of a final row is found through the
+ * same K/V row indirection the attention uses.  The vocabulary head and the whole-row top-M run with max(M, n) candidates; a
+ * traced 16-bit call runs the head in its generic form.  The log and the engine's output copies are allocated by the first
+ * arming call: engines that never trace keep their footprint, and a call that is not traced launches what it did.  The hipGraph
+ * key gains "trace" (0, or 1 + n) and traced calls have graph slots of their own, so plain and traced calls alternate without
+ * re-capture and traced calls of equal shape replay one graph. */
 int  gitmi_generate_prefixed(gitmi_engine* e, const float* const* frames, int F, int B,
                              const int64_t* prefixes, int ld_prefix, const int32_t* prefix_len_host,
                              const int32_t* image_of_host, int Q, const gitmi_search* search,
